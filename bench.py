@@ -1,6 +1,6 @@
 """Headline benchmark: audio-seconds generated per wall-second for the Foley sampling path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--bs B] [--precision bf16|fp32] [--progress]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--bs B] [--precision bf16|fp32] [--progress] [--dump-outputs DIR]
 
 A "step" is ONE pass of the whole hot path over one batch of synthetic input, host to host: H2D of
 the CPU-generator noise, step-invariant precompute, the 50-iteration Euler/CFG loop over the xxl
@@ -301,7 +301,33 @@ def parse_args(argv=None):
                          "(graph replay + D2D copy + stream synchronise per iteration, foley_rt.hip foley_sample)")
     ap.add_argument("--dry-run", action="store_true",
                     help="setup only (pack, the single broadcast, sharding) on CPU tensors - no HIP work; used by the gloo tests")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the waveform of every rank's clips, in clip "
+                         "order) to DIR/<name>.npy in float32; beyond 64 MB a fixed seeded sample of the elements is written")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays) -> dict:
+    """Write each array of `arrays` as out_dir/<name>.npy in float32, at most DUMP_LIMIT_BYTES in all: an array beyond its share is
+    replaced by the elements at a fixed sample of flat indices (seed 0, ascending), so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // 4 // len(arrays)     # 4096: room for each file's .npy header
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        sampled = t.numel() > share
+        if sampled:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            arr = t.reshape(-1)[idx].numpy()
+        else:
+            arr = t.numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        info[name] = {"shape": list(t.shape), "written": list(arr.shape), "sampled": sampled}
+    return info
 
 
 def main(argv=None):
@@ -309,6 +335,9 @@ def main(argv=None):
     a = parse_args(argv)
     if a.gpus < 1:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
+        return 2
+    if a.steps < 1 or a.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
         return 2
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not launched and a.gpus > 1:
@@ -472,6 +501,7 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
                 print(f"bench.py: pass {1e3 * (time.perf_counter() - tq):.1f} ms", file=sys.stderr)
         barrier()
         dt = time.perf_counter() - t0
+        pieces["audio"] = audio           # what the last timed pass returned (--dump-outputs)
         # pieces of one more pass: precompute (host clock around a synchronised call), loop / decode (HIP events
         # recorded by the library on the launch stream)
         lat = noise_cpu.to(dev).float().contiguous()
@@ -512,6 +542,15 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
         return recs
 
     dt, loop_ms, dac_ms = measure(bs_main, noise_all[lo:hi], a.steps, a.warmup)
+    dumped = None
+    if a.dump_outputs:
+        audio = pieces["audio"]
+        if use_dist:                     # every rank's clips, in rank (= clip) order
+            parts = [None] * world
+            dist.all_gather_object(parts, audio)
+            audio = torch.cat(parts)
+        if rank == 0:
+            dumped = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, {"audio": audio})}
     prepare_ms = pieces.get("prepare_ms")
     rank_records = gather_ranks(dict(pieces["local"], shard=[lo, hi]))
     f_clip = flops_clip(cfg, duration, STEPS_PER_CLIP, GUIDANCE)
@@ -660,6 +699,8 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
             out["end_to_end_ms_per_step"] = encoders["total_ms"] + 1e3 * dt / a.steps
         if extra:
             out["extra"] = extra
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and not a.no_cpu_baseline and a.model == "xxl" and a.config != "c5":
             out["cpu_baseline"] = cpu_baseline(sd, dsd, cfg, cond, noise_all, duration, full=a.cpu_baseline_full)
         emit(out)

@@ -79,8 +79,11 @@ def test_interleave_gate_and_qkv_permutation():
     p = packers.interleave_gate(w1, w3)
     assert torch.equal(p[0:32], w1[0:32]) and torch.equal(p[32:64], w3[0:32]) and torch.equal(p[64:96], w1[32:64])
     H, hd = 2, 4
-    w = torch.randn(3 * H * hd, 5, generator=_g(10))
-    x = torch.randn(7, 5, generator=_g(11))
+    # integer-valued operands: every product and partial sum is exact in fp32, so the bitwise comparison below holds whatever
+    # order the host BLAS reduces in (MKL's sgemm kernels, and with them the rounding, differ between CPUs and output columns)
+    w = torch.randint(-8, 9, (3 * H * hd, 5), generator=_g(10)).float()
+    x = torch.randint(-8, 9, (7, 5), generator=_g(11)).float()
+    assert len({tuple(r) for r in w.tolist()}) == w.shape[0]           # distinct rows: any wrong permutation shows
     y = (x @ w.t()).view(7, H, hd, 3)                                  # reference '(H D K)'
     yp = (x @ packers.qkv_hdk_to_khd(w, H).t()).view(7, 3, H, hd)      # packed '(K H D)'
     for k in range(3):
@@ -455,3 +458,36 @@ def test_no_kernel_keeps_accumulators_in_scratch():
         if " scratch " in line:
             worst = max(worst, int(line.split(" scratch ")[1].split()[0]))
     assert worst <= 32, out
+
+
+def test_bench_dump_outputs_writes_float32_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an array within its share of the budget is written whole in float32; a larger one is replaced by a
+    fixed seeded sample of its elements (the same indices on every call), and the files stay under the budget."""
+    import numpy as np
+    import bench
+    small = torch.randn(2, 1, 300, generator=torch.Generator().manual_seed(5)).to(torch.bfloat16)
+    info = bench.dump_outputs(str(tmp_path / "a"), {"audio": small})
+    got = np.load(tmp_path / "a" / "audio.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 1, 300) and np.array_equal(got, small.float().numpy())
+    assert info["audio"] == {"shape": [2, 1, 300], "written": [2, 1, 300], "sampled": False}
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 4096 + 4000)      # 500 elements per array for two arrays
+    big = torch.arange(6000, dtype=torch.float64).reshape(3, 2000)
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), {"x": big, "y": big + 0.5})
+        assert info["x"]["sampled"] and info["x"]["written"] == [500]
+    x, x2 = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    y = np.load(tmp_path / "b" / "y.npy")
+    assert x.dtype == np.float32 and x.shape == (500,) and np.array_equal(x, x2) and np.array_equal(y, x + 0.5)
+    assert len(np.unique(x)) == 500 and np.all(np.diff(x) > 0)          # distinct flat indices, ascending
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in ("x.npy", "y.npy")) <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_rejects_zero_steps():
+    """--steps sets the number of timed steps, so it must be at least one (ms_per_step divides by it)."""
+    import subprocess
+    import sys
+    for args in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--model", "tiny", "--duration", "1"] + args,
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--steps" in r.stderr, r.stderr[-2000:]

@@ -949,6 +949,30 @@ def test_bench_single_rank_forced_dist(dev):
     assert out["config"]["ranks"][0]["clips"] == 1 and out["config"]["ranks"][0]["uuid"]
 
 
+def test_bench_dump_outputs(dev, tmp_path):
+    """bench.py --dump-outputs: the waveform of the last timed step lands in DIR/audio.npy (float32, the clip's full shape), the
+    line reports the timed steps it was asked for, and two runs with the same arguments (different step counts) dump the same
+    waveform - the inputs are a pure function of the arguments."""
+    import json, os, subprocess, sys
+    import numpy as np
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    outs = []
+    for i, (steps, warmup) in enumerate([(2, 0), (1, 1)]):
+        d = str(tmp_path / f"run{i}")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--duration", "1",
+                            "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-extra", "--dump-outputs", d],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads(r.stdout)
+        assert out["steps"] == steps and out["warmup"] == warmup and out["ms_per_step"] > 0
+        assert out["dump_outputs"]["arrays"]["audio"] == {"shape": [1, 1, 48000], "written": [1, 1, 48000], "sampled": False}
+        a = np.load(os.path.join(d, "audio.npy"))
+        assert a.dtype == np.float32 and a.shape == (1, 1, 48000) and np.isfinite(a).all() and np.abs(a).max() > 0
+        outs.append(a)
+    assert np.array_equal(outs[0], outs[1])
+
+
 def test_denoise_process_multi_shards_the_batch(tiny, dev):
     """Node-level data parallelism inside one process (host/sampler.py::replicate / denoise_process_multi): the
     clips of a batch are sharded over replicas, one host thread and one context each, with no collective.  On a
