@@ -14,8 +14,13 @@
 
 namespace {
 
-// head dim: 128 (the Foley DiT) or 64 (the conditioning encoders: Synchformer / SigLIP2 ViT-B, host/encoders.py) - a template
-// parameter of the fp32 kernel and of the 16-bit wide kernel
+// head dim: 128 (the Foley DiT), 64 (the conditioning encoders: Synchformer / SigLIP2 ViT-B, host/encoders.py) or 96 (the
+// Synchformer sync head, host/sync_score.py: 8 heads x 96) - a template parameter of the fp32 kernel and of the 16-bit wide kernel
+
+// 1/sqrt(HD), a compile-time constant of each instance
+template <int HD> __device__ constexpr float attn_scale() {
+  return HD == 128 ? 0.08838834764831845f : HD == 64 ? 0.125f : 0.10206207261596575f;
+}
 
 // 1-D grid -> (query tile, head, batch) with a bijective XCD-aware remap: workgroup id i runs on XCD
 // i % 8, so ids are regrouped such that all query tiles of one (batch, head) - which read the same
@@ -65,7 +70,7 @@ __global__ __launch_bounds__(64) void attn_kernel(const AttnArgs a) {
   const float* __restrict__ Q = (const float*)a.q + ((long)(b * a.H + h) * a.Sq) * HD;
   const float* __restrict__ K = (const float*)a.k + ((long)(bk * a.H + h) * a.Skv) * HD;
   const float* __restrict__ V = (const float*)a.v + ((long)(bk * a.H + h) * a.Skv) * HD;
-  const float scale = HD == 128 ? 0.08838834764831845f : 0.125f;  // 1/sqrt(HD)
+  const float scale = attn_scale<HD>();
 
   // B operand of S^T = K Q^T: lane (j, kh) holds Q[q0 + j][kh*HD/2 .. +HD/2-1]
   constexpr int HH = HD / 2, NC = HD / 8;   // floats / float4 chunks of a half head
@@ -613,7 +618,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const T* __restrict__ Q = (const T*)a.q + ((long)(b * a.H + h) * a.Sq) * HD;
   const T* __restrict__ K = (const T*)a.k + ((long)(bk * a.H + h) * a.Skv) * HD;
   const T* __restrict__ VT = (const T*)a.v + ((long)(bk * a.H + h) * HD) * a.vt_pitch;
-  const float scale2 = (HD == 128 ? 0.08838834764831845f : 0.125f) * 1.4426950408889634f;   // log2(e) / sqrt(HD)
+  const float scale2 = attn_scale<HD>() * 1.4426950408889634f;   // log2(e) / sqrt(HD)
 
   bf16x8 qf[NS];
   {
@@ -641,21 +646,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   // staging: 4*HD + 4*HD pieces of 16 B per tile, NP + NP per thread
   const int k_row0 = tid / CK, k_col = tid % CK;       // K tile: 32 rows x CK chunks, 256 / CK rows per pass
   const int v_row0 = tid >> 2, v_col = tid & 3;        // V^T tile: HD rows x 4 chunks, 64 rows per pass
-  u32x4 rk[NP], rv[NP];
+  // HD = 96: 384 + 384 pieces - every thread stages piece tid, the first 128 threads (waves 0 and 1) also piece 256 + tid
+  constexpr int NPX = HD % 64 ? 2 : NP;
+  u32x4 rk[NPX], rv[NPX];
   auto gload = [&](int t) {
     const int kt = t * 32;
+    if constexpr (HD % 64 == 0) {
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      rk[i] = *(const u32x4*)(K + (long)min(kt + k_row0 + i * (256 / CK), a.Skv - 1) * HD + k_col * 8);
-      rv[i] = *(const u32x4*)(VT + (long)(v_row0 + i * 64) * a.vt_pitch + kt + v_col * 8);
+      for (int i = 0; i < NP; ++i) {
+        rk[i] = *(const u32x4*)(K + (long)min(kt + k_row0 + i * (256 / CK), a.Skv - 1) * HD + k_col * 8);
+        rv[i] = *(const u32x4*)(VT + (long)(v_row0 + i * 64) * a.vt_pitch + kt + v_col * 8);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NPX; ++i) {
+        const int p = tid + 256 * i;
+        if (p < 4 * HD) {
+          rk[i] = *(const u32x4*)(K + (long)min(kt + p / CK, a.Skv - 1) * HD + (p % CK) * 8);
+          rv[i] = *(const u32x4*)(VT + (long)(p >> 2) * a.vt_pitch + kt + (p & 3) * 8);
+        }
+      }
     }
   };
   auto lstore = [&](int stage) {
     unsigned char* base = lds + stage * STG;
+    if constexpr (HD % 64 == 0) {
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      *(u32x4*)(base + (k_row0 + i * (256 / CK)) * KP + k_col * 16) = rk[i];
-      *(u32x4*)(base + 32 * KP + (v_row0 + i * 64) * VP + v_col * 16) = rv[i];
+      for (int i = 0; i < NP; ++i) {
+        *(u32x4*)(base + (k_row0 + i * (256 / CK)) * KP + k_col * 16) = rk[i];
+        *(u32x4*)(base + 32 * KP + (v_row0 + i * 64) * VP + v_col * 16) = rv[i];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NPX; ++i) {
+        const int p = tid + 256 * i;
+        if (p < 4 * HD) {
+          *(u32x4*)(base + (p / CK) * KP + (p % CK) * 16) = rk[i];
+          *(u32x4*)(base + 32 * KP + (p >> 2) * VP + (p & 3) * 16) = rv[i];
+        }
+      }
     }
   };
   const int nt = (a.Skv + 31) >> 5;
@@ -1106,7 +1135,7 @@ int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
   a.dbg = g_attn_dbg;
   if (a.Sq <= 0 || a.Skv <= 0) return foley_set_err("attention: empty sequence", __FILE__, __LINE__);
   const int hd = a.head_dim > 0 ? a.head_dim : 128;
-  if (hd != 128 && hd != 64) return foley_set_err("attention: head_dim must be 128 or 64", __FILE__, __LINE__);
+  if (hd != 128 && hd != 64 && hd != 96) return foley_set_err("attention: head_dim must be 128, 96 or 64", __FILE__, __LINE__);
   if (a.grp_q > 0 || a.grp_kv > 0) {
     if (hd != 64 || !foley_is_half(a.in_dtype) || a.grp_q < 1 || a.grp_kv < 1 || a.kv_bdiv != 1 ||
         (long)((a.Sq + a.grp_q - 1) / a.grp_q) * a.grp_kv > a.Skv)
@@ -1120,10 +1149,10 @@ int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
       return foley_set_err("attention: V^T pitch must cover Skv rounded up to 32 (multiple of 8)", __FILE__, __LINE__);
     if (out_dtype != a.in_dtype && out_dtype != FOLEY_F32)
       return foley_set_err("attention: 16-bit operands produce the same type or fp32", __FILE__, __LINE__);
-    // enough 128-query workgroups to cover the chip => the wide kernel (operands read once per 128 queries); head dim 64
-    // (the conditioning encoders) exists in the wide form only
+    // enough 128-query workgroups to cover the chip => the wide kernel (operands read once per 128 queries); head dims 64
+    // (the conditioning encoders) and 96 (the sync head) exist in the wide form only
     const dim3 gw(((a.Sq + 127) / 128) * a.H * a.Bq);
-    const bool wide = (long)gw.x >= 256 || hd == 64, h16 = a.in_dtype == FOLEY_F16, o32 = out_dtype == FOLEY_F32;
+    const bool wide = (long)gw.x >= 256 || hd != 128, h16 = a.in_dtype == FOLEY_F16, o32 = out_dtype == FOLEY_F32;
     // long key sequences on grids of at most ~2 waves per SIMD: 64 keys per iteration of each wave's dependent chain (attn_bf16_long_kernel;
     // FOLEY_ATTN_LONG=0 keeps the 32-key form)
     static const bool long_on = []() { const char* e = getenv("FOLEY_ATTN_LONG"); return !(e && e[0] == '0'); }();
@@ -1173,6 +1202,7 @@ int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
       } else                                                                                         \
       if (wide && hd == 64 && a.grp_q > 0) FOLEY_LAUNCH((attn_bf16_wide_kernel<T, O, 64, true>), gw, dim3(256), 0, st, a);  \
       else if (wide && hd == 64) FOLEY_LAUNCH((attn_bf16_wide_kernel<T, O, 64>), gw, dim3(256), 0, st, a);  \
+      else if (wide && hd == 96) FOLEY_LAUNCH((attn_bf16_wide_kernel<T, O, 96>), gw, dim3(256), 0, st, a);  \
       else if (wide) FOLEY_LAUNCH((attn_bf16_wide_kernel<T, O, 128>), gw, dim3(256), 0, st, a);        \
       else FOLEY_LAUNCH((attn_bf16_kernel<T, O>), grid1, dim3(256), 0, st, a);                         \
     } while (0)
@@ -1186,6 +1216,7 @@ int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
 #define FOLEY_ATTN32(O)                                                          \
   do {                                                                           \
     if (hd == 64) FOLEY_LAUNCH((attn_kernel<O, 64>), grid, block, 0, st, a);     \
+    else if (hd == 96) FOLEY_LAUNCH((attn_kernel<O, 96>), grid, block, 0, st, a); \
     else FOLEY_LAUNCH((attn_kernel<O, 128>), grid, block, 0, st, a);             \
   } while (0)
   if (out_dtype == FOLEY_F32) FOLEY_ATTN32(float);

@@ -1469,6 +1469,18 @@ extern "C" int foley_op_qkv_regroup(const void* qkv, int n_rows, int dtype, int 
   return launch_qkv_regroup(qkv, n_rows, dtype, H, idx_q, G, Sq, idx_kv, Skv, q, k, v, vt_pitch, (hipStream_t)stream);
 }
 
+extern "C" int foley_op_resample_sinc(const float* x, int B, int N, int orig, int new_rate, const float* taps, int ntaps, int width,
+                                      float* out, int Nout, void* stream) {
+  if (!x || !taps || !out) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  return launch_resample_sinc(x, B, N, orig, new_rate, taps, ntaps, width, out, Nout, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_logmel(const float* w16, int B, int N16, const float* basis, const int32_t* mel_lo, const int32_t* mel_len,
+                               const float* mel_w, int mel_wp, void* patches, int out_dtype, float* mel_out, void* stream) {
+  if (!w16 || !basis || !mel_lo || !mel_len || !mel_w || !patches) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  return launch_logmel(w16, B, N16, basis, mel_lo, mel_len, mel_w, mel_wp, patches, out_dtype, mel_out, (hipStream_t)stream);
+}
+
 extern "C" int foley_op_resize_aa_u8(const uint8_t* in, long outer, int len_in, long inner, int len_out, const int32_t* xmin,
                                      const int32_t* xsize, const int16_t* weights, int kmax, int precision, uint8_t* out, void* stream) {
   if (!in || !xmin || !xsize || !weights || !out) return FAIL(FOLEY_ERR_INVALID, "null argument");

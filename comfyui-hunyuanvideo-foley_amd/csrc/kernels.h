@@ -227,5 +227,10 @@ int launch_qkv_regroup(const void* qkv, int n_rows, int dtype, int H, const int*
                        void* v, int vt_pitch, hipStream_t st);
 int launch_resize_aa_u8(const uint8_t* in, long outer, int len_in, long inner, int len_out, const int* xmin, const int* xsize,
                         const short* w, int kmax, int prec, uint8_t* out, hipStream_t st);
+// audio.hip: the sync scorer's front end (host/sync_score.py)
+int launch_resample_sinc(const float* x, int B, int N, int orig, int nnew, const float* taps, int ntaps, int width, float* out,
+                         int Nout, hipStream_t st);
+int launch_logmel(const float* w16, int B, int N16, const float* basis, const int* mel_lo, const int* mel_len, const float* mel_w,
+                  int mel_wp, void* patches, int out_dtype, float* mel_out, hipStream_t st);
 int launch_dac_out(const float* s, const float* w, const float* bias, int B, int T, int C, float* out,
                    hipStream_t st);

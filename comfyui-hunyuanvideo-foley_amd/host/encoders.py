@@ -346,6 +346,84 @@ def synchformer_schema(depth: int = 12, dim: int = 768, frames: int = 8, grid: i
     return s
 
 
+SYNC_PREFIXES = ("afeat_extractor.", "vproj.", "aproj.", "transformer.")
+
+
+def load_synchformer_sync_state(sd: SD, device, dtype: torch.dtype) -> SD:
+    """Keep what the sync score touches (host/sync_score.py): the audio branch `afeat_extractor.*` (AST + frequency aggregation)
+    and the sync head `vproj.*` / `aproj.*` / `transformer.*` (synchformer.py:54-68, 115-187) - the parts load_synchformer_state
+    drops.  Raises when the checkpoint lacks them (e.g. a visual-only state dict)."""
+    keep = {k: v.to(device=device, dtype=dtype) for k, v in sd.items()
+            if k.startswith(SYNC_PREFIXES) and v.is_floating_point()}
+    need = ("afeat_extractor.ast.embeddings.patch_embeddings.projection.weight", "vproj.weight", "aproj.weight",
+            "transformer.off_head.weight", "transformer.pos_emb_cfg.pos_emb")
+    missing = [k for k in need if k not in keep]
+    if missing:
+        raise ValueError("not a full Synchformer checkpoint: the sync score needs the audio branch and the sync head "
+                         f"(afeat_extractor.* / vproj.* / aproj.* / transformer.*); missing {', '.join(missing)}")
+    return keep
+
+
+def synchformer_sync_schema(depth: int = 12, dim: int = 768, heads_depth: int = 3, n_tokens: int = 74, n_pos: int = 198,
+                            n_off: int = 21):
+    """state-dict schema (key -> (shape, std, mean)) of the audio branch and the sync head for synthesised weights: same keys and
+    shapes as Synchformer().state_dict() under afeat_extractor. / vproj. / aproj. / transformer."""
+    s = {}
+
+    def lin(k, o, i):
+        s[k + ".weight"] = ((o, i), 1.0 / math.sqrt(i), 0.0)
+        s[k + ".bias"] = ((o,), 0.02, 0.0)
+
+    def ln(k):
+        s[k + ".weight"] = ((dim,), 0.05, 1.0)
+        s[k + ".bias"] = ((dim,), 0.02, 0.0)
+
+    a = "afeat_extractor.ast."
+    s[a + "embeddings.cls_token"] = ((1, 1, dim), 0.02, 0.0)
+    s[a + "embeddings.distillation_token"] = ((1, 1, dim), 0.02, 0.0)
+    s[a + "embeddings.position_embeddings"] = ((1, n_tokens, dim), 0.02, 0.0)
+    s[a + "embeddings.patch_embeddings.projection.weight"] = ((dim, 1, 16, 16), 1.0 / 16.0, 0.0)
+    s[a + "embeddings.patch_embeddings.projection.bias"] = ((dim,), 0.02, 0.0)
+    for i in range(depth):
+        l = f"{a}encoder.layer.{i}."
+        for n in ("query", "key", "value"):
+            lin(l + "attention.attention." + n, dim, dim)
+        lin(l + "attention.output.dense", dim, dim)
+        lin(l + "intermediate.dense", 4 * dim, dim)
+        lin(l + "output.dense", dim, 4 * dim)
+        ln(l + "layernorm_before")
+        ln(l + "layernorm_after")
+    ln(a + "layernorm")
+    f = "afeat_extractor.freq_attn_agg."
+    s[f + "cls_token"] = ((1, 1, dim), 0.02, 0.0)
+    s[f + "self_attn.in_proj_weight"] = ((3 * dim, dim), 1.0 / math.sqrt(dim), 0.0)
+    s[f + "self_attn.in_proj_bias"] = ((3 * dim,), 0.02, 0.0)
+    lin(f + "self_attn.out_proj", dim, dim)
+    lin(f + "linear1", 4 * dim, dim)
+    lin(f + "linear2", dim, 4 * dim)
+    ln(f + "norm1")
+    ln(f + "norm2")
+    lin("vproj", dim, dim)
+    lin("aproj", dim, dim)
+    t = "transformer."
+    s[t + "OFF_tok"] = ((1, 1, dim), 1.0, 0.0)
+    s[t + "MOD_tok"] = ((1, 1, dim), 1.0, 0.0)
+    ln(t + "vis_in_lnorm")
+    ln(t + "aud_in_lnorm")
+    s[t + "pos_emb_cfg.pos_emb"] = ((1, n_pos, dim), 1.0, 0.0)
+    for i in range(heads_depth):
+        b = f"{t}blocks.{i}."
+        ln(b + "ln1")
+        ln(b + "ln2")
+        for n in ("key", "query", "value", "proj"):
+            lin(b + "attn." + n, dim, dim)
+        lin(b + "mlp.0", 4 * dim, dim)
+        lin(b + "mlp.2", dim, 4 * dim)
+    ln(t + "ln_f")
+    lin(t + "off_head", n_off, dim)
+    return s
+
+
 # ----------------------------------------------------------------------------- SigLIP2 / CLAP (transformers)
 @torch.inference_mode()
 def encode_video_with_siglip2(model, frames: Tensor, batch_size: int = 16) -> Tensor:

@@ -135,6 +135,10 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_op_resize_aa_u8": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_void_p, C.c_void_p]),
+    "foley_op_resample_sinc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p]),
+    "foley_op_logmel": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_int, C.c_void_p, C.c_void_p]),
     "foley_op_qkv_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -499,7 +503,7 @@ def op_gemm(A, W, bias=None, *, M=None, epilogue=EPI_STORE_F32, out0=None, out1=
 
 
 def op_attention(q, k, v, outA, outB, split: int, kv_bdiv: int = 1):
-    """fp32 q/k/v [B,H,S,hd], or bf16 / fp16 q/k [B,H,S,hd] with v transposed [B,H,hd,pitch]; hd = 128 or 64."""
+    """fp32 q/k/v [B,H,S,hd], or bf16 / fp16 q/k [B,H,S,hd] with v transposed [B,H,hd,pitch]; hd = 128, 96 or 64."""
     lib = load_library()
     Bq, H, Sq, hd = q.shape
     Skv = k.shape[2]
@@ -572,6 +576,39 @@ def op_resize_aa_u8(x: torch.Tensor, axis: int, len_out: int, xmin: torch.Tensor
         _check(lib, lib.foley_op_resize_aa_u8(_ptr(x), outer, len_in, inner, len_out, _ptr(xmin), _ptr(xsize), _ptr(weights),
                                               weights.shape[1], precision, _ptr(out), _stream()), "foley_op_resize_aa_u8")
     return out
+
+
+def op_resample_sinc(x: torch.Tensor, orig: int, new: int, taps: torch.Tensor, width: int) -> torch.Tensor:
+    """x [B, N] fp32 -> [B, ceil(N * new / orig)] fp32 (foley_op_resample_sinc; orig / new reduced by their gcd, taps [new, ntaps]
+    fp32 on the device from host/sync_score.py::sinc_resample_taps)."""
+    lib = load_library()
+    if x.dim() != 2 or x.dtype != torch.float32 or taps.dtype != torch.float32 or taps.dim() != 2 or taps.shape[0] != new:
+        raise FoleyRuntimeError("op_resample_sinc: x [B, N] fp32, taps [new, ntaps] fp32")
+    B, N = x.shape
+    n_out = -(-N * new // orig)
+    out = torch.empty(B, n_out, device=x.device, dtype=torch.float32)
+    _check(lib, lib.foley_op_resample_sinc(_ptr(x), B, N, orig, new, _ptr(taps), taps.shape[1], width, _ptr(out), n_out, _stream()),
+           "foley_op_resample_sinc")
+    return out
+
+
+def op_logmel(w16: torch.Tensor, basis: torch.Tensor, mel_lo: torch.Tensor, mel_len: torch.Tensor, mel_w: torch.Tensor,
+              out_dtype: torch.dtype = torch.float32, with_mel: bool = False):
+    """16 kHz waveform [B, N16] fp32 -> AST patch matrix [B*S*72, 256] in out_dtype (foley_op_logmel), S = (N16 - 10240) // 5120 + 1;
+    with_mel: also the normalised log-mel [B*S, 128, 66] fp32.  Tables from host/sync_score.py::logmel_tables."""
+    lib = load_library()
+    if w16.dim() != 2 or w16.dtype != torch.float32 or w16.shape[1] < 10240:
+        raise FoleyRuntimeError("op_logmel: w16 [B, N16 >= 10240] fp32")
+    if basis.numel() != 2 * 400 * 544 or mel_lo.numel() != 128 or mel_len.numel() != 128 or mel_w.dim() != 2 or mel_w.shape[0] != 128 or \
+            mel_lo.dtype != torch.int32 or mel_len.dtype != torch.int32 or mel_w.dtype != torch.float32 or basis.dtype != torch.float32:
+        raise FoleyRuntimeError("op_logmel: basis [2, 400, 544] fp32, int32 mel_lo / mel_len [128], mel_w [128, pitch] fp32")
+    B, N16 = w16.shape
+    S = (N16 - 10240) // 5120 + 1
+    patches = torch.empty(B * S * 72, 256, device=w16.device, dtype=out_dtype)
+    mel = torch.empty(B * S, 128, 66, device=w16.device, dtype=torch.float32) if with_mel else None
+    _check(lib, lib.foley_op_logmel(_ptr(w16), B, N16, _ptr(basis), _ptr(mel_lo), _ptr(mel_len), _ptr(mel_w), mel_w.shape[1],
+                                    _ptr(patches), dt_of(patches), _ptr(mel) if with_mel else None, _stream()), "foley_op_logmel")
+    return (patches, mel) if with_mel else patches
 
 
 def op_ln_mod(x, eps, shift: Optional[RowBcastC], scale: Optional[RowBcastC], out):

@@ -228,3 +228,16 @@ def synth_conditioning(cfg: DiTConfig, duration_s: float, *, t2a: bool, sd=None,
         c["clip"] = synth_tensor("cond.clip", (1, lv, cfg.clip_dim), 1.0, device=device, seed=seed + 1)
         c["sync"] = synth_tensor("cond.sync", (1, ls, cfg.sync_dim), 1.0, device=device, seed=seed + 1)
     return c
+
+
+def synth_click_audio(clips: int, n: int, sample_rate: int, seed: int = 0) -> torch.Tensor:
+    """A deterministic test waveform [clips, n] fp32: a click train (a short decaying 1 kHz burst every 0.25 s, phase shifted per
+    clip) over hash noise at -26 dB - broadband onsets for the sync scorer's golden and tests."""
+    t = torch.arange(n, dtype=torch.float64) / sample_rate
+    out = torch.empty(clips, n, dtype=torch.float32)
+    for c in range(clips):
+        ph = (t - 0.037 * (c + 1)) % 0.25
+        click = torch.exp(-ph * 60.0) * torch.sin(2 * math.pi * 1000.0 * ph) * (ph < 0.05)
+        noise = synth_tensor(f"click_audio.{c}", (n,), 0.05, seed=seed).to(torch.float64)
+        out[c] = (0.5 * click + noise).to(torch.float32)
+    return out

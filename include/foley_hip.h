@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FOLEY_ABI_VERSION 12   /* 12: foley_op_qkv_regroup.n_rows / foley_op_attention_scatter.out_nrows (the caller-supplied row tables are range-checked on the device: source rows clamped, output rows outside the buffer dropped); 11: foley_op_resize_aa_u8 (the frames' antialiased uint8 resize, bit for bit), foley_op_attention_scatter, foley_rowbcast.periodic_cfgs; 10: foley_op_qkv_regroup (token regrouping of the conditioning encoders' attention); 9: foley_bcast_local (single-process grouped broadcast of the arenas); 8: foley_qkv_split_desc.attn_* (cross attention in the epilogue of its q projection), foley_abort / FOLEY_ERR_ABORTED; 7: FOLEY_DT_F16 as a compute dtype (foley_config.compute_dtype, op descriptors); 6: foley_rowbcast.Ls (mode 2: nearest-exact up-sampled operand); 5: reference-keyed loading (foley_weights_*, foley_load_tensor, foley_bcast_weights); 4: fp8 weight storage (dtype codes 3/4, foley_gemm_desc.ldw/.wfmt); 3: foley_profile_forward; 2: foley_gemm_desc gained partials / qkv / rstride; foley_op_ln_mod_pending, foley_dac_encode */
+#define FOLEY_ABI_VERSION 12   /* 12 (additions that leave every existing entry as it was, so the version stays): foley_op_resample_sinc, foley_op_logmel, head_dim 96 in foley_op_attention_hd (the sync scorer); 12: foley_op_qkv_regroup.n_rows / foley_op_attention_scatter.out_nrows (the caller-supplied row tables are range-checked on the device: source rows clamped, output rows outside the buffer dropped); 11: foley_op_resize_aa_u8 (the frames' antialiased uint8 resize, bit for bit), foley_op_attention_scatter, foley_rowbcast.periodic_cfgs; 10: foley_op_qkv_regroup (token regrouping of the conditioning encoders' attention); 9: foley_bcast_local (single-process grouped broadcast of the arenas); 8: foley_qkv_split_desc.attn_* (cross attention in the epilogue of its q projection), foley_abort / FOLEY_ERR_ABORTED; 7: FOLEY_DT_F16 as a compute dtype (foley_config.compute_dtype, op descriptors); 6: foley_rowbcast.Ls (mode 2: nearest-exact up-sampled operand); 5: reference-keyed loading (foley_weights_*, foley_load_tensor, foley_bcast_weights); 4: fp8 weight storage (dtype codes 3/4, foley_gemm_desc.ldw/.wfmt); 3: foley_profile_forward; 2: foley_gemm_desc gained partials / qkv / rstride; foley_op_ln_mod_pending, foley_dac_encode */
 
 enum foley_dtype {
   FOLEY_DT_F32 = 0, FOLEY_DT_BF16 = 1, FOLEY_DT_I32 = 2,
@@ -259,8 +259,9 @@ int foley_op_gemm(const foley_gemm_desc* d, void* stream);
 int foley_op_attention(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq, int H,
                        int Sq, int Skv, int kv_bdiv, void* outA, void* outB, int split, int out_dtype,
                        void* stream);
-/* the same with head_dim 128 or 64 (the ViT-B conditioning encoders, feature_utils.py:63-108): fp32 operands, or 16-bit
- * operands through the LDS-staged 128-query kernel (v transposed [B,H,head_dim,vt_pitch]) */
+/* the same with head_dim 128, 64 (the ViT-B conditioning encoders, feature_utils.py:63-108) or 96 (the Synchformer sync head,
+ * models/synchformer/synchformer.py:115-187: 8 heads x 96, scale 1/sqrt(96)): fp32 operands, or 16-bit operands through the
+ * LDS-staged 128-query kernel (v transposed [B,H,head_dim,vt_pitch]) */
 int foley_op_attention_hd(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq, int H,
                           int Sq, int Skv, int kv_bdiv, void* outA, void* outB, int split, int out_dtype,
                           int head_dim, void* stream);
@@ -292,6 +293,24 @@ int foley_op_qkv_regroup(const void* qkv, int n_rows, int dtype, int H, const in
  * 2*max(scale, 1), normalised, rounded half away from zero at the largest precision whose biggest weight fits int16). */
 int foley_op_resize_aa_u8(const uint8_t* in, long outer, int len_in, long inner, int len_out, const int32_t* xmin,
                           const int32_t* xsize, const int16_t* weights, int kmax, int precision, uint8_t* out, void* stream);
+/* Rational polyphase windowed-sinc resampling (torchaudio.functional.resample with orig / new reduced by their gcd): x [B, N]
+ * fp32 -> out [B, Nout] fp32, out[b, j*new_rate + p] = sum_{t < ntaps} x[b, j*orig + t - width] * taps[p*ntaps + t] (x is zero
+ * outside [0, N)), Nout = ceil(N * new_rate / orig) for torchaudio's length.  taps [new_rate, ntaps] fp32 on the device, built by
+ * the caller (host/sync_score.py::sinc_resample_taps: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; 48 kHz -> 16 kHz is
+ * orig 3, new_rate 1, width 19, 41 taps).  Used by the sync scorer ahead of foley_op_logmel. */
+int foley_op_resample_sinc(const float* x, int B, int N, int orig, int new_rate, const float* taps, int ntaps, int width,
+                           float* out, int Nout, void* stream);
+/* The fused log-mel front end of the Synchformer audio branch (encode_audio_with_sync, models/synchformer/synchformer.py:294-317):
+ * w16 [B, N16] fp32 at 16 kHz -> S = (N16 - 10240) / 5120 + 1 segments per clip, each torch.stft(n_fft 1024, hop 160, win 400
+ * periodic Hann, center, reflect) -> |X|^2 -> 128 HTK mel triangles (torchaudio MelSpectrogram defaults, norm None) -> log(x + 1e-6)
+ * -> time axis padded 65 -> 66 with 0 -> (x + 4.2677393) / (2 * 4.5689974), written as the im2col matrix of the AST patch
+ * embedding: patches [B*S*72, 256] in out_dtype (f32 / bf16 / f16), row (b*S + s)*72 + fi*6 + ti, column kf*16 + kt = spectrogram
+ * (mel 10*fi + kf, frame 10*ti + kt) - one GEMM with the Conv2d(1, 768, 16, stride 10) weight [768, 256] is the patch embedding.
+ * Tables (device, fp32 / int32, built by host/sync_score.py): basis [2][400][544] = Hann(m) * cos / sin(2 pi k (m + 312) / 1024),
+ * bins k >= 513 zero; mel c = sum_{k < mel_len[c]} |X|^2[mel_lo[c] + k] * mel_w[c*mel_wp + k].  mel_out (nullable): the
+ * normalised spectrogram [B*S, 128, 66] fp32 as well (its rows 126 and 127 reach no patch). */
+int foley_op_logmel(const float* w16, int B, int N16, const float* basis, const int32_t* mel_lo, const int32_t* mel_len,
+                    const float* mel_w, int mel_wp, void* patches, int out_dtype, float* mel_out, void* stream);
 int foley_op_ln_mod(const float* x, int M, int D, float eps, const foley_rowbcast* shift,
                     const foley_rowbcast* scale, void* out, int out_dtype, void* stream);
 /* LayerNorm (+ modulation) of a residual stream that first receives the pending update of a deferred
