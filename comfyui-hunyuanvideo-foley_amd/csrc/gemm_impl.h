@@ -534,6 +534,15 @@ int check_args(const GemmArgs& g) {
   return 0;
 }
 
+// Bytes the A / W operands span from their base pointers (A: every source row the virtual rows touch; W: N rows of ldw
+// elements, one byte each in fp8 storage), and whether both fit the 32-bit buffer offsets of the direct-to-LDS loops
+template <typename T>
+long gemm_a_bytes(const GemmArgs& q) { return (long)((q.M + q.segV - 1) / q.segV) * q.segS * q.lda * (long)sizeof(T); }
+template <typename T>
+long gemm_w_bytes(const GemmArgs& q) { return (long)q.N * q.ldw * (q.wfmt ? 1L : (long)sizeof(T)); }
+template <typename T>
+bool gemm_fits_buffer_range(const GemmArgs& q) { return gemm_a_bytes<T>(q) < 0x7fff0000L && gemm_w_bytes<T>(q) < 0x7fff0000L; }
+
 template <typename T>
 int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile, hipStream_t st, int* ksplit_used) {
   GemmArgs g = g_in;
@@ -651,12 +660,15 @@ int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile,
   // route at mid-size grids: at M = 3000 + 480 they sat on 128x128 tiles (fc2 113 us where the single-problem form of the same shape
   // takes 57 - 59 on 72 tiles x three K ranges)
   static const bool wide_pair_on = []() { const char* e = getenv("FOLEY_WIDE_PAIR"); return !(e && e[0] == '0'); }();   // A/B switch
+  // The 256x256 tiles range every load against 32-bit buffer extents and have no register-staged twin: operands past the 2 GiB
+  // buffer-offset range (the `extent` check below) keep the tiles that fall back, in the wide route and the short-K rule alike
+  const bool wide_fits = gemm_fits_buffer_range<T>(g) && (!g1 || gemm_fits_buffer_range<T>(g1s));
   // ... where their 128x128 tiles do not fit ONE round of 256 workgroups (M = 3000 + 480: 336).  Where they do (bs = 4, M = 2000 + 320:
   // 228 tiles, no K split, no slabs for the next LayerNorm to read) the 256x256 route with four K ranges LOSES 1.1 % of the loop.
   const long pair_b128 = !g1 ? 0 : (long)((g.M + 127) / 128) * ((g.N + 127) / 128) + (long)((g1s.M + 127) / 128) * ((g1s.N + 127) / 128);
   const bool pair_ok = !g1 || (wide_pair_on && mid_split && pair_b128 > 256 && !ws_conv3_ok && g1s.taps == 1 && g1s.segV >= g1s.M && g1s.rstride <= 1 && g1s.tap0 == 0 &&
                                g1s.tapC % 32 == 0 && g1s.M >= 1 && g1s.N >= 256);
-  if (tile_auto && sizeof(T) == 2 && pair_ok && (tile == 23 || tile == 19 || tile == 29 || mid_split)) {
+  if (tile_auto && sizeof(T) == 2 && pair_ok && wide_fits && (tile == 23 || tile == 19 || tile == 29 || mid_split)) {
     static const bool wide_on = []() { const char* e = getenv("FOLEY_WIDE"); return !(e && e[0] == '0'); }();
     const bool conv = tile == 23 || tile == 21 || (mid_split && ws_conv3_ok);
     const bool epi_ok = epi == EPI_STORE_F32 || epi == EPI_GATE_RES || epi == EPI_SILUGATE_T || (!conv && epi == EPI_GELU_T);
@@ -769,7 +781,7 @@ int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile,
   // and fp8 storage: 45 / 43 us against 27.5 / 26 us; a 192x128 round 23.7 us = 0.86).  The 256x256 tile is taken where that count
   // says it wins by more than 5 %: fc1 of the two-stream blocks at bs = 8 (M = 4000 + 640: 2 rounds against 4), q/k/v of the 30 s
   // clip (M = 3000: 216 / 252 tiles = ONE round against two of 256x128).  FOLEY_WIDE_SHORTK=0 keeps the 256x128 / 192x128 tiles.
-  if (tile_auto && sizeof(T) == 2 && (epi == EPI_GELU_T || epi == EPI_QKV_SPLIT) && (tile == 19 || tile == 29 || tile == 28)) {
+  if (tile_auto && sizeof(T) == 2 && wide_fits && (epi == EPI_GELU_T || epi == EPI_QKV_SPLIT) && (tile == 19 || tile == 29 || tile == 28)) {
     static const bool on = []() { const char* e = getenv("FOLEY_WIDE_SHORTK"); return !(e && e[0] == '0'); }();
     auto plain = [&](const GemmArgs& q) {
       return q.taps == 1 && q.segV >= q.M && q.rstride <= 1 && q.tap0 == 0 && q.tapC % 32 == 0 && q.K >= 1024 && q.K < 2048 &&
@@ -821,11 +833,9 @@ int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile,
   {
     // the direct-to-LDS loop addresses its operands through 32-bit buffer offsets
     auto extent = [&](GemmArgs& q) {
-      const long rows_src = (long)((q.M + q.segV - 1) / q.segV) * q.segS;
-      const long ab = rows_src * q.lda * (long)sizeof(T), wb = (long)q.N * q.ldw * (q.wfmt ? 1L : (long)sizeof(T));
-      if (ab >= 0x7fff0000L || wb >= 0x7fff0000L) return false;
-      q.a_bytes = (unsigned)ab;
-      q.w_bytes = (unsigned)wb;
+      if (!gemm_fits_buffer_range<T>(q)) return false;
+      q.a_bytes = (unsigned)gemm_a_bytes<T>(q);
+      q.w_bytes = (unsigned)gemm_w_bytes<T>(q);
       return true;
     };
     bool ok = extent(g);

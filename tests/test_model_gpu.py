@@ -115,6 +115,45 @@ def test_long_clip_matches_oracle(tiny, dev, precision, tol):
     assert rel_err(lat, ref) < tol
 
 
+@pytest.mark.parametrize("bs,solver,steps", [(6, "euler", 100), (2, "kutta-4", 10)])
+def test_widget_extremes_match_oracle(tiny, dev, bs, solver, steps):
+    """The sampler node's extremes on the tiny model (fp32 parity mode, gate of test_long_clip_matches_oracle): 60 s clips
+    (S = 3480 joint tokens) with negative-prompt CFG 4.5 - six clips for 100 Euler steps (the top of both widgets: 100-entry
+    timestep / solver tables, a 100-iteration graph) and two clips for 10 kutta-4 steps (the step widget's minimum, four model
+    calls per step).  The oracle runs on each clip's own noise.  Its cost at 100 steps (0.5 s per CFG pair per step on 16 CPUs)
+    bounds it to the first and the last clip of the six; the middle ones are held to the same run of each clip on its own
+    (batch of one), which the first and last clip tie to the oracle."""
+    sd, _dsd, model, _dac = tiny
+    dur, g = 60.0, 4.5
+    La = int(dur * 50)
+    cond = synth.synth_conditioning(C.TINY, dur, t2a=False, sd=sd)
+    noise = torch.randn(bs, 128, La, generator=torch.Generator().manual_seed(60))
+    vis = {"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}
+    txt = {"text_feat": cond["text"], "uncond_text_feat": cond["uncond_text"]}
+
+    def run(nz):
+        model.ctx.prepare(sampler.build_plan(model, vis, txt, La, g, steps, nz.shape[0], solver))
+        lat = nz.clone().to(dev).contiguous()
+        model.ctx.sample(lat, use_graph=True)
+        return lat.cpu()
+
+    lat = run(noise)
+    assert bool(torch.isfinite(lat).all())
+    oracle_clips = [0, bs - 1]
+    errs = {}
+    with torch.inference_mode():
+        ref = O.sample_latents(sd, C.TINY.heads, noise[oracle_clips], cond["text"], cond["uncond_text"], cond["clip"], cond["sync"],
+                               steps, g, solver)
+    for i, b in enumerate(oracle_clips):
+        errs[b] = rel_err(lat[b], ref[i])
+    for b in range(1, bs - 1):
+        errs[b] = rel_err(lat[b], run(noise[b:b + 1])[0])
+    record_parity("widget_extremes_tiny_%s_%d_steps_bs%d" % (solver, steps, bs), worst=max(errs.values()))
+    print("tiny 60 s x %d, %s %d steps: %s" % (bs, solver, steps, " ".join("%.2e" % e for e in errs.values())))
+    for b, e in errs.items():
+        assert e < 2e-4, (b, e)
+
+
 def test_sampler_noise_matches_reference_draw(tiny):
     """The CPU-generator draw (utils.py:114-121) must reproduce the committed golden noise."""
     g = golden("g7_sampler")
@@ -149,6 +188,45 @@ def test_dac_golden_full_width(dev):
     y3 = model.ctx.dac_decode(z3)
     for i in range(3):
         assert rel_err(y3[i:i + 1], model.ctx.dac_decode(z3[i:i + 1].contiguous())) < 1e-6
+
+
+DAC_WINDOW_MARGIN = 16      # latent frames: tests/test_dac_window_cpu.py shows that it covers the decoder's receptive field
+
+
+def test_dac_decode_60s_six_clips(dev):
+    """The full-width decoder at the node's maximum: latents [6, 128, 3000] -> [6, 1, 2 880 000].  The last stage's activations
+    (dacP / Q / R) are 6 x 2 880 000 x 64 fp32 = 4.4 GB: past 2^31 and 2^32 bytes.  (a) every clip equals its own decode, also at
+    its edges (no bleeding across clip boundaries); (b) latent windows against the oracle, each with a margin of DAC_WINDOW_MARGIN
+    frames cut off before comparing: the head of clip 0, both sides of the clip 2 / 3 boundary, an interior window of clip 4 and
+    the tail of clip 5 (activations past 4 GiB)."""
+    clips, T, hop, m, w = 6, 3000, C.DAC48K.hop, DAC_WINDOW_MARGIN, 16
+    dsd = synth.synth_dac_state_dict(C.DAC48K)
+    model = sampler.FoleyModel(C.TINY, synth.synth_dit_state_dict(C.TINY), torch.float32, dev, dac_cfg=C.DAC48K)
+    model.attach_dac(sampler.FoleyDAC(dsd, dev, C.DAC48K))
+    z = torch.randn(clips, 128, T, generator=torch.Generator().manual_seed(66))
+    y = model.ctx.dac_decode(z.to(dev).contiguous()).cpu()
+    assert y.shape == (clips, 1, T * hop) and bool(torch.isfinite(y).all())
+    edge = m * hop
+    for i in range(clips):                                                                        # (a)
+        yi = model.ctx.dac_decode(z[i:i + 1].to(dev).contiguous()).cpu()
+        assert rel_err(y[i], yi[0]) <= 1e-6, i
+        assert rel_err(y[i, :, :edge], yi[0, :, :edge]) <= 1e-6 and rel_err(y[i, :, -edge:], yi[0, :, -edge:]) <= 1e-6, i
+    del model
+    torch.cuda.empty_cache()
+    errs = {}
+    with torch.inference_mode():                                                                  # (b)
+        heads = O.dac_decode(dsd, torch.stack([z[0, :, :w + m], z[3, :, :w + m]]), C.DAC48K.rates, C.DAC48K.dilations)
+        tails = O.dac_decode(dsd, torch.stack([z[2, :, -(w + m):], z[5, :, -(w + m):]]), C.DAC48K.rates, C.DAC48K.dilations)
+        mid = O.dac_decode(dsd, z[4:5, :, 1500 - m:1500 + w + m].contiguous(), C.DAC48K.rates, C.DAC48K.dilations)
+    errs["clip0_head"] = rel_err(y[0, :, :w * hop], heads[0, :, :w * hop])
+    errs["clip3_head"] = rel_err(y[3, :, :w * hop], heads[1, :, :w * hop])
+    errs["clip2_tail"] = rel_err(y[2, :, -w * hop:], tails[0, :, -w * hop:])
+    errs["clip5_tail"] = rel_err(y[5, :, -w * hop:], tails[1, :, -w * hop:])
+    errs["clip4_mid"] = rel_err(y[4, :, 1500 * hop:(1500 + w) * hop], mid[0, :, m * hop:(m + w) * hop])
+    record_parity("dac_60s_x6_windows", worst=max(errs.values()))
+    print("DAC 60 s x 6 windows: %s" % " ".join("%s %.2e" % kv for kv in errs.items()))
+    for k, e in errs.items():
+        assert e < 2e-5, (k, e)
 
 
 def test_dac_encoder_golden(dev):
@@ -425,6 +503,38 @@ def test_c5_full_size_properties(dev):
     assert 1e-4 < d < 0.2                                                                # (3)
 
 
+def test_full_depth_at_node_maximum(dev):
+    """The node's maximum through its own sampler entry point: xxl at full depth, bf16, text-to-audio 60 s x 6 clips with CFG 4.5,
+    10 Euler steps, then the full-width DAC -> audio [6, 1, 2 880 000], every value finite.  Each clip is then generated again in a
+    run of its own (batch of one, same noise).  The two are not bit-identical - K-origin rotation applies at one clip only, and the
+    tile choice depends on M - so each clip is held to the batch-of-one waveform.  Measured on an MI355X: the engine runs this
+    configuration (no limit refuses it) and every clip lands at 1.55e-2 from its batch-of-one run; the gate 3e-2 is twice that and
+    stays below the bf16 mode's own distance from fp32 on a waveform (d0 = 4.5e-2, g18_c2_loop_bf16)."""
+    from foley_amd import nodes
+    cfg, dur, bs, steps, g = C.XXL, 60.0, 6, 10, 4.5
+    sd = synth.synth_dit_state_dict(cfg, device=dev)
+    cond = synth.synth_conditioning(cfg, dur, t2a=True, sd=sd, device=dev)
+    model = nodes.HunyuanModelLoader.pack_state_dict(sd, "bf16", "none", device=dev, cfg=cfg)
+    del sd
+    dac = sampler.FoleyDAC(synth.synth_dac_state_dict(C.DAC48K, device=dev), dev)
+    visual = {"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}
+    text = {"text_feat": cond["text"], "uncond_text_feat": cond["uncond_text"]}
+    La = int(dur * cfg.frame_rate)
+    noise = sampler.draw_noise(bs, cfg.latent_dim, La, model.dtype, torch.Generator("cpu").manual_seed(6060))
+    audio, sr = sampler.denoise_process_with_generator(visual, text, dur, model, dac, g, steps, bs, "euler", noise=noise)
+    assert sr == 48000 and audio.shape == (bs, 1, 2_880_000)
+    assert bool(torch.isfinite(audio).all())
+    audio = audio.cpu()
+    errs = {}
+    for b in range(bs):
+        solo, _ = sampler.denoise_process_with_generator(visual, text, dur, model, dac, g, steps, 1, "euler", noise=noise[b:b + 1])
+        errs[b] = rel_err(audio[b], solo[0])
+    record_parity("node_maximum_xxl_60s_x6_batch_vs_solo", worst=max(errs.values()))
+    print("xxl 60 s x 6, batch vs batch of one: %s" % " ".join("%.2e" % e for e in errs.values()))
+    for b, e in errs.items():
+        assert e < 3e-2, (b, e)
+
+
 def _pair_forward(model, cond, La, noise, it, steps, dev):
     """The [uncond ; cond] model call of loop iteration `it` (CFG 4.5, one clip) -> [2, 128, La] on the CPU."""
     visual = {"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}
@@ -625,18 +735,29 @@ def test_large_grid_tiles_against_the_oracle(dev, name, hidden, heads, dtype, fm
                 assert e < tol, (name, prec, fmt, dur, b, e)
 
 
-@pytest.mark.parametrize("dur,clips,fmt", [(8.0, 2, "none"), (12.0, 3, "none"), (3.7, 5, "none"), (20.0, 1, "none"), (1.0, 16, "none"),
-                                           (12.0, 3, "fp8_e4m3fn"), (20.0, 1, "fp8_e4m3fn")])
-def test_tile_rules_across_shapes(dev, dur, clips, fmt):
-    """The launcher's tile rules change with the grid (one- vs multi-round launches, two-problem launches on the 256x256 tiles, the
-    pair-counting head-split rule, K-origin rotation for single clips): one depth-1+1 full-width forward per shape BETWEEN the benchmarked
-    ones (M = 800 ... 3600 audio rows, ragged durations), bf16 and fp8 storage, against the fp32 oracle on the same rounded weights."""
+@pytest.fixture(scope="module")
+def xxl11_weights():
+    """Depth-1+1 full-width weights and their bf16 / fp8-rounded fp32 copies for the oracle, built once per storage format."""
     from foley_amd import nodes
     c = C.DiTConfig(name="xxl-1-1", depth_triple=1, depth_single=1, hidden=1536, heads=12)
     sd = synth.synth_dit_state_dict(c)
+    rounded = {}
+
+    def sdq(fmt):
+        if fmt not in rounded:
+            q = nodes.fp8_round_state_dict(nodes.round_params(sd, torch.bfloat16), fmt, autocast=True, param_dtype=torch.bfloat16) \
+                if fmt != "none" else nodes.round_params(sd, torch.bfloat16)
+            rounded[fmt] = {k: v.float() for k, v in q.items()}
+        return rounded[fmt]
+    return c, sd, sdq
+
+
+def _depth11_forward_vs_oracle(dev, weights, dur, clips, fmt, sel=None):
+    """One depth-1+1 full-width bf16 forward of `clips` clips under CFG (iteration 6 of 10), each selected clip's two CFG halves
+    against the fp32 oracle on the same rounded weights; returns the relative error per clip."""
+    from foley_amd import nodes
+    c, sd, sdq = weights
     model = nodes.HunyuanModelLoader.pack_state_dict(sd, "bf16", fmt, device=dev, cfg=c)
-    sdq = nodes.fp8_round_state_dict(nodes.round_params(sd, torch.bfloat16), fmt, autocast=True, param_dtype=torch.bfloat16) if fmt != "none" else nodes.round_params(sd, torch.bfloat16)
-    sdq = {k: v.float() for k, v in sdq.items()}
     La, Lv, Ls = C.lengths(dur, c)
     cond = synth.synth_conditioning(c, dur, t2a=False, sd=sd)
     x = torch.randn(clips, 128, La, generator=torch.Generator().manual_seed(43)).to(torch.bfloat16).float()
@@ -644,19 +765,45 @@ def test_tile_rules_across_shapes(dev, dur, clips, fmt):
     vis = {"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}
     txt = {"text_feat": cond["text"], "uncond_text_feat": cond["uncond_text"]}
     model.ctx.prepare(sampler.build_plan(model, vis, txt, La, 4.5, steps, clips, "euler"))
-    rows = model.ctx.dit_forward(x.to(dev).contiguous(), it).float().cpu()
+    rows = model.ctx.dit_forward(x.to(dev).contiguous(), it).float().cpu().view(2, clips, La, 128)
+    del model
     t_it = tables.model_timesteps(tables.sigma_grid(steps))[it]
     text77, unc77 = O.pad_or_trim_text(cond["text"]), O.pad_or_trim_text(cond["uncond_text"])
     e_clip = sd["empty_clip_feat"].view(1, 1, -1).expand(1, Lv, -1)
     e_sync = sd["empty_sync_feat"].view(1, 1, -1).expand(1, Ls, -1)
-    b = clips - 1
+    errs = {}
     with torch.inference_mode():
-        ref = O.dit_forward(sdq, c.heads, torch.cat([x[b:b + 1], x[b:b + 1]]), t_it.expand(2), torch.cat([unc77, text77]),
-                            torch.cat([e_clip, cond["clip"]]), torch.cat([e_sync, cond["sync"]]))
-    got = torch.stack([rows.view(2, clips, La, 128)[0, b], rows.view(2, clips, La, 128)[1, b]]).transpose(1, 2)
-    e = rel_err(got, ref)
-    print("%gs x %d clips %s: %.2e" % (dur, clips, fmt, e))
-    assert e < (5e-3 if fmt == "none" else 8e-3), (dur, clips, fmt, e)
+        for b in (range(clips) if sel is None else sel):
+            ref = O.dit_forward(sdq(fmt), c.heads, torch.cat([x[b:b + 1], x[b:b + 1]]), t_it.expand(2), torch.cat([unc77, text77]),
+                                torch.cat([e_clip, cond["clip"]]), torch.cat([e_sync, cond["sync"]]))
+            errs[b] = rel_err(torch.stack([rows[0, b], rows[1, b]]).transpose(1, 2), ref)
+    return errs
+
+
+@pytest.mark.parametrize("dur,clips,fmt", [(8.0, 2, "none"), (12.0, 3, "none"), (3.7, 5, "none"), (20.0, 1, "none"), (1.0, 16, "none"),
+                                           (12.0, 3, "fp8_e4m3fn"), (20.0, 1, "fp8_e4m3fn")])
+def test_tile_rules_across_shapes(dev, xxl11_weights, dur, clips, fmt):
+    """The launcher's tile rules change with the grid (one- vs multi-round launches, two-problem launches on the 256x256 tiles, the
+    pair-counting head-split rule, K-origin rotation for single clips): one depth-1+1 full-width forward per shape BETWEEN the benchmarked
+    ones (M = 800 ... 3600 audio rows, ragged durations), bf16 and fp8 storage, against the fp32 oracle on the same rounded weights -
+    every clip of the batch (a clip-offset error in a two-problem launch, a K-split slab or a head-split epilogue shows in one clip)."""
+    errs = _depth11_forward_vs_oracle(dev, xxl11_weights, dur, clips, fmt)
+    print("%gs x %d clips %s: %s" % (dur, clips, fmt, " ".join("%.2e" % e for e in errs.values())))
+    for b, e in errs.items():
+        assert e < (5e-3 if fmt == "none" else 8e-3), (dur, clips, fmt, b, e)
+
+
+@pytest.mark.parametrize("dur,clips,fmt", [(60.0, 1, "none"), (59.9, 2, "none"), (45.0, 3, "none"), (30.0, 6, "none"), (60.0, 6, "none"),
+                                           (60.0, 1, "fp8_e4m3fn"), (60.0, 6, "fp8_e4m3fn")])
+def test_forward_at_widget_extremes(dev, xxl11_weights, dur, clips, fmt):
+    """The node's widget extremes (duration up to 60 s, batch up to 6): S = La + Lv = 3480 joint tokens, an odd Lv = 479 at 59.9 s,
+    up to 36 000 audio rows per forward.  Depth-1+1 full width, bf16 / fp8 storage, every clip and both CFG halves against the fp32
+    oracle (gates of test_tile_rules_across_shapes)."""
+    errs = _depth11_forward_vs_oracle(dev, xxl11_weights, dur, clips, fmt)
+    record_parity("widget_extremes_%gs_x%d_%s" % (dur, clips, fmt), worst=max(errs.values()))
+    print("%gs x %d clips %s: %s" % (dur, clips, fmt, " ".join("%.2e" % e for e in errs.values())))
+    for b, e in errs.items():
+        assert e < (5e-3 if fmt == "none" else 8e-3), (dur, clips, fmt, b, e)
 
 
 def test_xl_dimensions_forward(dev):

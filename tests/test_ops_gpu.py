@@ -493,6 +493,141 @@ def test_exact_gelu_fast_form_error_bound(dev, dtype):
     assert bool(main.sum() > M // 2) and bool((err[main] <= 0.56 * ulp[main]).all()), float((err[main] / ulp[main]).max())
 
 
+def _sdpa_rows(q, k, v, kv_bdiv):
+    """O.sdpa one query batch at a time ([B, Sq, H*D]): a 60 s score matrix of 12 heads is 0.6 GB per batch entry."""
+    B, H, Sq, D = q.shape
+    out = torch.empty(B, Sq, H * D)
+    for b in range(B):
+        out[b] = O.sdpa(q[b:b + 1], k[b // kv_bdiv:b // kv_bdiv + 1], v[b // kv_bdiv:b // kv_bdiv + 1]).transpose(1, 2).reshape(Sq, H * D)
+    return out
+
+
+@pytest.mark.parametrize("B,H,Sq,Skv,split,kv_bdiv", [
+    (2, 12, 2610, 2610, 360, 1),    # 45 s CFG pair: 504 workgroups of 128 queries, 4 x 504 <= 2048 -> long kernel, 82 key tiles
+    (1, 12, 3474, 3474, 479, 1),    # 59.9 s (odd Lv), one CFG half: 19 x 12 = 228 workgroups of 192 queries -> pair kernel, 109 key tiles
+    (2, 12, 3480, 3480, 480, 1),    # 60 s CFG pair: 672 workgroups -> wide kernel, 109 key tiles, 24 valid keys in the last
+    (12, 12, 3480, 3480, 480, 1),   # 60 s x 6 clips under CFG: 4032 workgroups -> wide kernel, 109 key tiles
+    (12, 12, 3000, 77, 0, 6),       # 60 s x 6 clips, cross attention on the text keys of each CFG half -> wide kernel, 3 key tiles
+])
+@pytest.mark.parametrize("half", [torch.bfloat16, torch.float16])
+def test_attention_long_clip_shapes(dev, B, H, Sq, Skv, split, kv_bdiv, half):
+    """The joint sequences of the node's long clips (45 / 59.9 / 60 s, up to six clips), past the 30 s shapes of
+    test_attention_bf16: 82 - 109 key tiles of online-softmax rescaling, ragged last tiles, V^T pitch padded with finite garbage."""
+    q, k, v = _rand((B, H, Sq, 128), 80), _rand((B // kv_bdiv, H, Skv, 128), 81), _rand((B // kv_bdiv, H, Skv, 128), 82)
+    qb, kb, vb = (t.to(half) for t in (q, k, v))
+    ref = _sdpa_rows(qb.float(), kb.float(), vb.float(), kv_bdiv)
+    pitch = (Skv + 31) // 32 * 32
+    vt = torch.full((B // kv_bdiv, H, 128, pitch), 7.0, dtype=half)
+    vt[..., :Skv] = vb.transpose(2, 3)
+    oa = torch.full((B, max(split, 1), H * 128), float("nan"), device=dev, dtype=half)
+    ob = torch.full((B, Sq - split, H * 128), float("nan"), device=dev, dtype=half)
+    rt.op_attention(qb.to(dev), kb.to(dev), vt.to(dev), oa, ob, split, kv_bdiv)
+    tol = 1e-2 if half == torch.bfloat16 else 2e-3
+    for b in range(B):      # every batch entry on its own: a misplaced batch offset must not hide in the norm of the others
+        if split:
+            assert rel_err(oa[b].float(), ref[b, :split]) < tol, b
+        assert rel_err(ob[b].float(), ref[b, split:]) < tol, b
+
+
+def test_attention_fp32_60s(dev):
+    """fp32 (parity mode) attention at the 60 s joint length: S = 3480, 109 key tiles of 32, the audio / visual split at 480."""
+    B, H, S, split = 2, 12, 3480, 480
+    q, k, v = _rand((B, H, S, 128), 83), _rand((B, H, S, 128), 84), _rand((B, H, S, 128), 85)
+    ref = _sdpa_rows(q, k, v, 1)
+    oa = torch.full((B, split, H * 128), float("nan"), device=dev)
+    ob = torch.full((B, S - split, H * 128), float("nan"), device=dev)
+    rt.op_attention(q.to(dev), k.to(dev), v.to(dev), oa, ob, split, 1)
+    for b in range(B):
+        assert rel_err(oa[b], ref[b, :split]) < 3e-6 and rel_err(ob[b], ref[b, split:]) < 3e-6, b
+
+
+# ----------------------------------------------------------------------------- GEMM operands past the 2 GiB buffer range
+def _sample_rows(M):
+    """A few hundred rows spread over M, always including the first and the last 16."""
+    idx = torch.cat((torch.arange(16), torch.randint(16, M - 16, (224,), generator=_g(90)), torch.arange(M - 16, M)))
+    return idx.unique()
+
+
+@pytest.mark.parametrize("tile", [0, 5, 6, 8])
+def test_gemm_fp32_past_2gib(dev, tile):
+    """fp32, K = 64, M = 8.6 M rows: A spans 2.2 GB (last rows past 2^31 bytes), the output 4.4 GB (past 2^32).  The direct-to-LDS
+    tiles address their operands through 32-bit buffer offsets: the launcher must move them (and the automatic choice) onto the
+    register-staged twins, and the result must match fp64 on sampled rows."""
+    M, N, K = 8_600_000, 128, 64
+    assert M * K * 4 > 2 ** 31 and M * N * 4 > 2 ** 32
+    gd = torch.Generator(device=dev).manual_seed(91)
+    A = torch.randn(M, K, device=dev, generator=gd)
+    W, b = _rand((N, K), 92, 1 / math.sqrt(K)), _rand((N,), 93, 0.1)
+    out = torch.full((M, N), float("nan"), device=dev)
+    rt.op_gemm(A, W.to(dev), b.to(dev), out0=out, tile=tile)
+    idx = _sample_rows(M)
+    ref = A[idx.to(dev)].double().cpu() @ W.double().t() + b.double()
+    e = rel_err(out[idx.to(dev)], ref)
+    del A, out
+    assert e <= 1e-6, e
+
+
+@pytest.fixture(scope="module")
+def big_bf16_a(dev):
+    """bf16 activations [720 000, 1536]: 2.2 GB, every row past 699 051 starts beyond 2^31 bytes."""
+    gd = torch.Generator(device=dev).manual_seed(94)
+    A = torch.randn(720_000, 1536, device=dev, generator=gd, dtype=torch.bfloat16)
+    assert A.numel() * 2 > 2 ** 31
+    yield A
+    del A
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("epi", ["plain", "gelu"])
+def test_gemm_bf16_past_2gib(dev, big_bf16_a, epi):
+    """bf16 at the fc1 shape (K = 1536, N = 6144) with an A operand past 2 GiB, automatic tile.  The GELU epilogue takes the short-K
+    rule towards the 256x256 tile, which has no register-staged twin: the launcher must pick a tile that falls back instead of
+    refusing a legal call.  The plain layer's fp32 output spans 17.7 GB, the GELU output 8.8 GB (both past 2^32 bytes)."""
+    A = big_bf16_a
+    M, K, N = A.shape[0], A.shape[1], 6144
+    W, b = _rand((N, K), 95, 1 / math.sqrt(K)).to(torch.bfloat16), _rand((N,), 96, 0.1)
+    if epi == "plain":
+        out = torch.full((M, N), float("nan"), device=dev)
+        rt.op_gemm(A, W.to(dev), b.to(dev), out0=out)
+    else:
+        out = torch.full((M, N), float("nan"), device=dev, dtype=torch.bfloat16)
+        rt.op_gemm(A, W.to(dev), b.to(dev), out0=out, epilogue=rt.EPI_GELU_T)
+    idx = _sample_rows(M)
+    y = A[idx.to(dev)].double().cpu() @ W.double().t() + b.double()
+    ref = y if epi == "plain" else F.gelu(y, approximate="tanh")
+    got = out[idx.to(dev)].float()
+    del out
+    torch.cuda.empty_cache()
+    assert rel_err(got, ref) < BF16_TOL
+    assert rel_err(got[-16:], ref[-16:]) < BF16_TOL      # the rows past 2^31 bytes of A on their own
+
+
+@pytest.mark.parametrize("case,tile", [("conv3", 21), ("conv3", 22), ("conv3", 23), ("conv3", 24), ("conv3", 31), ("plain", 32),
+                                       ("fp8", 0), ("fp8", 15)])
+def test_gemm_past_2gib_refused(dev, big_bf16_a, case, tile):
+    """Tiles without a register-staged twin - the tap-fused conv3 tiles 21 - 24, the 256x256 tiles 31 / 32 and every fp8-weight
+    tile - cannot address an operand past 2 GiB: requested explicitly (or, for fp8 weights, at all) the launcher must refuse with its
+    message and leave the output alone, never return a wrong answer."""
+    A = big_bf16_a
+    M, K, N = A.shape[0], A.shape[1], 256
+    W = _rand((N, K), 97, 1 / math.sqrt(K))
+    out = torch.full((M, N), float("nan"), device=dev)
+    if case == "conv3":       # channels-last k = 3 conv over two clips of 360 000 rows
+        Wc = packers.conv_to_gemm(_rand((N, K, 3), 98, 1 / math.sqrt(3 * K))).to(dev, torch.bfloat16)
+        msg = "256x256 tiles" if tile == 31 else "conv3 operands exceed"
+        with pytest.raises(rt.FoleyRuntimeError, match=msg):
+            rt.op_gemm(A, Wc, None, out0=out, conv=(M // 2, K, 3, 1), tile=tile)
+    elif case == "plain":
+        with pytest.raises(rt.FoleyRuntimeError, match="256x256 tiles"):
+            rt.op_gemm(A, W.to(dev, torch.bfloat16), None, out0=out, tile=tile)
+    else:
+        with pytest.raises(rt.FoleyRuntimeError, match="fp8-weight operands exceed"):
+            rt.op_gemm(A, W.to(torch.float8_e4m3fn).to(dev), None, out0=out, tile=tile)
+    torch.cuda.synchronize()
+    idx = _sample_rows(M).to(dev)
+    assert bool(torch.isnan(out[idx]).all())
+
+
 def test_attention_bf16_spiky(dev):
     q, k, v = _rand((1, 1, 64, 128), 33), _rand((1, 1, 200, 128), 34), _rand((1, 1, 200, 128), 35)
     k[0, 0, 150] = q[0, 0, 7] * 5.0
@@ -561,7 +696,7 @@ def test_ln_mod(dev, out_dtype, D, eps):
     assert rel_err(out.float(), ref) < tol
 
 
-@pytest.mark.parametrize("dur", [1.0, 1.1, 2.7, 3.3, 5.0, 6.6, 13.8, 30.0])
+@pytest.mark.parametrize("dur", [1.0, 1.1, 2.7, 3.3, 5.0, 6.6, 13.8, 30.0, 45.0, 59.9, 60.0])
 def test_rowbcast_nearest_exact_mode(dev, dur):
     """RowBcast mode 2: the operand keeps the Ls sync-token rows and every audio frame l addresses row
     nearest_exact(l) in the kernel (float32, as F.interpolate(mode='nearest-exact'), hifi_foley.py:759-762).
