@@ -1400,9 +1400,10 @@ static RowBcast to_rb(const foley_rowbcast* r) {
   return b;
 }
 
-extern "C" int foley_op_gemm(const foley_gemm_desc* d, void* stream) {
+// descriptor -> GemmArgs (foley_op_gemm and the test-only pair entry below)
+static int gemm_args_of(const foley_gemm_desc* d, GemmArgs& g) {
   if (!d) return FAIL(FOLEY_ERR_INVALID, "null descriptor");
-  GemmArgs g{};
+  g = GemmArgs{};
   g.A = d->A; g.W = d->W; g.bias = d->bias; g.M = d->M; g.N = d->N; g.K = d->K; g.lda = d->lda;
   g.segV = d->segV; g.segS = d->segS; g.taps = d->taps; g.tapC = d->tapC; g.dil = d->dil; g.tap0 = d->tap0;
   g.out0 = d->out0; g.out1 = d->out1; g.osegV = d->osegV; g.out_seg = d->out_seg; g.out_row = d->out_row;
@@ -1433,9 +1434,32 @@ extern "C" int foley_op_gemm(const foley_gemm_desc* d, void* stream) {
     a.attn_skv = q->attn_skv; a.attn_pitch = q->attn_pitch; a.attn_bdiv = q->attn_bdiv; a.attn_fused = q->attn_fused;
     if (q->attn_fused) *q->attn_fused = 0;
   }
+  return 0;
+}
+
+extern "C" int foley_op_gemm(const foley_gemm_desc* d, void* stream) {
+  GemmArgs g;
+  if (int rc = gemm_args_of(d, g)) return rc;
   int ks = 1;
   const int rc = launch_gemm(g, d->dtype, d->epilogue, d->tile, (hipStream_t)stream, &ks);
   if (d->ksplit_used) *d->ksplit_used = ks;
+  return rc;
+}
+
+// Test-only entries (not part of include/foley_hip.h; tests/test_pairs_gpu.py types them with ctypes): the two-problem launches
+// of run_forward's two-stream blocks at op level.  launch_gemm_pair picks its own tile and one K split for both problems (written
+// to d0->ksplit_used); both descriptors must name the same operand dtype and epilogue.
+extern "C" int foley_debug_gemm_pair(const foley_gemm_desc* d0, const foley_gemm_desc* d1, void* stream) {
+  if (!d0 || !d1) return FAIL(FOLEY_ERR_INVALID, "null descriptor");
+  if (d0->dtype != d1->dtype || d0->epilogue != d1->epilogue)
+    return FAIL(FOLEY_ERR_INVALID, "GEMM pair: the two problems must share the operand dtype and the epilogue");
+  if (d0->tile != 0 || d1->tile != 0) return FAIL(FOLEY_ERR_INVALID, "GEMM pair: the pair launcher picks its own tile (tile must be 0)");
+  GemmArgs g0, g1;
+  if (int rc = gemm_args_of(d0, g0)) return rc;
+  if (int rc = gemm_args_of(d1, g1)) return rc;
+  int ks = 1;
+  const int rc = launch_gemm_pair(g0, g1, d0->dtype, d0->epilogue, (hipStream_t)stream, &ks);
+  if (d0->ksplit_used) *d0->ksplit_used = ks;
   return rc;
 }
 
@@ -1499,6 +1523,28 @@ extern "C" int foley_op_ln_mod_pending2(float* x, int M, int D, float eps, const
   if (partial_dtype != 0 && partial_dtype != out_dtype) return FAIL(FOLEY_ERR_INVALID, "pending split-K: 16-bit slabs must have the output dtype");
   LnPending p{(const float*)partials, k, (long)M * D, bias, to_rb(gate), partial_dtype};
   return launch_ln_mod_pending(x, M, D, eps, to_rb(shift), to_rb(scale), out, out_dtype, p, (hipStream_t)stream);
+}
+
+// Test-only (see foley_debug_gemm_pair): launch_ln_mod_pair over two row sets, each with the arguments of foley_op_ln_mod_pending2;
+// a null `partials` means nothing is pending for that set
+extern "C" int foley_debug_ln_mod_pair(float* x0, int M0, const foley_rowbcast* shift0, const foley_rowbcast* scale0, void* out0,
+                                       const void* partials0, int partial_dtype0, int k0, const float* bias0, const foley_rowbcast* gate0,
+                                       float* x1, int M1, const foley_rowbcast* shift1, const foley_rowbcast* scale1, void* out1,
+                                       const void* partials1, int partial_dtype1, int k1, const float* bias1, const foley_rowbcast* gate1,
+                                       int D, float eps, int out_dtype, void* stream) {
+  LnArgs a[2] = {{x0, M0, to_rb(shift0), to_rb(scale0), out0, LnPending{}}, {x1, M1, to_rb(shift1), to_rb(scale1), out1, LnPending{}}};
+  const void* parts[2] = {partials0, partials1};
+  const int pdt[2] = {partial_dtype0, partial_dtype1}, ks[2] = {k0, k1};
+  const float* bias[2] = {bias0, bias1};
+  const foley_rowbcast* gate[2] = {gate0, gate1};
+  for (int i = 0; i < 2; ++i) {
+    if (a[i].M < 0) return FAIL(FOLEY_ERR_INVALID, "ln_mod pair: negative row count");
+    if (!parts[i]) continue;
+    if (ks[i] < 1 || !gate[i]) return FAIL(FOLEY_ERR_INVALID, "pending split-K: partials, k >= 1 and a gate are required");
+    if (pdt[i] != 0 && pdt[i] != out_dtype) return FAIL(FOLEY_ERR_INVALID, "pending split-K: 16-bit slabs must have the output dtype");
+    a[i].pend = LnPending{(const float*)parts[i], ks[i], (long)a[i].M * D, bias[i], to_rb(gate[i]), pdt[i]};
+  }
+  return launch_ln_mod_pair(a[0], a[1], D, eps, out_dtype, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_ln_mod_pending(float* x, int M, int D, float eps, const foley_rowbcast* shift,

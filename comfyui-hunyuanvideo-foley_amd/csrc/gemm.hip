@@ -9,6 +9,8 @@ int g_gemm_dbg_mode = 0;
 // run_forward); foley_prepare (its row-periodicity check compares bit patterns), batches (clips of a batch with equal noise stay
 // bit-identical) and the op-level entries do not.
 thread_local int g_gemm_krot_ok = 0;
+// tile, K split and k_rot of this thread's last dispatched GEMM (launch_typed, after every fallback): foley_debug_gemm_last
+thread_local int g_gemm_last[3] = {0, 0, 0};
 int g_gemm_pf_dist = 0;   // L2 prefetch distance of the wave-specialised mainloop (K-slices beyond the ring)
 
 int launch_gemm_typed_f32(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, hipStream_t st, int* ksplit_used);
@@ -40,4 +42,18 @@ extern "C" void foley_debug_gemm_prefetch(int dist) { g_gemm_pf_dist = dist < 0 
 extern "C" void foley_debug_gemm_timeline(void* p, int mode) {
   g_gemm_dbg = (long long*)p;
   g_gemm_dbg_mode = mode;
+}
+
+// Test-only hooks (tests/test_pairs_gpu.py; not part of include/foley_hip.h): opt the calling thread in to K-origin rotation as
+// run_forward does for single-clip forwards (returns the previous setting), and read back what the last launch of this thread ran.
+extern "C" int foley_debug_gemm_krot(int on) {
+  const int prev = g_gemm_krot_ok;
+  g_gemm_krot_ok = on ? 1 : 0;
+  return prev;
+}
+
+extern "C" void foley_debug_gemm_last(int* tile, int* ksplit, int* k_rot) {
+  if (tile) *tile = g_gemm_last[0];
+  if (ksplit) *ksplit = g_gemm_last[1];
+  if (k_rot) *k_rot = g_gemm_last[2];
 }

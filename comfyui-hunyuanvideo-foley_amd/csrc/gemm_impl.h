@@ -18,6 +18,7 @@ extern long long* g_gemm_dbg;
 extern int g_gemm_dbg_mode;
 extern int g_gemm_pf_dist;
 extern thread_local int g_gemm_krot_ok;
+extern thread_local int g_gemm_last[3];
 
 namespace {
 
@@ -900,6 +901,9 @@ int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile,
   if ((tile == 27 || tile == 26 || tile == 28) && (epi != EPI_QKV_SPLIT || g.wfmt)) return foley_set_err("GEMM: tile 27 (64x128) serves the fused head split with bf16 weights only", __FILE__, __LINE__);
   if ((g.ldw != g.K || (g1 && g1s.ldw != g1s.K)) && tile != 31 && tile != 32 && !(tile == 15 || tile == 19 || tile == 21 || tile == 22 || tile == 23 || tile == 24 || tile == 25 || tile == 26 || tile == 27 || tile == 28 || tile == 29))
     return foley_set_err("GEMM: padded weight rows (ldw != K) need a wave-specialised tile", __FILE__, __LINE__);
+  g_gemm_last[0] = tile;   // foley_debug_gemm_last (gemm.hip): the tile that is dispatched below
+  g_gemm_last[1] = g.ksplit;
+  g_gemm_last[2] = g.k_rot;
   if (tile == 31 || tile == 32) {   // 256x256 tiles on the BK = 32 mainloop (gemm_wide_impl.h)
     if (epi == EPI_QKV_SPLIT) {   // the fused cross attention exists on the 64-row tile only: the caller launches the attention
       if (g.qs.attn_fused) *g.qs.attn_fused = 0;

@@ -432,15 +432,22 @@ def rowbcast(t: Optional[torch.Tensor], mode: int = 0, rows_per_cfg: int = 1, L:
     return r
 
 
-def op_gemm(A, W, bias=None, *, M=None, epilogue=EPI_STORE_F32, out0=None, out1=None, ldc=None, conv=None,
-            convT=None, rb: Optional[RowBcastC] = None, res=None, alpha=None, alphaC=1, tile=0, ksplit=0,
-            partials=None, qkv: Optional["QkvSplitDescC"] = None, sconv=None, lda: Optional[int] = None,
-            ldw: Optional[int] = None, NK=None, gelu_erf: bool = False, vrows=None) -> int:
-    """Thin wrapper over foley_op_gemm.  conv=(seg, C, taps, dil) ; convT=(Tin, Cin, stride, Cout) ; vrows=(segV, segS) with M ;
+def op_gemm(A, W, bias=None, **kw) -> int:
+    """Thin wrapper over foley_op_gemm (arguments: gemm_desc).  Returns the K split the launcher used."""
+    lib = load_library()
+    d = gemm_desc(A, W, bias, **kw)
+    _check(lib, lib.foley_op_gemm(C.byref(d), _stream()), "foley_op_gemm")
+    return int(d._used.value)
+
+
+def gemm_desc(A, W, bias=None, *, M=None, epilogue=EPI_STORE_F32, out0=None, out1=None, ldc=None, conv=None,
+              convT=None, rb: Optional[RowBcastC] = None, res=None, alpha=None, alphaC=1, tile=0, ksplit=0,
+              partials=None, qkv: Optional["QkvSplitDescC"] = None, sconv=None, lda: Optional[int] = None,
+              ldw: Optional[int] = None, NK=None, gelu_erf: bool = False, vrows=None) -> GemmDescC:
+    """foley_gemm_desc of one GEMM.  conv=(seg, C, taps, dil) ; convT=(Tin, Cin, stride, Cout) ; vrows=(segV, segS) with M ;
     sconv=(Tin, Cin, stride): strided conv k=2*stride, pad ceil(stride/2) over clips of Tin rows.
     partials: fp32 [slabs, M, N] workspace for the deferred split-K of the gated-residual epilogue.
-    Returns the K split the launcher used."""
-    lib = load_library()
+    After the launch, d._used holds the K split the launcher used."""
     d = GemmDescC()
     N, K = NK if NK is not None else W.shape      # NK: logical shape when W / A are row-padded storage (lda / ldw)
     d.A, d.W, d.bias = _ptr(A), _ptr(W), _ptr(bias) if bias is not None else None
@@ -491,15 +498,14 @@ def op_gemm(A, W, bias=None, *, M=None, epilogue=EPI_STORE_F32, out0=None, out1=
     d.res = _ptr(res) if res is not None else None
     d.alpha = _ptr(alpha) if alpha is not None else None
     d.alphaC = alphaC
-    used = C.c_int32(1)
-    d.ksplit_used = C.pointer(used)
+    d._used = C.c_int32(1)
+    d.ksplit_used = C.pointer(d._used)
     if partials is not None:      # fp32 slabs, or slabs in the (16-bit) operand dtype
         d.partials, d.partial_slabs = _ptr(partials), partials.shape[0]
         d.partial_dtype = 0 if partials.dtype == torch.float32 else dt_of(partials)
     if qkv is not None:
         d.qkv = C.pointer(qkv)
-    _check(lib, lib.foley_op_gemm(C.byref(d), _stream()), "foley_op_gemm")
-    return int(used.value)
+    return d
 
 
 def op_attention(q, k, v, outA, outB, split: int, kv_bdiv: int = 1):

@@ -298,8 +298,11 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199: the
     batch only repeats the conditioning), so there is no collective: the noise of the WHOLE batch is drawn once
     from `generator` exactly like the single-GPU call does and sliced (`distributed.shard_range`), which makes the
-    result bit-identical to one GPU running the full batch whenever the shards use the same tile shapes - and
-    equal to bf16 / fp32 accuracy otherwise.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
+    result bit-identical to one GPU running the full batch whenever the shards use the same tile shapes and the same
+    summation order - and equal to bf16 / fp32 accuracy otherwise.  A shard of ONE clip never is bit-identical to that
+    clip inside a larger shard: single-clip forwards rotate the K origin of their small-grid GEMMs per M tile (K-origin
+    rotation, gemm.hip g_gemm_krot_ok), a different but deterministic summation order (tests/test_pairs_gpu.py pins how
+    far it moves a result).  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
     from .distributed import shard_range
     if not replicas:
         raise FoleyRuntimeError("no replicas")
