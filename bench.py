@@ -1,6 +1,6 @@
 """Headline benchmark: audio-seconds generated per wall-second for the Foley sampling path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--bs B] [--precision bf16|fp32] [--progress] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--bs B] [--precision bf16|fp32] [--progress] [--dump-outputs DIR] [--full]
 
 A "step" is ONE pass of the whole hot path over one batch of synthetic input, host to host: H2D of
 the CPU-generator noise, step-invariant precompute, the 50-iteration Euler/CFG loop over the xxl
@@ -13,7 +13,9 @@ Configurations (BASELINE.json `configs`):
   c4            V2A features, bs = 8 clips per GPU: with --gpus 8 this is BASELINE configs[3] (bs=64 over 8 GPUs)
   c5            fp8_e4m3fn weight storage, 30 s clip, negative-prompt CFG
 
-The default line (c2, bs=1/GPU at every N, so that the driver's per-N values are one scaling curve) also carries, as
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: nothing else.  Everything the
+headline value does not need is behind --full: the event-timed loop / DAC decode of one more pass, the per-kernel `roofline`,
+the CPU baseline and, on the default line (c2, bs=1/GPU at every N, so that the per-N values are one scaling curve),
 `extra`: bs8 (the bs=8/GPU half of the metric), c4 (V2A features, bs=8/GPU - at N=8 the C4 workload), progress (the
 per-iteration host callback path ComfyUI's progress bar takes) and, at N=1, c3 and c5 - three timed passes each (four for the bs=8 lines).
 
@@ -131,14 +133,14 @@ def physical_cores() -> int:
 
 def cpu_baseline(sd_gpu, dsd_gpu, cfg, cond, noise, duration, threads=16, full=False):
     """The CPU oracle (a port of the reference's fp32 CPU path) on this box's host cores, per BASELINE.md section 4, bounded to
-    ~35 s of CPU work in the default run:
+    ~35 s of CPU work in a --full run:
       * BASELINE configs[0] (C1: text-to-audio 1 s, 10 Euler iterations, CFG off + DAC decode) run IN FULL once at `threads`
         (16: where the torch CPU kernels stop scaling on these hosts);
       * the metric's own configuration (C2): three DiT forwards of the CFG pair's conditional half + the DAC decode of the same
         clip, extrapolated to the 2 x 50 forwards of a clip (the extrapolation is stated in `sample`).
     `full` (--cpu-baseline-full, minutes): C1 three times (median) at `threads` AND at threads = physical cores - on the 128-core
     hosts of this pool one C1 pass takes 154 s at 128 threads against 24 s at 16 (profiles/r05_bench_c2.json), which is why the
-    default run does not pay for it.  `value` is the C2 figure (the metric's configuration); a reported baseline only."""
+    --full alone does not pay for it.  `value` is the C2 figure (the metric's configuration); a reported baseline only."""
     from oracle import foley_oracle as O
     try:
         avail = len(os.sched_getaffinity(0))
@@ -288,10 +290,14 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--model", default="xxl", choices=["xxl", "xl", "tiny"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline value does not need: the event-timed loop / DAC decode of one more pass, "
+                         "the per-kernel roofline, the extra configurations and the CPU baseline (about a minute and a half)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="BASELINE.md section 4 to the letter: C1 three times (median) at 16 threads AND at threads = physical cores (minutes)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the per-kernel profile pass and the bs=8 measurement")
+                    help="with --full: BASELINE.md section 4 to the letter: C1 three times (median) at 16 threads AND at threads = "
+                         "physical cores (minutes)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the per-kernel profile pass and the extra configurations")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--with-encoders", action="store_true",
                     help="c3 / c4: compute the conditioning from synthetic uint8 frames (seed 3) through the full-size SigLIP2 "
@@ -304,7 +310,10 @@ def parse_args(argv=None):
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (the waveform of every rank's clips, in clip "
                          "order) to DIR/<name>.npy in float32; beyond 64 MB a fixed seeded sample of the elements is written")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.cpu_baseline_full and not a.full:
+        ap.error("--cpu-baseline-full needs --full (a plain run has no CPU baseline)")
+    return a
 
 
 DUMP_LIMIT_BYTES = 64 << 20
@@ -477,8 +486,9 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
     pieces = {}
 
     def measure(bs: int, noise_cpu: torch.Tensor, steps: int, warmup: int, visual=visual, text=text, model=model,
-                duration=duration, progress=a.progress):
-        """Host-to-host passes: pinned CPU noise in, CPU waveform out."""
+                duration=duration, progress=a.progress, events=True):
+        """Host-to-host passes: pinned CPU noise in, CPU waveform out.  `events`: then one more pass, untimed, for the HIP-event
+        times of the loop and the DAC decode (loop_ms / dac_ms are None without it)."""
         noise_cpu = noise_cpu.pin_memory()
         la = noise_cpu.shape[2]
         ticks = []
@@ -502,22 +512,25 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
         barrier()
         dt = time.perf_counter() - t0
         pieces["audio"] = audio           # what the last timed pass returned (--dump-outputs)
-        # pieces of one more pass: precompute (host clock around a synchronised call), loop / decode (HIP events
-        # recorded by the library on the launch stream)
-        lat = noise_cpu.to(dev).float().contiguous()
-        plan = sampler.build_plan(model, visual, text, la, GUIDANCE, STEPS_PER_CLIP, bs, "euler")
-        torch.cuda.synchronize()
-        tp = time.perf_counter()
-        model.ctx.prepare(plan)
-        torch.cuda.synchronize()
-        pieces["prepare_ms"] = 1e3 * (time.perf_counter() - tp)
-        model.ctx.sample(lat, use_graph=graph)
-        torch.cuda.synchronize()
-        loop_ms = model.ctx.last_elapsed_ms()
-        model.ctx.dac_decode(lat)
-        torch.cuda.synchronize()
-        dac_ms = model.ctx.last_elapsed_ms()
-        pieces["local"] = {"clips": bs * steps, "pass_ms": round(1e3 * dt / steps, 2), "loop_ms": round(loop_ms, 2)}
+        pieces["local"] = {"clips": bs * steps, "pass_ms": round(1e3 * dt / steps, 2)}
+        loop_ms = dac_ms = None
+        if events:
+            # pieces of one more pass: precompute (host clock around a synchronised call), loop / decode (HIP events
+            # recorded by the library on the launch stream)
+            lat = noise_cpu.to(dev).float().contiguous()
+            plan = sampler.build_plan(model, visual, text, la, GUIDANCE, STEPS_PER_CLIP, bs, "euler")
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            model.ctx.prepare(plan)
+            torch.cuda.synchronize()
+            pieces["prepare_ms"] = 1e3 * (time.perf_counter() - tp)
+            model.ctx.sample(lat, use_graph=graph)
+            torch.cuda.synchronize()
+            loop_ms = model.ctx.last_elapsed_ms()
+            model.ctx.dac_decode(lat)
+            torch.cuda.synchronize()
+            dac_ms = model.ctx.last_elapsed_ms()
+            pieces["local"]["loop_ms"] = round(loop_ms, 2)
         if use_dist:
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -541,7 +554,7 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
         dist.all_gather_object(recs, rec)
         return recs
 
-    dt, loop_ms, dac_ms = measure(bs_main, noise_all[lo:hi], a.steps, a.warmup)
+    dt, loop_ms, dac_ms = measure(bs_main, noise_all[lo:hi], a.steps, a.warmup, events=a.full)
     dumped = None
     if a.dump_outputs:
         audio = pieces["audio"]
@@ -559,7 +572,7 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
 
     # ---- per-kernel profile (HIP-event brackets around every launch of an eager forward, mid-loop iteration)
     kernels, bracket_us = [], None
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         lat = noise_all[lo:hi].to(dev).float().contiguous()
         prof, bracket_us = model.ctx.profile_forward(lat, it=STEPS_PER_CLIP // 2, repeats=2)
         for e in prof:
@@ -574,7 +587,7 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
 
     # ---- the bs=8-per-GPU half of the BASELINE metric, same JSON line
     extra = {}
-    if not a.no_extra and a.bs is None and a.config == "c2" and not a.progress:
+    if a.full and not a.no_extra and a.bs is None and a.config == "c2" and not a.progress:
         def extra_line(bs, dur, workload, passes=3, **kw):
             """`passes` timed passes (1 warm-up) of another configuration of the same path; clips sharded like the main line."""
             la_x = int(dur * cfg.frame_rate)
@@ -623,62 +636,63 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
 
     if rank == 0:
         clips = world * bs_main * a.steps
-        loop_tf = bs_main * f_loop / (loop_ms * 1e-3) / 1e12
-        traffic, traffic_src = None, None
-        import glob
-        for tf_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):   # newest round first
-            try:
-                tj = json.load(open(tf_path))
-            except Exception:
-                continue
-            # only a counter pass taken on exactly these kernel sources and this workload is reported
-            if tj.get("kernel_src_sha") == kernel_src_sha() and tj.get("workload") == f"{a.config}/bs{bs_main}/{a.precision}/{a.model}":
-                traffic = tj["hbm_bytes_per_loop_iteration"]
-                traffic_src = {"file": os.path.relpath(tf_path, ROOT), "kernel_src_sha": tj["kernel_src_sha"],
-                               "unit": "bytes per loop iteration (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes on these kernel sources)"}
-                break
-        mfma_busy = None
-        for mf_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_mfma.json")), reverse=True):
-            try:
-                mj = json.load(open(mf_path))
-            except Exception:
-                continue
-            if mj.get("kernel_src_sha") == kernel_src_sha() and mj.get("workload") == f"{a.config}/bs{bs_main}/{a.precision}/{a.model}":
-                mfma_busy = {"value": mj["mfma_busy"], "kernel": mj["kernel"], "file": os.path.relpath(mf_path, ROOT),
-                             "definition": mj["definition"]}
-                break
-        dom = next((k for k in kernels if k["gflop_per_launch"] > 0), None)   # largest time per iteration among the MFMA kernels
-        # the same kernel's average in the rocprofv3 --kernel-trace --stats run of this command (profiles/rNN_rocprof_dominant.json,
-        # written by tools/collect_profiles.sh; reported only for exactly these kernel sources): the dispatch-event average above
-        # and the traced one differ by ~3 %
-        rocprof = None
-        for rp_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_rocprof_dominant.json")), reverse=True):
-            try:
-                rj = json.load(open(rp_path))
-            except Exception:
-                continue
-            if rj.get("kernel_src_sha") == kernel_src_sha() and rj.get("workload") == f"{a.config}/bs{bs_main}/{a.precision}/{a.model}" and dom:
-                # the traced row is matched BY NAME: the symbol foley_profile_forward reports for the dominant op (the kernel its
-                # launch ran, demangled) against the rows of the trace, both normalised; no row or more than one -> null.  When other
-                # ops run the same kernel instance the traced average covers them too: `ops_sharing_kernel` lists them.
-                cand = [k for k in rj.get("kernels", []) if kernel_key(k["name"]) == kernel_key(dom.get("kernel", "")) and dom.get("kernel")]
-                if len(cand) == 1:
-                    rk = cand[0]
-                    sharing = [k["name"] for k in kernels if k is not dom and kernel_key(k.get("kernel", "")) == kernel_key(dom["kernel"])]
-                    tfr = dom["gflop_per_launch"] * 1e9 / (rk["avg_us"] * 1e-6) / 1e12
-                    rocprof = {"kernel": rk["name"], "avg_us": rk["avg_us"], "calls": rk["calls"], "achieved": round(tfr, 1),
-                               "frac": round(tfr / peak, 4), "file": os.path.relpath(rp_path, ROOT), "matched_by": "kernel symbol",
-                               "ops_sharing_kernel": sharing}
-                break
-        roof = {"bound": "mfma", "peak": peak, "unit": "TFLOP/s",
-                "achieved": dom["tflops"] if dom else loop_tf, "frac": dom["frac"] if dom else loop_tf / peak,
-                "kernel": dom["name"] if dom else "whole sampler loop",
-                "launch": ("dominant kernel of the loop (largest time per iteration): algorithmic FLOPs of one launch / the dispatch's own "
-                           "start->stop HIP events on the launch stream (hipExtLaunchKernelGGL), eager forward at iteration 25, after the timed region"),
-                "frac_rocprof": rocprof["frac"] if rocprof else None, "rocprof": rocprof,
-                "traffic": traffic, "traffic_source": traffic_src, "mfma_busy": mfma_busy,
-                "loop_frac": loop_tf / peak, "loop_achieved": loop_tf, "loop_ms": loop_ms, "dac_decode_ms": dac_ms, "prepare_ms": prepare_ms,
-                "algorithmic_tflop_per_clip": f_clip / 1e12, "event_bracket_us": bracket_us, "kernels": kernels}
+        if a.full:
+            loop_tf = bs_main * f_loop / (loop_ms * 1e-3) / 1e12
+            traffic, traffic_src = None, None
+            import glob
+            for tf_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")), reverse=True):   # newest round first
+                try:
+                    tj = json.load(open(tf_path))
+                except Exception:
+                    continue
+                # only a counter pass taken on exactly these kernel sources and this workload is reported
+                if tj.get("kernel_src_sha") == kernel_src_sha() and tj.get("workload") == f"{a.config}/bs{bs_main}/{a.precision}/{a.model}":
+                    traffic = tj["hbm_bytes_per_loop_iteration"]
+                    traffic_src = {"file": os.path.relpath(tf_path, ROOT), "kernel_src_sha": tj["kernel_src_sha"],
+                                   "unit": "bytes per loop iteration (rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE passes on these kernel sources)"}
+                    break
+            mfma_busy = None
+            for mf_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_mfma.json")), reverse=True):
+                try:
+                    mj = json.load(open(mf_path))
+                except Exception:
+                    continue
+                if mj.get("kernel_src_sha") == kernel_src_sha() and mj.get("workload") == f"{a.config}/bs{bs_main}/{a.precision}/{a.model}":
+                    mfma_busy = {"value": mj["mfma_busy"], "kernel": mj["kernel"], "file": os.path.relpath(mf_path, ROOT),
+                                 "definition": mj["definition"]}
+                    break
+            dom = next((k for k in kernels if k["gflop_per_launch"] > 0), None)   # largest time per iteration among the MFMA kernels
+            # the same kernel's average in the rocprofv3 --kernel-trace --stats run of this command (profiles/rNN_rocprof_dominant.json,
+            # written by tools/collect_profiles.sh; reported only for exactly these kernel sources): the dispatch-event average above
+            # and the traced one differ by ~3 %
+            rocprof = None
+            for rp_path in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_rocprof_dominant.json")), reverse=True):
+                try:
+                    rj = json.load(open(rp_path))
+                except Exception:
+                    continue
+                if rj.get("kernel_src_sha") == kernel_src_sha() and rj.get("workload") == f"{a.config}/bs{bs_main}/{a.precision}/{a.model}" and dom:
+                    # the traced row is matched BY NAME: the symbol foley_profile_forward reports for the dominant op (the kernel its
+                    # launch ran, demangled) against the rows of the trace, both normalised; no row or more than one -> null.  When other
+                    # ops run the same kernel instance the traced average covers them too: `ops_sharing_kernel` lists them.
+                    cand = [k for k in rj.get("kernels", []) if kernel_key(k["name"]) == kernel_key(dom.get("kernel", "")) and dom.get("kernel")]
+                    if len(cand) == 1:
+                        rk = cand[0]
+                        sharing = [k["name"] for k in kernels if k is not dom and kernel_key(k.get("kernel", "")) == kernel_key(dom["kernel"])]
+                        tfr = dom["gflop_per_launch"] * 1e9 / (rk["avg_us"] * 1e-6) / 1e12
+                        rocprof = {"kernel": rk["name"], "avg_us": rk["avg_us"], "calls": rk["calls"], "achieved": round(tfr, 1),
+                                   "frac": round(tfr / peak, 4), "file": os.path.relpath(rp_path, ROOT), "matched_by": "kernel symbol",
+                                   "ops_sharing_kernel": sharing}
+                    break
+            roof = {"bound": "mfma", "peak": peak, "unit": "TFLOP/s",
+                    "achieved": dom["tflops"] if dom else loop_tf, "frac": dom["frac"] if dom else loop_tf / peak,
+                    "kernel": dom["name"] if dom else "whole sampler loop",
+                    "launch": ("dominant kernel of the loop (largest time per iteration): algorithmic FLOPs of one launch / the dispatch's own "
+                               "start->stop HIP events on the launch stream (hipExtLaunchKernelGGL), eager forward at iteration 25, after the timed region"),
+                    "frac_rocprof": rocprof["frac"] if rocprof else None, "rocprof": rocprof,
+                    "traffic": traffic, "traffic_source": traffic_src, "mfma_busy": mfma_busy,
+                    "loop_frac": loop_tf / peak, "loop_achieved": loop_tf, "loop_ms": loop_ms, "dac_decode_ms": dac_ms, "prepare_ms": prepare_ms,
+                    "algorithmic_tflop_per_clip": f_clip / 1e12, "event_bracket_us": bracket_us, "kernels": kernels}
         out = {
             "metric": f"audio-sec/sec ({duration:g}s clip, 50-step Euler, CFG 4.5)",
             "value": clips * duration / dt, "unit": "audio-sec/sec", "n_gpus": world, "steps": a.steps,
@@ -692,8 +706,9 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
                        "collectives": 1 if use_dist else 0, "broadcast_s": bcast_s, "bundle_bytes": spec.total,
                        "rccl_nranks": dist.get_world_size() if use_dist else 1, "backend": a.backend if use_dist else None,
                        "ranks": rank_records},
-            "roofline": roof,
         }
+        if a.full:
+            out["roofline"] = roof
         if encoders is not None:
             out["encoder_ms"] = encoders
             out["end_to_end_ms_per_step"] = encoders["total_ms"] + 1e3 * dt / a.steps
@@ -701,7 +716,7 @@ def run_rank(a, world: int, rank: int, local: int, launched: bool) -> int:
             out["extra"] = extra
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if world == 1 and not a.no_cpu_baseline and a.model == "xxl" and a.config != "c5":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.model == "xxl" and a.config != "c5":
             out["cpu_baseline"] = cpu_baseline(sd, dsd, cfg, cond, noise_all, duration, full=a.cpu_baseline_full)
         emit(out)
     if use_dist:

@@ -491,3 +491,13 @@ def test_bench_rejects_zero_steps():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--model", "tiny", "--duration", "1"] + args,
                            capture_output=True, text=True, timeout=120)
         assert r.returncode == 2 and "--steps" in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_full_is_opt_in(capsys):
+    """What the headline value does not need runs only under --full; --cpu-baseline-full alone is refused rather than ignored."""
+    import bench
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    assert bench.parse_args(["--full", "--cpu-baseline-full"]).cpu_baseline_full
+    with pytest.raises(SystemExit) as e:
+        bench.parse_args(["--cpu-baseline-full"])
+    assert e.value.code == 2 and "--full" in capsys.readouterr().err

@@ -1074,7 +1074,7 @@ def test_single_rank_nccl_bundle_adoption(tiny, dev):
 
 
 def test_bench_single_rank_forced_dist(dev):
-    """bench.py under a launcher-style environment (RANK/WORLD_SIZE set, nccl process group, the single
+    """bench.py --full under a launcher-style environment (RANK/WORLD_SIZE set, nccl process group, the single
     broadcast) on one GPU: exits 0 and prints the JSON line with the per-kernel roofline."""
     import json, os, socket, subprocess, sys
     from conftest import ROOT
@@ -1085,7 +1085,7 @@ def test_bench_single_rank_forced_dist(dev):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                FOLEY_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--duration", "1",
-                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([ln for ln in r.stdout.splitlines() if ln.strip()]) == 1, r.stdout[:500]     # RCCL's banner went to stderr
@@ -1118,6 +1118,23 @@ def test_bench_dump_outputs(dev, tmp_path):
         assert a.dtype == np.float32 and a.shape == (1, 1, 48000) and np.isfinite(a).all() and np.abs(a).max() > 0
         outs.append(a)
     assert np.array_equal(outs[0], outs[1])
+
+
+def test_bench_plain_run_is_lean(dev):
+    """A plain bench.py run (no --full) on the default configuration prints the headline line and nothing that takes runs of its
+    own: no roofline (per-kernel profile, event-timed loop), no extra configurations, no CPU baseline."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "tiny", "--duration", "1",
+                        "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads(r.stdout)
+    assert out["metric"].startswith("audio-sec/sec (1s clip") and out["unit"] == "audio-sec/sec" and out["higher_is_better"] is True
+    assert out["dtype"] == "bf16" and out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 1.0 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]       # one 1 s clip per step
+    assert not {"roofline", "extra", "cpu_baseline"} & set(out), sorted(out)
+    assert out["config"]["ranks"][0]["clips"] == 2 and "loop_ms" not in out["config"]["ranks"][0]
 
 
 def test_denoise_process_multi_shards_the_batch(tiny, dev):
@@ -1267,7 +1284,7 @@ def test_bench_two_ranks_sharing_one_gpu(dev):
     env["FOLEY_BENCH_SHARE_DEVICE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", "c4",
                         "--model", "tiny", "--duration", "1", "--bs", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-extra"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-extra", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["config"]["collectives"] == 1 and out["config"]["clips_per_gpu"] == 2

@@ -30,5 +30,5 @@ if "--dominant-json" in sys.argv:
     ks = [{"name": r[0].replace("(anonymous namespace)::", "").replace("unsigned short", "bf16")[:120], "calls": r[1], "avg_us": round(r[3], 3)}
           for r in rows if "gemm_" in r[0]]
     json.dump({"kernel_src_sha": h.hexdigest()[:16], "workload": workload, "loop_iterations": 100, "kernels": ks,
-               "source": "rocprofv3 --kernel-trace --stats of `python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra` "
+               "source": "rocprofv3 --kernel-trace --stats of `python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra` "
                          "(two 50-iteration loops: the timed pass and the event-timed one)"}, open(out, "w"))
