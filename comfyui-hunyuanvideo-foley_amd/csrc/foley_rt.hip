@@ -4,6 +4,7 @@
 // include/foley_hip.h.  No torch types, no CPU fallback.
 #include "../../include/foley_hip.h"
 #include "kernels.h"
+#include "gemm_plan.h"   // foley_debug_gemm_plan
 
 #include <algorithm>
 #include <climits>
@@ -774,13 +775,12 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   const foley_plan& pl = c->plan;
   const ForwardW& W = c->fw;
   if (!W.ok) return FAIL(FOLEY_ERR_STATE, "forward weights are not resolved (foley_prepare)");
-  // one clip per CFG half: the small-grid GEMMs may rotate their K origin per M tile (gemm.hip: g_gemm_krot_ok) - with several clips
+  // one clip per CFG half: the small-grid GEMMs may rotate their K origin per M tile (GemmArgs::krot_ok) - with several clips
   // in the batch, clips with equal noise must stay bit-identical, so their rows keep one summation order
-  struct KRotScope {
-    int prev;
-    explicit KRotScope(int v) : prev(g_gemm_krot_ok) { g_gemm_krot_ok = v; }
-    ~KRotScope() { g_gemm_krot_ok = prev; }
-  } krot_scope(pl.clips == 1 ? 1 : 0);
+  auto krot = [&pl](GemmArgs g) {
+    g.krot_ok = pl.clips == 1 ? 1 : 0;
+    return g;
+  };
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const int ncfg = pl.ncfg, clips = pl.clips, La = pl.La, Lv = pl.Lv, Ls = pl.Ls, Lt = pl.Lt, NI = pl.n_iter;
   const int Bc = ncfg * clips, M = Bc * La, Mv = Bc * Lv, S = La + Lv;
@@ -817,7 +817,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     if (f.depth_single > 0) {
       // one GEMM for all blocks: [R, D] x [n_single*6D, D]^T -> smod [R, n_single*6D]
       const double n = (double)f.depth_single * 6 * D;
-      GemmArgs gm = gemm_plain(c->svec, R, W.smod, c->smod, (long)f.depth_single * 6 * D);
+      GemmArgs gm = krot(gemm_plain(c->svec, R, W.smod, c->smod, (long)f.depth_single * 6 * D));
       TRY(prof_begin(c, st, "single.modulation (all blocks, one GEMM)", gf(R, n, D), gb(R, n, D, 4)));
       TRY(launch_gemm(gm, T, EPI_STORE_F32, 0, sd));
       TRY(prof_end(c, st));
@@ -829,7 +829,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
 
   // audio_embedder (conv k=1 == linear over the transposed latents) + add_sync (hifi_foley.py:768, 838-839)
   {
-    GemmArgs g = gemm_plain(c->xin, M, W.audio_in, c->audio, D);
+    GemmArgs g = krot(gemm_plain(c->xin, M, W.audio_in, c->audio, D));
     g.rb = rb_up(c->sync_tok, D, clips * La, La, Ls);
     PROF("audio_embedder", gf(M, D, C), gb(M, D, C, 4), launch_gemm(g, T, EPI_STORE_F32, 0, st));
   }
@@ -868,8 +868,8 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
       return 0;
     };
     auto gated2 = [&](const char* label, const Lin& la, const Lin& lv, bool from_hid, int c_gate) -> int {
-      GemmArgs g0 = gemm_plain(from_hid ? ss[0].hid : ss[0].att, ss[0].rows, la, ss[0].x, D);
-      GemmArgs g1 = gemm_plain(from_hid ? ss[1].hid : ss[1].att, ss[1].rows, lv, ss[1].x, D);
+      GemmArgs g0 = krot(gemm_plain(from_hid ? ss[0].hid : ss[0].att, ss[0].rows, la, ss[0].x, D));
+      GemmArgs g1 = krot(gemm_plain(from_hid ? ss[1].hid : ss[1].att, ss[1].rows, lv, ss[1].x, D));
       g0.rb = tb(0, c_gate);
       g1.rb = tb(1, c_gate);
       with_partials(g0, c->part_a);
@@ -900,8 +900,8 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     // 1. joint self attention (hifi_foley.py:215-269)
     {
       TRY(ln2(0, 1));
-      GemmArgs g0 = gemm_plain(ss[0].xn, ss[0].rows, w.qkv[0], ss[0].qkv, 3 * D);
-      GemmArgs g1 = gemm_plain(ss[1].xn, ss[1].rows, w.qkv[1], ss[1].qkv, 3 * D);
+      GemmArgs g0 = krot(gemm_plain(ss[0].xn, ss[0].rows, w.qkv[0], ss[0].qkv, 3 * D));
+      GemmArgs g1 = krot(gemm_plain(ss[1].xn, ss[1].rows, w.qkv[1], ss[1].qkv, 3 * D));
       g0.qs = split_args(0, 3, w.qn[0], w.kn[0], ss[0].pos);
       g1.qs = split_args(1, 3, w.qn[1], w.kn[1], ss[1].pos);
       PROF("triple.qkv GEMM + RMSNorm/RoPE head split", gf(M + Mv, 3 * D, D), gb(M + Mv, 3 * D, D, es) + 3.0 * D * D * es,
@@ -913,8 +913,8 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     // 2. cross attention to the (cached) text keys/values (hifi_foley.py:271-319)
     {
       TRY(ln2(3, 4));
-      GemmArgs g0 = gemm_plain(ss[0].xn, ss[0].rows, w.cq[0], ss[0].qkv, D);
-      GemmArgs g1 = gemm_plain(ss[1].xn, ss[1].rows, w.cq[1], ss[1].qkv, D);
+      GemmArgs g0 = krot(gemm_plain(ss[0].xn, ss[0].rows, w.cq[0], ss[0].qkv, D));
+      GemmArgs g1 = krot(gemm_plain(ss[1].xn, ss[1].rows, w.cq[1], ss[1].qkv, D));
       g0.qs = split_args(0, 1, w.cqn[0], nullptr, pl.pos_linear);
       g1.qs = split_args(1, 1, w.cqn[1], nullptr, pl.pos_linear);
       const int Ltp = (Lt + 31) & ~31;
@@ -943,8 +943,8 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     {
       TRY(ln2(6, 7));
       PROF("triple.mlp fc1 GEMM + GELU", gf(M + Mv, f.mlp_hidden, D), gb(M + Mv, f.mlp_hidden, D, es) + (double)f.mlp_hidden * D * es,
-           launch_gemm_pair(gemm_plain(ss[0].xn, ss[0].rows, w.fc1[0], ss[0].hid, f.mlp_hidden),
-                            gemm_plain(ss[1].xn, ss[1].rows, w.fc1[1], ss[1].hid, f.mlp_hidden), T, EPI_GELU_T, st));
+           launch_gemm_pair(krot(gemm_plain(ss[0].xn, ss[0].rows, w.fc1[0], ss[0].hid, f.mlp_hidden)),
+                            krot(gemm_plain(ss[1].xn, ss[1].rows, w.fc1[1], ss[1].hid, f.mlp_hidden)), T, EPI_GELU_T, st));
       TRY(gated2("triple.mlp fc2 GEMM (gated residual)", w.fc2[0], w.fc2[1], true, 8));
     }
   }
@@ -970,7 +970,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     PROF("single.layernorm+modulate (+pending split-K sum)", 0.0, ln_bytes_s,
          launch_ln_mod_pending(c->audio, M, D, 1e-5f, sm(0), sm(1), c->xn_a, T, pend[0], st));
     pend[0] = LnPending{};
-    GemmArgs gq = gemm_plain(c->xn_a, M, w.qkv, c->qkv_a, 3 * D);
+    GemmArgs gq = krot(gemm_plain(c->xn_a, M, w.qkv, c->qkv_a, 3 * D));
     QkvSplitArgs q{};
     q.qkv = c->qkv_a; q.M = M; q.L = La; q.H = H; q.nK = 3;
     q.gain[0] = w.qn; q.gain[1] = w.kn;
@@ -987,7 +987,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
       PROF("single.self attention", af(Bc, La, La), ab(Bc, La, La), launch_attention(a, T, st));
     }
     {
-      GemmArgs g = gemm_conv(c->att_a, M, La, D, 3, 1, w.lin1, c->audio, D);
+      GemmArgs g = krot(gemm_conv(c->att_a, M, La, D, 3, 1, w.lin1, c->audio, D));
       g.rb = sm(2);
       with_partials(g, c->part_a);
       int ks = 1;
@@ -998,9 +998,9 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
          launch_ln_mod_pending(c->audio, M, D, 1e-5f, sm(3), sm(4), c->xn_a, T, pend[0], st));
     pend[0] = LnPending{};
     PROF("single.w1/w3 conv3 GEMM + SiLU gate", gf(M, 2 * Hc, 3 * D), gb(M, 2 * Hc, 3 * D, es) - (double)M * Hc * es,
-         launch_gemm(gemm_conv(c->xn_a, M, La, D, 3, 1, w.w13, c->hid_a, Hc), T, EPI_SILUGATE_T, 0, st));
+         launch_gemm(krot(gemm_conv(c->xn_a, M, La, D, 3, 1, w.w13, c->hid_a, Hc)), T, EPI_SILUGATE_T, 0, st));
     {
-      GemmArgs g = gemm_conv(c->hid_a, M, La, Hc, 3, 1, w.w2, c->audio, D);
+      GemmArgs g = krot(gemm_conv(c->hid_a, M, La, Hc, 3, 1, w.w2, c->audio, D));
       g.rb = sm(5);
       with_partials(g, c->part_a);
       int ks = 1;
@@ -1013,7 +1013,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   {
     PROF("final.layernorm", 0.0, ln_bytes_s,
          launch_ln_mod_pending(c->audio, M, D, 1e-6f, rb_none(), rb_none(), c->xn_a, T, pend[0], st));
-    PROF("final.linear", gf(M, C, D), gb(M, C, D, 4), launch_gemm(gemm_plain(c->xn_a, M, W.fin, c->pred, C), T, EPI_STORE_F32, 0, st));
+    PROF("final.linear", gf(M, C, D), gb(M, C, D, 4), launch_gemm(krot(gemm_plain(c->xn_a, M, W.fin, c->pred, C)), T, EPI_STORE_F32, 0, st));
   }
   return 0;
 }
@@ -1420,7 +1420,6 @@ static int gemm_args_of(const foley_gemm_desc* d, GemmArgs& g) {
     g.partial_half = d->partial_dtype != 0;
     if (d->partial_dtype != 0 && d->partial_dtype != d->dtype) return FAIL(FOLEY_ERR_INVALID, "partial_dtype must be 0 (fp32) or the operand dtype");
   }
-  g.zeros = zero_page();
   if (g.segV < 1 || g.segS < 1 || g.osegV < 1 || g.taps < 1) return FAIL(FOLEY_ERR_INVALID, "bad GEMM descriptor");
   if (d->epilogue == EPI_QKV_SPLIT) {
     const foley_qkv_split_desc* q = d->qkv;
@@ -1437,9 +1436,20 @@ static int gemm_args_of(const foley_gemm_desc* d, GemmArgs& g) {
   return 0;
 }
 
+// Test-only hook (tests/test_pairs_gpu.py; not part of include/foley_hip.h): the op-level GEMM entries of the calling thread opt in
+// to K-origin rotation (GemmArgs::krot_ok) as run_forward does for single-clip forwards; returns the previous setting.
+static thread_local int g_gemm_krot_ok = 0;
+extern "C" int foley_debug_gemm_krot(int on) {
+  const int prev = g_gemm_krot_ok;
+  g_gemm_krot_ok = on ? 1 : 0;
+  return prev;
+}
+
 extern "C" int foley_op_gemm(const foley_gemm_desc* d, void* stream) {
   GemmArgs g;
   if (int rc = gemm_args_of(d, g)) return rc;
+  g.zeros = zero_page();
+  g.krot_ok = g_gemm_krot_ok;
   int ks = 1;
   const int rc = launch_gemm(g, d->dtype, d->epilogue, d->tile, (hipStream_t)stream, &ks);
   if (d->ksplit_used) *d->ksplit_used = ks;
@@ -1449,18 +1459,45 @@ extern "C" int foley_op_gemm(const foley_gemm_desc* d, void* stream) {
 // Test-only entries (not part of include/foley_hip.h; tests/test_pairs_gpu.py types them with ctypes): the two-problem launches
 // of run_forward's two-stream blocks at op level.  launch_gemm_pair picks its own tile and one K split for both problems (written
 // to d0->ksplit_used); both descriptors must name the same operand dtype and epilogue.
-extern "C" int foley_debug_gemm_pair(const foley_gemm_desc* d0, const foley_gemm_desc* d1, void* stream) {
+static int gemm_pair_args_of(const foley_gemm_desc* d0, const foley_gemm_desc* d1, GemmArgs& g0, GemmArgs& g1) {
   if (!d0 || !d1) return FAIL(FOLEY_ERR_INVALID, "null descriptor");
   if (d0->dtype != d1->dtype || d0->epilogue != d1->epilogue)
     return FAIL(FOLEY_ERR_INVALID, "GEMM pair: the two problems must share the operand dtype and the epilogue");
   if (d0->tile != 0 || d1->tile != 0) return FAIL(FOLEY_ERR_INVALID, "GEMM pair: the pair launcher picks its own tile (tile must be 0)");
-  GemmArgs g0, g1;
   if (int rc = gemm_args_of(d0, g0)) return rc;
-  if (int rc = gemm_args_of(d1, g1)) return rc;
+  return gemm_args_of(d1, g1);
+}
+
+extern "C" int foley_debug_gemm_pair(const foley_gemm_desc* d0, const foley_gemm_desc* d1, void* stream) {
+  GemmArgs g0, g1;
+  if (int rc = gemm_pair_args_of(d0, d1, g0, g1)) return rc;
+  g0.zeros = g1.zeros = zero_page();
+  g0.krot_ok = g1.krot_ok = g_gemm_krot_ok;
   int ks = 1;
   const int rc = launch_gemm_pair(g0, g1, d0->dtype, d0->epilogue, (hipStream_t)stream, &ks);
   if (d0->ksplit_used) *d0->ksplit_used = ks;
   return rc;
+}
+
+// Test-only (tests/test_gemm_plan_cpu.py): the launcher's plan for one problem (d1 null) or a pair, without touching the device -
+// descriptors may carry fake (16-byte aligned) addresses.  out = {tile, K split, panel groups, k_rot}; krot_ok opts in to K-origin
+// rotation as run_forward does for single-clip forwards.
+extern int g_gemm_pf_dist;   // gemm.hip: foley_debug_gemm_prefetch
+extern "C" int foley_debug_gemm_plan(const foley_gemm_desc* d0, const foley_gemm_desc* d1, int krot_ok, int32_t out[4]) {
+  if (!out) return FAIL(FOLEY_ERR_INVALID, "null output");
+  GemmArgs g0, g1;
+  if (int rc = d1 ? gemm_pair_args_of(d0, d1, g0, g1) : gemm_args_of(d0, g0)) return rc;
+  const GemmOpts opt{krot_ok ? 1 : 0, g_gemm_pf_dist};
+  GemmPlan p;
+  switch (d0->dtype) {
+    case FOLEY_F32: p = plan_gemm<float>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, opt); break;
+    case FOLEY_BF16: p = plan_gemm<bf16_t>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, opt); break;
+    case FOLEY_F16: p = plan_gemm<f16_t>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, opt); break;
+    default: return FAIL(FOLEY_ERR_INVALID, "GEMM: unsupported operand dtype");
+  }
+  if (p.err) return FAIL(FOLEY_ERR_INVALID, p.err);
+  out[0] = p.tile; out[1] = p.ksplit; out[2] = p.n_groups; out[3] = p.k_rot;
+  return 0;
 }
 
 extern "C" int foley_op_attention_hd(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq,

@@ -4,11 +4,6 @@
 
 long long* g_gemm_dbg = nullptr;
 int g_gemm_dbg_mode = 0;
-// K-origin rotation (GemmArgs::k_rot) is an option of the CALLER: a row's summation order then depends on the M tile it falls into, so
-// rows with equal inputs no longer come out bit-identical.  The DiT forward of a single clip per CFG half opts in (foley_rt.hip::
-// run_forward); foley_prepare (its row-periodicity check compares bit patterns), batches (clips of a batch with equal noise stay
-// bit-identical) and the op-level entries do not.
-thread_local int g_gemm_krot_ok = 0;
 // tile, K split and k_rot of this thread's last dispatched GEMM (launch_typed, after every fallback): foley_debug_gemm_last
 thread_local int g_gemm_last[3] = {0, 0, 0};
 int g_gemm_pf_dist = 0;   // L2 prefetch distance of the wave-specialised mainloop (K-slices beyond the ring)
@@ -44,14 +39,7 @@ extern "C" void foley_debug_gemm_timeline(void* p, int mode) {
   g_gemm_dbg_mode = mode;
 }
 
-// Test-only hooks (tests/test_pairs_gpu.py; not part of include/foley_hip.h): opt the calling thread in to K-origin rotation as
-// run_forward does for single-clip forwards (returns the previous setting), and read back what the last launch of this thread ran.
-extern "C" int foley_debug_gemm_krot(int on) {
-  const int prev = g_gemm_krot_ok;
-  g_gemm_krot_ok = on ? 1 : 0;
-  return prev;
-}
-
+// Test-only hook (tests/test_pairs_gpu.py; not part of include/foley_hip.h): read back what the last launch of this thread ran.
 extern "C" void foley_debug_gemm_last(int* tile, int* ksplit, int* k_rot) {
   if (tile) *tile = g_gemm_last[0];
   if (ksplit) *ksplit = g_gemm_last[1];

@@ -82,14 +82,10 @@ __device__ __forceinline__ void gemm_wide_body(const GemmPair& pr) {
   }
   int ks = 0;
   if constexpr (EPI == EPI_GATE_RES) {
-    if (g.ks_major) {   // K-range-major order: only the one or two XCDs that run a range fetch its activation columns (gemm_ws_impl.h)
-      const int tiles = tiles_m * tiles_n;
-      ks = bid / tiles;
-      bid -= ks * tiles;
-    } else {
-      ks = bid % g.ksplit;
-      bid /= g.ksplit;
-    }
+    // K-range-major order: only the one or two XCDs that run a range fetch its activation columns (gemm_ws_impl.h)
+    const int tiles = tiles_m * tiles_n;
+    ks = bid / tiles;
+    bid -= ks * tiles;
   }
   int tm, tn;
   tile_coords(bid, tiles_m, tiles_n, g.n_groups, tm, tn);

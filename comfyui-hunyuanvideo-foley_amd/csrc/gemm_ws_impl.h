@@ -36,13 +36,6 @@ __device__ __forceinline__ void buf_lds16(const void* base, unsigned bytes, unsi
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
 }
 
-// the same with cache-policy bits (aux 2 = nt: a weight stream every line of which is read once or twice and never again)
-template <int AUX>
-__device__ __forceinline__ void buf_lds16_aux(const void* base, unsigned bytes, unsigned char* lds_wave_base, int voff, int soff) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, AUX);
-}
-
 // logical tile id -> (tm, tn).  Default order [panel][M tile]: the M tiles of a weight panel are neighbours (one XCD after the remap).
 // Large grids (GemmArgs::n_groups > 0): [panel group][M tile][panel inside the group] - the ~32 workgroups an XCD runs at a time then
 // cover a near-square block (a few M tiles x the group's panels) instead of all M tiles of one or two panels, so that every line
@@ -158,14 +151,9 @@ __device__ __forceinline__ void gemm_ws_body(const GemmPair& pr) {
     // K-range-major order (round 5): the XCD remap above hands consecutive ids to one XCD, so all tiles of a K range sit on one or
     // two XCDs and only those L2s fetch the range's activation columns (range-fastest order: every XCD fetches ALL of A - 8 x 4 MB
     // of fabric reads per w2 launch against 4 MB of activations)
-    if (g.ks_major) {
-      const int tiles = tiles_m * tiles_n;
-      ks = bid / tiles;
-      bid -= ks * tiles;
-    } else {
-      ks = bid % g.ksplit;
-      bid /= g.ksplit;
-    }
+    const int tiles = tiles_m * tiles_n;
+    ks = bid / tiles;
+    bid -= ks * tiles;
   }
   int tm, tn;
   tile_coords(bid, tiles_m, tiles_n, g.n_groups, tm, tn);
@@ -576,14 +564,9 @@ __global__ __launch_bounds__((WM * WN + LW) * 64) void gemm_ws_conv3_kernel(cons
     // K-range-major order (round 5): the XCD remap above hands consecutive ids to one XCD, so all tiles of a K range sit on one or
     // two XCDs and only those L2s fetch the range's activation columns (range-fastest order: every XCD fetches ALL of A - 8 x 4 MB
     // of fabric reads per w2 launch against 4 MB of activations)
-    if (g.ks_major) {
-      const int tiles = tiles_m * tiles_n;
-      ks = bid / tiles;
-      bid -= ks * tiles;
-    } else {
-      ks = bid % g.ksplit;
-      bid /= g.ksplit;
-    }
+    const int tiles = tiles_m * tiles_n;
+    ks = bid / tiles;
+    bid -= ks * tiles;
   }
   int tm, tn;
   tile_coords(bid, tiles_m, tiles_n, g.n_groups, tm, tn);
@@ -786,7 +769,7 @@ __global__ __launch_bounds__((WM * WN + LW) * 64) void gemm_ws_conv3_kernel(cons
 //    K-STEPS of every slice (0 / 1 and 2 / 3): 8 fragment reads per 8 MFMAs instead of 12, two sets = 64 registers, 64
 //    accumulator registers; the partner's partial tile is added once, through the dead ring, before the epilogue.
 // Loader waves, ring protocol, K permutation, zero padding and epilogues are those of gemm_ws_conv3_kernel<256, 64, 8, 1, 6, 3, 4>.
-template <typename T, int EPI, int WNT>
+template <typename T, int EPI>
 __global__ __launch_bounds__(768) void gemm_ws_conv3_ks_kernel(const GemmPair pr) {
   const GemmArgs& g = pr.g[0];
   constexpr int BM = 256, BN = 64, LW = 4, NSB = 6, NAB = 3, NW = 8;
@@ -811,14 +794,9 @@ __global__ __launch_bounds__(768) void gemm_ws_conv3_ks_kernel(const GemmPair pr
     // K-range-major order (round 5): the XCD remap above hands consecutive ids to one XCD, so all tiles of a K range sit on one or
     // two XCDs and only those L2s fetch the range's activation columns (range-fastest order: every XCD fetches ALL of A - 8 x 4 MB
     // of fabric reads per w2 launch against 4 MB of activations)
-    if (g.ks_major) {
-      const int tiles = tiles_m * tiles_n;
-      ks = bid / tiles;
-      bid -= ks * tiles;
-    } else {
-      ks = bid % g.ksplit;
-      bid /= g.ksplit;
-    }
+    const int tiles = tiles_m * tiles_n;
+    ks = bid / tiles;
+    bid -= ks * tiles;
   }
   int tm, tn;
   tile_coords(bid, tiles_m, tiles_n, g.n_groups, tm, tn);
@@ -864,7 +842,7 @@ __global__ __launch_bounds__(768) void gemm_ws_conv3_ks_kernel(const GemmPair pr
       unsigned char* Bs = lds + NAB * ABUF + (sl % NSB) * BSL;
       const int sW = (tap * C + ch) * ESZ;
 #pragma unroll
-      for (int i = 0; i < BI; ++i) buf_lds16_aux<WNT ? 2 : 0>(g.W, g.w_bytes, Bs + (lw * BI + i) * 1024, vW[i], sW);
+      for (int i = 0; i < BI; ++i) buf_lds16(g.W, g.w_bytes, Bs + (lw * BI + i) * 1024, vW[i], sW);
     };
 #pragma unroll
     for (int sl = 0; sl < NSB - 1; ++sl)
@@ -1044,19 +1022,13 @@ int launch_ws_conv3_ks(const GemmArgs& g, hipStream_t st) {
   pr.g[0] = g;
   pr.g[1] = g;
   pr.tiles0 = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) * (EPI == EPI_GATE_RES ? g.ksplit : 1);
-  static const bool nt = []() { const char* e = getenv("FOLEY_W_NT"); return e && e[0] == '1'; }();
-  static std::atomic<unsigned long long> raised{0}, raised_nt{0};
-  if (nt) {
-    auto k = gemm_ws_conv3_ks_kernel<T, EPI, 1>;
-    hipError_t e = foley_raise_lds((const void*)k, (int)lds, raised_nt);
-    if (e != hipSuccess) return foley_set_err(hipGetErrorString(e), __FILE__, __LINE__);
-    FOLEY_LAUNCH(k, dim3(pr.tiles0), dim3(768), lds, st, pr);
-  } else {
-    auto k = gemm_ws_conv3_ks_kernel<T, EPI, 0>;
+  auto k = gemm_ws_conv3_ks_kernel<T, EPI>;
+  static std::atomic<unsigned long long> raised{0};
+  {
     hipError_t e = foley_raise_lds((const void*)k, (int)lds, raised);
     if (e != hipSuccess) return foley_set_err(hipGetErrorString(e), __FILE__, __LINE__);
-    FOLEY_LAUNCH(k, dim3(pr.tiles0), dim3(768), lds, st, pr);
   }
+  FOLEY_LAUNCH(k, dim3(pr.tiles0), dim3(768), lds, st, pr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return foley_set_err(hipGetErrorString(e), __FILE__, __LINE__);
   return 0;
@@ -1181,9 +1153,8 @@ int launch_gemm_ws_t(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, h
     return foley_set_err("wave-specialised GEMM: bad / mixed weight formats", __FILE__, __LINE__);
   if (tile == 22) {   // tap-fused conv k=3, 256x64 (bf16 weights; gated residual / fp32 store)
     if (g1 || g.wfmt) return foley_set_err("wave-specialised conv3 256x64: single problem, bf16 weights", __FILE__, __LINE__);
-    // round 5: K-split wave pairs + slice read-ahead (vector epilogue only; FOLEY_CONV3_KS=0 keeps the early / late form)
-    static const bool ksp = []() { const char* e = getenv("FOLEY_CONV3_KS"); return !(e && e[0] == '0'); }();
-    if (ksp && g.vec_out) {
+    // round 5: K-split wave pairs + slice read-ahead (vector epilogue only)
+    if (g.vec_out) {
       if (epi == EPI_GATE_RES) return launch_ws_conv3_ks<T, EPI_GATE_RES>(g, st);
       if (epi == EPI_STORE_F32) return launch_ws_conv3_ks<T, EPI_STORE_F32>(g, st);
       if (epi == EPI_SILUGATE_T) return launch_ws_conv3_ks<T, EPI_SILUGATE_T>(g, st);

@@ -90,11 +90,13 @@ struct GemmArgs {
   int partial_cap;
   int n_groups;       // set by the launcher, large grids: > 0 = tile order [column-panel group][M tile][panel inside the group] with this many
                       // groups (the workgroups that run together then cover a near-square block of tiles); 0 = [panel][M tile]
-  int ks_major;       // set by the launcher: workgroup order of a split - 1: K range slowest (all tiles of a range are neighbours, i.e. on
-                      // one or two XCDs: only those L2s fetch that range's activation columns), 0: K range fastest
   int k_rot;          // set by the launcher (small grids, plain layers): M tile tm of a weight panel starts its K walk at slice tm * nk / tiles_m
                       // and wraps - the M tiles of a panel (neighbours on one XCD) then reach every weight line at different times: ONE of
                       // them takes the HBM miss, the others find the line in their L2 instead of all waiting for the same fill in lockstep
+  int krot_ok;        // set by the CALLER: k_rot may be used.  A row's summation order then depends on the M tile it falls into, so rows
+                      // with equal inputs no longer come out bit-identical: the DiT forward of a single clip per CFG half opts in
+                      // (foley_rt.hip::run_forward); foley_prepare (its row-periodicity check compares bit patterns), batches (clips of a
+                      // batch with equal noise stay bit-identical) and the op-level entries do not
   QkvSplitArgs qs;    // EPI_QKV_SPLIT: destination / norm / rotation description (qs.qkv, qs.M unused)
   int vec_out;        // set by the launcher: the problem qualifies for the LDS-transposed vector epilogue
   int wfmt;           // storage of W: 0 = the operand dtype, 1 = fp8 e4m3fn, 2 = fp8 e5m2 (bf16 activations; wave-specialised
@@ -120,7 +122,6 @@ int launch_gemm_ws_bf16(const GemmArgs& g, const GemmArgs* g1, int epi, int tile
 int launch_gemm_ws_f16(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, hipStream_t st);
 // 256x256 tiles on the BK = 32 mainloop (gemm_wide_impl.h): tile 31 = tap-fused conv k=3, 32 = plain linear layer (eight waves of
 // 128x64); single problem, vector epilogue, any weight storage
-extern thread_local int g_gemm_krot_ok;   // gemm.hip
 int launch_gemm_wide_bf16(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, hipStream_t st);
 int launch_gemm_wide_f16(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, hipStream_t st);
 

@@ -2,7 +2,7 @@
 
 run_forward's triple-stream blocks launch the audio and the (much smaller) visual stream as ONE GEMM / LayerNorm
 (launch_gemm_pair, launch_ln_mod_pair) and, for single-clip forwards, let the small-grid GEMMs rotate their K origin per M tile
-(g_gemm_krot_ok).  None of that is reachable through the C ABI, so the library carries test-only entries (foley_debug_gemm_pair,
+(GemmArgs::krot_ok).  None of that is reachable through the C ABI, so the library carries test-only entries (foley_debug_gemm_pair,
 foley_debug_gemm_krot, foley_debug_gemm_last, foley_debug_ln_mod_pair; not in include/foley_hip.h, typed here with ctypes).
 
 Every pair is checked three ways: each problem against an fp64 CPU reference; the pair against two single launches forced to
@@ -538,7 +538,7 @@ def _single_rot_run(dev, epi, A, W, b, dt, M, N, tile, opts, H, krot):
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("name,epi,M,N,K,tile,opts", ROT_CASES, ids=[c[0] for c in ROT_CASES])
 def test_k_origin_rotation_single(dev, name, epi, M, N, K, tile, opts, dt):
-    """Rotated K walk (g_gemm_krot_ok, as run_forward sets it for single-clip forwards): k_rot reported, fp64 within the gate of the
+    """Rotated K walk (GemmArgs::krot_ok, as run_forward sets it for single-clip forwards): k_rot reported, fp64 within the gate of the
     unrotated launch, M tile 0 (rotation 0) bit-identical to the unrotated launch, and the whole result within ROT_BOUND of it."""
     H = opts.get("H", 1)
     A = _rand((M, K), 4010).to(dt)
