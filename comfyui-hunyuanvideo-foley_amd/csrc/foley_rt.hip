@@ -174,6 +174,11 @@ struct foley_ctx {
   // graph: one captured loop iteration; valid while the workspace and weights stay put
   hipGraphExec_t graph_exec = nullptr;
   float graph_guidance = 0.f;
+  int graph_key = 0;                // edit_key() of the run the graph was captured for (0: a plain iteration)
+  // edit state (foley_set_edit; cleared by foley_prepare): ctx-owned copies of the source latents, the run's noise and the mask
+  bool edit = false;
+  DevBuf edit_x0, edit_noise, edit_mask;
+  int edit_x0_clips = 1, edit_mask_clips = 0;   // mask clips 0: no mask (all ones)
   // side stream: work that depends only on the iteration index (single-block AdaLN GEMMs) overlaps
   // the latent-dependent chain; joined through events (also inside the captured graph)
   hipStream_t side = nullptr;
@@ -364,7 +369,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   ctx_free_plan(c);
-  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab})
+  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask})
     if (b->p) hipFree(b->p);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
@@ -463,6 +468,7 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
   const bool reuse = c->have_buffers && same_dims(c->plan, *pl);
   if (!reuse) ctx_free_plan(c);
   c->prepared = false;
+  c->edit = false;                  // a plan without foley_set_edit is a plain run
 
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const size_t es = esize(T);
@@ -1116,7 +1122,55 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
   s.clips = pl.clips; s.C = c->cfg.latent_dim; s.L = pl.La; s.ncfg = pl.ncfg;
   s.guidance = pl.guidance; s.coef = pl.solver_coef; s.step_ptr = c->step_ctr;
   s.rows_out = c->xin; s.rows_dtype = c->cfg.compute_dtype;
+  if (c->edit) {
+    StepEditArgs e{};
+    e.s = s;
+    e.x0 = (const float*)c->edit_x0.p; e.noise = (const float*)c->edit_noise.p;
+    e.mask = c->edit_mask_clips ? (const float*)c->edit_mask.p : nullptr;
+    e.x0_clips = c->edit_x0_clips; e.mask_clips = c->edit_mask_clips;
+    return launch_solver_step_edit(e, st);
+  }
   return launch_solver_step(s, st);
+}
+
+// What a captured iteration depends on beyond the plan: plain vs edit, and the clip strides / presence of the edit operands
+// (their addresses are ctx-owned; foley_set_edit drops the graph when one moves).  A plain graph replayed for an edit run
+// would skip the blend, an edit graph replayed for a plain run would apply a stale one.
+static int edit_key(const foley_ctx* c) {
+  if (!c->edit) return 0;
+  return 1 | (c->edit_x0_clips == 1 ? 2 : 0) | (c->edit_mask_clips ? 4 : 0) | (c->edit_mask_clips == 1 ? 8 : 0);
+}
+
+extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const float* noise, const float* mask, int mask_clips,
+                              void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_edit: foley_prepare has not been called");
+  if (!x0 && !noise && !mask) {
+    c->edit = false;
+    return 0;
+  }
+  if (!x0 || !noise) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0 and noise are required (all three null clears the edit state)");
+  const foley_plan& pl = c->plan;
+  if (x0_clips != 1 && x0_clips != pl.clips) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0_clips must be 1 or the plan's clips");
+  if (mask && mask_clips != 1 && mask_clips != pl.clips)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: mask_clips must be 1 or the plan's clips");
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the buffers may be in use by a previous loop on this stream
+  const size_t plane = (size_t)c->cfg.latent_dim * pl.La * 4;
+  const void* old[3] = {c->edit_x0.p, c->edit_noise.p, c->edit_mask.p};
+  TRY(grow(c->edit_x0, (size_t)x0_clips * plane));
+  TRY(grow(c->edit_noise, (size_t)pl.clips * plane));
+  if (mask) TRY(grow(c->edit_mask, (size_t)mask_clips * pl.La * 4));
+  if (old[0] != c->edit_x0.p || old[1] != c->edit_noise.p || old[2] != c->edit_mask.p) ctx_drop_graph(c);
+  HIPTRY(hipMemcpyAsync(c->edit_x0.p, x0, (size_t)x0_clips * plane, hipMemcpyDeviceToDevice, st));
+  HIPTRY(hipMemcpyAsync(c->edit_noise.p, noise, (size_t)pl.clips * plane, hipMemcpyDeviceToDevice, st));
+  if (mask) HIPTRY(hipMemcpyAsync(c->edit_mask.p, mask, (size_t)mask_clips * pl.La * 4, hipMemcpyDeviceToDevice, st));
+  c->edit = true;
+  c->edit_x0_clips = x0_clips;
+  c->edit_mask_clips = mask ? mask_clips : 0;
+  return 0;
 }
 
 extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_progress_cb cb, void* user,
@@ -1127,6 +1181,7 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   HIPTRY(hipSetDevice(c->device));
   const foley_plan& pl = c->plan;
   const size_t xbytes = (size_t)pl.clips * c->cfg.latent_dim * pl.La * 4;
+  if (c->graph_exec && c->graph_key != edit_key(c)) ctx_drop_graph(c);
   if (use_graph && !c->graph_exec) {
     // Every per-iteration value is read from device memory (step counter, tables) and every
     // buffer is context-owned, so ONE captured iteration replays for the whole loop and for
@@ -1149,6 +1204,7 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
     if (rc != 0) return rc;
     if (e != hipSuccess) return FAIL(FOLEY_ERR_HIP, hipGetErrorString(e));
     c->graph_guidance = pl.guidance;
+    c->graph_key = edit_key(c);
   }
   c->abort_req.store(0, std::memory_order_relaxed);   // a request left over from before this loop is not for it
   HIPTRY(hipEventRecord(c->ev0, st));
@@ -1612,6 +1668,21 @@ extern "C" int foley_op_solver_step(const float* pred, float* x, float* x_saved,
                                     void* rows_out, int rows_dtype, void* stream) {
   StepArgs s{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
   return launch_solver_step(s, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
+                                         int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
+                                         int rows_dtype, const float* x0, int x0_clips, const float* noise, const float* mask,
+                                         int mask_clips, void* stream) {
+  StepEditArgs e{};
+  e.s = StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
+  e.x0 = x0; e.noise = noise; e.mask = mask; e.x0_clips = x0_clips; e.mask_clips = mask_clips;
+  return launch_solver_step_edit(e, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma,
+                                 float* out, void* stream) {
+  return launch_flow_mix(noise, x0, x0_clips, clips, C, L, sigma, out, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_latent_rows(const float* x, int clips, int C, int L, int ncfg, void* out, int out_dtype,

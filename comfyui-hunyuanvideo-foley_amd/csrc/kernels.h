@@ -218,6 +218,19 @@ struct StepArgs {
   int rows_dtype;
 };
 int launch_solver_step(const StepArgs& a, hipStream_t st);
+// Edit form of the same step (audio-to-audio / span regeneration): after a row flagged STEP_BLEND (8) - the iteration that
+// ends a solver step - x <- m*x + (1-m)*(s*noise + (1-s)*x0) with s = coef row column 5 (sigma_{k+1}); mask null = all ones.
+struct StepEditArgs {
+  StepArgs s;
+  const float* x0;     // [x0_clips, C, L] source latents (clip stride 0 when x0_clips == 1)
+  const float* noise;  // [clips, C, L] the run's initial noise
+  const float* mask;   // [mask_clips, L] 1 = regenerate (or null)
+  int x0_clips, mask_clips;
+};
+int launch_solver_step_edit(const StepEditArgs& a, hipStream_t st);
+// out [clips, C, L] = sigma*noise + (1-sigma)*x0 (x0 clip stride 0 when x0_clips == 1): the flow-match path's start state
+int launch_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma, float* out,
+                    hipStream_t st);
 
 // DAC tail: out[b, t] = tanh(bias + sum_{j<7, c<C} w[j*C + c] * s[b, t + j - 3, c])
 // DAC encoder: input conv 1 -> C (k=7) writing y and snake(y); rows [B*T, C] -> planes [B, C, T]

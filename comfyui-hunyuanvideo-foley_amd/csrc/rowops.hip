@@ -517,6 +517,89 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
   }
 }
 
+// Edit form (audio-to-audio / span regeneration): the same step, then - on rows flagged STEP_BLEND, the iterations that end a
+// solver step - the kept frames are pulled back onto the source's forward-noised path:
+//   x <- m*x + (1-m)*(s*noise + (1-s)*x0),  s = sigma_{k+1} (column 5 of the row), m = mask[clip][l] (1 = regenerate).
+// The blend is written as two products so that m = 1 returns x and m = 0 the target bit for bit under any contraction; the
+// un-blended update is the expression of solver_step_kernel, so an all-ones mask reproduces a plain run exactly.  Only plain
+// runs take solver_step_kernel.
+constexpr int STEP_BLEND = 8;
+
+template <typename OutT>
+__global__ __launch_bounds__(256) void solver_step_edit_kernel(const StepEditArgs e) {
+  __shared__ float tile[32][33];
+  const StepArgs& a = e.s;
+  const int it = *a.step_ptr;
+  const float* cf = a.coef + (long)it * 8;
+  const float w_new = cf[0], w_acc = cf[1], dt = cf[2], w_store = cf[3];
+  const int flags = (int)cf[4];
+  const float s_next = cf[5];
+  const int b = blockIdx.z;
+  const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const long rows = (long)a.clips * a.L;
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    float v = 0.f;
+    if (l < a.L && c < a.C) {
+      const long r = (long)b * a.L + l;
+      if (a.ncfg == 2) {
+        const float u = a.pred[r * a.C + c], cnd = a.pred[(rows + r) * a.C + c];
+        v = u + a.guidance * (cnd - u);
+      } else {
+        v = a.pred[r * a.C + c];
+      }
+    }
+    tile[i][tx] = v;
+  }
+  __syncthreads();
+  const float* x0b = e.x0 + (e.x0_clips == 1 ? 0L : (long)b * a.C * a.L);
+  const float* mb = e.mask ? e.mask + (e.mask_clips == 1 ? 0L : (long)b * a.L) : nullptr;
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, l = l0 + tx;
+    float xn = 0.f;
+    if (c < a.C && l < a.L) {
+      const long xi = ((long)b * a.C + c) * a.L + l;
+      const float v = tile[tx][i];
+      const float xc = a.x[xi];
+      float acc = 0.f;
+      if (a.d_acc) acc = (flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
+      const float deriv = (w_acc != 0.f) ? (w_new * v + w_acc * acc) : (w_new * v);
+      const float base = (flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
+      if (flags & STEP_SAVE_X) a.x_saved[xi] = xc;
+      xn = base + deriv * dt;
+      if (flags & STEP_BLEND) {
+        const float m = mb ? mb[l] : 1.f;
+        const float tgt = s_next * e.noise[xi] + (1.f - s_next) * x0b[(long)c * a.L + l];
+        xn = m * xn + (1.f - m) * tgt;
+      }
+      a.x[xi] = xn;
+      if (a.d_acc) a.d_acc[xi] = acc + w_store * v;
+    }
+    tile[tx][i] = xn;
+  }
+  __syncthreads();
+  if (a.rows_out) {
+    for (int i = ty; i < 32; i += 8) {
+      const int l = l0 + i, c = c0 + tx;
+      if (l < a.L && c < a.C) {
+        const OutT v = Cvt<OutT>::to(tile[i][tx]);
+        for (int g = 0; g < a.ncfg; ++g)
+          ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + l) * a.C + c] = v;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void flow_mix_kernel(const float* __restrict__ noise, const float* __restrict__ x0,
+                                                       long plane, long n, int x0_per_clip, float sigma,
+                                                       float* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float src = x0[x0_per_clip ? i : i % plane];
+  out[i] = sigma * noise[i] + (1.f - sigma) * src;
+}
+
 __global__ void step_increment_kernel(int* p) { *p = *p + 1; }
 
 // ------------------------------------------------------------------ DAC output conv (64 -> 1, k=7) + tanh
@@ -833,6 +916,32 @@ int launch_solver_step(const StepArgs& a, hipStream_t st) {
   else FOLEY_LAUNCH(solver_step_kernel<float>, grid, block, 0, st, a);
   FOLEY_LAUNCH_CHECK();
   FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_solver_step_edit(const StepEditArgs& e, hipStream_t st) {
+  const StepArgs& a = e.s;
+  if (!e.x0 || !e.noise) return foley_set_err("solver_step_edit: x0 and noise are required", __FILE__, __LINE__);
+  if ((e.x0_clips != 1 && e.x0_clips != a.clips) || (e.mask && e.mask_clips != 1 && e.mask_clips != a.clips))
+    return foley_set_err("solver_step_edit: x0 / mask clip count must be 1 or clips", __FILE__, __LINE__);
+  dim3 grid((a.L + 31) / 32, (a.C + 31) / 32, a.clips), block(256);
+  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(solver_step_edit_kernel<bf16_t>, grid, block, 0, st, e);
+  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(solver_step_edit_kernel<f16_t>, grid, block, 0, st, e);
+  else FOLEY_LAUNCH(solver_step_edit_kernel<float>, grid, block, 0, st, e);
+  FOLEY_LAUNCH_CHECK();
+  FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma, float* out,
+                    hipStream_t st) {
+  if (!noise || !x0 || !out || clips < 1 || C < 1 || L < 1 || (x0_clips != 1 && x0_clips != clips))
+    return foley_set_err("flow_mix: bad arguments (x0 clip count must be 1 or clips)", __FILE__, __LINE__);
+  const long plane = (long)C * L, n = plane * clips;
+  FOLEY_LAUNCH(flow_mix_kernel, dim3(grid1d(n, 256)), dim3(256), 0, st, noise, x0, plane, n, x0_clips != 1 || clips == 1 ? 1 : 0,
+               sigma, out);
   FOLEY_LAUNCH_CHECK();
   return 0;
 }

@@ -110,6 +110,7 @@ _SIGNATURES = {
     "foley_dit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, PROGRESS_CB, C.c_void_p, C.c_void_p]),
     "foley_abort": (C.c_int, [C.c_void_p]),
+    "foley_set_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_dac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                    C.c_void_p, C.c_void_p]),
@@ -144,6 +145,11 @@ _SIGNATURES = {
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "foley_op_solver_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p,
                                                                           C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_solver_step_edit": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                               C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                                               C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_flow_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                    C.c_void_p]),
     "foley_op_latent_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                        C.c_void_p]),
     "foley_op_dac_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -331,6 +337,23 @@ class FoleyContext:
             raise raised[0]
         _check(self.lib, rc, "foley_sample")
         return latents
+
+    def set_edit(self, x0: Optional[torch.Tensor], noise: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None):
+        """foley_set_edit after prepare(): x0 [1 | clips, C, La] and noise [clips, C, La] fp32, mask [La] or [1 | clips, La] fp32
+        (None: all ones) - all on this context's device; the library copies them.  x0 = noise = None clears the edit state."""
+        def _f32(t):
+            if t is None:
+                return None
+            if t.dtype != torch.float32 or t.device != self.device:
+                raise FoleyRuntimeError("set_edit: operands must be fp32 tensors on the context's device")
+            return t.contiguous()
+        x0, noise, mask = _f32(x0), _f32(noise), _f32(mask)
+        x0_clips = x0.shape[0] if x0 is not None else 0
+        mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_set_edit(self._h, _ptr(x0), x0_clips, _ptr(noise), _ptr(mask), mask_clips, _stream()),
+                   "foley_set_edit")
+        self._edit_keep = (x0, noise, mask)     # borrowed only until the copies on the stream are done
 
     def abort(self) -> None:
         """Ask a foley_sample running on another thread to stop after its current iteration (it raises FoleyRuntimeError)."""
@@ -682,6 +705,31 @@ def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows
     _check(lib, lib.foley_op_solver_step(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
                                          float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out),
                                          dt_of(rows_out), _stream()), "foley_op_solver_step")
+
+
+def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, x0, noise, mask=None):
+    """foley_op_solver_step_edit: x0 [1 | clips, C, L], noise [clips, C, L], mask [1 | clips, L] or None (all ones)."""
+    lib = load_library()
+    clips, Cc, L = x.shape
+    mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
+    _check(lib, lib.foley_op_solver_step_edit(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
+                                              float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), dt_of(rows_out),
+                                              _ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips, _stream()),
+           "foley_op_solver_step_edit")
+
+
+def op_flow_mix(noise: torch.Tensor, x0: torch.Tensor, sigma: float) -> torch.Tensor:
+    """foley_op_flow_mix: sigma*noise + (1 - sigma)*x0 -> new [clips, C, L] fp32; x0 [1 | clips, C, L] (1: shared)."""
+    lib = load_library()
+    if noise.dtype != torch.float32 or x0.dtype != torch.float32 or noise.dim() != 3 or x0.dim() != 3:
+        raise FoleyRuntimeError("op_flow_mix: noise [clips, C, L] and x0 [1 | clips, C, L] fp32")
+    clips, Cc, L = noise.shape
+    if tuple(x0.shape[1:]) != (Cc, L):
+        raise FoleyRuntimeError(f"op_flow_mix: x0 {tuple(x0.shape)} does not match noise {tuple(noise.shape)}")
+    out = torch.empty_like(noise)
+    _check(lib, lib.foley_op_flow_mix(_ptr(noise), _ptr(x0), x0.shape[0], clips, Cc, L, float(sigma), _ptr(out), _stream()),
+           "foley_op_flow_mix")
+    return out
 
 
 def op_latent_rows(x, ncfg, out):

@@ -13,7 +13,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
-from . import packers, tables
+from . import packers, runtime, tables
 from .config import DAC48K, DACConfig, DiTConfig
 from .runtime import FoleyContext, FoleyRuntimeError
 
@@ -144,8 +144,10 @@ def fp8_time_dtype(model):
 
 
 def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_feats: Dict[str, torch.Tensor],
-               La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str) -> dict:
-    """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables."""
+               La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str,
+               edit_i0: Optional[int] = None) -> dict:
+    """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables.
+    edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows."""
     cfg, dev = model.cfg, model.device
     f32 = lambda t: t.to(device=dev, dtype=torch.float32)
     clip, sync = f32(visual_feats["siglip2_feat"]), f32(visual_feats["syncformer_feat"])
@@ -169,17 +171,18 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     # The run's tables (schedule, solver coefficients, RoPE rows, position / up-sampling maps) depend on these scalars
     # only: built once per distinct run shape and kept on the device (host-side table building is milliseconds of
     # Python per call - more than the whole precompute on the GPU)
-    key = (La, Lv, Ls, Lt, steps, sampler, float(cfg.flow_shift), cfg.time_freq_dim, str(fp8_time), str(dev))
+    key = (La, Lv, Ls, Lt, steps, sampler, float(cfg.flow_shift), cfg.time_freq_dim, str(fp8_time), str(dev), edit_i0)
     cache = model.__dict__.setdefault("_tables_cache", {})
     tabs = cache.get(key)
     if tabs is None:
-        tb = tables.build_tables(La, Lv, Ls, Lt, steps, sampler, cfg.flow_shift, cfg.time_freq_dim, fp8_time=fp8_time)
+        tb = tables.build_tables(La, Lv, Ls, Lt, steps, sampler, cfg.flow_shift, cfg.time_freq_dim, fp8_time=fp8_time,
+                                 edit_i0=edit_i0)
         tabs = {k: tb[k].to(dev).contiguous() for k in ("t_feat", "rope_cos", "rope_sin", "pos_audio_self", "pos_visual_self",
                                                         "pos_linear", "sync_gather", "solver_coef")}
         if len(cache) >= 16:
             cache.pop(next(iter(cache)))
         cache[key] = tabs
-    plan = {"ncfg": ncfg, "clips": batch_size, "La": La, "Lv": Lv, "Ls": Ls, "Lt": Lt, "n_iter": steps,
+    plan = {"ncfg": ncfg, "clips": batch_size, "La": La, "Lv": Lv, "Ls": Ls, "Lt": Lt, "n_iter": tabs["solver_coef"].shape[0],
             "guidance": float(guidance_scale), "rope_len": tabs["rope_cos"].shape[0],
             "text": text_in.contiguous(), "clip": clip_in.contiguous(), "sync": sync_in.contiguous()}
     plan.update(tabs)
@@ -191,17 +194,32 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
                                    generator: Optional[torch.Generator] = None, use_graph: bool = True,
                                    progress: Optional[Callable[[int, int], None]] = None,
                                    return_latents: bool = False, noise: Optional[torch.Tensor] = None,
-                                   _abort_event: Optional[threading.Event] = None):
+                                   _abort_event: Optional[threading.Event] = None, edit=None):
     """Same contract as the reference function of this name (utils.py:125-258):
-    returns (audio [bs, 1, T] fp32 on the model's device, sample_rate)."""
+    returns (audio [bs, 1, T] fp32 on the model's device, sample_rate).
+
+    edit (host/audio_edit.EditSpec: x0, strength, mask): audio-to-audio / span regeneration - the suffix of the plain run's
+    iterations that `strength` selects, started from the source latents x0 noised to that point, with the kept frames of the
+    mask held on the source's forward-noised path (foley_set_edit).  The noise is drawn exactly as for a plain run."""
     cfg = model.cfg
     La = int(audio_len_in_s * cfg.frame_rate)
     if noise is None:
         noise = draw_noise(batch_size, cfg.latent_dim, La, model.dtype, generator)
     latents = noise.to(device=model.device, dtype=torch.float32).contiguous()
-    plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler)
-    model.attach_dac(dac)
-    model.ctx.prepare(plan)
+    if edit is None:
+        plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler)
+        model.attach_dac(dac)
+        model.ctx.prepare(plan)
+    else:
+        k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
+        x0, mask = edit.device_operands(model.device, batch_size, La)
+        plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
+                          edit_i0=i0)
+        model.attach_dac(dac)
+        model.ctx.prepare(plan)
+        model.ctx.set_edit(x0, latents, mask)
+        sigma0 = float(tables.sigma_grid(num_inference_steps, cfg.flow_shift)[k0])
+        latents = runtime.op_flow_mix(latents, x0, sigma0)
     if _abort_event is not None and _abort_event.is_set():      # another replica of a data-parallel run failed meanwhile
         raise FoleyRuntimeError("sampling aborted: another replica failed")
     model.ctx.sample(latents, use_graph=use_graph, progress=progress)
@@ -293,7 +311,7 @@ def replicate(model: FoleyModel, dac: Optional[FoleyDAC], devices: Sequence) -> 
 def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Sequence, guidance_scale: float,
                           num_inference_steps: int, batch_size: int, sampler: str,
                           generator: Optional[torch.Generator] = None, use_graph: bool = True,
-                          progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False):
+                          progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None):
     """`denoise_process_with_generator` with the clips of the batch sharded over `replicas` (the pairs
     `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199: the
     batch only repeats the conditioning), so there is no collective: the noise of the WHOLE batch is drawn once
@@ -302,7 +320,8 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     summation order - and equal to bf16 / fp32 accuracy otherwise.  A shard of ONE clip never is bit-identical to that
     clip inside a larger shard: single-clip forwards rotate the K origin of their small-grid GEMMs per M tile (K-origin
     rotation, gemm.hip g_gemm_krot_ok), a different but deterministic summation order (tests/test_pairs_gpu.py pins how
-    far it moves a result).  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
+    far it moves a result).  `edit` as for denoise_process_with_generator: per-clip source latents and masks are sharded with
+    the noise.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
     from .distributed import shard_range
     if not replicas:
         raise FoleyRuntimeError("no replicas")
@@ -349,7 +368,8 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                 results[r] = denoise_process_with_generator(
                     visual_feats, text_feats, audio_len_in_s, model, dac, guidance_scale, num_inference_steps, hi - lo,
                     sampler, use_graph=use_graph, noise=noise[lo:hi], return_latents=True,
-                    progress=progress if r == 0 else None, _abort_event=failed)
+                    progress=progress if r == 0 else None, _abort_event=failed,
+                    edit=edit.shard(lo, hi, batch_size) if edit is not None else None)
                 torch.cuda.current_stream().synchronize()
         except Exception as e:          # surfaced on the calling thread
             running[r] = False          # FIRST: a second failing (or aborted) worker must not keep the first one waiting on it

@@ -18,6 +18,8 @@ import torch
 
 SOLVERS = ("euler", "heun-2", "midpoint-2", "kutta-4")
 STEP_SAVE_X, STEP_USE_SAVED, STEP_ACC_RESET = 1, 2, 4
+STEP_BLEND = 8          # edit runs only (foley_set_edit): blend towards the source after this row, sigma_{k+1} in column 5
+SOLVER_STAGES = {"euler": 1, "heun-2": 2, "midpoint-2": 2, "kutta-4": 4}
 
 
 def sigma_grid(steps: int, shift: float = 1.0) -> torch.Tensor:
@@ -76,6 +78,36 @@ def solver_table(sigmas: torch.Tensor, solver: str, n_iter: int) -> torch.Tensor
     return rows
 
 
+def edit_start(steps: int, solver: str, strength: float):
+    """(k0, i0) of an edit run at `strength`: the run is the suffix [i0, steps) of the plain run's iterations, starting from the
+    source noised to sigma_{k0}.  Counted in whole solver steps (the diffusers img2img rule): n_full = steps // stages,
+    n_keep = min(int(n_full * strength), n_full), k0 = n_full - n_keep, i0 = k0 * stages.  n_keep = 0 is refused."""
+    if solver not in SOLVERS:
+        raise ValueError(f"Solver {solver} not supported. Supported solvers: {list(SOLVERS)}")
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must lie in (0, 1], got {strength}")
+    stages = SOLVER_STAGES[solver]
+    n_full = int(steps) // stages
+    n_keep = min(int(n_full * strength), n_full)
+    if n_keep < 1:
+        raise ValueError(f"strength {strength} leaves no {solver} step of {steps} to run (n_full = {n_full}): raise the "
+                         "strength or the step count")
+    k0 = n_full - n_keep
+    return k0, k0 * stages
+
+
+def edit_solver_table(sigmas: torch.Tensor, solver: str, n_iter: int, i0: int = 0) -> torch.Tensor:
+    """Rows [i0:] of solver_table with STEP_BLEND and sigma_{k+1} (column 5) on every iteration that ends a solver step."""
+    rows = solver_table(sigmas, solver, n_iter).clone()
+    stages = SOLVER_STAGES[solver]
+    for i in range(stages - 1, n_iter, stages):
+        k = i // stages
+        rows[i, 4] = float(int(rows[i, 4]) | STEP_BLEND)
+        rows[i, 5] = sigmas[k + 1]
+    return rows[i0:].contiguous()
+
+
 def timestep_features(t: torch.Tensor, dim: int = 256, max_period: int = 10000) -> torch.Tensor:
     half = dim // 2
     freqs = torch.exp(-math.log(max_period) * torch.arange(0, half, dtype=torch.float32) / half)
@@ -112,16 +144,18 @@ def interleaved_positions(la: int, lv: int):
 
 
 def build_tables(la: int, lv: int, ls: int, lt: int, steps: int, solver: str, shift: float,
-                 time_freq_dim: int = 256, fp8_time: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
+                 time_freq_dim: int = 256, fp8_time: Optional[torch.dtype] = None,
+                 edit_i0: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """fp8_time: round the sinusoid timestep features through this fp8 type (fp8-wrapped model under
-    autocast, embed_layers.py:134 - golden g8)."""
+    autocast, embed_layers.py:134 - golden g8).  edit_i0 (edit runs): the per-iteration tables are the rows [edit_i0:] of the
+    plain run's, the solver rows carry the blend (edit_solver_table)."""
     sig = sigma_grid(steps, shift)
     ts = model_timesteps(sig)
     n_iter = steps
     pa, pv = interleaved_positions(la, lv)
     rope_len = max(2 * la, lt, lv) + 1
     cos, sin = rope_table(rope_len)
-    return {
+    out = {
         "sigmas": sig,
         "timesteps": ts,
         "t_feat": (timestep_features(ts, time_freq_dim) if fp8_time is None
@@ -132,3 +166,7 @@ def build_tables(la: int, lv: int, ls: int, lt: int, steps: int, solver: str, sh
         "pos_linear": torch.arange(max(la, lv, lt), dtype=torch.int32),
         "sync_gather": nearest_exact_index(la, ls).to(torch.int32),
     }
+    if edit_i0 is not None:
+        out["t_feat"] = out["t_feat"][edit_i0:].contiguous()
+        out["solver_coef"] = edit_solver_table(sig, solver, n_iter, edit_i0)
+    return out

@@ -321,9 +321,14 @@ class HunyuanFoleySampler:
 
     def generate_audio(self, hunyuan_model, hunyuan_deps, frame_rate, duration, prompt, negative_prompt, cfg_scale,
                        steps, sampler, batch_size, seed, force_offload, image=None, torch_compile_cfg=None,
-                       block_swap_args=None, features=None):
+                       block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
-        {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench."""
+        {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.
+
+        Audio editing (keyword-only, not sockets; host/audio_edit.py): `audio` (an AUDIO dict, batch 1 or batch_size) is
+        re-sampled from part-way down the schedule - `strength` in (0, 1] selects how far (1.0: from pure noise) - and
+        `regenerate` [(start_s, end_s), ...] limits the change to those spans (crossfade_s linear ramps at their edges; the
+        rest of the clip keeps the source).  A duration past the end of `audio` extends it (strength 1.0 only)."""
         model, deps = hunyuan_model, hunyuan_deps
         device = model.device
         rng = torch.Generator(device="cpu").manual_seed(seed)          # nodes.py:273
@@ -343,6 +348,13 @@ class HunyuanFoleySampler:
                       "syncformer_feat": model.get_empty_sync_sequence(bs=1, len=sync_len)}
             res = encode_text_feat([negative_prompt, prompt], deps, device, model.dtype)
             text = {"text_feat": res[1:], "uncond_text_feat": res[:1]}
+        edit = None
+        if audio is not None:
+            from .host import audio_edit as _edit
+            edit = _edit.prepare_edit(audio, model, deps["dac_model"], audio_len_in_s, steps, sampler, batch_size,
+                                      strength=strength, regenerate=regenerate, crossfade_s=crossfade_s)
+        elif strength != 1.0 or regenerate is not None:
+            raise ValueError("strength / regenerate edit an input clip: pass it as audio=")
         pbar = None
         try:
             import comfy.utils  # type: ignore
@@ -357,11 +369,12 @@ class HunyuanFoleySampler:
             devs = [model.device] + [torch.device("cuda", i) for i in range(n_dev) if i != model.device.index]
             reps = _sampler.replicate(model, deps["dac_model"], devs[:batch_size])
             audio, sr = _sampler.denoise_process_multi(visual, text, audio_len_in_s, reps, cfg_scale, steps, batch_size,
-                                                       sampler, generator=rng, progress=progress)
+                                                       sampler, generator=rng, progress=progress, edit=edit)
         else:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
-                num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress)
+                num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
+                edit=edit)
         waveform_batch = audio.float().cpu()
         first = {"waveform": waveform_batch[0].unsqueeze(0), "sample_rate": sr}
         return (first, {"waveform": waveform_batch, "sample_rate": sr})

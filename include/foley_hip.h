@@ -150,6 +150,25 @@ int foley_sample(foley_ctx* ctx, float* latents, int use_graph, foley_progress_c
  * stops; one that arrives while no loop runs is dropped by the next foley_sample on entry. */
 int foley_abort(foley_ctx* ctx);
 
+/* Audio editing (additive within ABI 12): audio-to-audio variation and time-span regeneration.  Called after foley_prepare with
+ * the plan of the SUFFIX [i0, n_iter) of the plain run's iterations (its t_feat and solver_coef rows); the caller starts the loop
+ * from sigma_{k0}*noise + (1 - sigma_{k0})*x0 (foley_op_flow_mix).  Rows of solver_coef whose flags (column 4) carry
+ * FOLEY_STEP_BLEND - the iterations that END a solver step, after which the sigma index moves to k+1 - hold sigma_{k+1} in
+ * column 5, and after them every element is pulled back onto the source's forward-noised path:
+ *   x <- m*x + (1 - m)*(sigma_{k+1}*noise + (1 - sigma_{k+1})*x0)     (m = mask[clip][l], 1 = regenerate)
+ * and the next model input is staged from the blended value.  Intermediate stages of multi-stage solvers are not blended.
+ * m = 1 leaves x bit for bit (an all-ones mask at i0 = 0 is the plain run exactly), m = 0 gives the target bit for bit.
+ *   x0    [x0_clips, latent_dim, La] fp32: source latents (the DAC posterior mean), x0_clips 1 (shared) or plan.clips
+ *   noise [plan.clips, latent_dim, La] fp32: the run's initial noise
+ *   mask  [mask_clips, La] fp32 in [0, 1] or NULL (all ones), mask_clips 1 or plan.clips
+ * The operands are copied into context-owned buffers (captured graphs never hold the caller's pointers); the captured iteration
+ * is keyed on plain vs edit, so a context alternates between the two safely.  foley_prepare clears the edit state, as does a call
+ * with x0, noise and mask all NULL.  x0 / noise missing with a mask, or clip counts other than 1 / plan.clips: FOLEY_ERR_INVALID;
+ * before foley_prepare: FOLEY_ERR_STATE. */
+#define FOLEY_STEP_BLEND 8
+int foley_set_edit(foley_ctx* ctx, const float* x0, int x0_clips, const float* noise, const float* mask, int mask_clips,
+                   void* stream);
+
 /* DAC-VAE decoder: latents [clips, latent_dim, T] fp32 -> waveform [clips, 1, T*hop] fp32. */
 int foley_dac_decode(foley_ctx* ctx, const float* latents, int clips, int T, float* wave, void* stream);
 
@@ -329,6 +348,15 @@ int foley_op_qkv_split(const float* qkv, int M, int L, int H, int nK, const floa
 int foley_op_solver_step(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
                          int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
                          int rows_dtype, void* stream);
+/* foley_op_solver_step's edit form (see foley_set_edit): the same update, then the blend after FOLEY_STEP_BLEND rows;
+ * x0 [x0_clips, C, L], noise [clips, C, L], mask [mask_clips, L] or NULL (all ones); x0_clips / mask_clips 1 or clips. */
+int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
+                              int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
+                              int rows_dtype, const float* x0, int x0_clips, const float* noise, const float* mask,
+                              int mask_clips, void* stream);
+/* Start state of an edit run: out [clips, C, L] = sigma*noise + (1 - sigma)*x0, x0 [x0_clips, C, L] with x0_clips 1 or clips. */
+int foley_op_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma,
+                      float* out, void* stream);
 int foley_op_latent_rows(const float* x, int clips, int C, int L, int ncfg, void* out, int out_dtype,
                          void* stream);
 int foley_op_dac_out(const float* s, const float* w, const float* bias, int B, int T, int C, float* out,
