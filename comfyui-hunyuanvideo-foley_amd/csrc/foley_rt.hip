@@ -132,6 +132,15 @@ struct foley_ctx {
   int sync_per = 0;                 // 8 when the token rows of the first sync_lead cfg halves repeat with period 8 (empty sync features), else 0
   int sync_lead = 0;                // number of leading 8-periodic halves: ncfg = all of them (text-to-audio); 1 of 2 = a video clip under
                                     // CFG (unconditional half first, utils.py:150-176); 0 = none
+  // conditioning layout (foley_prepare_sets): the text K/V sets and the visual halves (sync_tok, svec, smod) are held per cfg half
+  // (ncfg slots, read by divisor clips) or per batch row (ncfg*clips slots, divisor 1); v_cond0 holds the distinct visual sets
+  bool sets_mode = false, txt_rows = false, vis_rows = false;
+  int vis_src = 0;                  // sets in v_cond0
+  std::vector<int32_t> set_maps;    // text_of ++ vis_of of the prepared run (empty: foley_prepare); keys the captured graph
+  int* set_idx = nullptr;           // [ncfg*clips*(Lt + Ls + 8)] row gather tables of the per-row layouts (text, sync, periodic lead)
+  float* sync_lead_rows = nullptr;  // per-row visual layout: [ncfg*clips*8, D] the 8 distinct rows of each leading periodic half,
+                                    // packed - the per-iteration SiLU(token + vec) of all of them is then one launch
+  float* tG = nullptr;              // [ncfg*clips*Lt, 2D] text K/V rows gathered per batch row
   int* flag = nullptr;              // device scratch word of the periodicity check
   int* ident_idx = nullptr;         // 0..max(Lv,La)-1
   // forward workspace
@@ -454,7 +463,19 @@ static int resolve_forward_weights(foley_ctx* c) {
 // --------------------------------------------------------------------------- prepare
 // Everything that does not depend on the latents: time embedding for every loop
 // iteration, the triple blocks' AdaLN tables, text K/V per block, cond/visual/sync embedders.
+static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, void* stream_v);
+
 extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v) {
+  return prepare_impl(c, pl, nullptr, stream_v);
+}
+
+extern "C" int foley_prepare_sets(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, void* stream_v) {
+  if (!sets) return prepare_impl(c, pl, nullptr, stream_v);
+  if (!sets->text_of || !sets->vis_of) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: null set map");
+  return prepare_impl(c, pl, sets, stream_v);
+}
+
+static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, void* stream_v) {
   if (!c || !pl) return FAIL(FOLEY_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
   hipStream_t st = (hipStream_t)stream_v;
@@ -464,19 +485,50 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
       pl->Lt < 1 || pl->n_iter < 1)
     return FAIL(FOLEY_ERR_INVALID, "bad plan dimensions");
   if (pl->rope_len < 2 * pl->La) return FAIL(FOLEY_ERR_INVALID, "rope table shorter than 2*La");
+  // Conditioning sets: foley_prepare has one text set and one visual set per cfg half.  With set maps, a stream whose map is
+  // b -> b / clips over ncfg sets keeps that layout; any other map lays the stream out per batch row.
+  int n_text = pl->ncfg, n_vis = pl->ncfg;
+  bool t_rows = false, v_rows = false;
+  std::vector<int32_t> maps;
+  if (sets) {
+    const int Bc0 = pl->ncfg * pl->clips;
+    if (sets->n_text < 1 || sets->n_vis < 1 || sets->n_text > Bc0 || sets->n_vis > Bc0)
+      return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: set counts must be in [1, ncfg*clips]");
+    maps.assign(sets->text_of, sets->text_of + Bc0);
+    maps.insert(maps.end(), sets->vis_of, sets->vis_of + Bc0);
+    bool t_half = sets->n_text == pl->ncfg, v_half = sets->n_vis == pl->ncfg;
+    for (int b = 0; b < Bc0; ++b) {
+      const int t = maps[b], v = maps[Bc0 + b];
+      if (t < 0 || t >= sets->n_text || v < 0 || v >= sets->n_vis) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: set index out of range");
+      t_half = t_half && t == b / pl->clips;
+      v_half = v_half && v == b / pl->clips;
+    }
+    n_text = sets->n_text;
+    n_vis = sets->n_vis;
+    t_rows = !t_half;
+    v_rows = !v_half;
+    if (v_rows && Bc0 > 32) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: per-clip visual features take at most 32 batch rows");
+  }
   HIPTRY(hipStreamSynchronize(st));
-  const bool reuse = c->have_buffers && same_dims(c->plan, *pl);
+  const bool reuse = c->have_buffers && same_dims(c->plan, *pl) && c->sets_mode == (sets != nullptr) && c->txt_rows == t_rows &&
+                     c->vis_rows == v_rows;
   if (!reuse) ctx_free_plan(c);
   c->prepared = false;
   c->edit = false;                  // a plan without foley_set_edit is a plain run
+  c->sets_mode = sets != nullptr;
+  c->txt_rows = t_rows;
+  c->vis_rows = v_rows;
+  c->vis_src = n_vis;
 
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const size_t es = esize(T);
   const int ncfg = pl->ncfg, clips = pl->clips, La = pl->La, Lv = pl->Lv, Ls = pl->Ls, Lt = pl->Lt;
   const int Bc = ncfg * clips, M = Bc * La, Mv = Bc * Lv, S = La + Lv, NI = pl->n_iter;
+  const int th = t_rows ? Bc : ncfg, vh = v_rows ? Bc : ncfg;   // text K/V slots, visual halves
   const int hidmax = f.mlp_hidden > f.conv_hidden ? f.mlp_hidden : f.conv_hidden;
   const int Lmax = std::max(std::max(La, Lv), Lt);
-  const int rmax = std::max(std::max(NI, ncfg * Lt), std::max(ncfg * Lv, ncfg * Ls));
+  const int rsets = sets ? Bc : ncfg;   // set maps: sized for the most sets a plan of these dimensions can carry
+  const int rmax = std::max(std::max(NI, rsets * Lt), std::max(rsets * Lv, rsets * Ls));
   // widest row any precompute stage writes into the scratch (every configurable feature width)
   const size_t tcols = std::max({D, f.sync_hidden, f.cond_dim, f.clip_dim, f.sync_dim, f.time_freq_dim});
 
@@ -484,11 +536,14 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
   if (!reuse) {
     ALLOC(c->vec_table, (size_t)NI * D * 4);
     ALLOC(c->modtab, (size_t)f.depth_triple * 2 * NI * 9 * D * 4);
-    ALLOC(c->txt_k, (size_t)f.depth_triple * ncfg * H * Lt * 128 * es);
-    ALLOC(c->txt_v, (size_t)f.depth_triple * ncfg * H * ((Lt + 31) & ~31) * 128 * es);
-    HIPTRY(hipMemsetAsync(c->txt_v, 0, (size_t)f.depth_triple * ncfg * H * ((Lt + 31) & ~31) * 128 * es, st));
-    ALLOC(c->v_cond0, (size_t)ncfg * Lv * D * 4);
-    ALLOC(c->sync_tok, (size_t)ncfg * Ls * D * 4);
+    ALLOC(c->txt_k, (size_t)f.depth_triple * th * H * Lt * 128 * es);
+    ALLOC(c->txt_v, (size_t)f.depth_triple * th * H * ((Lt + 31) & ~31) * 128 * es);
+    HIPTRY(hipMemsetAsync(c->txt_v, 0, (size_t)f.depth_triple * th * H * ((Lt + 31) & ~31) * 128 * es, st));
+    ALLOC(c->v_cond0, (size_t)vh * Lv * D * 4);
+    ALLOC(c->sync_tok, (size_t)vh * Ls * D * 4);
+    if (sets) ALLOC(c->set_idx, (size_t)Bc * (Lt + Ls + 8) * 4);
+    if (v_rows) ALLOC(c->sync_lead_rows, (size_t)Bc * 8 * D * 4);
+    if (t_rows) ALLOC(c->tG, (size_t)Bc * Lt * 2 * D * 4);
     ALLOC(c->flag, 256);
     ALLOC(c->xin, (size_t)M * C * es);
     ALLOC(c->audio, (size_t)M * D * 4);
@@ -505,8 +560,8 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     ALLOC(c->att_v, (size_t)Mv * D * es);
     ALLOC(c->hid_a, (size_t)M * hidmax * es);
     ALLOC(c->hid_v, (size_t)Mv * f.mlp_hidden * es);
-    ALLOC(c->svec, (size_t)ncfg * Ls * D * es);
-    ALLOC(c->smod, (size_t)f.depth_single * ncfg * Ls * 6 * D * 4);
+    ALLOC(c->svec, (size_t)vh * Ls * D * es);
+    ALLOC(c->smod, (size_t)f.depth_single * vh * Ls * 6 * D * 4);
     ALLOC(c->pred, (size_t)M * C * 4);
     ALLOC(c->part_a, (size_t)PART_CAP * M * D * 4);     // sized for fp32 slabs; 16-bit slabs (slab16()) use half of it
     ALLOC(c->part_v, (size_t)PART_CAP * Mv * D * 4);
@@ -521,7 +576,7 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     ALLOC(c->pos_visual_self, (size_t)Lv * 4);
     ALLOC(c->pos_linear, (size_t)Lmax * 4);
     ALLOC(c->sync_gather, (size_t)La * 4);
-    ALLOC(c->rep_idx, (size_t)clips * Lv * 4);
+    ALLOC(c->rep_idx, (size_t)(v_rows ? Bc : clips) * Lv * 4);
     {
       const int rl[3] = {La, Lv, Lmax};
       for (int k = 0; k < 3; ++k) {
@@ -529,7 +584,7 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
         ALLOC(c->rot_sin[k], (size_t)rl[k] * 64 * 4);
       }
     }
-    {
+    if (!v_rows) {
       std::vector<int> idx((size_t)clips * Lv);
       for (size_t j = 0; j < idx.size(); ++j) idx[j] = (int)(j % Lv);
       HIPTRY(hipMemcpy(c->rep_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
@@ -540,6 +595,25 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     ALLOC(c->tF, (size_t)rmax * 2 * D * 4);
     c->have_buffers = true;
   }
+  if (sets) {
+    // per-row gather tables: text K/V rows (row b, token t) <- set text_of[b]; sync token rows and the visual stream's start
+    // rows (rep_idx, read by every forward) <- set vis_of[b].  Copied while nothing on `st` reads them (synchronised above).
+    std::vector<int> idx((size_t)Bc * (Lt + Ls));
+    for (int b = 0; b < Bc; ++b) {
+      for (int t = 0; t < Lt; ++t) idx[(size_t)b * Lt + t] = maps[b] * Lt + t;
+      for (int s = 0; s < Ls; ++s) idx[(size_t)Bc * Lt + (size_t)b * Ls + s] = maps[Bc + b] * Ls + s;
+    }
+    HIPTRY(hipMemcpy(c->set_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    if (v_rows) {
+      std::vector<int> rep((size_t)Bc * Lv);
+      for (int b = 0; b < Bc; ++b)
+        for (int j = 0; j < Lv; ++j) rep[(size_t)b * Lv + j] = maps[Bc + b] * Lv + j;
+      HIPTRY(hipMemcpy(c->rep_idx, rep.data(), rep.size() * 4, hipMemcpyHostToDevice));
+    }
+  }
+  // a captured iteration belongs to one set map (the tables it reads are rewritten in place, so this is for safety, not layout)
+  if (c->graph_exec && maps != c->set_maps) ctx_drop_graph(c);
+  c->set_maps = std::move(maps);
   if (c->graph_exec && c->graph_guidance != pl->guidance) ctx_drop_graph(c);
   // the plan's lookup tables are copied so that captured kernels keep valid addresses
   const foley_plan in = *pl;
@@ -592,21 +666,23 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     Lin c1, c2;
     TRY(get_lin(c, "cond1", T, D, f.cond_dim, true, &c1));
     TRY(get_lin(c, "cond2", T, D, D, true, &c2));
-    TRY(launch_cast(pl->text, FOLEY_F32, tA, T, (long)ncfg * Lt * f.cond_dim, st));
-    TRY(launch_gemm(gemm_plain(tA, ncfg * Lt, c1, tB, D), T, EPI_SILU_T, 0, st));
-    TRY(launch_gemm(gemm_plain(tB, ncfg * Lt, c2, tA, D), T, EPI_STORE_T, 0, st));  // tA = cond embedding
+    TRY(launch_cast(pl->text, FOLEY_F32, tA, T, (long)n_text * Lt * f.cond_dim, st));
+    TRY(launch_gemm(gemm_plain(tA, n_text * Lt, c1, tB, D), T, EPI_SILU_T, 0, st));
+    TRY(launch_gemm(gemm_plain(tB, n_text * Lt, c2, tA, D), T, EPI_STORE_T, 0, st));  // tA = cond embedding
     for (int b = 0; b < f.depth_triple; ++b) {
       Lin kv;
       const void* kn;
       TRY(get_lin(c, "t" + std::to_string(b) + ".t_kv", T, 2 * D, D, true, &kv));
       TRY(get_tensor(c, "t" + std::to_string(b) + ".t_kn", FOLEY_F32, {128}, &kn));
-      TRY(launch_gemm(gemm_plain(tA, ncfg * Lt, kv, tF, 2 * D), T, EPI_STORE_F32, 0, st));
+      TRY(launch_gemm(gemm_plain(tA, n_text * Lt, kv, tF, 2 * D), T, EPI_STORE_F32, 0, st));
+      // per-row layout: the distinct sets' K/V rows are gathered into one set per batch row before the head split
+      if (t_rows) TRY(launch_gather_rows(tF, c->set_idx, Bc * Lt, 1, n_text * Lt, 2 * D, c->tG, st));
       QkvSplitArgs q{};
-      q.qkv = tF; q.M = ncfg * Lt; q.L = Lt; q.H = H; q.nK = 2;
+      q.qkv = t_rows ? c->tG : tF; q.M = th * Lt; q.L = Lt; q.H = H; q.nK = 2;
       q.gain[0] = (const float*)kn; q.pos[0] = pl->pos_linear;
       const int Ltp = (Lt + 31) & ~31;
-      q.dst[0] = (char*)c->txt_k + (size_t)b * ncfg * H * Lt * 128 * es;
-      q.dst[1] = (char*)c->txt_v + (size_t)b * ncfg * H * (foley_is_half(T) ? Ltp : Lt) * 128 * es;
+      q.dst[0] = (char*)c->txt_k + (size_t)b * th * H * Lt * 128 * es;
+      q.dst[1] = (char*)c->txt_v + (size_t)b * th * H * (foley_is_half(T) ? Ltp : Lt) * 128 * es;
       q.out_dtype = T; q.vt_pitch = foley_is_half(T) ? Ltp : 0;
       q.S_tot = Lt; q.tok_off = 0; q.eps = 1e-6f; q.cos_tab = pl->rope_cos; q.sin_tab = pl->rope_sin;
       TRY(launch_qkv_split(q, st));
@@ -618,9 +694,9 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     Lin w13, w2;
     TRY(get_lin(c, "vis.w13", T, 2 * D, f.clip_dim, false, &w13));
     TRY(get_lin(c, "vis.w2", T, D, D, false, &w2));
-    TRY(launch_cast(pl->clip, FOLEY_F32, tA, T, (long)ncfg * Lv * f.clip_dim, st));
-    TRY(launch_gemm(gemm_plain(tA, ncfg * Lv, w13, tB, D), T, EPI_SILUGATE_T, 0, st));
-    TRY(launch_gemm(gemm_plain(tB, ncfg * Lv, w2, c->v_cond0, D), T, EPI_STORE_F32, 0, st));
+    TRY(launch_cast(pl->clip, FOLEY_F32, tA, T, (long)n_vis * Lv * f.clip_dim, st));
+    TRY(launch_gemm(gemm_plain(tA, n_vis * Lv, w13, tB, D), T, EPI_SILUGATE_T, 0, st));
+    TRY(launch_gemm(gemm_plain(tB, n_vis * Lv, w2, c->v_cond0, D), T, EPI_STORE_F32, 0, st));
   }
 
   // 5. sync features: + pos emb, Linear, SiLU, ConvMLP(k=1), nearest-exact up-sampling (hifi_foley.py:755-762)
@@ -631,21 +707,24 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     TRY(get_lin(c, "sync.w13", T, 2 * f.sync_hidden, D, false, &w13));
     TRY(get_lin(c, "sync.w2", T, D, f.sync_hidden, false, &w2));
     TRY(get_tensor(c, "sync_pos", FOLEY_F32, {8, f.sync_dim}, &pos));
-    TRY(launch_add_periodic(pl->sync, (const float*)pos, ncfg * Ls, f.sync_dim, 8, tA, T, st));
-    TRY(launch_gemm(gemm_plain(tA, ncfg * Ls, s0, tB, D), T, EPI_SILU_T, 0, st));
-    TRY(launch_gemm(gemm_plain(tB, ncfg * Ls, w13, tA, f.sync_hidden), T, EPI_SILUGATE_T, 0, st));
+    TRY(launch_add_periodic(pl->sync, (const float*)pos, n_vis * Ls, f.sync_dim, 8, tA, T, st));
+    TRY(launch_gemm(gemm_plain(tA, n_vis * Ls, s0, tB, D), T, EPI_SILU_T, 0, st));
+    TRY(launch_gemm(gemm_plain(tB, n_vis * Ls, w13, tA, f.sync_hidden), T, EPI_SILUGATE_T, 0, st));
     // The up-sampling to the audio frame rate is not materialised: consumers address the Ls token rows
     // through RowBcast mode 2 (common.h), so everything derived from the tokens alone - SiLU(token + vec)
     // and the single-stream blocks' modulation GEMM - runs on ncfg*Ls rows instead of ncfg*La.
-    TRY(launch_gemm(gemm_plain(tA, ncfg * Ls, w2, c->sync_tok, D), T, EPI_STORE_F32, 0, st));
+    // Per-row layout: the distinct sets' token rows are gathered into one half per batch row.
+    TRY(launch_gemm(gemm_plain(tA, n_vis * Ls, w2, v_rows ? tF : c->sync_tok, D), T, EPI_STORE_F32, 0, st));
+    if (v_rows) TRY(launch_gather_rows(tF, c->set_idx + (size_t)Bc * Lt, Bc * Ls, 1, n_vis * Ls, D, c->sync_tok, st));
     // Empty sync features (text-to-audio; the unconditional half of a CFG pair) are one learned row plus
     // sync_pos_emb, which repeats every 8 tokens: the token rows are then 8-periodic and the per-token work of the
     // single-stream blocks only has 8 distinct rows per half.  Detected on the data (bit patterns), not assumed.
     // One flag per cfg half: under CFG a video clip's unconditional half carries the empty features (periodic) next to the dense
     // conditional half - the modulation GEMM then runs on 8 + Ls rows instead of 2 Ls (round 5).
-    if (ncfg > 32) return FAIL(FOLEY_ERR_INVALID, "more than 32 cfg halves");
+    // (per-row layout: one "half" per batch row, the unconditional rows first)
+    if (vh > 32) return FAIL(FOLEY_ERR_INVALID, "more than 32 cfg halves");
     HIPTRY(hipMemsetAsync(c->flag, 0, 4 * 32, st));
-    TRY(launch_rows_periodic_check(c->sync_tok, ncfg, Ls, 8, D, c->flag, st));
+    TRY(launch_rows_periodic_check(c->sync_tok, vh, Ls, 8, D, c->flag, st));
   }
   HIPTRY(hipStreamSynchronize(st));
   {
@@ -653,12 +732,20 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     HIPTRY(hipMemcpy(differs, c->flag, 4 * 32, hipMemcpyDeviceToHost));
     static const bool mixed_on = []() { const char* e = getenv("FOLEY_SYNC_MIXED"); return !(e && e[0] == '0'); }();
     int lead = 0;
-    while (Ls > 8 && lead < ncfg && !differs[lead]) ++lead;
-    if (!mixed_on && lead < ncfg) lead = 0;                      // A/B switch: all halves periodic or none (rounds 2-4)
+    while (Ls > 8 && lead < vh && !differs[lead]) ++lead;
+    if (!mixed_on && lead < vh) lead = 0;                        // A/B switch: all halves periodic or none (rounds 2-4)
     const int per = lead > 0 ? 8 : 0;
     if (c->graph_exec && (per != c->sync_per || lead != c->sync_lead)) ctx_drop_graph(c);   // the captured modulation GEMM has another M
     c->sync_per = per;
     c->sync_lead = lead;
+    if (v_rows && lead > 1) {   // pack the leading periodic halves' rows (st is idle: synchronised above)
+      std::vector<int> idx((size_t)lead * 8);
+      for (int h = 0; h < lead; ++h)
+        for (int r = 0; r < 8; ++r) idx[(size_t)h * 8 + r] = h * Ls + r;
+      int* lead_idx = c->set_idx + (size_t)Bc * (Lt + Ls);
+      HIPTRY(hipMemcpy(lead_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+      TRY(launch_gather_rows(c->sync_tok, lead_idx, lead * 8, 1, vh * Ls, D, c->sync_lead_rows, st));
+    }
   }
   if (!c->fw.ok) TRY(resolve_forward_weights(c));
   {
@@ -669,13 +756,13 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     // FOLEY_SMOD_TABLE_GB (default 24; 1.06 GB for the 16 distinct rows of text-to-audio, 14.9 GB for the 224 rows of a 5 s
     // video clip); longer clips keep the per-iteration GEMM of run_forward.
     static const double cap_gb = []() { const char* e = getenv("FOLEY_SMOD_TABLE_GB"); return e ? atof(e) : 24.0; }();
-    const int P = (c->sync_per && c->sync_lead == ncfg) ? c->sync_per : Ls;   // hoisting serves the all-periodic case
+    const int P = (c->sync_per && c->sync_lead == vh) ? c->sync_per : Ls;   // hoisting serves the all-periodic case
     const size_t ncol = (size_t)f.depth_single * 6 * D;
-    const size_t tab_bytes = (size_t)NI * ncfg * P * ncol * 4;
+    const size_t tab_bytes = (size_t)NI * vh * P * ncol * 4;
     // ... and only where the weight stream is what the per-iteration GEMM costs (a few distinct rows: the 8-periodic empty sync
     // features).  With the 224 dense rows of a video clip the batched GEMM costs what the 50 small ones do (18.3 vs 19 ms).
-    bool hoist = f.depth_single > 0 && ncfg * P <= 64 && (double)tab_bytes <= cap_gb * 1073741824.0;
-    const size_t svec_bytes = (size_t)NI * ncfg * Ls * D * es;
+    bool hoist = f.depth_single > 0 && vh * P <= 64 && (double)tab_bytes <= cap_gb * 1073741824.0;
+    const size_t svec_bytes = (size_t)NI * vh * Ls * D * es;
     if (hoist) {
       // ... and only while the tables (they scale with n_iter: 1.06 GB at 50 steps, 4.2 GB at 200) take at most half of what the
       // device has free, counting what this context already holds - every data-parallel replica keeps its own
@@ -701,9 +788,9 @@ extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v)
     if (hoist) {
       if (c->graph_exec && old_tab != c->smod_tab.p) ctx_drop_graph(c);   // captured kernels hold the table's address
       for (int it = 0; it < NI; ++it)
-        TRY(launch_rows_add_act(c->sync_tok, rb_vec(c->vec_table + (size_t)it * D, 0, nullptr), ncfg * Ls, D, 1,
-                                (char*)c->svec_tab.p + (size_t)it * ncfg * Ls * D * es, T, st));
-      GemmArgs gm = gemm_plain(c->svec_tab.p, NI * ncfg * P, c->fw.smod, c->smod_tab.p, (long)ncol);
+        TRY(launch_rows_add_act(c->sync_tok, rb_vec(c->vec_table + (size_t)it * D, 0, nullptr), vh * Ls, D, 1,
+                                (char*)c->svec_tab.p + (size_t)it * vh * Ls * D * es, T, st));
+      GemmArgs gm = gemm_plain(c->svec_tab.p, NI * vh * P, c->fw.smod, c->smod_tab.p, (long)ncol);
       gm.segV = P; gm.segS = Ls;     // virtual rows: row r of the product is token r % P of (iteration, half) r / P
       TRY(launch_gemm(gm, T, EPI_STORE_F32, 0, st));
       c->smod_hoisted = true;
@@ -790,6 +877,9 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const int ncfg = pl.ncfg, clips = pl.clips, La = pl.La, Lv = pl.Lv, Ls = pl.Ls, Lt = pl.Lt, NI = pl.n_iter;
   const int Bc = ncfg * clips, M = Bc * La, Mv = Bc * Lv, S = La + Lv;
+  // conditioning layout (foley_prepare_sets): batch row b reads text slot b / tdiv and visual half b / vdiv - clips for the
+  // per-half layout, 1 for the per-row one
+  const int th = c->txt_rows ? Bc : ncfg, vh = c->vis_rows ? Bc : ncfg, tdiv = Bc / th, vdiv = Bc / vh;
   const bool bf = foley_is_half(T);   // 16-bit throughput mode (bf16 or fp16 operands): transposed V, fused head split
   const size_t es = esize(T);
   const int Sp = (S + 31) & ~31, Lap = (La + 31) & ~31;  // V^T row pitches (bf16 attention)
@@ -813,12 +903,15 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     }
     // distinct rows only: 8 per 8-periodic half (the leading sync_lead halves), Ls per dense half - packed back to back, which
     // is the row order of the modulation table (RowBcast::dense_from / dense_base)
-    const int lead = c->sync_per ? c->sync_lead : 0, R = lead * c->sync_per + (ncfg - lead) * Ls;
-    for (int h = 0; h < lead; ++h)
-      TRY(launch_rows_add_act(c->sync_tok + (size_t)h * Ls * D, rb_vec(c->vec_table, D, sp), c->sync_per, D, 1,
-                              (char*)c->svec + (size_t)h * c->sync_per * D * es, T, sd));
-    if (lead < ncfg)
-      TRY(launch_rows_add_act(c->sync_tok + (size_t)lead * Ls * D, rb_vec(c->vec_table, D, sp), (ncfg - lead) * Ls, D, 1,
+    const int lead = c->sync_per ? c->sync_lead : 0, R = lead * c->sync_per + (vh - lead) * Ls;
+    if (c->vis_rows && lead > 1)   // per-row layout: the leading halves' rows were packed by foley_prepare_sets - one launch
+      TRY(launch_rows_add_act(c->sync_lead_rows, rb_vec(c->vec_table, D, sp), lead * c->sync_per, D, 1, c->svec, T, sd));
+    else
+      for (int h = 0; h < lead; ++h)
+        TRY(launch_rows_add_act(c->sync_tok + (size_t)h * Ls * D, rb_vec(c->vec_table, D, sp), c->sync_per, D, 1,
+                                (char*)c->svec + (size_t)h * c->sync_per * D * es, T, sd));
+    if (lead < vh)
+      TRY(launch_rows_add_act(c->sync_tok + (size_t)lead * Ls * D, rb_vec(c->vec_table, D, sp), (vh - lead) * Ls, D, 1,
                               (char*)c->svec + (size_t)lead * c->sync_per * D * es, T, sd));
     if (f.depth_single > 0) {
       // one GEMM for all blocks: [R, D] x [n_single*6D, D]^T -> smod [R, n_single*6D]
@@ -836,11 +929,15 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   // audio_embedder (conv k=1 == linear over the transposed latents) + add_sync (hifi_foley.py:768, 838-839)
   {
     GemmArgs g = krot(gemm_plain(c->xin, M, W.audio_in, c->audio, D));
-    g.rb = rb_up(c->sync_tok, D, clips * La, La, Ls);
+    g.rb = rb_up(c->sync_tok, D, vdiv * La, La, Ls);
     PROF("audio_embedder", gf(M, D, C), gb(M, D, C, 4), launch_gemm(g, T, EPI_STORE_F32, 0, st));
   }
-  // visual stream starts from the step-invariant projection, replicated per clip (one gather launch)
-  TRY(launch_gather_rows(c->v_cond0, c->rep_idx, clips * Lv, ncfg, Lv, D, c->vcond, st));
+  // visual stream starts from the step-invariant projection, replicated per clip (one gather launch); per-row layout: every
+  // batch row gathers its own set's rows of the distinct projections
+  if (c->vis_rows)
+    TRY(launch_gather_rows(c->v_cond0, c->rep_idx, Bc * Lv, 1, c->vis_src * Lv, D, c->vcond, st));
+  else
+    TRY(launch_gather_rows(c->v_cond0, c->rep_idx, clips * Lv, ncfg, Lv, D, c->vcond, st));
 
   // residual updates left pending by deferred split-K GEMMs, per stream (audio, visual); the next
   // LayerNorm of that stream applies them
@@ -924,8 +1021,8 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
       g0.qs = split_args(0, 1, w.cqn[0], nullptr, pl.pos_linear);
       g1.qs = split_args(1, 1, w.cqn[1], nullptr, pl.pos_linear);
       const int Ltp = (Lt + 31) & ~31;
-      const size_t offk = (size_t)blk * ncfg * H * Lt * 128 * es;
-      const size_t offv = (size_t)blk * ncfg * H * (bf ? Ltp : Lt) * 128 * es;
+      const size_t offk = (size_t)blk * th * H * Lt * 128 * es;
+      const size_t offv = (size_t)blk * th * H * (bf ? Ltp : Lt) * 128 * es;
       // 16-bit modes: the projection may run the attention against the <= 96 cached text keys in its epilogue (small grids:
       // gemm_impl.h decides and reports through attn_fused); the q tensor and the attention launch are then gone
       int fused = 0;
@@ -933,13 +1030,13 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
         for (int s = 0; s < 2; ++s) {
           QkvSplitArgs& q = s ? g1.qs : g0.qs;
           q.attn_k = (char*)c->txt_k + offk; q.attn_vt = (char*)c->txt_v + offv; q.attn_out = ss[s].att;
-          q.attn_skv = Lt; q.attn_pitch = Ltp; q.attn_bdiv = clips; q.attn_fused = &fused;
+          q.attn_skv = Lt; q.attn_pitch = Ltp; q.attn_bdiv = tdiv; q.attn_fused = &fused;   // gemm_plan.h: <= 2 sets per tile
         }
       }
       PROF("triple.cross q GEMM + head split (+ cross attention on small grids)", gf(M + Mv, D, D),
            gb(M + Mv, D, D, es) + 1.0 * D * D * es, launch_gemm_pair(g0, g1, T, EPI_QKV_SPLIT, st));
       if (!fused) {
-        AttnArgs a{c->Q, (char*)c->txt_k + offk, (char*)c->txt_v + offv, Bc, H, S, Lt, clips, c->att_v, c->att_a, Lv,
+        AttnArgs a{c->Q, (char*)c->txt_k + offk, (char*)c->txt_v + offv, Bc, H, S, Lt, tdiv, c->att_v, c->att_a, Lv,
                    T, bf ? Ltp : 0};
         PROF("triple.cross attention", af(Bc, S, Lt), ab(Bc, S, Lt), launch_attention(a, T, st));
       }
@@ -963,13 +1060,13 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     const float* smod_b = (c->smod_hoisted ? (const float*)c->smod_tab.p : c->smod) + (size_t)blk * 6 * D;   // column block of the fused table
     // table layout per iteration: every half periodic (8 rows each) | the leading halves periodic, the others dense (the
     // per-iteration GEMM only - a hoisted table that is not all-periodic is dense) | every half dense
-    const bool allper = c->sync_per && c->sync_lead == ncfg;
+    const bool allper = c->sync_per && c->sync_lead == vh;
     const int per_eff = (allper || !c->smod_hoisted) ? c->sync_per : 0;
     auto sm = [&](int chunk) {
-      RowBcast r = rb_up(smod_b + (size_t)chunk * D, 6L * D * f.depth_single, clips * La, La, Ls, per_eff, allper ? -1 : c->sync_lead);
-      if (c->smod_hoisted) {   // the table of every iteration: this iteration's rows start at step * ncfg*P*ld
+      RowBcast r = rb_up(smod_b + (size_t)chunk * D, 6L * D * f.depth_single, vdiv * La, La, Ls, per_eff, allper ? -1 : c->sync_lead);
+      if (c->smod_hoisted) {   // the table of every iteration: this iteration's rows start at step * vh*P*ld
         r.step_ptr = sp;
-        r.step_stride = (long)ncfg * (allper ? c->sync_per : Ls) * 6L * D * f.depth_single;
+        r.step_stride = (long)vh * (allper ? c->sync_per : Ls) * 6L * D * f.depth_single;
       }
       return r;
     };

@@ -44,6 +44,10 @@ class FoleyPlanC(C.Structure):
     ]
 
 
+class CondSetsC(C.Structure):
+    _fields_ = [("n_text", C.c_int32), ("n_vis", C.c_int32), ("text_of", C.POINTER(C.c_int32)), ("vis_of", C.POINTER(C.c_int32))]
+
+
 class RowBcastC(C.Structure):
     _fields_ = [("p", C.c_void_p), ("ld", C.c_int64), ("mode", C.c_int32), ("rows_per_cfg", C.c_int32),
                 ("L", C.c_int32), ("Ls", C.c_int32), ("period", C.c_int32), ("periodic_cfgs", C.c_int32)]
@@ -107,6 +111,7 @@ _SIGNATURES = {
     "foley_bcast_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_bcast_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "foley_prepare": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.c_void_p]),
+    "foley_prepare_sets": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.POINTER(CondSetsC), C.c_void_p]),
     "foley_dit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, PROGRESS_CB, C.c_void_p, C.c_void_p]),
     "foley_abort": (C.c_int, [C.c_void_p]),
@@ -294,7 +299,8 @@ class FoleyContext:
 
     # ---- run
     def prepare(self, plan: dict):
-        """plan: ncfg, clips, La, Lv, Ls, Lt, n_iter, guidance + device tensors (see foley_plan)."""
+        """plan: ncfg, clips, La, Lv, Ls, Lt, n_iter, guidance + device tensors (see foley_plan).  Per-clip conditioning
+        (host/cond_sets.py): `text_of` / `vis_of` lists of ncfg*clips set indices -> foley_prepare_sets."""
         p = FoleyPlanC()
         for k in ("ncfg", "clips", "La", "Lv", "Ls", "Lt", "n_iter", "rope_len"):
             setattr(p, k, int(plan[k]))
@@ -303,7 +309,15 @@ class FoleyContext:
                   "pos_linear", "sync_gather", "solver_coef"):
             setattr(p, k, _ptr(plan[k]))
         with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.foley_prepare(self._h, C.byref(p), _stream()), "foley_prepare")
+            if plan.get("text_of") is None:
+                _check(self.lib, self.lib.foley_prepare(self._h, C.byref(p), _stream()), "foley_prepare")
+            else:
+                n = len(plan["text_of"])
+                t_of, v_of = (C.c_int32 * n)(*plan["text_of"]), (C.c_int32 * n)(*plan["vis_of"])
+                s = CondSetsC(int(plan["text"].shape[0]), int(plan["clip"].shape[0]), t_of, v_of)
+                if n != p.ncfg * p.clips or len(plan["vis_of"]) != n:
+                    raise FoleyRuntimeError("set maps must have ncfg*clips entries")
+                _check(self.lib, self.lib.foley_prepare_sets(self._h, C.byref(p), C.byref(s), _stream()), "foley_prepare_sets")
         self._plan_keep = plan    # the ctx borrows the plan's tables until the next prepare
         self.plan = plan
 

@@ -13,7 +13,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
-from . import packers, runtime, tables
+from . import cond_sets, packers, runtime, tables
 from .config import DAC48K, DACConfig, DiTConfig
 from .runtime import FoleyContext, FoleyRuntimeError
 
@@ -147,26 +147,44 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
                La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str,
                edit_i0: Optional[int] = None) -> dict:
     """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables.
-    edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows."""
+    edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows.
+    Each conditioning tensor has batch 1 (shared by all clips) or batch_size (one row per clip, host/cond_sets.py): the plan
+    then holds the distinct sets and the maps `text_of` / `vis_of` (None when every clip shares its conditioning)."""
     cfg, dev = model.cfg, model.device
     f32 = lambda t: t.to(device=dev, dtype=torch.float32)
     clip, sync = f32(visual_feats["siglip2_feat"]), f32(visual_feats["syncformer_feat"])
     text, unc = f32(text_feats["text_feat"]), f32(text_feats["uncond_text_feat"])
-    if clip.shape[0] != 1 or sync.shape[0] != 1 or text.shape[0] != 1 or unc.shape[0] != 1:
-        raise FoleyRuntimeError("conditioning tensors must have batch 1 (they are shared by all clips)")
+    try:
+        per_clip = any(cond_sets.batch_of(t, batch_size, n) > 1 for t, n in (
+            (clip, "siglip2_feat"), (sync, "syncformer_feat"), (text, "text_feat"), (unc, "uncond_text_feat")))
+    except cond_sets.CondSetsError as e:
+        raise FoleyRuntimeError(str(e)) from None
     Lv, Ls = clip.shape[1], sync.shape[1]
     # two-bucket text length policy, sticky per model (utils.py:166-188)
     t_fixed = min(77 if text.shape[1] <= 77 else 128, cfg.text_len)
     model._text_len_fixed = max(model._text_len_fixed or 0, t_fixed)
     Lt = model._text_len_fixed
     text, unc = pad_or_trim_text(text, Lt), pad_or_trim_text(unc, Lt)
-    if guidance_scale > 1.0:                      # [uncond ; cond]  (utils.py:193-195)
-        ncfg = 2
+    text_of = vis_of = None
+    if per_clip:
+        sets = cond_sets.build(text, unc, clip, sync, model.empty_clip_feat, model.empty_sync_feat, batch_size,
+                               guidance_scale > 1.0)
+        if sets.homogeneous:          # every clip shares its conditioning: the batch-1 plan exactly
+            h = 1 if guidance_scale > 1.0 else 0
+            text, clip, sync = sets.text[h:h + 1], sets.clip[h:h + 1], sets.sync[h:h + 1]
+            unc = sets.text[:1]
+            per_clip = False
+        else:
+            text_in, clip_in, sync_in, text_of, vis_of = sets.text, sets.clip, sets.sync, sets.text_of, sets.vis_of
+    ncfg = 2 if guidance_scale > 1.0 else 1
+    if per_clip:                                  # distinct sets in [uncond ; cond] order, the maps say which row reads which
+        pass
+    elif guidance_scale > 1.0:                    # [uncond ; cond]  (utils.py:193-195)
         text_in = torch.cat([unc, text])
         clip_in = torch.cat([model.get_empty_clip_sequence(bs=1, len=Lv).float(), clip])
         sync_in = torch.cat([model.get_empty_sync_sequence(bs=1, len=Ls).float(), sync])
     else:
-        ncfg, text_in, clip_in, sync_in = 1, text, clip, sync
+        text_in, clip_in, sync_in = text, clip, sync
     fp8_time = fp8_time_dtype(model)
     # The run's tables (schedule, solver coefficients, RoPE rows, position / up-sampling maps) depend on these scalars
     # only: built once per distinct run shape and kept on the device (host-side table building is milliseconds of
@@ -184,7 +202,8 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
         cache[key] = tabs
     plan = {"ncfg": ncfg, "clips": batch_size, "La": La, "Lv": Lv, "Ls": Ls, "Lt": Lt, "n_iter": tabs["solver_coef"].shape[0],
             "guidance": float(guidance_scale), "rope_len": tabs["rope_cos"].shape[0],
-            "text": text_in.contiguous(), "clip": clip_in.contiguous(), "sync": sync_in.contiguous()}
+            "text": text_in.contiguous(), "clip": clip_in.contiguous(), "sync": sync_in.contiguous(),
+            "text_of": text_of, "vis_of": vis_of}
     plan.update(tabs)
     return plan
 
@@ -313,11 +332,14 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                           generator: Optional[torch.Generator] = None, use_graph: bool = True,
                           progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None):
     """`denoise_process_with_generator` with the clips of the batch sharded over `replicas` (the pairs
-    `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199: the
-    batch only repeats the conditioning), so there is no collective: the noise of the WHOLE batch is drawn once
-    from `generator` exactly like the single-GPU call does and sliced (`distributed.shard_range`), which makes the
-    result bit-identical to one GPU running the full batch whenever the shards use the same tile shapes and the same
-    summation order - and equal to bf16 / fp32 accuracy otherwise.  A shard of ONE clip never is bit-identical to that
+    `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199 batches clips that
+    share their conditioning; per-clip conditioning, host/cond_sets.py, only changes what each clip reads), so there is no
+    collective: the noise of the WHOLE batch is drawn once from `generator` exactly like the single-GPU call does and sliced
+    (`distributed.shard_range`), and per-clip conditioning tensors are sliced with their clips (`cond_sets.shard`).  With
+    shared conditioning the result is bit-identical to one GPU running the full batch whenever the shards use the same tile
+    shapes and the same summation order - and equal to bf16 / fp32 accuracy otherwise.  With per-clip conditioning a shard
+    de-duplicates its own clips and may take another layout than the full batch (per cfg half instead of per batch row, when
+    the clips of the shard share their conditioning): the results then agree to bf16 / fp32 accuracy.  A shard of ONE clip never is bit-identical to that
     clip inside a larger shard: single-clip forwards rotate the K origin of their small-grid GEMMs per M tile (K-origin
     rotation, gemm.hip g_gemm_krot_ok), a different but deterministic summation order (tests/test_pairs_gpu.py pins how
     far it moves a result).  `edit` as for denoise_process_with_generator: per-clip source latents and masks are sharded with
@@ -365,8 +387,9 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                 if failed.is_set():
                     return
                 running[r] = True
-                results[r] = denoise_process_with_generator(
-                    visual_feats, text_feats, audio_len_in_s, model, dac, guidance_scale, num_inference_steps, hi - lo,
+                results[r] = denoise_process_with_generator(     # per-clip conditioning travels with its clips
+                    cond_sets.shard(visual_feats, lo, hi, batch_size), cond_sets.shard(text_feats, lo, hi, batch_size),
+                    audio_len_in_s, model, dac, guidance_scale, num_inference_steps, hi - lo,
                     sampler, use_graph=use_graph, noise=noise[lo:hi], return_latents=True,
                     progress=progress if r == 0 else None, _abort_event=failed,
                     edit=edit.shard(lo, hi, batch_size) if edit is not None else None)

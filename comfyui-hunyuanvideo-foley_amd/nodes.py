@@ -19,6 +19,7 @@ import os
 
 import torch
 
+from .host import cond_sets as _cond_sets
 from .host import config as _cfg
 from .host import encoders as _enc
 from .host import sampler as _sampler
@@ -321,9 +322,17 @@ class HunyuanFoleySampler:
 
     def generate_audio(self, hunyuan_model, hunyuan_deps, frame_rate, duration, prompt, negative_prompt, cfg_scale,
                        steps, sampler, batch_size, seed, force_offload, image=None, torch_compile_cfg=None,
-                       block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1):
+                       block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1,
+                       prompts=None, negative_prompts=None, images=None):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
-        {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.
+        {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
+        or batch_size (one row per clip).
+
+        Per-clip conditioning (keyword-only, not sockets; host/cond_sets.py): `prompts` / `negative_prompts` - one string per clip
+        (CLAP runs on each clip's [negative, prompt] pair, as for that clip alone) - and `images` - one IMAGE frame batch per clip,
+        all of one resulting duration.  A list replaces its widget; the clips of the batch then differ in what they are conditioned
+        on, not only in their noise.  Different videos take per-row buffers: at most 32 batch rows (16 clips under
+        CFG), and the single blocks' modulation rows grow with the clips (about 15 GB at 30 s x 8 clips under CFG).
 
         Audio editing (keyword-only, not sockets; host/audio_edit.py): `audio` (an AUDIO dict, batch 1 or batch_size) is
         re-sampled from part-way down the schedule - `strength` in (0, 1] selects how far (1.0: from pure noise) - and
@@ -333,10 +342,19 @@ class HunyuanFoleySampler:
         device = model.device
         rng = torch.Generator(device="cpu").manual_seed(seed)          # nodes.py:273
         audio_len_in_s = duration
+        for name, lst in (("prompts", prompts), ("negative_prompts", negative_prompts), ("images", images)):
+            if lst is not None and len(lst) != batch_size:
+                raise ValueError(f"{name} has {len(lst)} entries: one per clip, batch_size = {batch_size}")
+        if features is not None and (prompts is not None or negative_prompts is not None or images is not None):
+            raise ValueError("features= already holds the conditioning: pass prompts / negative_prompts / images without it")
         if features is not None:
             visual = {k: features[k] for k in ("siglip2_feat", "syncformer_feat")}
             text = {k: features[k] for k in ("text_feat", "uncond_text_feat")}
             audio_len_in_s = features.get("audio_len_in_s", duration)
+        elif prompts is not None or negative_prompts is not None or images is not None:
+            visual, text, audio_len_in_s = self._per_clip_features(
+                images if images is not None else ([image] if image is not None else None), duration, frame_rate, prompts or [prompt] * batch_size, negative_prompts or [negative_prompt] * batch_size,
+                model, deps, device)
         elif image is not None:
             visual, text, audio_len_in_s = self._video_features(image, duration, frame_rate, prompt,
                                                                 negative_prompt, deps, device, model.dtype)
@@ -391,6 +409,41 @@ class HunyuanFoleySampler:
                                                      model_dtype=dtype)
         res = encode_text_feat([negative_prompt, prompt], deps, device, dtype)
         return visual, {"text_feat": res[1:], "uncond_text_feat": res[:1]}, audio_len_in_s
+
+    @staticmethod
+    @torch.inference_mode()
+    def _per_clip_features(images, duration, frame_rate, prompts, negative_prompts, model, deps, device):
+        """Per-clip conditioning: CLAP per clip over its [negative, prompt] pair (what the single-clip branches encode, so a clip
+        is conditioned on what a run of that clip alone gives); SigLIP2 / Synchformer per clip of `images` (each as
+        _video_features), or the learned empty rows for text-to-audio.  Clips whose durations differ are refused."""
+        if images is not None:
+            _ensure_visual_encoders(deps, device, model.dtype)
+            parts, lens = [], []
+            for img in images:
+                f8, f25 = _enc.select_frames(img, duration, frame_rate,
+                                             device=device if torch.device(device).type == "cuda" else None)
+                v, a_len = _enc.video_features(f8, f25, deps["siglip2_model"], deps["syncformer_model"], device,
+                                               model_dtype=model.dtype)
+                parts.append(v)
+                lens.append(a_len)
+            if len(set(lens)) != 1:
+                raise ValueError(f"the clips of one batch share one duration: images give audio_len_in_s {lens}")
+            visual, audio_len_in_s = _cond_sets.stack_features(parts, ("siglip2_feat", "syncformer_feat")), lens[0]
+        else:
+            clip_len = int(duration * 8)
+            sync_len = int(((int(duration * 25) - 16) // 8 + 1) * 8)
+            visual = {"siglip2_feat": model.get_empty_clip_sequence(bs=1, len=clip_len),
+                      "syncformer_feat": model.get_empty_sync_sequence(bs=1, len=sync_len)}
+            audio_len_in_s = duration
+        # CLAP pads a call's prompts to its longest one and those pad rows reach the DiT unmasked: one call per distinct pair keeps
+        # each clip's rows what its own [negative, prompt] call gives.  The pairs are then stacked with ZERO rows up to the longest
+        # pair - the rows pad_or_trim_text adds on the way to the run's text length anyway.
+        pairs = list(zip(negative_prompts, prompts))
+        enc = {p: encode_text_feat(list(p), deps, device, model.dtype) for p in dict.fromkeys(pairs)}
+        T = max(e.shape[1] for e in enc.values())
+        res = [torch.nn.functional.pad(enc[p], (0, 0, 0, T - enc[p].shape[1])) for p in pairs]
+        return visual, {"text_feat": torch.cat([r[1:] for r in res]), "uncond_text_feat": torch.cat([r[:1] for r in res])}, \
+            audio_len_in_s
 
 
 # ----------------------------------------------------------------------------- compat nodes

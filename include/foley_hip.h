@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FOLEY_ABI_VERSION 12   /* 12 (additions that leave every existing entry as it was, so the version stays): foley_op_resample_sinc, foley_op_logmel, head_dim 96 in foley_op_attention_hd (the sync scorer); 12: foley_op_qkv_regroup.n_rows / foley_op_attention_scatter.out_nrows (the caller-supplied row tables are range-checked on the device: source rows clamped, output rows outside the buffer dropped); 11: foley_op_resize_aa_u8 (the frames' antialiased uint8 resize, bit for bit), foley_op_attention_scatter, foley_rowbcast.periodic_cfgs; 10: foley_op_qkv_regroup (token regrouping of the conditioning encoders' attention); 9: foley_bcast_local (single-process grouped broadcast of the arenas); 8: foley_qkv_split_desc.attn_* (cross attention in the epilogue of its q projection), foley_abort / FOLEY_ERR_ABORTED; 7: FOLEY_DT_F16 as a compute dtype (foley_config.compute_dtype, op descriptors); 6: foley_rowbcast.Ls (mode 2: nearest-exact up-sampled operand); 5: reference-keyed loading (foley_weights_*, foley_load_tensor, foley_bcast_weights); 4: fp8 weight storage (dtype codes 3/4, foley_gemm_desc.ldw/.wfmt); 3: foley_profile_forward; 2: foley_gemm_desc gained partials / qkv / rstride; foley_op_ln_mod_pending, foley_dac_encode */
+#define FOLEY_ABI_VERSION 12   /* 12 (additions that leave every existing entry as it was, so the version stays): foley_prepare_sets, foley_op_resample_sinc, foley_op_logmel, head_dim 96 in foley_op_attention_hd (the sync scorer); 12: foley_op_qkv_regroup.n_rows / foley_op_attention_scatter.out_nrows (the caller-supplied row tables are range-checked on the device: source rows clamped, output rows outside the buffer dropped); 11: foley_op_resize_aa_u8 (the frames' antialiased uint8 resize, bit for bit), foley_op_attention_scatter, foley_rowbcast.periodic_cfgs; 10: foley_op_qkv_regroup (token regrouping of the conditioning encoders' attention); 9: foley_bcast_local (single-process grouped broadcast of the arenas); 8: foley_qkv_split_desc.attn_* (cross attention in the epilogue of its q projection), foley_abort / FOLEY_ERR_ABORTED; 7: FOLEY_DT_F16 as a compute dtype (foley_config.compute_dtype, op descriptors); 6: foley_rowbcast.Ls (mode 2: nearest-exact up-sampled operand); 5: reference-keyed loading (foley_weights_*, foley_load_tensor, foley_bcast_weights); 4: fp8 weight storage (dtype codes 3/4, foley_gemm_desc.ldw/.wfmt); 3: foley_profile_forward; 2: foley_gemm_desc gained partials / qkv / rstride; foley_op_ln_mod_pending, foley_dac_encode */
 
 enum foley_dtype {
   FOLEY_DT_F32 = 0, FOLEY_DT_BF16 = 1, FOLEY_DT_I32 = 2,
@@ -73,7 +73,7 @@ typedef struct foley_config {
 /* One sampling run: conditioning + host-built index/trig tables (all device pointers). */
 typedef struct foley_plan {
   int32_t ncfg;          /* 2 with classifier-free guidance ([uncond ; cond]), else 1 (utils.py:193-199) */
-  int32_t clips;         /* batch_size: independent clips sharing the conditioning   */
+  int32_t clips;         /* batch_size: independent clips sharing the conditioning (per clip: foley_prepare_sets) */
   int32_t La, Lv, Ls, Lt;/* audio / visual / sync / text token counts                */
   int32_t n_iter;        /* loop iterations (= steps; multi-stage solvers still do one model call per iteration) */
   float guidance;
@@ -135,6 +135,20 @@ int foley_bcast_local(int ndev, const int* devices, int nbuf, void* const* bufs,
 
 /* Step-invariant precompute for one run; allocates/reuses the context workspace. */
 int foley_prepare(foley_ctx* ctx, const foley_plan* plan, void* stream);
+
+/* Per-clip conditioning (additive within ABI 12): every batch row (cfg half h, clip k), row b = h*clips + k, reads its own text set
+ * text_of[b] in [0, n_text) and its own visual set (clip and sync features together) vis_of[b] in [0, n_vis); plan.text then holds
+ * [n_text, Lt, cond_dim], plan.clip [n_vis, Lv, clip_dim] and plan.sync [n_vis, Ls, sync_dim].  The maps are host memory of
+ * ncfg*clips entries, read during the call.  The conditioning GEMMs run once per distinct set; a stream whose map gives one set
+ * per cfg half (b -> b / clips with n = ncfg) keeps foley_prepare's per-half layout, any other map lays that stream's
+ * conditioning out per batch row (visual: at most 32 rows).  sets == NULL is foley_prepare.  A captured loop iteration is keyed
+ * on the maps as well. */
+typedef struct foley_cond_sets {
+  int32_t n_text, n_vis;
+  const int32_t* text_of;   /* [ncfg*clips] */
+  const int32_t* vis_of;    /* [ncfg*clips] */
+} foley_cond_sets;
+int foley_prepare_sets(foley_ctx* ctx, const foley_plan* plan, const foley_cond_sets* sets, void* stream);
 
 /* One DiT evaluation at loop iteration `iter` (its timestep modulation): latents [clips,C,La]
  * fp32 -> velocity rows [ncfg*clips*La, C] fp32 (row = (cfg*clips + clip)*La + l). */
