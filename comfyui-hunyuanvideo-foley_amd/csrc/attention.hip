@@ -7,7 +7,6 @@
 // in the B-operand layout of the second MFMA (O^T += V^T P^T) - no LDS, no cross-lane shuffles.
 //   MFMA 32x32x2 operand layout: A[i = lane&31][k = lane>>5], B[k = lane>>5][j = lane&31],
 //   D[row = (e&3) + 8*(e>>2) + 4*(lane>>5)][col = lane&31].
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
@@ -264,7 +263,7 @@ __global__ __launch_bounds__(256) void attn_bf16_kernel(const AttnArgs a) {
 #pragma unroll
       for (int d = 0; d < 4; ++d) vf[u][d] = *(const bf16x8*)(VT + (long)(d * 32 + j) * a.vt_pitch + kt + 16 * kh + 8 * u);
   };
-  if (!a.no_preload && t1 - t0 <= 2) {
+  if (t1 - t0 <= 2) {
     // The small grids this kernel serves (S <= ~300: one or two key tiles per wave) are a chain of
     // dependent memory latencies - K tile, then V tile, per key tile.  Every operand of the wave's
     // (at most two) tiles is requested up front, before the first MFMA: one round trip instead of four.
@@ -1129,9 +1128,7 @@ static long long* g_attn_dbg = nullptr;
 extern "C" void foley_debug_attn_timeline(void* p) { g_attn_dbg = (long long*)p; }
 
 int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
-  static const int no_preload = []() { const char* e = getenv("FOLEY_ATTN_PRELOAD"); return (e && e[0] == '0') ? 1 : 0; }();
   AttnArgs a = a_in;
-  a.no_preload = no_preload;
   a.dbg = g_attn_dbg;
   if (a.Sq <= 0 || a.Skv <= 0) return foley_set_err("attention: empty sequence", __FILE__, __LINE__);
   const int hd = a.head_dim > 0 ? a.head_dim : 128;
@@ -1153,15 +1150,12 @@ int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
     // (the conditioning encoders) and 96 (the sync head) exist in the wide form only
     const dim3 gw(((a.Sq + 127) / 128) * a.H * a.Bq);
     const bool wide = (long)gw.x >= 256 || hd != 128, h16 = a.in_dtype == FOLEY_F16, o32 = out_dtype == FOLEY_F32;
-    // long key sequences on grids of at most ~2 waves per SIMD: 64 keys per iteration of each wave's dependent chain (attn_bf16_long_kernel;
-    // FOLEY_ATTN_LONG=0 keeps the 32-key form)
-    static const bool long_on = []() { const char* e = getenv("FOLEY_ATTN_LONG"); return !(e && e[0] == '0'); }();
-    const bool longk = long_on && wide && hd == 128 && a.Skv >= 512 && (long)gw.x * 4 <= 2048;
+    // long key sequences on grids of at most ~2 waves per SIMD: 64 keys per iteration of each wave's dependent chain (attn_bf16_long_kernel)
+    const bool longk = wide && hd == 128 && a.Skv >= 512 && (long)gw.x * 4 <= 2048;
     // ... and where 128 / 160 / 192-query workgroups of key-split wave pairs cover the problem in ONE round of 256 CUs, that form
-    // (attn_bf16_pair_kernel; FOLEY_ATTN_PAIR=0 keeps the 64-key chain): the largest workgroup count <= 256 wins
-    static const bool pair_on = []() { const char* e = getenv("FOLEY_ATTN_PAIR"); return !(e && e[0] == '0'); }();
+    // (attn_bf16_pair_kernel): the largest workgroup count <= 256 wins
     int pair_nq = 0;
-    if (pair_on && longk) {
+    if (longk) {
       long best = 0;
       for (int nq = 6; nq >= 4; --nq) {
         const long wgs = (long)((a.Sq + 32 * nq - 1) / (32 * nq)) * a.H * a.Bq;
@@ -1169,12 +1163,11 @@ int launch_attention(const AttnArgs& a_in, int out_dtype, hipStream_t st) {
       }
       if (best < 160) pair_nq = 0;              // too few workgroups: the chain kernel's two per CU do better
     }
-    // small grids whose operands fit the LDS: the DMA-staged form (FOLEY_ATTN_LDS=0 keeps the register-loaded kernel)
-    static const bool lds_on = []() { const char* e = getenv("FOLEY_ATTN_LDS"); return !(e && e[0] == '0'); }();
+    // small grids whose operands fit the LDS: the DMA-staged form (attn_lds_kernel); the register-loaded kernel serves the rest
     const int nt = (a.Skv + 31) >> 5;
     const long img = (long)nt * 32 * 256 + (128L << ((a.vt_pitch > 128 ? 5 : 4) + 4)) + 32 * 256, mrg = 4 * 3 * 16 * 64 * 4 + 2 * 4 * 32 * 4;
     // (three key tiles or fewer - the 77 text keys - are a wash: 5.95 vs 6.2 us in the loop; single-block self-attention 8.4 -> 7.3 us)
-    const bool staged = lds_on && !wide && hd == 128 && nt >= 4 && a.vt_pitch <= 256 && img <= 160 * 1024;
+    const bool staged = !wide && hd == 128 && nt >= 4 && a.vt_pitch <= 256 && img <= 160 * 1024;
     const int merge_off = staged && img + mrg <= 160 * 1024 ? (int)img : 0;
     const size_t lds16 = staged ? (size_t)(merge_off ? img + mrg : (img > mrg ? img : mrg)) : 0;
 #define FOLEY_ATTN16(T, O)                                                                         \

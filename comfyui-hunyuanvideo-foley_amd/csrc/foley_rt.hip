@@ -188,11 +188,6 @@ struct foley_ctx {
   bool edit = false;
   DevBuf edit_x0, edit_noise, edit_mask;
   int edit_x0_clips = 1, edit_mask_clips = 0;   // mask clips 0: no mask (all ones)
-  // side stream: work that depends only on the iteration index (single-block AdaLN GEMMs) overlaps
-  // the latent-dependent chain; joined through events (also inside the captured graph)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr;
-  std::vector<hipEvent_t> ev_mod;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -366,10 +361,6 @@ extern "C" int foley_ctx_create(int device, const foley_config* cfg, foley_ctx**
   c->cfg = *cfg;
   (void)hipEventCreate(&c->ev0);
   (void)hipEventCreate(&c->ev1);
-  (void)hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
-  (void)hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-  c->ev_mod.resize(cfg->depth_single > 0 ? cfg->depth_single : 1);
-  for (auto& e : c->ev_mod) (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
   *out = c;
   return 0;
 }
@@ -382,9 +373,6 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
     if (b->p) hipFree(b->p);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
-  if (c->side) hipStreamDestroy(c->side);
-  if (c->ev_fork) hipEventDestroy(c->ev_fork);
-  for (auto e : c->ev_mod) hipEventDestroy(e);
   for (auto e : c->prof.pool) hipEventDestroy(e);
   if (c->wstore && c->wstore_free) c->wstore_free(c->wstore);
   delete c;
@@ -730,10 +718,8 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   {
     int differs[32];
     HIPTRY(hipMemcpy(differs, c->flag, 4 * 32, hipMemcpyDeviceToHost));
-    static const bool mixed_on = []() { const char* e = getenv("FOLEY_SYNC_MIXED"); return !(e && e[0] == '0'); }();
     int lead = 0;
     while (Ls > 8 && lead < vh && !differs[lead]) ++lead;
-    if (!mixed_on && lead < vh) lead = 0;                        // A/B switch: all halves periodic or none (rounds 2-4)
     const int per = lead > 0 ? 8 : 0;
     if (c->graph_exec && (per != c->sync_per || lead != c->sync_lead)) ctx_drop_graph(c);   // the captured modulation GEMM has another M
     c->sync_per = per;
@@ -753,15 +739,15 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     // iteration only (vec) and on the sync tokens - not on the latents.  Like the two-stream blocks' AdaLN tables it is therefore
     // computed HERE for all n_iter iterations in one GEMM ([n_iter*ncfg*P, D] x [n_single*6D, D]^T; the 1.02 GB weight panel is
     // streamed once per run instead of once per iteration: 0.21 ms x 50 -> ~1 ms at 5 s text-to-audio) when the table fits
-    // FOLEY_SMOD_TABLE_GB (default 24; 1.06 GB for the 16 distinct rows of text-to-audio, 14.9 GB for the 224 rows of a 5 s
-    // video clip); longer clips keep the per-iteration GEMM of run_forward.
-    static const double cap_gb = []() { const char* e = getenv("FOLEY_SMOD_TABLE_GB"); return e ? atof(e) : 24.0; }();
+    // SMOD_TABLE_CAP (1.06 GB for the 16 distinct rows of text-to-audio, 14.9 GB for the 224 rows of a 5 s video clip); longer
+    // clips keep the per-iteration GEMM of run_forward.
+    constexpr size_t SMOD_TABLE_CAP = (size_t)24 << 30;   // 24 GiB
     const int P = (c->sync_per && c->sync_lead == vh) ? c->sync_per : Ls;   // hoisting serves the all-periodic case
     const size_t ncol = (size_t)f.depth_single * 6 * D;
     const size_t tab_bytes = (size_t)NI * vh * P * ncol * 4;
     // ... and only where the weight stream is what the per-iteration GEMM costs (a few distinct rows: the 8-periodic empty sync
     // features).  With the 224 dense rows of a video clip the batched GEMM costs what the 50 small ones do (18.3 vs 19 ms).
-    bool hoist = f.depth_single > 0 && vh * P <= 64 && (double)tab_bytes <= cap_gb * 1073741824.0;
+    bool hoist = f.depth_single > 0 && vh * P <= 64 && tab_bytes <= SMOD_TABLE_CAP;
     const size_t svec_bytes = (size_t)NI * vh * Ls * D * es;
     if (hoist) {
       // ... and only while the tables (they scale with n_iter: 1.06 GB at 50 steps, 4.2 GB at 200) take at most half of what the
@@ -857,12 +843,7 @@ static int prof_end(foley_ctx* c, hipStream_t st) {
 // The single-block modulation GEMM (510 GFLOP, depends on the iteration index only) runs IN LINE at the head
 // of the forward.  Round 1 overlapped it with the two-stream blocks on a side stream; with the faster block
 // kernels of round 2 its 5184 workgroups only steal CUs from them (A/B in one box: 448.5 -> 439.5 ms per
-// 50-iteration loop at bs=1, 1753 -> 1741 ms at bs=8).  FOLEY_SMOD_SIDE=1 restores the side stream.
-static bool smod_inline() {
-  static const bool v = []() { const char* e = getenv("FOLEY_SMOD_SIDE"); return !(e && e[0] == '1'); }();
-  return v;
-}
-
+// 50-iteration loop at bs=1, 1753 -> 1741 ms at bs=8).
 static int run_forward(foley_ctx* c, hipStream_t st) {
   const foley_config& f = c->cfg;
   const foley_plan& pl = c->plan;
@@ -893,37 +874,26 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   // ---- per-token conditioning of the single-stream blocks, SiLU(add_sync + vec) (hifi_foley.py:866-867),
   // and every single block's modulation GEMM (hifi_foley.py:366).  They depend on the iteration only, are
   // identical for every clip of a CFG half, and - add_sync being an up-sampling of the Ls sync tokens - have
-  // only Ls distinct rows per half: M = ncfg*Ls (224 instead of 500 at 5 s).  In line by default (smod_inline()).
+  // only Ls distinct rows per half: M = ncfg*Ls (224 instead of 500 at 5 s).
   if (!c->smod_hoisted) {
-    const bool inl = c->prof.on || smod_inline();
-    hipStream_t sd = inl ? st : c->side;
-    if (!inl) {
-      HIPTRY(hipEventRecord(c->ev_fork, st));
-      HIPTRY(hipStreamWaitEvent(sd, c->ev_fork, 0));
-    }
     // distinct rows only: 8 per 8-periodic half (the leading sync_lead halves), Ls per dense half - packed back to back, which
     // is the row order of the modulation table (RowBcast::dense_from / dense_base)
     const int lead = c->sync_per ? c->sync_lead : 0, R = lead * c->sync_per + (vh - lead) * Ls;
     if (c->vis_rows && lead > 1)   // per-row layout: the leading halves' rows were packed by foley_prepare_sets - one launch
-      TRY(launch_rows_add_act(c->sync_lead_rows, rb_vec(c->vec_table, D, sp), lead * c->sync_per, D, 1, c->svec, T, sd));
+      TRY(launch_rows_add_act(c->sync_lead_rows, rb_vec(c->vec_table, D, sp), lead * c->sync_per, D, 1, c->svec, T, st));
     else
       for (int h = 0; h < lead; ++h)
         TRY(launch_rows_add_act(c->sync_tok + (size_t)h * Ls * D, rb_vec(c->vec_table, D, sp), c->sync_per, D, 1,
-                                (char*)c->svec + (size_t)h * c->sync_per * D * es, T, sd));
+                                (char*)c->svec + (size_t)h * c->sync_per * D * es, T, st));
     if (lead < vh)
       TRY(launch_rows_add_act(c->sync_tok + (size_t)lead * Ls * D, rb_vec(c->vec_table, D, sp), (vh - lead) * Ls, D, 1,
-                              (char*)c->svec + (size_t)lead * c->sync_per * D * es, T, sd));
+                              (char*)c->svec + (size_t)lead * c->sync_per * D * es, T, st));
     if (f.depth_single > 0) {
       // one GEMM for all blocks: [R, D] x [n_single*6D, D]^T -> smod [R, n_single*6D]
       const double n = (double)f.depth_single * 6 * D;
       GemmArgs gm = krot(gemm_plain(c->svec, R, W.smod, c->smod, (long)f.depth_single * 6 * D));
-      TRY(prof_begin(c, st, "single.modulation (all blocks, one GEMM)", gf(R, n, D), gb(R, n, D, 4)));
-      TRY(launch_gemm(gm, T, EPI_STORE_F32, 0, sd));
-      TRY(prof_end(c, st));
+      PROF("single.modulation (all blocks, one GEMM)", gf(R, n, D), gb(R, n, D, 4), launch_gemm(gm, T, EPI_STORE_F32, 0, st));
     }
-    // the join point always exists (also with depth_single == 0): a forked capture stream must be
-    // joined before the capture ends, and eager callers must not race on svec
-    if (!inl) HIPTRY(hipEventRecord(c->ev_mod[0], sd));
   }
 
   // audio_embedder (conv k=1 == linear over the transposed latents) + add_sync (hifi_foley.py:768, 838-839)
@@ -943,9 +913,8 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   // LayerNorm of that stream applies them
   LnPending pend[2] = {LnPending{}, LnPending{}};
   // deferred split-K slabs in the operand type (bf16 / fp16 compute): half the bytes the GEMM epilogues write and the next
-  // LayerNorm reads (that kernel runs at the fabric's bandwidth: 22 MB in 3.4 us at M = 500).  FOLEY_SLAB16=0 keeps fp32.
-  static const bool slab16_on = []() { const char* e = getenv("FOLEY_SLAB16"); return !(e && e[0] == '0'); }();
-  const int slab_half = (bf && slab16_on) ? T : 0;
+  // LayerNorm reads (that kernel runs at the fabric's bandwidth: 22 MB in 3.4 us at M = 500).  fp32 compute keeps fp32 slabs.
+  const int slab_half = bf ? T : 0;
   auto with_partials = [&](GemmArgs& g, float* slabs) {
     g.partial_half = slab_half ? 1 : 0;
     g.partials = slabs;
@@ -1052,8 +1021,6 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     }
   }
 
-  // join: the single blocks' modulation table is ready (profiling ran it in line)
-  if (!c->smod_hoisted && !c->prof.on && !smod_inline()) HIPTRY(hipStreamWaitEvent(st, c->ev_mod[0], 0));
   const int Hc = f.conv_hidden;
   for (int blk = 0; blk < f.depth_single; ++blk) {
     const SingleW& w = W.s[blk];
@@ -1635,17 +1602,15 @@ extern "C" int foley_debug_gemm_pair(const foley_gemm_desc* d0, const foley_gemm
 // Test-only (tests/test_gemm_plan_cpu.py): the launcher's plan for one problem (d1 null) or a pair, without touching the device -
 // descriptors may carry fake (16-byte aligned) addresses.  out = {tile, K split, panel groups, k_rot}; krot_ok opts in to K-origin
 // rotation as run_forward does for single-clip forwards.
-extern int g_gemm_pf_dist;   // gemm.hip: foley_debug_gemm_prefetch
 extern "C" int foley_debug_gemm_plan(const foley_gemm_desc* d0, const foley_gemm_desc* d1, int krot_ok, int32_t out[4]) {
   if (!out) return FAIL(FOLEY_ERR_INVALID, "null output");
   GemmArgs g0, g1;
   if (int rc = d1 ? gemm_pair_args_of(d0, d1, g0, g1) : gemm_args_of(d0, g0)) return rc;
-  const GemmOpts opt{krot_ok ? 1 : 0, g_gemm_pf_dist};
   GemmPlan p;
   switch (d0->dtype) {
-    case FOLEY_F32: p = plan_gemm<float>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, opt); break;
-    case FOLEY_BF16: p = plan_gemm<bf16_t>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, opt); break;
-    case FOLEY_F16: p = plan_gemm<f16_t>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, opt); break;
+    case FOLEY_F32: p = plan_gemm<float>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, krot_ok); break;
+    case FOLEY_BF16: p = plan_gemm<bf16_t>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, krot_ok); break;
+    case FOLEY_F16: p = plan_gemm<f16_t>(g0, d1 ? &g1 : nullptr, d0->epilogue, d0->tile, krot_ok); break;
     default: return FAIL(FOLEY_ERR_INVALID, "GEMM: unsupported operand dtype");
   }
   if (p.err) return FAIL(FOLEY_ERR_INVALID, p.err);

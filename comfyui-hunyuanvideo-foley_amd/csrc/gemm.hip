@@ -6,7 +6,6 @@ long long* g_gemm_dbg = nullptr;
 int g_gemm_dbg_mode = 0;
 // tile, K split and k_rot of this thread's last dispatched GEMM (launch_typed, after every fallback): foley_debug_gemm_last
 thread_local int g_gemm_last[3] = {0, 0, 0};
-int g_gemm_pf_dist = 0;   // L2 prefetch distance of the wave-specialised mainloop (K-slices beyond the ring)
 
 int launch_gemm_typed_f32(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, hipStream_t st, int* ksplit_used);
 int launch_gemm_typed_bf16(const GemmArgs& g, const GemmArgs* g1, int epi, int tile, hipStream_t st, int* ksplit_used);
@@ -32,8 +31,6 @@ int launch_gemm_pair(const GemmArgs& g0, const GemmArgs& g1, int dtype, int epi,
 
 // Debug hook for tools/gemm_timeline.py (not part of include/foley_hip.h): every following GEMM
 // launch writes 4 wall-clock stamps per workgroup to `p` (device memory, 4 * grid * 8 bytes).
-extern "C" void foley_debug_gemm_prefetch(int dist) { g_gemm_pf_dist = dist < 0 ? 0 : dist; }
-
 extern "C" void foley_debug_gemm_timeline(void* p, int mode) {
   g_gemm_dbg = (long long*)p;
   g_gemm_dbg_mode = mode;

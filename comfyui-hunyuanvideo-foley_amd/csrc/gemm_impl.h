@@ -14,7 +14,6 @@
 // shared by the per-dtype translation units (defined in gemm.hip)
 extern long long* g_gemm_dbg;
 extern int g_gemm_dbg_mode;
-extern int g_gemm_pf_dist;
 extern thread_local int g_gemm_last[3];
 
 namespace {
@@ -519,14 +518,14 @@ int launch_tile(const GemmArgs& g, const GemmArgs* g1, int epi, hipStream_t st) 
 
 template <typename T>
 int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile_req, hipStream_t st, int* ksplit_used) {
-  const GemmPlan plan = plan_gemm<T>(g_in, g1_in, epi, tile_req, GemmOpts{g_in.krot_ok, g_gemm_pf_dist});
+  const GemmPlan plan = plan_gemm<T>(g_in, g1_in, epi, tile_req, g_in.krot_ok);
   if (plan.err) return foley_set_err(plan.err, __FILE__, __LINE__);
   if (ksplit_used) *ksplit_used = plan.ksplit;
   // the problems as the kernels read them: defaults filled in, the plan applied
   auto resolve = [&](const GemmArgs& q, int vec_out) {
     GemmArgs r = q;
     if (r.ldw <= 0) r.ldw = r.K;
-    r.ksplit = plan.ksplit, r.n_groups = plan.n_groups, r.k_rot = plan.k_rot, r.vec_out = vec_out, r.pf_dist = g_gemm_pf_dist;
+    r.ksplit = plan.ksplit, r.n_groups = plan.n_groups, r.k_rot = plan.k_rot, r.vec_out = vec_out;
     if (gemm_fits_buffer_range<T>(r)) {   // the direct-to-LDS loops address their operands through 32-bit buffer offsets
       r.a_bytes = (unsigned)gemm_a_bytes<T>(r);
       r.w_bytes = (unsigned)gemm_w_bytes<T>(r);

@@ -60,9 +60,6 @@ inline const TileInfo& tile_info(int tile) {
   return tile >= 0 && tile < 33 ? kTiles[tile] : none;
 }
 
-// Decided outside the planner: the caller's opt-in to K-origin rotation (GemmArgs::krot_ok) and the debug prefetch distance
-struct GemmOpts { int krot_ok, pf_dist; };
-
 struct GemmPlan {
   int tile = 0, ksplit = 1, n_groups = 0, k_rot = 0;
   int vec_out[2] = {0, 0};   // per problem: the LDS-transposed vector epilogue
@@ -110,9 +107,10 @@ long gemm_w_bytes(const GemmArgs& q) { return (long)q.N * q.ldw * (q.wfmt ? 1L :
 template <typename T>
 bool gemm_fits_buffer_range(const GemmArgs& q) { return gemm_a_bytes<T>(q) < 0x7fff0000L && gemm_w_bytes<T>(q) < 0x7fff0000L; }
 
-// One problem (g1 null) or the two problems of a pair launch; tile 0 = automatic.  Reads no globals, writes nothing but the plan.
+// One problem (g1 null) or the two problems of a pair launch; tile 0 = automatic; krot_ok: the caller's opt-in to K-origin rotation
+// (GemmArgs::krot_ok, decided outside the planner).  Reads no globals, writes nothing but the plan.
 template <typename T>
-GemmPlan plan_gemm(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile, const GemmOpts& opt) {
+GemmPlan plan_gemm(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile, int krot_ok) {
   GemmPlan plan;
   auto fail = [&](const char* msg) { plan.err = msg; return plan; };
   GemmArgs g = g_in, g1s = g1_in ? *g1_in : g_in;
@@ -364,10 +362,9 @@ GemmPlan plan_gemm(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int til
     // gemm_ws_impl.h).  All M tiles of a weight panel start together and walk K in step, so every one of them waits for the SAME cold
     // line (one HBM fill, the others queued behind it in the L2) - each holds a slot of its CU's memory queue for the full HBM latency.
     // Started 1 / tiles_m of the range apart they take turns at the miss and find the other lines in the L2.  Only where the caller
-    // opted in (GemmArgs::krot_ok: the summation order of a row then depends on its tile), and not under the debug prefetch stream,
-    // which does not follow the rotated walk.
+    // opted in (GemmArgs::krot_ok: the summation order of a row then depends on its tile).
     const int rbm = (ti.fam == FAM_WS8 || ti.fam == FAM_WS4 || ti.fam == FAM_HEAD) ? ti.bm : 0;
-    if (opt.krot_ok && opt.pf_dist <= 0 && rbm && sizeof(T) == 2 && g.taps == 1 && (!g1 || g1s.taps == 1)) {
+    if (krot_ok && rbm && sizeof(T) == 2 && g.taps == 1 && (!g1 || g1s.taps == 1)) {
       const long ks_ = epi == EPI_GATE_RES ? g.ksplit : 1;
       long n = (long)((g.M + rbm - 1) / rbm) * ((g.N + 127) / 128) * ks_;
       if (g1) n += (long)((g1s.M + rbm - 1) / rbm) * ((g1s.N + 127) / 128) * ks_;

@@ -72,14 +72,6 @@ __device__ __forceinline__ void hard_barrier() {
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// L2 prefetch: one dword per lane into a pinned scratch register (see the consumer loop); out-of-range
-// lanes touch nothing.
-__device__ __forceinline__ void buf_prefetch4(const void* base, unsigned bytes, int voff, int soff, int& sink) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-  const int so = __builtin_amdgcn_readfirstlane(soff);
-  asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(sink) : "v"(voff), "s"(r), "s"(so) : "memory");
-}
-
 // fp8 -> bf16 (exact: every e4m3fn / e5m2 value is a bf16 value): 16 weights of one ds_read_b128 become
 // the B fragments of two consecutive k-steps.  v_cvt_scalef32_pk_bf16_{fp8,bf8} with scale 1.
 template <int WF, typename T>
@@ -309,47 +301,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmPair& pr) {
   // 2t+1, and the bf16 operands read their 16-byte chunk 4t + 2kh + u.  The bf16-weight kernel uses the
   // same order, which makes fp8 storage bit-identical to the same weights widened at load time.
   auto a_chunk = [&](int s) { return 4 * (s >> 1) + 2 * kh + (s & 1); };
-  // ---- L2 prefetch stream (GemmArgs::pf_dist > 0).  The direct-to-LDS ring can only keep NS-1 slices
-  // in flight (LDS capacity), so with weights arriving cold from HBM (~2 us under load) a loader moves
-  // bytes-in-flight / latency = ~64 GB/s per CU - that, not the LDS or the matrix pipe, bounds the K
-  // loop at M = 500.  The consumer waves (their vmcnt is otherwise idle) therefore touch one dword of
-  // every 128-byte row line `pf_dist` slices beyond the ring: the line is in this XCD's L2 when the
-  // ring asks for it.  The loaded dword is never used; the register is pinned ("+v") so that the
-  // asynchronous write-back cannot land in a live register.
-  const int PF = g.pf_dist;
-  int pf_a = OOB, pf_w = OOB, pf_sink = 0;   // every consumer wave covers BM/NW rows of A and BN/NW rows of W
-  if (PF > 0) {
-    constexpr int RA = BM / NW, RB = BN / NW;
-    static_assert(RA <= 64 && RB <= 64, "prefetch: one line per lane");
-    const int r = m0 + wave * RA + lane;
-    if (lane < RA && r < g.M) {
-      const int b = g.segV >= g.M ? 0 : r / g.segV, q = r - b * g.segV;
-      pf_a = (int)((unsigned)(b * g.segS + q * (g.rstride > 1 ? g.rstride : 1)) * (unsigned)(g.lda * ESZ));
-    }
-    const int n = n0 + wave * RB + lane;
-    if (lane < RB && n < g.N) pf_w = (int)((unsigned)n * (unsigned)(g.ldw * ESZ));
-  }
-  int pf_k0 = (kt_begin + NS - 1 + PF) * BK, pf_c0 = 0, pf_toff = g.tap0;
-  if (PF > 0) {
-    const int tap = pf_k0 / g.tapC;
-    pf_c0 = pf_k0 - tap * g.tapC;
-    pf_toff = g.tap0 + tap * g.dil;
-  }
-  const int pf_end = (kt_begin + nk) * BK;
-  auto prefetch = [&]() {   // row validity of conv taps is ignored on purpose: a neighbouring row is real memory,
-    if (PF > 0) {           // the array ends are range-checked by the buffer resource
-      if (pf_k0 < pf_end) {
-        buf_prefetch4(g.A, g.a_bytes, pf_a, (pf_toff * (int)g.lda + pf_c0) * ESZ, pf_sink);
-        buf_prefetch4(g.W, g.w_bytes, pf_w, pf_k0 * ESZ, pf_sink);
-      }
-      pf_k0 += BK;
-      pf_c0 += BK;
-      if (pf_c0 >= g.tapC) {
-        pf_c0 = 0;
-        pf_toff += g.dil;
-      }
-    }
-  };
   if constexpr (NW == 4) {
     // ---- one consumer wave per SIMD (wave tile TM x TN >= 64 x 64): fewer, larger wave tiles cut the
     // LDS fragment traffic per MFMA (128x128 tile: 64 KiB of reads per K-slice instead of 96 KiB with
@@ -404,7 +355,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmPair& pr) {
       rda(S1{}, 1, As);
       rdb(S1{}, 1, Bs);
       mm(S0{});
-      prefetch();
       rda(S0{}, 2, As);
       rdb(S0{}, 2, Bs);
       mm(S1{});
@@ -448,7 +398,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmPair& pr) {
     if constexpr (TWOB) hard_barrier();
     else __builtin_amdgcn_s_barrier();
     if (kt == 0) tl_stamp(g, 1);
-    prefetch();
     if (late && kt > 0) {
       cvtb();
       mma();
@@ -486,7 +435,6 @@ __device__ __forceinline__ void gemm_ws_body(const GemmPair& pr) {
   if (late && nk > 0) cvtb();
   if (late && nk > 0) mma();
   }
-  if (PF > 0) asm volatile("s_waitcnt vmcnt(0)" : "+v"(pf_sink)::"memory");   // every prefetch has written back: the register is free again
   tl_stamp(g, 2);
   constexpr int XW = NW == 4 ? LW : 0;   // helper waves of the epilogue (see the loader branch)
   if constexpr (EPI == EPI_QKV_SPLIT) {

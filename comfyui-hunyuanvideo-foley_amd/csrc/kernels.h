@@ -102,7 +102,6 @@ struct GemmArgs {
   int wfmt;           // storage of W: 0 = the operand dtype, 1 = fp8 e4m3fn, 2 = fp8 e5m2 (bf16 activations; wave-specialised
                       // tiles only - widened to bf16 in registers, reference FP8WeightWrapper utils.py:316-366)
   int gelu_erf;       // EPI_GELU_T: exact (erf) GELU instead of the tanh form (the conditioning encoders' nn.GELU())
-  int pf_dist;        // wave-specialised mainloop: L2 prefetch distance in K-slices beyond the LDS ring (0 = off; set by the launcher)
   int dbg_mode;
   long long* dbg;     // tools/gemm_timeline.py: 4 wall-clock stamps per workgroup (entry, first slice
                       // landed, K loop done, epilogue done); null in production
@@ -144,7 +143,6 @@ struct AttnArgs {
   int in_dtype;
   int vt_pitch;
   int head_dim;     // 0 / 128: the Foley DiT; 64: the conditioning encoders (fp32 kernel and the 16-bit wide kernel)
-  int no_preload;   // set by the launcher (A/B switch FOLEY_ATTN_PRELOAD=0): small-grid kernel without the up-front operand requests
   long long* dbg;   // tools/attn_timeline.py: 5 wall-clock stamps per workgroup of the small-grid bf16 kernel; null in production
   int grp_q, grp_kv;     // head_dim 64, 16-bit operands: > 0 = block-diagonal attention - query t attends keys [g*grp_kv, (g+1)*grp_kv), g = t / grp_q
                          // (small groups packed into one sequence: the Synchformer's 8-frame time groups, 14 of them per 128-query workgroup)

@@ -1,7 +1,6 @@
 // HBM-bound row kernels of the Foley path: LayerNorm+modulate, RMSNorm+RoPE head split, small
 // elementwise helpers, the solver update and the DAC output convolution.  All arithmetic fp32;
 // one wavefront per row with 16-byte vector accesses and wave-level (DPP) reductions.
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.h"
@@ -724,44 +723,33 @@ int launch_ln_mod_pair(const LnArgs& a0, const LnArgs& a1, int D, float eps, int
       else FOLEY_LAUNCH((ln_mod_kernel<bf16_t, V, false>), grid, block, 0, st, pr, D, eps);          \
     }                                                                                                      \
   }
-  // rows that split evenly over 2 / 3 waves (D = 1536: 2 waves x 3 float4 per lane, or 3 x 2; 1408 / 256: one wave).  Two waves
-  // per row since the slabs are 16-bit (round 3, one box: bs=1 loop 347.4 -> 345.8 ms, bs=8 1525.7 -> 1520.2, 30 s 1488.7 -> 1478.6);
-  // three were better with fp32 slabs (round 2)
-  static const int wide = []() { const char* e = getenv("FOLEY_LN_WIDE"); return e ? atoi(e) : 2; }();   // A/B switch (0 = one wave per row, 3)
+  // rows that split evenly over 2 waves (D = 1536: 2 waves x 3 float4 per lane; 1408 / 256: one wave).  Two waves per row since
+  // the slabs are 16-bit (round 3, one box: bs=1 loop 347.4 -> 345.8 ms, bs=8 1525.7 -> 1520.2, 30 s 1488.7 -> 1478.6 against three
+  // waves, which were better with fp32 slabs in round 2)
   const int total_rows = a0.M + a1.M;
-  LnPair prw = pr;   // the multi-wave kernels take FOLEY_LN_RPB rows per workgroup
-  prw.blocks0 = (a0.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB;
-  const dim3 gridw(prw.blocks0 + (a1.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB);
-  if (wide && total_rows <= 4096 && D % (4 * 64 * 3) == 0 && D / (4 * 64 * 3) <= 4 && wide == 3) {
-#define FOLEY_LNW(V, W)                                                                                               \
+  if (total_rows <= 4096 && D % (4 * 64 * 2) == 0 && D / (4 * 64 * 2) <= 4) {
+    LnPair prw = pr;   // the two-wave kernel takes FOLEY_LN_RPB rows per workgroup
+    prw.blocks0 = (a0.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB;
+    const dim3 gridw(prw.blocks0 + (a1.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB), blk(64 * FOLEY_LN_RPB * 2);
+#define FOLEY_LNW(V)                                                                                                  \
     {                                                                                                                  \
-      dim3 blk(64 * FOLEY_LN_RPB * W);                                                                                               \
       if (pend) {                                                                                                      \
-        if (f32o) FOLEY_LAUNCH((ln_mod_wide_kernel<float, V, true, W>), gridw, blk, 0, st, prw, D, eps);                \
-        else if (f16o && s16) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, true, W, true>), gridw, blk, 0, st, prw, D, eps);  \
-        else if (f16o) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, true, W>), gridw, blk, 0, st, prw, D, eps);           \
-        else if (s16) FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, true, W, true>), gridw, blk, 0, st, prw, D, eps);     \
-        else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, true, W>), gridw, blk, 0, st, prw, D, eps);                    \
+        if (f32o) FOLEY_LAUNCH((ln_mod_wide_kernel<float, V, true, 2>), gridw, blk, 0, st, prw, D, eps);                \
+        else if (f16o && s16) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, true, 2, true>), gridw, blk, 0, st, prw, D, eps);  \
+        else if (f16o) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, true, 2>), gridw, blk, 0, st, prw, D, eps);           \
+        else if (s16) FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, true, 2, true>), gridw, blk, 0, st, prw, D, eps);     \
+        else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, true, 2>), gridw, blk, 0, st, prw, D, eps);                    \
       } else {                                                                                                         \
-        if (f32o) FOLEY_LAUNCH((ln_mod_wide_kernel<float, V, false, W>), gridw, blk, 0, st, prw, D, eps);               \
-        else if (f16o) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, false, W>), gridw, blk, 0, st, prw, D, eps);          \
-        else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, false, W>), gridw, blk, 0, st, prw, D, eps);                   \
+        if (f32o) FOLEY_LAUNCH((ln_mod_wide_kernel<float, V, false, 2>), gridw, blk, 0, st, prw, D, eps);               \
+        else if (f16o) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, false, 2>), gridw, blk, 0, st, prw, D, eps);          \
+        else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, false, 2>), gridw, blk, 0, st, prw, D, eps);                   \
       }                                                                                                                \
     }
-    const int v3 = D / (4 * 64 * 3);
-    if (v3 == 1) FOLEY_LNW(1, 3)
-    else if (v3 == 2) FOLEY_LNW(2, 3)
-    else if (v3 == 3) FOLEY_LNW(3, 3)
-    else FOLEY_LNW(4, 3)
-    FOLEY_LAUNCH_CHECK();
-    return 0;
-  }
-  if (wide == 2 && total_rows <= 4096 && D % (4 * 64 * 2) == 0 && D / (4 * 64 * 2) <= 4) {
     const int v2 = D / (4 * 64 * 2);
-    if (v2 == 1) FOLEY_LNW(1, 2)
-    else if (v2 == 2) FOLEY_LNW(2, 2)
-    else if (v2 == 3) FOLEY_LNW(3, 2)
-    else FOLEY_LNW(4, 2)
+    if (v2 == 1) FOLEY_LNW(1)
+    else if (v2 == 2) FOLEY_LNW(2)
+    else if (v2 == 3) FOLEY_LNW(3)
+    else FOLEY_LNW(4)
     FOLEY_LAUNCH_CHECK();
     return 0;
   }

@@ -422,18 +422,3 @@ def test_plan_needs_no_device_and_checks_its_arguments():
     d1 = _desc("bf16", "store", 80, 6144, 1536, {}, keep)
     assert lib.foley_debug_gemm_plan(C.byref(d0), C.byref(d1), 0, out) != 0   # the two problems must share the epilogue
     assert "epilogue" in lib.foley_last_error().decode()
-
-
-def test_debug_prefetch_turns_rotation_off():
-    """The debug L2 prefetch stream (foley_debug_gemm_prefetch) does not follow a rotated K walk: under it the plan never rotates."""
-    lib = _lib()
-    lib.foley_debug_gemm_prefetch.argtypes = [C.c_int]
-    lib.foley_debug_gemm_prefetch.restype = None
-    case, want = CASES["qkv_500_krot"]
-    assert want[3] == 1 and plan(case) == want
-    lib.foley_debug_gemm_prefetch(2)
-    try:
-        assert plan(case) == want[:3] + (0,)
-    finally:
-        lib.foley_debug_gemm_prefetch(0)
-    assert plan(case) == want

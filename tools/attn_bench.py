@@ -1,5 +1,5 @@
 """Time the 16-bit attention kernels at the shapes of the sampler (HIP events, operands rotated between launches).
-    FOLEY_ATTN_LDS=0|1 python tools/attn_bench.py
+    [FOLEY_HIP_LIB=<another build of the library>] python tools/attn_bench.py
 """
 import os
 import sys

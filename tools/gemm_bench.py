@@ -26,18 +26,12 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--check", action="store_true")
 ap.add_argument("--conv", action="store_true", help="treat K as 3*C of a channels-last conv k=3 over clips of 250 tokens")
-ap.add_argument("--pf", default="0", help="comma list of L2 prefetch distances (K-slices beyond the ring) for the wave-specialised tiles")
 ap.add_argument("--pad", default="0", help="comma list: row padding (elements) of BOTH operands' storage (lda = C + pad, ldw = K + pad)")
 ap.add_argument("--ksplits", default="", help="comma list: benchmark the gated-residual epilogue with these K splits")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
 tiles = [int(t) for t in a.tiles.split(",")]
-import ctypes as _C
-_lib = rt.load_library()
-_lib.foley_debug_gemm_prefetch.argtypes = [_C.c_int]
-_lib.foley_debug_gemm_prefetch.restype = None
-pfs = [int(v) for v in a.pf.split(",")]
 print(f"M={a.m} dtype={a.dtype}")
 for name in a.shapes.split(","):
     N, K = SHAPES[name]
@@ -75,8 +69,7 @@ for name in a.shapes.split(","):
                 line += f" t{t}k{ksp}:{us:6.1f}us {2 * a.m * N * K / us / 1e6:4.0f}TF |"
         print(line, flush=True)
         continue
-    for t, pf, pad in [(t, pf, pad) for t in tiles for pf in pfs for pad in [int(v) for v in a.pad.split(",")]]:
-        _lib.foley_debug_gemm_prefetch(pf)
+    for t, pad in [(t, pad) for t in tiles for pad in [int(v) for v in a.pad.split(",")]]:
         if pad:      # row-padded copies of the same operands
             Ca = A.shape[1]
             Ap = torch.zeros(a.m, Ca + pad, device=dev, dtype=dt)
@@ -106,7 +99,7 @@ for name in a.shapes.split(","):
         torch.cuda.synchronize()
         ts = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
         us = ts[len(ts) // 2] * 1e3
-        line += f" t{t}p{pf}d{pad}:{us:6.1f}us {2 * a.m * N * K / us / 1e6:5.0f}TF{err} |"
+        line += f" t{t}d{pad}:{us:6.1f}us {2 * a.m * N * K / us / 1e6:5.0f}TF{err} |"
         if pad:
             del Wps, Ap
     print(line, flush=True)
