@@ -1,0 +1,314 @@
+"""Per-element error bounds and guard bands for the op-level kernel tests.
+
+The norm gates of test_ops_gpu.py / test_pairs_gpu.py (conftest.rel_err against a per-dtype tolerance) average an error over the
+whole tensor: a wrong tile corner, a K slice skipped on a few rows or a bias missed on one column vanish in them.  The checks
+here hold EVERY element against a bound that is derived from the arithmetic (never from what a kernel was seen to do), and
+look at the memory around an output.
+
+Conventions
+    ref64     the fp64 result computed from the operands AS ROUNDED to the compute dtype (16-bit operands are exact in fp64).
+    U32       2^-23: the fp32 unit round-off (2^-24) doubled, so that a bound also holds for an accumulator that truncates.
+    U16       per-rounding relative error taken for a value rounded once to a 16-bit type: 2^-9 (bf16), 2^-12 (fp16) - half
+              the worst-case unit round-off (2^-8 / 2^-11), which the terms below may use because each of them multiplies it
+              with a magnitude (`mag`, P @ |V|) that bounds the rounded value by its sum of absolute products, not by the value.
+    output    a 16-bit store adds half an ulp of max(|ref|, |got|) in that type, times (1 + 2^-6) for the double rounding
+              of an fp32 value that sits on a tie (fp16: ulp never below the subnormal spacing 2^-24).
+
+GEMM accumulation term: e_y = (K + 4) * U32 * mag, mag = |A| @ |W|^T + |bias| - the deterministic worst case of K fp32
+additions in ANY order (split-K, K-origin rotation, atomics, tap fusion), plus the bias add and the epilogue's own roundings.
+"""
+import math
+
+import torch
+
+from conftest import record_parity, rel_err  # noqa: F401  (re-exported: the test files import them from here or conftest)
+
+U32 = 2.0 ** -23
+U16 = {torch.bfloat16: 2.0 ** -9, torch.float16: 2.0 ** -12}
+MANT = {torch.bfloat16: 8, torch.float16: 11}      # significand bits, the implicit one included
+LIP_SILU, LIP_GELU = 1.1, 1.13                     # Lipschitz constants: max |silu'| = 1.0998, max |gelu'| = 1.129
+LIP_SNAKE = 2.0                                    # snake(v) = v + sin(a v)^2 / a: |1 + sin(2 a v)| <= 2 for every a
+A_ACT_ERF16 = 8e-7                                 # common.h::gelu_erf_fast, absolute (test_exact_gelu_fast_form_error_bound)
+GUARD_BITS = {4: 0x5A5A5A5A, 2: 0x5A5A, 1: 0x5A}   # finite, non-NaN in fp32 (1.5e16), bf16 (1.5e16), fp16 (203.25)
+_INT = {4: torch.int32, 2: torch.int16, 1: torch.int8}
+
+
+# ----------------------------------------------------------------------------- ulps and the output term
+def ulp16(x, dtype):
+    """Spacing of the 16-bit `dtype` at |x| (fp64 tensor): 2^(floor(log2 |x|) - (mant - 1)); fp16 never below its subnormal
+    spacing 2^-24, bf16 (8 exponent bits) never below 2^-133."""
+    x = x.double().abs()
+    _, e = torch.frexp(x.clamp_min(1e-300))          # |x| = m * 2^e, m in [0.5, 1)
+    ulp = torch.ldexp(torch.ones_like(x), e - MANT[dtype])
+    return ulp.clamp_min(2.0 ** -24 if dtype == torch.float16 else 2.0 ** -133)
+
+
+def output_term(ref, got, out_dtype):
+    """Error a correctly rounded store of the exact fp32 result may add: 0 for fp32 (covered by the accumulation term)."""
+    if out_dtype not in MANT:
+        return torch.zeros_like(ref, dtype=torch.float64)
+    return 0.5 * (1 + 2.0 ** -6) * ulp16(torch.maximum(ref.double().abs(), got.double().abs()), out_dtype)
+
+
+class Bound:
+    """An absolute per-element bound `e` (fp64) on the value BEFORE the store, plus the store's type."""
+
+    def __init__(self, e, out_dtype=torch.float32):
+        self.e, self.out_dtype = e, out_dtype
+
+    def total(self, ref, got):
+        return self.e + output_term(ref, got, self.out_dtype)
+
+
+# ----------------------------------------------------------------------------- GEMM
+def gemm_ref64(A, W, bias=None):
+    """(ref64, mag) of y = A @ W^T + bias from the operands as given (already rounded to the compute dtype), in fp64."""
+    A, W = A.double().cpu(), W.double().cpu()
+    ref, mag = A @ W.t(), A.abs() @ W.abs().t()
+    if bias is not None:
+        b = bias.double().cpu()
+        ref, mag = ref + b, mag + b.abs()
+    return ref, mag
+
+
+def conv3_cols(x):
+    """x [B, L, C] -> the [B*L, 3C] rows a channels-last conv k = 3, pad 1 multiplies with packers.conv_to_gemm(w) (K = tap*C + c)."""
+    B, L, C = x.shape
+    p = torch.nn.functional.pad(x, (0, 0, 1, 1))
+    return torch.cat((p[:, :L], p[:, 1:L + 1], p[:, 2:L + 2]), dim=-1).reshape(B * L, 3 * C)
+
+
+def elementwise_gemm_bound(A, W, bias, K, out_dtype=torch.float32, extra=None, mag=None):
+    """Bound on y = A @ W^T + bias accumulated in fp32 in any order: (K + 4) * U32 * mag (+ extra), stored as out_dtype.
+    `mag` may be passed when gemm_ref64 already computed it (the 4000-row cases share it across dtypes)."""
+    if mag is None:
+        _, mag = gemm_ref64(A, W, bias)
+    e = (K + 4) * U32 * mag
+    if extra is not None:
+        e = e + extra
+    return Bound(e, out_dtype)
+
+
+def gated_residual_bound(e_y, gate, x0, y):
+    """x0 + g * y in fp32: |g| * e_y + U32 * (|x0| + |g * y|)."""
+    g = gate.double().abs()
+    return Bound(g * e_y + U32 * (x0.double().abs() + g * y.double().abs()))
+
+
+def slab_bound(e_y, mag, ks, slab_dtype):
+    """Sum over the ks deferred split-K slabs against y - bias (e_y, mag computed WITHOUT the bias): e_y for fp32 slabs; 16-bit
+    slabs add ks * U16 * mag - each partial is bounded by mag and rounded once."""
+    return Bound(e_y + (ks * U16[slab_dtype] * mag if slab_dtype in U16 else 0.0))
+
+
+def act64(name, y):
+    y = y.double()
+    if name == "silu":
+        return y * torch.sigmoid(y)
+    return torch.nn.functional.gelu(y, approximate="tanh" if name == "gelu" else "none")
+
+
+def measure_a_act(name, y64, dev):
+    """4 x the largest |PyTorch's fp32 device activation of fp32(y) - the fp64 activation of y|: reference against reference
+    (the factor 4 covers one more approximate instruction each for the exponential and the reciprocal of a fast form)."""
+    y32 = y64.float().to(dev)
+    if name == "silu":
+        a32 = torch.nn.functional.silu(y32)
+    else:
+        a32 = torch.nn.functional.gelu(y32, approximate="tanh" if name == "gelu" else "none")
+    return 4.0 * float((a32.double().cpu() - act64(name, y64)).abs().max())
+
+
+def act_bound(name, e_y, a_act, out_dtype):
+    """act(y): Lipschitz constant of the activation times e_y, plus the activation's own error a_act."""
+    return Bound((LIP_SILU if name == "silu" else LIP_GELU) * e_y + a_act, out_dtype)
+
+
+def silugate_bound(a, b, e_a, e_b, a_act, out_dtype):
+    """silu(a) * b: |silu(a)| e_b + 1.1 |b| e_a, and - beyond that first-order expression, each needed and tiny against it - the
+    second-order product 1.1 e_a e_b, the activation's error a_act scaled by the factor it multiplies (|b| + e_b, not 1), and the
+    fp32 product's own rounding U32 |silu(a) b|."""
+    sa, bb = act64("silu", a).abs(), b.double().abs()
+    return Bound(sa * e_b + LIP_SILU * bb * e_a + LIP_SILU * e_a * e_b + a_act * (bb + e_b) + U32 * sa * bb, out_dtype)
+
+
+def snake64(v, alpha):
+    """DAC snake in fp64: v + sin(alpha v)^2 / (alpha + 1e-9), alpha broadcast over the last (channel) dimension."""
+    v, a = v.double(), alpha.double()
+    return v + torch.sin(a * v) ** 2 / (a + 1e-9)
+
+
+def measure_a_act_snake(v64, alpha, dev):
+    """4 x the largest |PyTorch's fp32 device snake of fp32(v) - the fp64 snake of v| (reference against reference, as measure_a_act)."""
+    v32, a32 = v64.float().to(dev), alpha.float().to(dev)
+    s32 = v32 + (1.0 / (a32 + 1e-9)) * torch.sin(a32 * v32) ** 2
+    return 4.0 * float((s32.double().cpu() - snake64(v64, alpha)).abs().max())
+
+
+def dac_bounds(e_y, v, res, a_act):
+    """DAC residual epilogue (fp32 only): out0 = v = y (+ res), out1 = snake(v).  out0: e_y, plus one fp32 addition U32 (|res| + |v|)
+    when a residual is added; out1: the snake's Lipschitz constant 2 times that, plus the activation's own error a_act."""
+    e_v = e_y + (U32 * (res.double().abs() + v.double().abs()) if res is not None else 0.0)
+    return Bound(e_v), Bound(LIP_SNAKE * e_v + a_act)
+
+
+def head_split_bound(e_y, y_head, out_dtype, gain=None):
+    """RMSNorm (+ RoPE, a rotation of pairs: it moves an error vector without stretching it beyond the two partners' sum) of a
+    128-wide head: the GEMM term pushed through the norm, 2 * e_y / rms per element, times |gain|; V (gain None) passes e_y
+    through unchanged.  Two departures from the plain '2 e_y / rms per element', both needed for the bound to be true: e_y is
+    the head's LARGEST (RoPE mixes an element with its pair partner, the rms with all 128), and 8 U32 |gain| max|y| / rms covers
+    the fp32 roundings of the norm, the gain and the rotation themselves (at e_y ~ 1e-3 it is four orders below the first term)."""
+    if gain is None:
+        return Bound(e_y, out_dtype)
+    rms = y_head.double().pow(2).mean(-1, keepdim=True).sqrt()
+    g = float(gain.double().abs().max())
+    return Bound((2.0 * g * e_y.amax(-1, keepdim=True) / rms).expand_as(e_y).clone() + 8 * U32 * g * (y_head.double().abs() / rms).amax(-1, keepdim=True), out_dtype)
+
+
+# ----------------------------------------------------------------------------- the check
+def assert_elementwise(got, ref64, bound, what):
+    """Every element of `got` within `bound` (a Bound, a tensor or a number) of ref64.  A failure reports the count of offending
+    elements, the worst (row, col) with its got / ref / bound, and the bounding box of all offenders (what tells a tile edge from
+    a stray lane); NaN offends.  Returns the largest err / bound."""
+    got, ref = got.detach().double().cpu(), ref64.detach().double().cpu()
+    assert got.shape == ref.shape, (what, tuple(got.shape), tuple(ref.shape))
+    if isinstance(bound, Bound):
+        b = bound.total(ref, got)
+    else:
+        b = torch.as_tensor(bound, dtype=torch.float64)
+    b = b.expand_as(ref)
+    err = (got - ref).abs()
+    bad = ~(err <= b)
+    if bool(bad.any()):
+        cols = ref.shape[-1] if ref.dim() else 1
+        bad2, ratio = bad.reshape(-1, cols), torch.nan_to_num(err / b.clamp_min(1e-300), nan=float("inf")).reshape(-1, cols)
+        idx = bad2.nonzero()
+        r0, c0 = (int(v) for v in idx.min(0).values)
+        r1, c1 = (int(v) for v in idx.max(0).values)
+        w = int(ratio.argmax())
+        wr, wc = divmod(w, cols)
+        raise AssertionError(
+            f"{what}: {int(bad.sum())} of {bad.numel()} elements outside their bound; worst at (row {wr}, col {wc}) of "
+            f"[{bad2.shape[0]}, {cols}]: got {float(got.reshape(-1, cols)[wr, wc])!r} ref {float(ref.reshape(-1, cols)[wr, wc])!r} "
+            f"bound {float(b.reshape(-1, cols)[wr, wc]):.3e} (err / bound {float(ratio[wr, wc]):.3g}); offenders lie in rows "
+            f"[{r0}, {r1}] x cols [{c0}, {c1}]")
+    return float((err / b.clamp_min(1e-300)).max()) if err.numel() else 0.0
+
+
+# ----------------------------------------------------------------------------- guard bands
+class Guarded:
+    """A [rows, cols] interior (NaN-filled, row pitch cols + pad_cols) inside a larger buffer filled with a fixed non-NaN bit
+    pattern: `before` / `after` guard rows (or guard slabs: a row is everything but the leading dimension) and pad columns.
+    `view` is the interior to launch into (its data_ptr() and `pitch` go into the descriptor), check() asserts that every guard
+    word is bit-identical afterwards (compared through an integer view)."""
+
+    def __init__(self, shape, dtype, dev, rows=(2, 3), pad_cols=0, misalign=0, fill=float("nan")):
+        lead, rest = shape[0], tuple(shape[1:])
+        inner = 1
+        for s in rest:
+            inner *= s
+        self.pitch = inner + pad_cols
+        es = torch.empty((), dtype=dtype).element_size()
+        self.n0 = rows[0] * self.pitch + misalign
+        total = self.n0 + lead * self.pitch + rows[1] * self.pitch
+        self.ibuf = torch.full((total,), GUARD_BITS[es], dtype=_INT[es], device=dev)
+        self.buf = self.ibuf.view(dtype)
+        self.view = torch.as_strided(self.buf, (lead,) + rest, (self.pitch,) + tuple(torch.empty(rest).stride()), self.n0)
+        self.view.fill_(fill)
+        mask = torch.ones(total, dtype=torch.bool, device=dev)
+        torch.as_strided(mask, (lead, inner), (self.pitch, 1), self.n0).fill_(False)
+        self.mask, self.bits, self.lead, self.inner = mask, GUARD_BITS[es], lead, inner
+
+    def check(self, what="guard"):
+        hit = (self.ibuf != self.bits) & self.mask
+        if bool(hit.any()):
+            at = hit.nonzero().flatten().cpu() - self.n0
+            r, c = at // self.pitch, at % self.pitch       # floor division: rows before the interior are negative
+            raise AssertionError(
+                f"{what}: {at.numel()} guard words overwritten around the [{self.lead}, {self.inner}] interior (pitch {self.pitch}); "
+                f"rows [{int(r.min())}, {int(r.max())}] x cols [{int(c.min())}, {int(c.max())}], first at (row {int(r[0])}, col {int(c[0])})")
+
+
+def guarded(shape, dtype, dev, rows=(2, 3), pad_cols=0, misalign=0, fill=float("nan")):
+    return Guarded(shape, dtype, dev, rows, pad_cols, misalign, fill)
+
+
+# ----------------------------------------------------------------------------- LayerNorm (+ pending split-K slabs)
+def layernorm_ref_and_bound(x0, shift, scale, eps, out_dtype, slabs=None, bias=None, gate=None):
+    """fp64 reference and per-element bounds of  x = x0 + gate * (sum_s slabs[s] + bias)  (written back in place) and
+    out = (x - mean) * rstd * (1 + scale) + shift  from the fp32 inputs; all arguments fp64-convertible CPU tensors broadcastable
+    to [M, D] (slabs [k, M, D]).  Returns (x64, out64, bound_x, bound_out).
+
+    Derivation (u = U32; c = D / 64 + 8 is the longest chain of fp32 additions a row reduction of either kernel form has: a lane
+    sums its D / 64 elements one after the other, the butterfly over 64 lanes adds 6 levels, the two-wave form one more, the
+    division by D one rounding - a reduction of depth c has an error of at most c u sum|terms|):
+        e_x   = (k + 3) u (|x0| + |g| (sum|slab| + |bias|))      k + 1 sequential adds, the product with g, the add to x0
+        d_m   = c u mean|x| + mean(e_x)                          the mean
+        e_d   = d_m + e_x + u |x - mean|                         one centred element
+        d_var = (c + 4) u var + 2 mean(|d| e_d) + mean(e_d^2)    squares, their reduction, the division
+        d_r   = d_var / (2 (var + eps) (1 - d_var / (var + eps))) + 3 u      relative, on rstd (add eps, sqrt, reciprocal)
+        e_out = (e_d rstd + |xhat| (d_r + 4 u)) (1 + |scale|) + u |out|
+    With rows of 1e3 + N(0, 1) the leading term is d_m ~ 32 * 1.2e-7 * 1e3 = 4e-3: a one-pass variance (error ~ 1e6 u D) or a
+    neighbour's mean (|difference| ~ 0.04) lie far outside, the reduction order of either kernel form inside.
+    This departs from a bound c u |xhat| (1 + |scale|) with c = D: that expression is zero at xhat = 0, where the rounding of the
+    mean (absolute, ~ u |mean|) still lands, so no fp32 kernel meets it at |x| ~ 1e3.  Two limits follow and are meant to be known:
+    (1) c is read from TODAY's reduction shape (rowops.hip: D / 64 elements per lane, a 64-lane butterfly, two waves at most).  A
+    kernel that legitimately lets a lane sum more elements raises its own worst case above this c (MI355X uses 0.54 of the bound
+    now): c must then be re-derived from the new data path, not scaled to fit.  (2) At |x| ~ 1e3 the bound is ~ 4e-3 ABSOLUTE, so
+    for an fp32 output it is weaker than the 1e-4 norm gate of test_ln_mod_width for an error spread over the whole tensor; what
+    it adds is the localised defect (one row, one lane's columns), the written-back x and the guards.  The norm gates stay."""
+    x0 = x0.double()
+    M, D = x0.shape
+    u, c = U32, D / 64 + 8
+    if slabs is not None:
+        k = slabs.shape[0]
+        s, g = slabs.double(), gate.double().expand(M, D)
+        b = bias.double().expand(M, D) if bias is not None else torch.zeros(M, D, dtype=torch.float64)
+        x = x0 + g * (s.sum(0) + b)
+        e_x = (k + 3) * u * (x0.abs() + g.abs() * (s.abs().sum(0) + b.abs()))
+    else:
+        x, e_x = x0, torch.zeros_like(x0)
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    var = d.pow(2).mean(-1, keepdim=True)
+    d_m = c * u * x.abs().mean(-1, keepdim=True) + e_x.mean(-1, keepdim=True)
+    e_d = d_m + e_x + u * d.abs()
+    d_var = (c + 4) * u * var + 2 * (d.abs() * e_d).mean(-1, keepdim=True) + e_d.pow(2).mean(-1, keepdim=True)
+    rel = d_var / (var + eps)
+    d_r = torch.where(rel < 0.5, 0.5 * rel / (1 - rel.clamp_max(0.5)), torch.full_like(rel, float("inf"))) + 3 * u
+    rstd = torch.rsqrt(var + eps)
+    xhat = d * rstd
+    sc = scale.double().expand(M, D) if scale is not None else torch.zeros(M, D, dtype=torch.float64)
+    sh = shift.double().expand(M, D) if shift is not None else torch.zeros(M, D, dtype=torch.float64)
+    out = xhat * (1 + sc) + sh
+    e_out = (e_d * rstd + xhat.abs() * (d_r + 4 * u)) * (1 + sc.abs()) + u * out.abs()
+    return x, out, Bound(e_x + u * x.abs()), Bound(e_out, out_dtype)
+
+
+# ----------------------------------------------------------------------------- attention
+def attention_ref_and_bound(q, k, v, out_dtype, p_dtype=None):
+    """softmax(q k^T / sqrt(hd)) v in fp64 from the operands as rounded (q [B, H, Sq, hd], k / v [Bk, H, Skv, hd], Bk divides B:
+    batch b reads k / v entry b // (B / Bk)), as [B, Sq, H * hd], with the bound
+        (c_p u_p + 2 d_s) (P @ |V|)  (+ output term),
+    d_s = (hd + 4) U32 max_keys(|q| . |k|) / sqrt(hd) the worst-case error of a score (hd fp32 additions in any order), felt once
+    in the numerator and once in the row sum; u_p the rounding of a probability to the operand type before the P V MFMA.
+    Read from attention.hip: every 16-bit kernel (attn_bf16 / lds / wide / long / pair) rounds P ONCE, right after the
+    exponential (to_carrier), and sums the row from the UNROUNDED fp32 values, so c_p = 1 and u_p = U16[p_dtype]; the fp32 kernel
+    rounds nothing: c_p = 1 with u_p = U32.
+    NOT rigorous for the fp32 kernel (and, to a lesser degree, the others): the expression leaves out the Skv fp32 additions of the
+    P V product and of the row sum (worst case (Skv + 4) U32 P @ |V|: 4e-4 at Skv = 3480 against 2 d_s ~ 2e-4) and the error of the
+    exponential.  It holds in practice because those errors add like a random walk while d_s is a worst case (MI355X: fp32 kernel at
+    7e-3 of the bound); a kernel that exceeds it on long keys with a clean score path must be judged against the full expression."""
+    B, H, Sq, hd = q.shape
+    div = B // k.shape[0]
+    u_p = U16[p_dtype] if p_dtype in U16 else U32
+    ref = torch.empty(B, Sq, H * hd, dtype=torch.float64)
+    e = torch.empty_like(ref)
+    for b in range(B):
+        qb, kb, vb = q[b].double(), k[b // div].double(), v[b // div].double()
+        s = qb @ kb.transpose(1, 2) / math.sqrt(hd)
+        d_s = (hd + 4) * U32 * (qb.abs() @ kb.abs().transpose(1, 2)).amax(-1, keepdim=True) / math.sqrt(hd)
+        p = torch.softmax(s, -1)
+        ref[b] = (p @ vb).transpose(0, 1).reshape(Sq, H * hd)
+        e[b] = ((u_p + 2 * d_s) * (p @ vb.abs())).transpose(0, 1).reshape(Sq, H * hd)
+    return ref, Bound(e, out_dtype)

@@ -1,0 +1,368 @@
+"""The element-wise checker (tests/opcheck.py) tested on the CPU.
+
+For each bound, a CPU "kernel" that does what the HIP kernel does in a different order (fp32 accumulation over 4 K ranges summed
+in reverse; a tiled online softmax with P rounded to the operand type; a two-pass fp32 LayerNorm with the lane / butterfly
+reduction order) must stay inside it, and each planted defect - the kind a ragged tile, one wave's fragment or a skipped K
+range leaves - must be MISSED by the norm gate the GPU suites use (conftest.rel_err against the per-dtype tolerance) and CAUGHT
+by the element-wise check.  For fp32 operands, whose 2e-6 gate already sees most of them, only the catch is asserted.
+
+Shapes: 500 x 1536 x 1536 for bf16 and fp32 operands.  fp16 operands use the bs = 8 grid 4000 x 6144 x 1536: at 500 x 1536 the fp16
+gate (8e-4) already sees a 64-wide K slice lost on a 1 x 16 strip (0.2 * 4 / 876 = 9e-4), so "missed by the old gate" can only be
+stated for fp16 where the grid is large - which is where the 256x256 tiles and the panel-group order run.
+"""
+import math
+import re
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import opcheck as oc
+from conftest import rel_err
+
+F32_TOL, BF16_TOL, F16_TOL = 2e-6, 6e-3, 8e-4                         # test_ops_gpu.py: the per-dtype GEMM gates
+GATE = {torch.float32: F32_TOL, torch.bfloat16: BF16_TOL, torch.float16: F16_TOL}
+LN_TOL = {torch.float32: 1e-4, torch.bfloat16: 4e-3, torch.float16: 5e-4}       # test_pairs_gpu.py
+ATTN_TOL = {torch.float32: 3e-6, torch.bfloat16: 1e-2, torch.float16: 2e-3}     # test_attention / test_attention_bf16
+SHAPE = {torch.bfloat16: (500, 1536, 1536), torch.float32: (500, 1536, 1536), torch.float16: (4000, 6144, 1536)}
+DT = [torch.bfloat16, torch.float16, torch.float32]
+IDS = ["bf16", "f16", "f32"]
+
+
+def _rand(shape, seed, scale=1.0):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
+
+
+def _gemm_kernel(A, W, b, drop=None):
+    """fp32 accumulation over 4 K ranges, the ranges summed in reverse, then the bias.  drop = (rows, cols, k0): those outputs lose
+    the 64-wide K slice at k0."""
+    A, W = A.float(), W.float()
+    K = A.shape[1]
+    edges = [0, K // 4 // 64 * 64, K // 2 // 64 * 64, 3 * K // 4 // 64 * 64, K]
+    parts = [A[:, lo:hi] @ W[:, lo:hi].t() for lo, hi in zip(edges[:-1], edges[1:])]
+    y = parts[3]
+    for p in parts[2::-1]:
+        y = y + p
+    if drop is not None:
+        rows, cols, k0 = drop
+        y[rows, cols] -= A[rows, k0:k0 + 64] @ W[cols, k0:k0 + 64].t()
+    return y + b if b is not None else y
+
+
+_cache = {}
+
+
+def _problem(dt):
+    """Operands rounded to dt, the emulated fp32 result, ref64 and mag - once per dtype."""
+    if dt not in _cache:
+        M, N, K = SHAPE[dt]
+        A, W, b = _rand((M, K), 1).to(dt), _rand((N, K), 2, 1 / math.sqrt(K)).to(dt), _rand((N,), 3, 0.1)
+        ref, mag = oc.gemm_ref64(A, W, b)
+        _cache[dt] = dict(A=A, W=W, b=b, ref=ref, mag=mag, y=_gemm_kernel(A, W, b), M=M, N=N, K=K)
+    return _cache[dt]
+
+
+def _missed_and_caught(dt, got, ref, bound, what, gate=None, box=None):
+    """The planted defect passes the norm gate (16-bit operands) and fails the element-wise check, inside `box`."""
+    if dt != torch.float32:
+        e = rel_err(got, ref)
+        assert e < (gate or GATE[dt]), (what, "the old gate sees this defect already", e)
+    with pytest.raises(AssertionError) as ei:
+        oc.assert_elementwise(got, ref, bound, what)
+    msg = str(ei.value)
+    assert "outside their bound" in msg
+    if box is not None:      # every offender lies inside the planted region (an element whose own error is tiny may stay inside its bound)
+        r0, r1, c0, c1 = (int(v) for v in re.search(r"rows \[(-?\d+), (-?\d+)\] x cols \[(-?\d+), (-?\d+)\]", msg).groups())
+        assert box[0] <= r0 <= r1 <= box[1] and box[2] <= c0 <= c1 <= box[3], msg
+
+
+# ----------------------------------------------------------------------------- helpers of the checker
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_ulp16_is_the_spacing_of_the_type(dt):
+    x = torch.cat((_rand((4096,), 5).double() * 10, torch.tensor([1.0, 2.0, 0.5, 3e-5, 1e-7, 65504.0 if dt == torch.float16 else 1e30],
+                                                                  dtype=torch.float64)))
+    xq = x.to(dt)
+    up = (xq.abs().view(torch.int16) + 1).view(dt)                       # the next representable value: one step in the bit pattern
+    ok = torch.isfinite(up.float())
+    assert torch.equal((up.double() - xq.abs().double())[ok], oc.ulp16(xq.double(), dt)[ok])
+    # rounding any fp64 value to the type stays within the output term
+    assert bool(((xq.double() - x).abs() <= oc.output_term(x, xq, dt)).all())
+
+
+def test_guard_band_reports_strays_and_keeps_quiet_otherwise():
+    dev = torch.device("cpu")
+    for dt in (torch.float32, torch.bfloat16, torch.float16):
+        g = oc.guarded((5, 24), dt, dev, rows=(2, 3), pad_cols=8)
+        assert g.pitch == 32 and g.view.shape == (5, 24) and bool(torch.isnan(g.view).all())
+        assert bool(torch.isfinite(g.buf[:2 * 32].float()).all()), "the guard pattern must not be NaN"
+        g.view.copy_(torch.ones(5, 24))
+        g.check()
+        for off, where in ((g.n0 - 1, "row -1, col 31"), (g.n0 + 24, "row 0, col 24"), (g.n0 + 5 * 32, "row 5, col 0")):
+            g2 = oc.guarded((5, 24), dt, dev, rows=(2, 3), pad_cols=8)
+            g2.buf[off] = 1.0
+            with pytest.raises(AssertionError, match=where):
+                g2.check()
+    g = oc.guarded((8, 4, 6), torch.float32, dev, rows=(1, 1))       # guard slabs around [ks, M, N]
+    assert g.view.is_contiguous() and g.view.shape == (8, 4, 6)
+    g.view.zero_()
+    g.check()
+    m = oc.guarded((5, 24), torch.float32, dev, pad_cols=8, misalign=2)
+    assert (m.view.data_ptr() - m.buf.data_ptr()) % 16 == 8
+
+
+def test_assert_elementwise_reports_box_and_nan():
+    ref = torch.zeros(10, 20, dtype=torch.float64)
+    got = ref.clone()
+    assert oc.assert_elementwise(got, ref, 1e-3, "clean") == 0.0
+    got[3:5, 7:9] = 1.0
+    got[4, 8] = float("nan")
+    with pytest.raises(AssertionError) as ei:
+        oc.assert_elementwise(got, ref, 1e-3, "planted")
+    assert "4 of 200" in str(ei.value) and "rows [3, 4] x cols [7, 8]" in str(ei.value) and "(row 4, col 8)" in str(ei.value)
+
+
+# ----------------------------------------------------------------------------- GEMM bounds
+@pytest.mark.parametrize("dt", DT, ids=IDS)
+@pytest.mark.parametrize("shape", [(500, 1536, 1536), (1000, 1536, 6144)], ids=["k1536", "k6144"])
+def test_reordered_accumulation_stays_inside(dt, shape):
+    M, N, K = shape
+    A, W, b = _rand((M, K), 11).to(dt), _rand((N, K), 12, 1 / math.sqrt(K)).to(dt), _rand((N,), 13, 0.1)
+    ref, mag = oc.gemm_ref64(A, W, b)
+    y = _gemm_kernel(A, W, b)
+    r32 = oc.assert_elementwise(y, ref, oc.elementwise_gemm_bound(A, W, b, K, mag=mag), "fp32 store")
+    assert r32 < 0.05, r32            # the bound is worst-case: a real accumulation uses a sliver of it
+    if dt != torch.float32:
+        r16 = oc.assert_elementwise(y.to(dt), ref, oc.elementwise_gemm_bound(A, W, b, K, dt, mag=mag), "16-bit store")
+        assert r16 <= 1.0
+
+
+@pytest.mark.parametrize("dt", DT, ids=IDS)
+@pytest.mark.parametrize("rows", [1, 16], ids=["strip_1x16", "patch_16x16"])
+def test_dropped_k_slice(dt, rows):
+    """One 64-wide K slice lost on a 1 x 16 strip of the last row / on a 16 x 16 patch at the ragged corner."""
+    p = _problem(dt)
+    M, N, K = p["M"], p["N"], p["K"]
+    rs, cs = slice(M - rows, M), slice(N - 16, N)
+    y = _gemm_kernel(p["A"], p["W"], p["b"], drop=(rs, cs, K - 128))
+    bound = oc.elementwise_gemm_bound(p["A"], p["W"], p["b"], K, mag=p["mag"])
+    _missed_and_caught(dt, y, p["ref"], bound, "dropped K slice", box=(M - rows, M - 1, N - 16, N - 1))
+
+
+@pytest.mark.parametrize("dt", DT, ids=IDS)
+def test_dropped_bias_on_one_element(dt):
+    p = _problem(dt)
+    y = p["y"].clone()
+    c = int(p["b"].abs().argmax())                      # the tail column whose bias matters most (|b| ~ 0.3)
+    r = p["M"] - 1
+    y[r, c] -= p["b"][c]
+    bound = oc.elementwise_gemm_bound(p["A"], p["W"], p["b"], p["K"], mag=p["mag"])
+    _missed_and_caught(dt, y, p["ref"], bound, "dropped bias", box=(r, r, c, c))
+
+
+@pytest.mark.parametrize("dt", DT, ids=IDS)
+def test_gate_of_the_other_cfg_half_on_a_strip(dt):
+    """Gated residual x0 + g * y with per-(cfg, token) gate rows: a 1 x 16 strip of the first half reads the second half's gate."""
+    p = _problem(dt)
+    M, N = p["M"], p["N"]
+    L = M // 2
+    x0, gate = _rand((M, N), 21), _rand((2, L, N), 22, 0.3)
+    g = gate.reshape(M, N)
+    out = x0 + g * p["y"]
+    r, cs = L - 1, slice(N - 16, N)
+    out[r, cs] = x0[r, cs] + gate[1, L - 1, cs] * p["y"][r, cs]
+    ref = x0.double() + g.double() * p["ref"]
+    e_y = oc.elementwise_gemm_bound(p["A"], p["W"], p["b"], p["K"], mag=p["mag"]).e
+    bound = oc.gated_residual_bound(e_y, g, x0, p["ref"])
+    oc.assert_elementwise(x0 + g * p["y"], ref, bound, "clean gated residual")
+    _missed_and_caught(dt, out, ref, bound, "wrong CFG half's gate", box=(r, r, N - 16, N - 1))
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_sixteen_bit_store_off_by_four_ulp(dt):
+    """One stored element moved by 4 ulp of the output type, planted on the element of largest |y| (|y| ~ 5: 4 ulp = 0.125 bf16, 0.0156 fp16).
+    Limits, stated rather than hidden: the accumulation term (K + 4) 2^-23 mag is ~ 4.6e-3 at K = 1536 (mag ~ 0.64 sqrt(K)) - that is
+    4.7 ulp of fp16 for |y| in [1, 2), so on fp16 a 4-ulp error is caught only where |y| >= 2; at K = 6144 it is 3.7e-2 = 4.7 ulp of
+    bf16 in [1, 2) and the same holds for bf16.  Smaller stray errors on a 16-bit store need the fp32-store epilogue of the same tile."""
+    p = _problem(dt)
+    y16 = p["y"].to(dt)
+    bound = oc.elementwise_gemm_bound(p["A"], p["W"], p["b"], p["K"], dt, mag=p["mag"])
+    assert oc.assert_elementwise(y16, p["ref"], bound, "clean 16-bit store") <= 1.0
+    flat = int(p["ref"].abs().argmax())
+    r, c = divmod(flat, p["N"])
+    bad = y16.clone()
+    bad[r, c] = (y16[r, c].double() + 4 * oc.ulp16(y16[r, c].double(), dt)).to(dt)
+    assert float((bad[r, c].double() - y16[r, c].double()).abs()) == float(4 * oc.ulp16(y16[r, c].double(), dt))
+    _missed_and_caught(dt, bad, p["ref"], bound, "4 ulp", box=(r, r, c, c))
+    # a TYPICAL element (|y| in [1, 2)): caught on bf16 (4 ulp = 3.1e-2 against ~ 4.6e-3 + half an ulp); on fp16 it is the stated limit -
+    # 4 ulp = 3.9e-3 lies inside the accumulation term, and the check must NOT claim it
+    idx = ((p["ref"].abs() >= 1.25) & (p["ref"].abs() < 1.75)).nonzero()[0]
+    r, c = int(idx[0]), int(idx[1])
+    typ = y16.clone()
+    typ[r, c] = (y16[r, c].double() + 4 * oc.ulp16(y16[r, c].double(), dt)).to(dt)
+    if dt == torch.bfloat16:
+        _missed_and_caught(dt, typ, p["ref"], bound, "4 ulp on a typical element", box=(r, r, c, c))
+    else:
+        assert oc.assert_elementwise(typ, p["ref"], bound, "4 ulp of fp16 at |y| ~ 1.5: inside the bound") <= 1.0
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_sixteen_bit_slabs_and_activations_stay_inside(dt):
+    """Deferred split-K slabs rounded once each to the operand type, and the activation epilogues on the fp32 accumulator."""
+    M, N, K, ks = 300, 512, 1536, 3
+    A, W, b = _rand((M, K), 31).to(dt), _rand((N, K), 32, 1 / math.sqrt(K)).to(dt), _rand((N,), 33, 0.5)
+    ref, mag = oc.gemm_ref64(A, W, None)
+    e_y = oc.elementwise_gemm_bound(A, W, None, K, mag=mag).e
+    slabs = torch.stack([(A.float()[:, i * 512:(i + 1) * 512] @ W.float()[:, i * 512:(i + 1) * 512].t()).to(dt) for i in range(ks)])
+    r = oc.assert_elementwise(slabs.double().sum(0), ref, oc.slab_bound(e_y, mag, ks, dt), "16-bit slabs")
+    assert r < 1.0
+    lost = slabs.clone()
+    lost[2, M - 1, N - 16:] = 0                                      # one K range missing on a strip
+    with pytest.raises(AssertionError, match=rf"rows \[{M - 1}, {M - 1}\] x cols \[{N - 16}, {N - 1}\]"):
+        oc.assert_elementwise(lost.double().sum(0), ref, oc.slab_bound(e_y, mag, ks, dt), "slab strip lost")
+    refb, magb = ref + b.double(), mag + b.double().abs()
+    e_b = (K + 4) * oc.U32 * magb
+    y32 = (A.float() @ W.float().t()) + b
+    for name, fn in (("silu", F.silu), ("gelu", lambda t: F.gelu(t, approximate="tanh")), ("gelu_erf", F.gelu)):
+        a_act = oc.measure_a_act(name, refb, torch.device("cpu"))
+        assert 0 < a_act < 1e-5, (name, a_act)
+        oc.assert_elementwise(fn(y32).to(dt), oc.act64(name, refb), oc.act_bound(name, e_b, a_act, dt), name)
+    h = N // 2
+    a_act = oc.measure_a_act("silu", refb[:, :h], torch.device("cpu"))
+    bound = oc.silugate_bound(refb[:, :h], refb[:, h:], e_b[:, :h], e_b[:, h:], a_act, dt)
+    oc.assert_elementwise((F.silu(y32[:, :h]) * y32[:, h:]).to(dt), oc.act64("silu", refb[:, :h]) * refb[:, h:], bound, "silu gate")
+
+
+# ----------------------------------------------------------------------------- LayerNorm
+def _ln_kernel(x, shift, scale, eps, odt):
+    """Two-pass fp32 LayerNorm in the kernel's reduction order: every lane sums its D / 64 elements (stride 64 float4) in turn, a
+    butterfly adds the 64 lanes."""
+    M, D = x.shape
+
+    def wave_sum(t):                                   # t [M, D] fp32
+        lanes = t.view(M, D // 256, 64, 4).permute(0, 2, 1, 3)            # [M, lane, i, e]
+        s = torch.zeros(M, 64)
+        for i in range(D // 256):
+            s = s + ((lanes[:, :, i, 0] + lanes[:, :, i, 1]) + (lanes[:, :, i, 2] + lanes[:, :, i, 3]))
+        w = 64
+        while w > 1:
+            w //= 2
+            s = s[:, :w] + s[:, w:2 * w]
+        return s                                       # [M, 1]
+    mean = wave_sum(x) / float(D)
+    d = x - mean
+    rstd = 1.0 / torch.sqrt(wave_sum(d * d) / float(D) + eps)
+    return (d * rstd * (1.0 + scale) + shift).to(odt), mean
+
+
+@pytest.mark.parametrize("odt", DT, ids=IDS)
+def test_layernorm_two_pass_inside_and_neighbours_mean_caught(odt):
+    """Rows of 1e3 + N(0, 1) at D = 1536, M = 6000 (test_ln_mod_width's grid).  The planted row is normalised with the next row's
+    mean; it is the row whose mean differs from its neighbour's by the amount closest to 0.02 - large against the bound (~ 4e-3 + the
+    output term), small enough (0.02 / sqrt(6000) = 2.6e-4) for the fp16 norm gate of 5e-4 to miss."""
+    M, D, eps = 6000, 1536, 1e-6
+    x = 1e3 + _rand((M, D), 41)
+    shift, scale = _rand((D,), 42, 0.3), _rand((D,), 43, 0.3)
+    out, mean = _ln_kernel(x, shift, scale, eps, odt)
+    _, ref, _, bound = oc.layernorm_ref_and_bound(x, shift, scale, eps, odt)
+    assert oc.assert_elementwise(out, ref, bound, "two-pass fp32 LayerNorm") <= 1.0
+    one_pass = ((x * x).mean(-1, keepdim=True) - x.mean(-1, keepdim=True) ** 2)      # E[x^2] - E[x]^2 in fp32: garbage at |x| ~ 1e3
+    bad1 = ((x - x.mean(-1, keepdim=True)) * torch.rsqrt(one_pass.clamp_min(0) + eps) * (1 + scale) + shift).to(odt)
+    with pytest.raises(AssertionError):
+        oc.assert_elementwise(bad1, ref, bound, "one-pass variance")
+    dm = (mean[1:, 0] - mean[:-1, 0]).abs()
+    r = int((dm - 0.02).abs().argmin())
+    assert 0.015 < float(dm[r]) < 0.025
+    d = x[r] - mean[r + 1]
+    var = ((x[r] - mean[r]) ** 2).mean()
+    bad = out.clone()
+    bad[r] = (d / torch.sqrt(var + eps) * (1 + scale) + shift).to(odt)
+    _missed_and_caught(odt, bad, ref, bound, "neighbour's mean", gate=LN_TOL[odt])
+    with pytest.raises(AssertionError, match=rf"rows \[{r}, {r}\]"):
+        oc.assert_elementwise(bad, ref, bound, "neighbour's mean")
+
+
+def test_layernorm_pending_slabs_inside():
+    M, D, k = 64, 1536, 7
+    x0 = 1e3 + _rand((M, D), 44)
+    slabs, bias, gate = _rand((k, M, D), 45, 0.5).to(torch.bfloat16), _rand((D,), 46, 0.1), _rand((M, D), 47, 0.3)
+    acc = bias.expand(M, D).clone()
+    for s in range(k):
+        acc = acc + slabs[s].float()
+    x = x0 + gate * acc
+    out, _ = _ln_kernel(x, torch.zeros(D), torch.zeros(D), 1e-6, torch.bfloat16)
+    x64, ref, bx, bo = oc.layernorm_ref_and_bound(x0, None, None, 1e-6, torch.bfloat16, slabs, bias, gate)
+    assert oc.assert_elementwise(x, x64, bx, "x written back") <= 1.0
+    assert oc.assert_elementwise(out, ref, bo, "LayerNorm after the pending slabs") <= 1.0
+
+
+# ----------------------------------------------------------------------------- attention
+def _attn_kernel(q, k, v, dt, skip_last_tile_of=None):
+    """Tiled online softmax over 32-key tiles in fp32, P rounded to the operand type before P V, the row sum from the unrounded
+    P (attention.hip).  skip_last_tile_of = (b, h, row): that query never sees the last key tile."""
+    B, H, Sq, hd = q.shape
+    Skv = k.shape[2]
+    qf, kf, vf = q.float(), k.float(), v.float()
+    m = torch.full((B, H, Sq, 1), float("-inf"))
+    l = torch.zeros(B, H, Sq, 1)
+    o = torch.zeros(B, H, Sq, hd)
+    tiles = list(range(0, Skv, 32))
+    for kt in tiles:
+        s = qf @ kf[:, :, kt:kt + 32].transpose(2, 3) / math.sqrt(hd)
+        m_new = torch.maximum(m, s.amax(-1, keepdim=True))
+        p = torch.exp(s - m_new)
+        if skip_last_tile_of is not None and kt == tiles[-1]:
+            b, h, r = skip_last_tile_of
+            p[b, h, r] = 0.0
+            m_new[b, h, r] = m[b, h, r]
+        alpha = torch.exp(m - m_new)
+        l = l * alpha + p.sum(-1, keepdim=True)
+        pr = p.to(dt).float() if dt != torch.float32 else p
+        o = o * alpha + pr @ vf[:, :, kt:kt + 32]
+        m = m_new
+    return (o / l).transpose(1, 2).reshape(B, Sq, H * hd).to(dt)
+
+
+@pytest.mark.parametrize("dt", DT, ids=IDS)
+def test_attention_tiled_inside_and_missing_key_tile_caught(dt):
+    # 5 s self-attention under CFG, two clips: ten key tiles, 2 keys in the ragged last one - the planted row loses ~ 2 / 290 of its
+    # weights (error ~ 7e-3 against outputs of ~ 6e-2), one row of 13 920: 1e-3 in the norm
+    B, H, Sq, Skv, hd = 4, 12, 290, 290, 128
+    q, k, v = (_rand((B, H, S, hd), 50 + i).to(dt) for i, S in enumerate((Sq, Skv, Skv)))
+    ref, bound = oc.attention_ref_and_bound(q, k, v, dt, p_dtype=dt)
+    assert oc.assert_elementwise(_attn_kernel(q, k, v, dt), ref, bound, "tiled attention") <= 1.0
+    bad = _attn_kernel(q, k, v, dt, skip_last_tile_of=(1, 2, 289))
+    _missed_and_caught(dt, bad, ref, bound, "last key tile missing", gate=ATTN_TOL[dt], box=(290 + 289, 290 + 289, 2 * hd, 3 * hd - 1))
+
+
+# ----------------------------------------------------------------------------- DAC residual epilogue
+def test_dac_residual_and_snake_inside_and_defects_caught():
+    """Dilated conv k = 7 in fp32 with the taps summed in reverse, + residual, + snake (what EPI_DAC does in another order) stays inside
+    opcheck.dac_bounds; a residual dropped on one element and a 1 x 16 strip whose snake reads the NEXT channel's alpha fail the
+    element-wise check (fp32 operands: only the catch is asserted, as for the other fp32 defects)."""
+    B, T, C, dil = 2, 2000, 64, 3
+    x, w, b = _rand((B, C, T), 61), _rand((C, C, 7), 62, 1 / math.sqrt(7 * C)), _rand((C,), 63, 0.1)
+    alpha, res = 1 + 0.2 * _rand((C,), 64), _rand((B * T, C), 65, 0.01)
+    conv = lambda a, ww: F.conv1d(a, ww, None, dilation=dil, padding=3 * dil)
+    rows = lambda t: t.transpose(1, 2).reshape(B * T, C)
+    y = rows(conv(x.double(), w.double()) + b.double().view(1, C, 1))
+    mag = rows(conv(x.double().abs(), w.double().abs()) + b.double().abs().view(1, C, 1))
+    acc = torch.zeros(B, C, T)
+    xp = F.pad(x, (3 * dil, 3 * dil))
+    for t in reversed(range(7)):                                   # fp32, one tap at a time, last tap first
+        acc = acc + torch.einsum("oc,bct->bot", w[:, :, t], xp[:, :, t * dil:t * dil + T])
+    v32 = rows(acc + b.view(1, C, 1)) + res
+    s32 = v32 + (1.0 / (alpha + 1e-9)) * torch.sin(alpha * v32) ** 2
+    v = y + res.double()
+    a_act = oc.measure_a_act_snake(v, alpha, torch.device("cpu"))
+    assert 0 < a_act < 1e-5, a_act
+    b0, b1 = oc.dac_bounds((7 * C + 4) * oc.U32 * mag, v, res, a_act)
+    assert oc.assert_elementwise(v32, v, b0, "out0") <= 1.0
+    assert oc.assert_elementwise(s32, oc.snake64(v, alpha), b1, "out1") <= 1.0
+    r = B * T - 1
+    bad0 = v32.clone()
+    bad0[r, 5] -= res[r, 5]
+    _missed_and_caught(torch.float32, bad0, v, b0, "residual dropped", box=(r, r, 5, 5))
+    bad1 = s32.clone()
+    a_next = alpha.roll(-1)
+    bad1[r, 16:32] = (v32 + (1.0 / (a_next + 1e-9)) * torch.sin(a_next * v32) ** 2)[r, 16:32]
+    _missed_and_caught(torch.float32, bad1, oc.snake64(v, alpha), b1, "neighbour channel's alpha", box=(r, r, 16, 31))

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from opcheck import ulp16
 from foley_amd.host import packers, runtime as rt, tables
 from oracle import foley_oracle as O
 
@@ -484,9 +485,7 @@ def test_exact_gelu_fast_form_error_bound(dev, dtype):
     ref = 0.5 * xd * (1.0 + torch.erf(xd / math.sqrt(2.0)))
     got = out[:, 0].double().cpu()
     assert torch.equal(out.cpu(), out[:, :1].expand(M, N).cpu())    # every column saw the same y
-    mant = 8 if dtype == torch.bfloat16 else 11
-    ulp = torch.maximum(torch.ldexp(torch.ones_like(ref), torch.floor(torch.log2(ref.abs().clamp_min(1e-30))) - (mant - 1)),
-                        torch.full_like(ref, 2.0 ** -24 if dtype == torch.float16 else 0.0))   # fp16 subnormal spacing
+    ulp = ulp16(ref, dtype)      # spacing of the output type at |ref| (fp16: never below the subnormal spacing)
     err = (got - ref).abs()
     assert bool((err <= 0.5 * ulp + 8e-7).all()), float((err - 0.5 * ulp).max())
     main = ulp >= 1.2e-5      # |GELU| > ~2e-3 (bf16) / ~1.6e-2 (fp16): 6e-7 is < 5 % of an ulp there - the form IS exact to 16-bit rounding

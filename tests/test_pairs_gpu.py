@@ -17,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import opcheck as oc
 from conftest import record_parity, rel_err
 from foley_amd.host import runtime as rt, tables
 
@@ -122,7 +123,8 @@ def _rand(shape, seed, scale=1.0):
 
 
 def _sample_rows(M):
-    """Every row below 3000; above, a few hundred spread over M including the first and the last 16 (test_gemm_bf16_past_2gib)."""
+    """Every row below 3000; above, a few hundred spread over M including the first and the last 16 (test_gemm_bf16_past_2gib).
+    The LayerNorm cases below sample with it; the GEMM pairs check every row (Problem)."""
     if M < 3000:
         return torch.arange(M)
     idx = torch.cat((torch.arange(16), torch.randint(16, M - 16, (224,), generator=_g(90)), torch.arange(M - 16, M)))
@@ -184,17 +186,23 @@ def ln_mod_pair(sets, D, eps, out_dtype_code):
 
 # ----------------------------------------------------------------------------- GEMM pair problems
 class Problem:
-    """One stream's GEMM: operands rounded through the compute dtype, fp64 reference of the sampled rows, output buffers."""
+    """One stream's GEMM: operands rounded through the compute dtype, fp64 reference of ALL rows, output buffers.  ew: the problem
+    belongs to a large-grid case (M >= 3000 - the 256x256 tiles, the three-range split-K route) and is checked element by element
+    as well (tests/opcheck.py); it then carries mag = |A| @ |W|^T + |bias| for the bound."""
 
-    def __init__(self, dev, kind, epi, M, N, K, seed, opts, S=None):
+    def __init__(self, dev, kind, epi, M, N, K, seed, opts, S=None, ew=False):
         self.dev, self.epi, self.M, self.N, self.K = dev, epi, M, N, K
         self.dt = {"f32": torch.float32, "h": opts["dt"], "fp8": torch.bfloat16}[kind]
         A = _rand((M, K), seed).to(self.dt)
         W = _rand((N, K), seed + 1, 1 / math.sqrt(K))
         W = W.to(torch.float8_e4m3fn) if kind == "fp8" else W.to(self.dt)
         b = _rand((N,), seed + 2, 0.1)
-        self.rows = _sample_rows(M)
-        self.y = A[self.rows].double() @ W.double().t() + b.double()           # [rows, N] fp64
+        self.rows = torch.arange(M)
+        self.y = A.double() @ W.double().t() + b.double()                      # [M, N] fp64
+        self.ew = ew
+        if ew:
+            self.mag0 = A.double().abs() @ W.double().abs().t()
+            self.e_y = (K + 4) * oc.U32 * (self.mag0 + b.double().abs())
         self.Ad, self.Wd, self.bd = A.to(dev), W.to(dev), b.to(dev)
         self.seed = seed
 
@@ -233,7 +241,9 @@ class PairCase:
     def __init__(self, dev, case, dt):
         kind, epi, s0, s1, opts, self.want_tile = PAIR_TILES[case]
         self.kind, self.epi, self.opts, self.dev = kind, epi, dict(opts, dt=dt), dev
-        self.p = [Problem(dev, kind, epi, *s0, 1000, self.opts), Problem(dev, kind, epi, *s1, 2000, self.opts)]
+        ew = s0[0] >= 3000
+        self.p = [Problem(dev, kind, epi, *s0, 1000, self.opts, ew=ew), Problem(dev, kind, epi, *s1, 2000, self.opts, ew=ew)]
+        self.ew_ratio = 0.0      # largest err / bound of the element-wise checks (recorded by test_gemm_pair)
         self.dt = self.p[0].dt
         P0, P1 = self.p
         if epi in ("qkv", "cross"):
@@ -334,6 +344,11 @@ class PairCase:
                 e = rel_err(o[Pi.rows.to(dev)].float(), F.gelu(Pi.y, approximate="tanh"))
                 assert e < _tol(dt), (i, e)
                 worst = max(worst, e)
+                if Pi.ew:
+                    a_act = oc.measure_a_act("gelu", Pi.y, dev)
+                    record_parity(f"pair_gemm.a_act.gelu.M{Pi.M}.{str(dt)[6:]}", a_act=a_act)
+                    self.ew_ratio = max(self.ew_ratio, oc.assert_elementwise(
+                        o, oc.act64("gelu", Pi.y), oc.act_bound("gelu", Pi.e_y, a_act, dt), f"problem {i}: GELU output"))
         elif self.epi == "qkv":
             S = self.S
             for name in ("q", "k"):
@@ -360,6 +375,11 @@ class PairCase:
                     e = rel_err(got, ref)
                     assert e < QKV_TOL[dt], (i, e)
                     worst = max(worst, e)
+                if Pi.ew:
+                    ey = Pi.e_y.view(len(r), 3, self.H, 128)
+                    for j, (got, ref) in enumerate(((gq, rq), (gk, rk), (gv, y[:, 2]))):
+                        bound = oc.head_split_bound(ey[:, j], y[:, j], dt, Pi.gains[j] if j < 2 else None)
+                        self.ew_ratio = max(self.ew_ratio, oc.assert_elementwise(got, ref, bound, f"problem {i}: head split {'qkv'[j]}"))
         elif self.epi == "cross":
             H, S = self.H, self.S
             if not fused:   # plain head split: q in dst[0], attention launched by the caller (run_forward's cross step)
@@ -397,12 +417,18 @@ class PairCase:
                     assert bool(torch.isnan(slabs[ks:]).all()), f"problem {i}: slabs beyond the K split written"
                     e = rel_err(slabs[:ks, rows].double().sum(0), yv)
                     assert e < SLAB_TOL[slabs.dtype], (i, e)
+                    if Pi.ew:
+                        bound = oc.slab_bound((Pi.K + 4) * oc.U32 * Pi.mag0, Pi.mag0, ks, slabs.dtype)
+                        self.ew_ratio = max(self.ew_ratio, oc.assert_elementwise(slabs[:ks].double().sum(0), yv, bound, f"problem {i}: slab sum"))
                 else:
                     if slabs is not None:
                         assert bool(torch.isnan(slabs).all()), f"problem {i}: slabs written without a K split"
                     ref = Pi.x0[Pi.rows].double() + Pi.y * Pi.g_full[Pi.rows].double()
                     e = rel_err(x[rows], ref)
                     assert e < RES_TOL, (i, e)
+                    if Pi.ew:
+                        bound = oc.gated_residual_bound(Pi.e_y, Pi.g_full, Pi.x0, Pi.y)
+                        self.ew_ratio = max(self.ew_ratio, oc.assert_elementwise(x, ref, bound, f"problem {i}: gated residual"))
                     assert bool(torch.isfinite(x).all())
                 worst = max(worst, e)
         record.append(worst)
@@ -466,6 +492,8 @@ def test_gemm_pair(dev, case, dt):
     worst = []
     pc.check_reference(b, ks, fused, worst)
     record_parity(f"pair_gemm.{case}.{str(dt)[6:]}", rel_err=worst[0], tile=tile, ksplit=ks)
+    if pc.p[0].ew:
+        record_parity(f"elementwise.pair_gemm.{case}.{str(dt)[6:]}", err_over_bound=pc.ew_ratio, tile=tile, ksplit=ks)
 
     if pc.epi == "gate" and ks > 1 and not pc.opts.get("slabs"):
         return          # fp32 atomics: bit-identity not defined
