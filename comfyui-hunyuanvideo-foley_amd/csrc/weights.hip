@@ -54,7 +54,8 @@ __host__ __device__ inline int dt_size(int dt) {
   return (dt == FOLEY_F8E4M3 || dt == FOLEY_F8E5M2) ? 1 : (dt == FOLEY_BF16 || dt == DT_F16) ? 2 : 4;
 }
 
-// ---- scalar conversions (device); fp8 follows the OCP formats torch implements, round-to-nearest-even
+// ---- scalar conversions (device); fp8 follows the OCP formats torch implements, round-to-nearest-even.  NaNs decode to the
+// bits torch's casts give (sign kept, payload left-aligned, quiet bit set), so a loaded arena equals the packers' byte for byte.
 __device__ inline float f16_to_f32(uint16_t h) {
   const uint32_t s = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 31, m = h & 1023;
   if (e == 0) {
@@ -62,7 +63,7 @@ __device__ inline float f16_to_f32(uint16_t h) {
     float v = (float)m * 5.9604644775390625e-08f;   // 2^-24
     return (h & 0x8000) ? -v : v;
   }
-  if (e == 31) return __uint_as_float(s | 0x7f800000u | (m << 13));
+  if (e == 31) return __uint_as_float(s | 0x7f800000u | (m ? 0x00400000u : 0u) | (m << 13));
   return __uint_as_float(s | ((e + 112) << 23) | (m << 13));
 }
 template <int EB, int MB, bool FN>   // exponent / mantissa bits; FN: no infinities, NaN = all ones (e4m3fn)
@@ -70,7 +71,8 @@ __device__ inline float f8_to_f32(uint8_t v) {
   constexpr int BIAS = (1 << (EB - 1)) - 1;
   const uint32_t s = (uint32_t)(v & 0x80) << 24;
   const int e = (v >> MB) & ((1 << EB) - 1), m = v & ((1 << MB) - 1);
-  if (FN ? ((v & 0x7f) == 0x7f) : (e == (1 << EB) - 1 && m != 0)) return __uint_as_float(0x7fc00000u);
+  if (FN ? ((v & 0x7f) == 0x7f) : (e == (1 << EB) - 1 && m != 0))
+    return __uint_as_float(s | 0x7f800000u | (FN ? 0u : 0x00400000u) | ((uint32_t)m << (23 - MB)));
   if (!FN && e == (1 << EB) - 1) return __uint_as_float(s | 0x7f800000u);
   if (e == 0) {
     float x = (float)m * exp2f((float)(1 - BIAS - MB));
@@ -679,6 +681,35 @@ extern "C" int foley_weights_arena(foley_ctx* c, void** dev_ptr, uint64_t* bytes
   if (!w || !w->begun || !dev_ptr || !bytes) return W_FAIL(FOLEY_ERR_STATE, "foley_weights_begin has not been called");
   *dev_ptr = w->arena;
   *bytes = w->bytes;
+  return 0;
+}
+
+// Read-only view of the layout: slot `index` (enumeration, name == NULL) or the slot called `name`.  Touches no device memory
+// and no loader state; 1 = past the last slot / no such name.
+extern "C" int foley_weights_slot(foley_ctx* c, int index, const char* name, char* name_out, void** dev_ptr, int* dtype,
+                                  int* ndim, int64_t* shape, uint64_t* offset, uint64_t* bytes) {
+  WStore* w = store_of(c);
+  if (!w || !w->begun) return W_FAIL(FOLEY_ERR_STATE, "foley_weights_begin has not been called");
+  if (name) {
+    auto it = w->index.find(name);
+    if (it == w->index.end()) return 1;
+    index = it->second;
+  } else if (index < 0) {
+    return W_FAIL(FOLEY_ERR_INVALID, "bad argument");
+  }
+  if ((size_t)index >= w->slots.size()) return 1;
+  const Slot& s = w->slots[(size_t)index];
+  if (s.shape.size() > 8 || s.name.size() >= FOLEY_SLOT_NAME_MAX) return W_FAIL(FOLEY_ERR_INVALID, "internal: slot does not fit the lookup");
+  if (name_out) {
+    memcpy(name_out, s.name.c_str(), s.name.size() + 1);
+  }
+  if (dev_ptr) *dev_ptr = (char*)w->arena + s.off;
+  if (dtype) *dtype = s.dt;
+  if (ndim) *ndim = (int)s.shape.size();
+  if (shape)
+    for (size_t k = 0; k < s.shape.size(); ++k) shape[k] = s.shape[k];
+  if (offset) *offset = s.off;
+  if (bytes) *bytes = s.bytes;
   return 0;
 }
 

@@ -19,6 +19,9 @@ DT_F32, DT_BF16, DT_I32, DT_F8E4M3, DT_F8E5M2, DT_F16 = 0, 1, 2, 3, 4, 5
 _TORCH2DT = {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.int32: DT_I32, torch.float8_e4m3fn: DT_F8E4M3,
              torch.float8_e5m2: DT_F8E5M2, torch.float16: DT_F16}
 
+_DT2TORCH = {v: k for k, v in _TORCH2DT.items()}
+SLOT_NAME_MAX = 64      # FOLEY_SLOT_NAME_MAX
+
 EPI_STORE_F32, EPI_STORE_T, EPI_SILU_T, EPI_GELU_T, EPI_SILUGATE_T, EPI_GATE_RES, EPI_DAC = range(7)
 
 
@@ -107,6 +110,8 @@ _SIGNATURES = {
     "foley_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p]),
     "foley_weights_end": (C.c_int, [C.c_void_p, C.c_void_p]),
     "foley_weights_arena": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "foley_weights_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "foley_weights_mark_received": (C.c_int, [C.c_void_p]),
     "foley_bcast_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_bcast_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
@@ -203,6 +208,19 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+_HIP: Optional[C.CDLL] = None
+
+
+def _hip() -> C.CDLL:
+    """The HIP runtime the process has already loaded (device-to-device copies out of library-owned memory)."""
+    global _HIP
+    if _HIP is None:
+        _HIP = C.cdll.LoadLibrary("libamdhip64.so")
+        _HIP.hipMemcpy.restype = C.c_int
+        _HIP.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return _HIP
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -291,6 +309,45 @@ class FoleyContext:
         p, n = C.c_void_p(), C.c_uint64()
         _check(self.lib, self.lib.foley_weights_arena(self._h, C.byref(p), C.byref(n)), "foley_weights_arena")
         return int(p.value), int(n.value)
+
+    def weights_slot(self, which):
+        """One slot of the ctx-owned arena, by enumeration index (int) or packed name (str): dict(name, ptr, dtype, shape,
+        offset, bytes), or None past the last index / for an unknown name.  Read-only (foley_weights_slot)."""
+        name_out = C.create_string_buffer(SLOT_NAME_MAX)
+        p, dt, nd, shape, off, nb = C.c_void_p(), C.c_int(), C.c_int(), (C.c_int64 * 8)(), C.c_uint64(), C.c_uint64()
+        by_name = isinstance(which, str)
+        rc = self.lib.foley_weights_slot(self._h, -1 if by_name else int(which), which.encode() if by_name else None, name_out,
+                                         C.byref(p), C.byref(dt), C.byref(nd), shape, C.byref(off), C.byref(nb))
+        if rc == 1:
+            return None
+        _check(self.lib, rc, f"foley_weights_slot({which})")
+        return {"name": name_out.value.decode(), "ptr": int(p.value), "dtype": _DT2TORCH[dt.value],
+                "shape": tuple(shape[i] for i in range(nd.value)), "offset": int(off.value), "bytes": int(nb.value)}
+
+    def weights_slots(self):
+        """Every slot of the arena in the library's own order."""
+        out, i = [], 0
+        while True:
+            s = self.weights_slot(i)
+            if s is None:
+                return out
+            out.append(s)
+            i += 1
+
+    def weights_slot_tensor(self, which) -> torch.Tensor:
+        """A copy of one packed tensor of the ctx-owned arena (device tensor of the slot's dtype and shape)."""
+        s = self.weights_slot(which)
+        if s is None:
+            raise FoleyRuntimeError(f"no packed tensor {which!r} in the weight arena")
+        out = torch.empty(s["shape"], dtype=s["dtype"], device=self.device)
+        if s["bytes"] != out.numel() * out.element_size():
+            raise FoleyRuntimeError(f"slot {s['name']}: {s['bytes']} bytes do not match {s['dtype']} {s['shape']}")
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            rc = _hip().hipMemcpy(C.c_void_p(out.data_ptr()), C.c_void_p(s["ptr"]), C.c_size_t(s["bytes"]), 3)
+        if rc != 0:
+            raise FoleyRuntimeError(f"hipMemcpy of slot {s['name']} failed ({rc})")
+        return out
 
     def bcast_weights(self, nccl_comm: int, root: int = 0):
         with torch.cuda.device(self.device):

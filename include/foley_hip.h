@@ -125,6 +125,15 @@ int foley_load_tensor(foley_ctx* ctx, const char* ref_key, const void* dev_ptr, 
                       const int64_t* shape, void* stream);
 int foley_weights_end(foley_ctx* ctx, void* stream);
 int foley_weights_arena(foley_ctx* ctx, void** dev_ptr, uint64_t* bytes);
+/* Read-only slot lookup (additive within ABI 12): where one packed tensor lives in the ctx-owned arena.  name == NULL: slot `index`
+ * of the layout's own order (0, 1, ... until the call returns 1); name != NULL: the slot of that packed name (`s0.qkv.w`,
+ * `dac.0.up.w`, ...; `index` is ignored), 1 if there is none.  Every output pointer may be NULL.  name_out receives at most
+ * FOLEY_SLOT_NAME_MAX bytes including the terminator, shape at most 8 entries; dev_ptr = arena + offset, `bytes` the tensor's own
+ * size (slot extents are 256-byte aligned, so the distance to the next slot may be larger).  Valid after foley_weights_begin; the
+ * call reads host-side bookkeeping only - no device work, no change of the loader's state. */
+#define FOLEY_SLOT_NAME_MAX 64
+int foley_weights_slot(foley_ctx* ctx, int index, const char* name, char* name_out, void** dev_ptr, int* dtype, int* ndim,
+                       int64_t* shape, uint64_t* offset, uint64_t* bytes);
 int foley_weights_mark_received(foley_ctx* ctx);
 int foley_bcast_weights(foley_ctx* ctx, void* nccl_comm, int root, void* stream);
 /* Single-process form of the same step (one host process that drives all GPUs of the node, e.g. a ComfyUI prompt worker; the
