@@ -16,6 +16,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -112,64 +113,41 @@ struct Profiler {
   }
 };
 
-struct foley_ctx {
-  int device = 0;
-  foley_config cfg{};
-  std::unordered_map<std::string, TensorRef> tensors;
-  ForwardW fw;
-  Profiler prof;
-  // run state (valid after foley_prepare)
-  bool prepared = false;
-  foley_plan plan{};
-  std::vector<DevBuf> owned;        // everything hipMalloc'ed for the current plan
+static int pad32(int x) { return (x + 31) & ~31; }
+
+// Everything ctx_alloc() hands out for the current plan's dimensions.  ctx_free_plan() resets the whole record, so no pointer
+// outlives its block; buffers a layout does not need (set_idx, sync_lead_rows, tG) are null in it.
+struct PlanBufs {
   // prepared tables
   float* vec_table = nullptr;       // [n_iter, D]
   float* modtab = nullptr;          // [n_triple][2][n_iter][9D]
-  void* txt_k = nullptr;            // [n_triple][ncfg, H, Lt, 128]     (same dtype rule as Q/K/V)
-  void* txt_v = nullptr;            // [n_triple][ncfg, H, Lt, 128] or transposed [.., 128, ceil32(Lt)]
-  float* v_cond0 = nullptr;         // [ncfg, Lv, D]
-  float* sync_tok = nullptr;        // [ncfg, Ls, D] sync tokens after sync_in; audio frame l reads row nearest_exact(l) (RowBcast mode 2)
-  int sync_per = 0;                 // 8 when the token rows of the first sync_lead cfg halves repeat with period 8 (empty sync features), else 0
-  int sync_lead = 0;                // number of leading 8-periodic halves: ncfg = all of them (text-to-audio); 1 of 2 = a video clip under
-                                    // CFG (unconditional half first, utils.py:150-176); 0 = none
-  // conditioning layout (foley_prepare_sets): the text K/V sets and the visual halves (sync_tok, svec, smod) are held per cfg half
-  // (ncfg slots, read by divisor clips) or per batch row (ncfg*clips slots, divisor 1); v_cond0 holds the distinct visual sets
-  bool sets_mode = false, txt_rows = false, vis_rows = false;
-  int vis_src = 0;                  // sets in v_cond0
-  std::vector<int32_t> set_maps;    // text_of ++ vis_of of the prepared run (empty: foley_prepare); keys the captured graph
+  void* txt_k = nullptr;            // [n_triple][th, H, Lt, 128]     (same dtype rule as Q/K/V)
+  void* txt_v = nullptr;            // [n_triple][th, H, Lt, 128] or transposed [.., 128, ceil32(Lt)]
+  float* v_cond0 = nullptr;         // [vh, Lv, D] the distinct visual sets
+  float* sync_tok = nullptr;        // [vh, Ls, D] sync tokens after sync_in; audio frame l reads row nearest_exact(l) (RowBcast mode 2)
   int* set_idx = nullptr;           // [ncfg*clips*(Lt + Ls + 8)] row gather tables of the per-row layouts (text, sync, periodic lead)
   float* sync_lead_rows = nullptr;  // per-row visual layout: [ncfg*clips*8, D] the 8 distinct rows of each leading periodic half,
                                     // packed - the per-iteration SiLU(token + vec) of all of them is then one launch
   float* tG = nullptr;              // [ncfg*clips*Lt, 2D] text K/V rows gathered per batch row
-  int* flag = nullptr;              // device scratch word of the periodicity check
-  int* ident_idx = nullptr;         // 0..max(Lv,La)-1
+  int* flag = nullptr;              // device scratch words of the periodicity check
   // forward workspace
   void* xin = nullptr;              // T [M, C]
   float* audio = nullptr;           // [M, D]
   float* vcond = nullptr;           // [Mv, D]
-  void* xn_a = nullptr;             // T [M, D]
-  void* xn_v = nullptr;             // T [Mv, D]
-  float* qkv_a = nullptr;           // [M, 3D]
-  float* qkv_v = nullptr;           // [Mv, 3D]
-  void* Q = nullptr;                // [Bc, H, S, 128]   fp32 (parity mode) or bf16
-  void* K = nullptr;
+  void *xn_a = nullptr, *xn_v = nullptr;       // T [M | Mv, D]
+  float *qkv_a = nullptr, *qkv_v = nullptr;    // [M | Mv, 3D]
+  void *Q = nullptr, *K = nullptr;  // [Bc, H, S, 128]   fp32 (parity mode) or bf16
   void* V = nullptr;                // fp32 [Bc, H, S, 128] or bf16 transposed [Bc, H, 128, ceil32(S)]
-  void* att_a = nullptr;            // T [M, D]
-  void* att_v = nullptr;            // T [Mv, D]
+  void *att_a = nullptr, *att_v = nullptr;     // T [M | Mv, D]
   void* hid_a = nullptr;            // T [M, max(mlp_hidden, conv_hidden)]
   void* hid_v = nullptr;            // T [Mv, mlp_hidden]
-  void* svec = nullptr;             // T [ncfg*Ls, D]
-  float* smod = nullptr;            // [ncfg*Ls, n_single*6D]
-  // the same table for EVERY loop iteration, built by foley_prepare when it fits (it depends on the iteration index only):
-  // [n_iter][ncfg*P][n_single*6D] fp32, P = sync_per or Ls; consumers add step * smod_step to their row address
-  DevBuf smod_tab, svec_tab;
-  bool smod_hoisted = false;
+  void* svec = nullptr;             // T [vh*Ls, D]
+  float* smod = nullptr;            // [vh*Ls, n_single*6D]
   float* pred = nullptr;            // [M, C]
   float *part_a = nullptr, *part_v = nullptr;   // deferred split-K partial products [PART_CAP][M | Mv][D]
-  float* x_saved = nullptr;         // [clips, C, La]
-  float* d_acc = nullptr;
-  int* step_ctr = nullptr;
+  float *x_saved = nullptr, *d_acc = nullptr;   // [clips, C, La]
   float* x_cur = nullptr;           // [clips, C, La] the sample being denoised (ctx-owned => stable address)
+  int* step_ctr = nullptr;
   // ctx-owned copies of the plan's lookup tables (stable addresses across foley_prepare calls)
   float *rope_cos = nullptr, *rope_sin = nullptr, *solver_coef = nullptr;
   int *pos_audio_self = nullptr, *pos_visual_self = nullptr, *pos_linear = nullptr, *sync_gather = nullptr;
@@ -178,12 +156,73 @@ struct foley_ctx {
   // (k: 0 audio self, 1 visual self, 2 linear positions)
   float *rot_cos[3] = {nullptr, nullptr, nullptr}, *rot_sin[3] = {nullptr, nullptr, nullptr};
   void *tA = nullptr, *tB = nullptr;  // precompute scratch
-  float* tF = nullptr;
-  bool have_buffers = false;        // workspace allocated for `plan`'s dimensions
-  // graph: one captured loop iteration; valid while the workspace and weights stay put
+  float* tF = nullptr;              // the last block foley_prepare allocates
+  bool complete() const { return tF != nullptr; }
+};
+
+// How the conditioning of the prepared run is laid out: foley_prepare derives it once (the slots before it sizes the workspace,
+// the rest from the sync tokens it computed) and the forward only reads it.  Integral members, no padding: compared bytewise.
+struct RunLayout {
+  // conditioning sets (foley_prepare_sets): the text K/V sets and the visual halves (sync_tok, svec, smod) are held per cfg half
+  // (ncfg slots, read by `clips` batch rows each) or per batch row (ncfg*clips slots)
+  int sets = 0, t_rows = 0, v_rows = 0;   // set maps given; text / visual stream laid out per batch row
+  int th = 0, vh = 0;               // text K/V slots, visual halves
+  int tdiv = 0, vdiv = 0;           // batch row b reads text slot b / tdiv and visual half b / vdiv
+  int Sp = 0, Lap = 0, Ltp = 0;     // V^T row pitches of the 16-bit attention: joint, audio-only, text
+  // sync tokens: the first `lead` halves repeat with period `per` = 8 (empty sync features): all of them for text-to-audio, 1 of
+  // 2 for a video clip under CFG (unconditional half first, utils.py:150-176), 0 (and per = 0) for none
+  int lead = 0, per = 0, allper = 0;   // allper: every half is periodic
+  // the single-stream blocks' modulation table of one iteration: R distinct rows - `per` of each leading half, then Ls of each
+  // dense half, the row order of RowBcast::dense_from / dense_base - of smod_ld floats
+  int R = 0;
+  long smod_ld = 0;
+  // hoisted: the table of EVERY iteration was built by foley_prepare, [n_iter][vh*P][smod_ld] with P = per (all halves periodic)
+  // or Ls rows per half (a hoisted table that is not all-periodic is dense); consumers add step * smod_step to their row address
+  int hoisted = 0, P = 0;
+  int mod_per = 0, mod_lead = 0;    // rb_up() arguments of the table the blocks read (0: dense rows; lead -1: every half periodic)
+  long smod_step = 0;
+  bool operator==(const RunLayout& o) const { return memcmp(this, &o, sizeof(o)) == 0; }
+};
+static_assert(std::has_unique_object_representations_v<RunLayout>, "RunLayout is compared bytewise");
+
+// Everything a captured loop iteration depends on beyond the workspace dimensions (a change of those frees the plan and the
+// graph with it).  foley_sample compares the key of the capture with the current one; nothing else decides a graph's validity.
+struct GraphKey {
+  float guidance = 0.f;             // a launch argument of the solver step
+  int edit = 0;                     // edit_key(): plain vs edit iteration, clip strides of the edit operands
+  std::vector<int32_t> set_maps;    // text_of ++ vis_of (empty: foley_prepare)
+  RunLayout layout;
+  const void* smod_tab = nullptr;   // the hoisted table (null: the per-iteration GEMM)
+  const void *edit_x0 = nullptr, *edit_noise = nullptr, *edit_mask = nullptr;
+  uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
+  uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
+  bool operator==(const GraphKey& o) const {
+    return guidance == o.guidance && edit == o.edit && set_maps == o.set_maps && layout == o.layout && smod_tab == o.smod_tab &&
+           edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && tensor_gen == o.tensor_gen &&
+           plan_gen == o.plan_gen;
+  }
+};
+
+struct foley_ctx {
+  int device = 0;
+  foley_config cfg{};
+  std::unordered_map<std::string, TensorRef> tensors;
+  uint64_t tensor_gen = 0;
+  ForwardW fw;
+  Profiler prof;
+  // run state (valid after foley_prepare)
+  bool prepared = false;
+  foley_plan plan{};
+  std::vector<DevBuf> owned;        // everything hipMalloc'ed for the current plan
+  uint64_t plan_gen = 0;
+  PlanBufs buf;
+  RunLayout layout;
+  int vis_src = 0;                  // sets in v_cond0 (the source stride of a one-group gather: no captured kernel reads it)
+  std::vector<int32_t> set_maps;    // text_of ++ vis_of of the prepared run (empty: foley_prepare)
+  DevBuf smod_tab, svec_tab;        // the hoisted modulation table and its SiLU(token + vec) input (layout.hoisted), grown on demand
+  // one captured loop iteration and what it was captured for
   hipGraphExec_t graph_exec = nullptr;
-  float graph_guidance = 0.f;
-  int graph_key = 0;                // edit_key() of the run the graph was captured for (0: a plain iteration)
+  GraphKey graph_key;
   // edit state (foley_set_edit; cleared by foley_prepare): ctx-owned copies of the source latents, the run's noise and the mask
   bool edit = false;
   DevBuf edit_x0, edit_noise, edit_mask;
@@ -217,17 +256,6 @@ static int ctx_alloc(foley_ctx* c, size_t bytes, void** out) {
   return 0;
 }
 
-static void ctx_free_plan(foley_ctx* c) {
-  if (c->graph_exec) {
-    hipGraphExecDestroy(c->graph_exec);
-    c->graph_exec = nullptr;
-  }
-  for (auto& b : c->owned) hipFree(b.p);
-  c->owned.clear();
-  c->prepared = false;
-  c->have_buffers = false;
-}
-
 static void ctx_drop_graph(foley_ctx* c) {
   if (c->graph_exec) {
     hipGraphExecDestroy(c->graph_exec);
@@ -235,16 +263,29 @@ static void ctx_drop_graph(foley_ctx* c) {
   }
 }
 
+static void ctx_free_plan(foley_ctx* c) {
+  ctx_drop_graph(c);   // eagerly, with the memory its kernels address; plan_gen keeps a later comparison from matching
+  ++c->plan_gen;
+  for (auto& b : c->owned) hipFree(b.p);
+  c->owned.clear();
+  c->buf = {};
+  c->layout = {};
+  c->prepared = false;
+}
+
 static bool same_dims(const foley_plan& a, const foley_plan& b) {
   return a.ncfg == b.ncfg && a.clips == b.clips && a.La == b.La && a.Lv == b.Lv && a.Ls == b.Ls && a.Lt == b.Lt &&
          a.n_iter == b.n_iter && a.rope_len == b.rope_len;
 }
 
+static void release(DevBuf& b) {
+  if (b.p) hipFree(b.p);
+  b = DevBuf{};
+}
+
 static int grow(DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes) return 0;
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
+  release(b);
   hipError_t e = hipMalloc(&b.p, bytes);
   if (e != hipSuccess) return FAIL(FOLEY_ERR_HIP, hipGetErrorString(e));
   b.bytes = bytes;
@@ -341,6 +382,27 @@ static GemmArgs gemm_conv(const void* A, int M, int seg, int C, int taps, int di
   return g;
 }
 
+// Head-split arguments of the text K/V (foley_prepare), the two-stream and the single-stream blocks.  An output with a gain is
+// RMS-normalised and rotated at the positions of rotation slot `rot` (0 audio self, 1 visual self, 2 linear positions); rot_rows:
+// the fused GEMM epilogues read the rotation from the per-token rows foley_prepare gathered for that slot.
+static QkvSplitArgs qkv_split_args(const foley_ctx* c, const float* qkv, int M, int L, int nK, const float* gain0, const float* gain1,
+                                   int rot, bool rot_rows, void* const dst[3], int S_tot, int tok_off, int vt_pitch, float eps) {
+  const foley_plan& pl = c->plan;
+  const int* const pos[3] = {pl.pos_audio_self, pl.pos_visual_self, pl.pos_linear};
+  QkvSplitArgs q{};
+  q.qkv = qkv; q.M = M; q.L = L; q.H = c->cfg.heads; q.nK = nK;
+  q.gain[0] = gain0; q.gain[1] = gain1;
+  for (int i = 0; i < 2; ++i) {
+    if (!q.gain[i]) continue;
+    q.pos[i] = pos[rot];
+    if (rot_rows) { q.rcos[i] = c->buf.rot_cos[rot]; q.rsin[i] = c->buf.rot_sin[rot]; }
+  }
+  for (int i = 0; i < 3; ++i) q.dst[i] = dst[i];
+  q.out_dtype = c->cfg.compute_dtype; q.vt_pitch = vt_pitch;
+  q.S_tot = S_tot; q.tok_off = tok_off; q.eps = eps; q.cos_tab = pl.rope_cos; q.sin_tab = pl.rope_sin;
+  return q;
+}
+
 // --------------------------------------------------------------------------- C ABI: context
 extern "C" uint32_t foley_abi_version(void) { return FOLEY_ABI_VERSION; }
 extern "C" const char* foley_last_error(void) { return g_err.c_str(); }
@@ -369,8 +431,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   ctx_free_plan(c);
-  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask})
-    if (b->p) hipFree(b->p);
+  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask}) release(*b);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   for (auto e : c->prof.pool) hipEventDestroy(e);
@@ -387,7 +448,7 @@ extern "C" int foley_set_tensor(foley_ctx* c, const char* name, const void* p, i
   t.dtype = dtype;
   t.shape.assign(shape, shape + ndim);
   auto it = c->tensors.find(name);
-  if (it != c->tensors.end() && it->second.p != p) ctx_drop_graph(c);  // captured kernels hold the old address
+  if (it != c->tensors.end() && it->second.p != p) ++c->tensor_gen;  // captured kernels hold the old address
   c->tensors[name] = t;
   c->fw.ok = false;     // resolved pointers are refreshed by the next foley_prepare
   c->prepared = false;  // cached tables depend on the weights
@@ -497,91 +558,91 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     v_rows = !v_half;
     if (v_rows && Bc0 > 32) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: per-clip visual features take at most 32 batch rows");
   }
-  HIPTRY(hipStreamSynchronize(st));
-  const bool reuse = c->have_buffers && same_dims(c->plan, *pl) && c->sets_mode == (sets != nullptr) && c->txt_rows == t_rows &&
-                     c->vis_rows == v_rows;
-  if (!reuse) ctx_free_plan(c);
-  c->prepared = false;
-  c->edit = false;                  // a plan without foley_set_edit is a plain run
-  c->sets_mode = sets != nullptr;
-  c->txt_rows = t_rows;
-  c->vis_rows = v_rows;
-  c->vis_src = n_vis;
-
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const size_t es = esize(T);
   const int ncfg = pl->ncfg, clips = pl->clips, La = pl->La, Lv = pl->Lv, Ls = pl->Ls, Lt = pl->Lt;
   const int Bc = ncfg * clips, M = Bc * La, Mv = Bc * Lv, S = La + Lv, NI = pl->n_iter;
-  const int th = t_rows ? Bc : ncfg, vh = v_rows ? Bc : ncfg;   // text K/V slots, visual halves
+  RunLayout slots;   // the part of the layout that sizes the workspace
+  slots.sets = sets != nullptr; slots.t_rows = t_rows; slots.v_rows = v_rows;
+  slots.th = t_rows ? Bc : ncfg; slots.vh = v_rows ? Bc : ncfg;
+  slots.tdiv = Bc / slots.th; slots.vdiv = Bc / slots.vh;
+  slots.Sp = pad32(S); slots.Lap = pad32(La); slots.Ltp = pad32(Lt);
+  slots.smod_ld = (long)f.depth_single * 6 * D;
+  HIPTRY(hipStreamSynchronize(st));
+  const bool reuse = c->buf.complete() && same_dims(c->plan, *pl) && c->layout.sets == slots.sets &&
+                     c->layout.t_rows == slots.t_rows && c->layout.v_rows == slots.v_rows;
+  if (!reuse) ctx_free_plan(c);
+  c->prepared = false;
+  c->edit = false;                  // a plan without foley_set_edit is a plain run
+  RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
+  c->vis_src = n_vis;
+  const int th = ly.th, vh = ly.vh;
   const int hidmax = f.mlp_hidden > f.conv_hidden ? f.mlp_hidden : f.conv_hidden;
   const int Lmax = std::max(std::max(La, Lv), Lt);
+  const int rl[3] = {La, Lv, Lmax};   // rows of the rotation tables rot_*[k]
   const int rsets = sets ? Bc : ncfg;   // set maps: sized for the most sets a plan of these dimensions can carry
   const int rmax = std::max(std::max(NI, rsets * Lt), std::max(rsets * Lv, rsets * Ls));
   // widest row any precompute stage writes into the scratch (every configurable feature width)
   const size_t tcols = std::max({D, f.sync_hidden, f.cond_dim, f.clip_dim, f.sync_dim, f.time_freq_dim});
 
+  // the plan's lookup tables, copied below so that captured kernels keep valid addresses
+#define PLAN_TABLES(X)                                                                                          \
+  X(rope_cos, (size_t)pl->rope_len * 64 * 4) X(rope_sin, (size_t)pl->rope_len * 64 * 4) X(solver_coef, (size_t)NI * 8 * 4) \
+  X(pos_audio_self, (size_t)La * 4) X(pos_visual_self, (size_t)Lv * 4) X(pos_linear, (size_t)Lmax * 4) X(sync_gather, (size_t)La * 4)
 #define ALLOC(ptr, bytes) TRY(ctx_alloc(c, (bytes), (void**)&(ptr)))
+#define ALLOCTAB(field, bytes) ALLOC(c->buf.field, bytes);
   if (!reuse) {
-    ALLOC(c->vec_table, (size_t)NI * D * 4);
-    ALLOC(c->modtab, (size_t)f.depth_triple * 2 * NI * 9 * D * 4);
-    ALLOC(c->txt_k, (size_t)f.depth_triple * th * H * Lt * 128 * es);
-    ALLOC(c->txt_v, (size_t)f.depth_triple * th * H * ((Lt + 31) & ~31) * 128 * es);
-    HIPTRY(hipMemsetAsync(c->txt_v, 0, (size_t)f.depth_triple * th * H * ((Lt + 31) & ~31) * 128 * es, st));
-    ALLOC(c->v_cond0, (size_t)vh * Lv * D * 4);
-    ALLOC(c->sync_tok, (size_t)vh * Ls * D * 4);
-    if (sets) ALLOC(c->set_idx, (size_t)Bc * (Lt + Ls + 8) * 4);
-    if (v_rows) ALLOC(c->sync_lead_rows, (size_t)Bc * 8 * D * 4);
-    if (t_rows) ALLOC(c->tG, (size_t)Bc * Lt * 2 * D * 4);
-    ALLOC(c->flag, 256);
-    ALLOC(c->xin, (size_t)M * C * es);
-    ALLOC(c->audio, (size_t)M * D * 4);
-    ALLOC(c->vcond, (size_t)Mv * D * 4);
-    ALLOC(c->xn_a, (size_t)M * D * es);
-    ALLOC(c->xn_v, (size_t)Mv * D * es);
-    ALLOC(c->qkv_a, (size_t)M * 3 * D * 4);
-    ALLOC(c->qkv_v, (size_t)Mv * 3 * D * 4);
-    ALLOC(c->Q, (size_t)Bc * H * S * 128 * es);
-    ALLOC(c->K, (size_t)Bc * H * S * 128 * es);
-    ALLOC(c->V, (size_t)Bc * H * ((S + 31) & ~31) * 128 * es);
-    HIPTRY(hipMemsetAsync(c->V, 0, (size_t)Bc * H * ((S + 31) & ~31) * 128 * es, st));  // V^T pad stays finite
-    ALLOC(c->att_a, (size_t)M * D * es);
-    ALLOC(c->att_v, (size_t)Mv * D * es);
-    ALLOC(c->hid_a, (size_t)M * hidmax * es);
-    ALLOC(c->hid_v, (size_t)Mv * f.mlp_hidden * es);
-    ALLOC(c->svec, (size_t)vh * Ls * D * es);
-    ALLOC(c->smod, (size_t)f.depth_single * vh * Ls * 6 * D * 4);
-    ALLOC(c->pred, (size_t)M * C * 4);
-    ALLOC(c->part_a, (size_t)PART_CAP * M * D * 4);     // sized for fp32 slabs; 16-bit slabs (slab16()) use half of it
-    ALLOC(c->part_v, (size_t)PART_CAP * Mv * D * 4);
-    ALLOC(c->x_saved, (size_t)clips * C * La * 4);
-    ALLOC(c->d_acc, (size_t)clips * C * La * 4);
-    ALLOC(c->x_cur, (size_t)clips * C * La * 4);
-    ALLOC(c->step_ctr, 256);
-    ALLOC(c->rope_cos, (size_t)pl->rope_len * 64 * 4);
-    ALLOC(c->rope_sin, (size_t)pl->rope_len * 64 * 4);
-    ALLOC(c->solver_coef, (size_t)NI * 8 * 4);
-    ALLOC(c->pos_audio_self, (size_t)La * 4);
-    ALLOC(c->pos_visual_self, (size_t)Lv * 4);
-    ALLOC(c->pos_linear, (size_t)Lmax * 4);
-    ALLOC(c->sync_gather, (size_t)La * 4);
-    ALLOC(c->rep_idx, (size_t)(v_rows ? Bc : clips) * Lv * 4);
-    {
-      const int rl[3] = {La, Lv, Lmax};
-      for (int k = 0; k < 3; ++k) {
-        ALLOC(c->rot_cos[k], (size_t)rl[k] * 64 * 4);
-        ALLOC(c->rot_sin[k], (size_t)rl[k] * 64 * 4);
-      }
+    ALLOC(c->buf.vec_table, (size_t)NI * D * 4);
+    ALLOC(c->buf.modtab, (size_t)f.depth_triple * 2 * NI * 9 * D * 4);
+    ALLOC(c->buf.txt_k, (size_t)f.depth_triple * th * H * Lt * 128 * es);
+    const size_t txt_v_bytes = (size_t)f.depth_triple * th * H * ly.Ltp * 128 * es, V_bytes = (size_t)Bc * H * ly.Sp * 128 * es;
+    ALLOC(c->buf.txt_v, txt_v_bytes);
+    HIPTRY(hipMemsetAsync(c->buf.txt_v, 0, txt_v_bytes, st));
+    ALLOC(c->buf.v_cond0, (size_t)vh * Lv * D * 4);
+    ALLOC(c->buf.sync_tok, (size_t)vh * Ls * D * 4);
+    if (sets) ALLOC(c->buf.set_idx, (size_t)Bc * (Lt + Ls + 8) * 4);
+    if (v_rows) ALLOC(c->buf.sync_lead_rows, (size_t)Bc * 8 * D * 4);
+    if (t_rows) ALLOC(c->buf.tG, (size_t)Bc * Lt * 2 * D * 4);
+    ALLOC(c->buf.flag, 256);
+    ALLOC(c->buf.xin, (size_t)M * C * es);
+    ALLOC(c->buf.audio, (size_t)M * D * 4);
+    ALLOC(c->buf.vcond, (size_t)Mv * D * 4);
+    ALLOC(c->buf.xn_a, (size_t)M * D * es);
+    ALLOC(c->buf.xn_v, (size_t)Mv * D * es);
+    ALLOC(c->buf.qkv_a, (size_t)M * 3 * D * 4);
+    ALLOC(c->buf.qkv_v, (size_t)Mv * 3 * D * 4);
+    ALLOC(c->buf.Q, (size_t)Bc * H * S * 128 * es);
+    ALLOC(c->buf.K, (size_t)Bc * H * S * 128 * es);
+    ALLOC(c->buf.V, V_bytes);
+    HIPTRY(hipMemsetAsync(c->buf.V, 0, V_bytes, st));  // V^T pad stays finite
+    ALLOC(c->buf.att_a, (size_t)M * D * es);
+    ALLOC(c->buf.att_v, (size_t)Mv * D * es);
+    ALLOC(c->buf.hid_a, (size_t)M * hidmax * es);
+    ALLOC(c->buf.hid_v, (size_t)Mv * f.mlp_hidden * es);
+    ALLOC(c->buf.svec, (size_t)vh * Ls * D * es);
+    ALLOC(c->buf.smod, (size_t)f.depth_single * vh * Ls * 6 * D * 4);
+    ALLOC(c->buf.pred, (size_t)M * C * 4);
+    ALLOC(c->buf.part_a, (size_t)PART_CAP * M * D * 4);     // sized for fp32 slabs; 16-bit slabs (slab16()) use half of it
+    ALLOC(c->buf.part_v, (size_t)PART_CAP * Mv * D * 4);
+    ALLOC(c->buf.x_saved, (size_t)clips * C * La * 4);
+    ALLOC(c->buf.d_acc, (size_t)clips * C * La * 4);
+    ALLOC(c->buf.x_cur, (size_t)clips * C * La * 4);
+    ALLOC(c->buf.step_ctr, 256);
+    PLAN_TABLES(ALLOCTAB)
+    ALLOC(c->buf.rep_idx, (size_t)(v_rows ? Bc : clips) * Lv * 4);
+    for (int k = 0; k < 3; ++k) {
+      ALLOC(c->buf.rot_cos[k], (size_t)rl[k] * 64 * 4);
+      ALLOC(c->buf.rot_sin[k], (size_t)rl[k] * 64 * 4);
     }
     if (!v_rows) {
       std::vector<int> idx((size_t)clips * Lv);
       for (size_t j = 0; j < idx.size(); ++j) idx[j] = (int)(j % Lv);
-      HIPTRY(hipMemcpy(c->rep_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+      HIPTRY(hipMemcpy(c->buf.rep_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
     }
     // scratch of the precompute
-    ALLOC(c->tA, (size_t)rmax * tcols * es);
-    ALLOC(c->tB, (size_t)rmax * tcols * es);
-    ALLOC(c->tF, (size_t)rmax * 2 * D * 4);
-    c->have_buffers = true;
+    ALLOC(c->buf.tA, (size_t)rmax * tcols * es);
+    ALLOC(c->buf.tB, (size_t)rmax * tcols * es);
+    ALLOC(c->buf.tF, (size_t)rmax * 2 * D * 4);
   }
   if (sets) {
     // per-row gather tables: text K/V rows (row b, token t) <- set text_of[b]; sync token rows and the visual stream's start
@@ -591,45 +652,31 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
       for (int t = 0; t < Lt; ++t) idx[(size_t)b * Lt + t] = maps[b] * Lt + t;
       for (int s = 0; s < Ls; ++s) idx[(size_t)Bc * Lt + (size_t)b * Ls + s] = maps[Bc + b] * Ls + s;
     }
-    HIPTRY(hipMemcpy(c->set_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(c->buf.set_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
     if (v_rows) {
       std::vector<int> rep((size_t)Bc * Lv);
       for (int b = 0; b < Bc; ++b)
         for (int j = 0; j < Lv; ++j) rep[(size_t)b * Lv + j] = maps[Bc + b] * Lv + j;
-      HIPTRY(hipMemcpy(c->rep_idx, rep.data(), rep.size() * 4, hipMemcpyHostToDevice));
+      HIPTRY(hipMemcpy(c->buf.rep_idx, rep.data(), rep.size() * 4, hipMemcpyHostToDevice));
     }
   }
-  // a captured iteration belongs to one set map (the tables it reads are rewritten in place, so this is for safety, not layout)
-  if (c->graph_exec && maps != c->set_maps) ctx_drop_graph(c);
   c->set_maps = std::move(maps);
-  if (c->graph_exec && c->graph_guidance != pl->guidance) ctx_drop_graph(c);
-  // the plan's lookup tables are copied so that captured kernels keep valid addresses
-  const foley_plan in = *pl;
-  c->plan = in;
+  c->plan = *pl;
 #define COPYTAB(field, bytes) \
-  HIPTRY(hipMemcpyAsync((void*)c->field, in.field, (bytes), hipMemcpyDeviceToDevice, st)); \
-  c->plan.field = c->field
-  COPYTAB(rope_cos, (size_t)in.rope_len * 64 * 4);
-  COPYTAB(rope_sin, (size_t)in.rope_len * 64 * 4);
-  COPYTAB(solver_coef, (size_t)NI * 8 * 4);
-  COPYTAB(pos_audio_self, (size_t)La * 4);
-  COPYTAB(pos_visual_self, (size_t)Lv * 4);
-  COPYTAB(pos_linear, (size_t)Lmax * 4);
-  COPYTAB(sync_gather, (size_t)La * 4);
+  HIPTRY(hipMemcpyAsync((void*)c->buf.field, pl->field, (bytes), hipMemcpyDeviceToDevice, st)); \
+  c->plan.field = c->buf.field;
+  PLAN_TABLES(COPYTAB)
 #undef COPYTAB
+#undef PLAN_TABLES
   pl = &c->plan;
-  {
-    const int* pt[3] = {pl->pos_audio_self, pl->pos_visual_self, pl->pos_linear};
-    const int rl[3] = {La, Lv, Lmax};
-    for (int k = 0; k < 3; ++k) {
-      TRY(launch_gather_rows(pl->rope_cos, pt[k], rl[k], 1, pl->rope_len, 64, c->rot_cos[k], st));
-      TRY(launch_gather_rows(pl->rope_sin, pt[k], rl[k], 1, pl->rope_len, 64, c->rot_sin[k], st));
-    }
+  const int* pt[3] = {pl->pos_audio_self, pl->pos_visual_self, pl->pos_linear};
+  for (int k = 0; k < 3; ++k) {
+    TRY(launch_gather_rows(pl->rope_cos, pt[k], rl[k], 1, pl->rope_len, 64, c->buf.rot_cos[k], st));
+    TRY(launch_gather_rows(pl->rope_sin, pt[k], rl[k], 1, pl->rope_len, 64, c->buf.rot_sin[k], st));
   }
-  HIPTRY(hipMemsetAsync(c->step_ctr, 0, 256, st));
-  void* tA = c->tA;
-  void* tB = c->tB;
-  float* tF = c->tF;
+  HIPTRY(hipMemsetAsync(c->buf.step_ctr, 0, 256, st));
+  void *tA = c->buf.tA, *tB = c->buf.tB;
+  float* tF = c->buf.tF;
 
   // 1. time embedding table: t_feat -> Linear -> SiLU -> Linear   (embed_layers.py:104-136)
   Lin time0, time2;
@@ -637,15 +684,15 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   TRY(get_lin(c, "time2", T, D, D, true, &time2));
   TRY(launch_cast(pl->t_feat, FOLEY_F32, tA, T, (long)NI * f.time_freq_dim, st));
   TRY(launch_gemm(gemm_plain(tA, NI, time0, tB, D), T, EPI_SILU_T, 0, st));
-  TRY(launch_gemm(gemm_plain(tB, NI, time2, c->vec_table, D), T, EPI_STORE_F32, 0, st));
+  TRY(launch_gemm(gemm_plain(tB, NI, time2, c->buf.vec_table, D), T, EPI_STORE_F32, 0, st));
 
   // 2. AdaLN tables of the triple blocks: Linear(SiLU(vec)) for every iteration (modulate_layers.py:15-16)
-  TRY(launch_rows_add_act(c->vec_table, rb_none(), NI, D, 1, tA, T, st));
+  TRY(launch_rows_add_act(c->buf.vec_table, rb_none(), NI, D, 1, tA, T, st));
   for (int b = 0; b < f.depth_triple; ++b)
     for (int s = 0; s < 2; ++s) {
       Lin m;
       TRY(get_lin(c, "t" + std::to_string(b) + (s ? ".v_mod" : ".a_mod"), T, 9 * D, D, true, &m));
-      float* dst = c->modtab + ((size_t)(b * 2 + s) * NI) * 9 * D;
+      float* dst = c->buf.modtab + ((size_t)(b * 2 + s) * NI) * 9 * D;
       TRY(launch_gemm(gemm_plain(tA, NI, m, dst, 9 * D), T, EPI_STORE_F32, 0, st));
     }
 
@@ -664,16 +711,12 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
       TRY(get_tensor(c, "t" + std::to_string(b) + ".t_kn", FOLEY_F32, {128}, &kn));
       TRY(launch_gemm(gemm_plain(tA, n_text * Lt, kv, tF, 2 * D), T, EPI_STORE_F32, 0, st));
       // per-row layout: the distinct sets' K/V rows are gathered into one set per batch row before the head split
-      if (t_rows) TRY(launch_gather_rows(tF, c->set_idx, Bc * Lt, 1, n_text * Lt, 2 * D, c->tG, st));
-      QkvSplitArgs q{};
-      q.qkv = t_rows ? c->tG : tF; q.M = th * Lt; q.L = Lt; q.H = H; q.nK = 2;
-      q.gain[0] = (const float*)kn; q.pos[0] = pl->pos_linear;
-      const int Ltp = (Lt + 31) & ~31;
-      q.dst[0] = (char*)c->txt_k + (size_t)b * th * H * Lt * 128 * es;
-      q.dst[1] = (char*)c->txt_v + (size_t)b * th * H * (foley_is_half(T) ? Ltp : Lt) * 128 * es;
-      q.out_dtype = T; q.vt_pitch = foley_is_half(T) ? Ltp : 0;
-      q.S_tot = Lt; q.tok_off = 0; q.eps = 1e-6f; q.cos_tab = pl->rope_cos; q.sin_tab = pl->rope_sin;
-      TRY(launch_qkv_split(q, st));
+      if (t_rows) TRY(launch_gather_rows(tF, c->buf.set_idx, Bc * Lt, 1, n_text * Lt, 2 * D, c->buf.tG, st));
+      const bool vt = foley_is_half(T);
+      void* dst[3] = {(char*)c->buf.txt_k + (size_t)b * th * H * Lt * 128 * es,
+                      (char*)c->buf.txt_v + (size_t)b * th * H * (vt ? ly.Ltp : Lt) * 128 * es, nullptr};
+      TRY(launch_qkv_split(qkv_split_args(c, t_rows ? c->buf.tG : tF, th * Lt, Lt, 2, (const float*)kn, nullptr, 2, false, dst, Lt, 0,
+                                          vt ? ly.Ltp : 0, 1e-6f), st));
     }
   }
 
@@ -684,7 +727,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     TRY(get_lin(c, "vis.w2", T, D, D, false, &w2));
     TRY(launch_cast(pl->clip, FOLEY_F32, tA, T, (long)n_vis * Lv * f.clip_dim, st));
     TRY(launch_gemm(gemm_plain(tA, n_vis * Lv, w13, tB, D), T, EPI_SILUGATE_T, 0, st));
-    TRY(launch_gemm(gemm_plain(tB, n_vis * Lv, w2, c->v_cond0, D), T, EPI_STORE_F32, 0, st));
+    TRY(launch_gemm(gemm_plain(tB, n_vis * Lv, w2, c->buf.v_cond0, D), T, EPI_STORE_F32, 0, st));
   }
 
   // 5. sync features: + pos emb, Linear, SiLU, ConvMLP(k=1), nearest-exact up-sampling (hifi_foley.py:755-762)
@@ -702,8 +745,8 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     // through RowBcast mode 2 (common.h), so everything derived from the tokens alone - SiLU(token + vec)
     // and the single-stream blocks' modulation GEMM - runs on ncfg*Ls rows instead of ncfg*La.
     // Per-row layout: the distinct sets' token rows are gathered into one half per batch row.
-    TRY(launch_gemm(gemm_plain(tA, n_vis * Ls, w2, v_rows ? tF : c->sync_tok, D), T, EPI_STORE_F32, 0, st));
-    if (v_rows) TRY(launch_gather_rows(tF, c->set_idx + (size_t)Bc * Lt, Bc * Ls, 1, n_vis * Ls, D, c->sync_tok, st));
+    TRY(launch_gemm(gemm_plain(tA, n_vis * Ls, w2, v_rows ? tF : c->buf.sync_tok, D), T, EPI_STORE_F32, 0, st));
+    if (v_rows) TRY(launch_gather_rows(tF, c->buf.set_idx + (size_t)Bc * Lt, Bc * Ls, 1, n_vis * Ls, D, c->buf.sync_tok, st));
     // Empty sync features (text-to-audio; the unconditional half of a CFG pair) are one learned row plus
     // sync_pos_emb, which repeats every 8 tokens: the token rows are then 8-periodic and the per-token work of the
     // single-stream blocks only has 8 distinct rows per half.  Detected on the data (bit patterns), not assumed.
@@ -711,26 +754,28 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     // conditional half - the modulation GEMM then runs on 8 + Ls rows instead of 2 Ls (round 5).
     // (per-row layout: one "half" per batch row, the unconditional rows first)
     if (vh > 32) return FAIL(FOLEY_ERR_INVALID, "more than 32 cfg halves");
-    HIPTRY(hipMemsetAsync(c->flag, 0, 4 * 32, st));
-    TRY(launch_rows_periodic_check(c->sync_tok, vh, Ls, 8, D, c->flag, st));
+    HIPTRY(hipMemsetAsync(c->buf.flag, 0, 4 * 32, st));
+    TRY(launch_rows_periodic_check(c->buf.sync_tok, vh, Ls, 8, D, c->buf.flag, st));
   }
   HIPTRY(hipStreamSynchronize(st));
   {
     int differs[32];
-    HIPTRY(hipMemcpy(differs, c->flag, 4 * 32, hipMemcpyDeviceToHost));
+    HIPTRY(hipMemcpy(differs, c->buf.flag, 4 * 32, hipMemcpyDeviceToHost));
     int lead = 0;
     while (Ls > 8 && lead < vh && !differs[lead]) ++lead;
-    const int per = lead > 0 ? 8 : 0;
-    if (c->graph_exec && (per != c->sync_per || lead != c->sync_lead)) ctx_drop_graph(c);   // the captured modulation GEMM has another M
-    c->sync_per = per;
-    c->sync_lead = lead;
+    ly.lead = lead;
+    ly.per = lead > 0 ? 8 : 0;
+    ly.allper = lead > 0 && lead == vh;
+    ly.R = lead * ly.per + (vh - lead) * Ls;
+    ly.P = ly.allper ? ly.per : Ls;   // hoisting serves the all-periodic case
+    ly.smod_step = (long)vh * ly.P * ly.smod_ld;
     if (v_rows && lead > 1) {   // pack the leading periodic halves' rows (st is idle: synchronised above)
       std::vector<int> idx((size_t)lead * 8);
       for (int h = 0; h < lead; ++h)
         for (int r = 0; r < 8; ++r) idx[(size_t)h * 8 + r] = h * Ls + r;
-      int* lead_idx = c->set_idx + (size_t)Bc * (Lt + Ls);
+      int* lead_idx = c->buf.set_idx + (size_t)Bc * (Lt + Ls);
       HIPTRY(hipMemcpy(lead_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-      TRY(launch_gather_rows(c->sync_tok, lead_idx, lead * 8, 1, vh * Ls, D, c->sync_lead_rows, st));
+      TRY(launch_gather_rows(c->buf.sync_tok, lead_idx, lead * 8, 1, vh * Ls, D, c->buf.sync_lead_rows, st));
     }
   }
   if (!c->fw.ok) TRY(resolve_forward_weights(c));
@@ -742,9 +787,8 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     // SMOD_TABLE_CAP (1.06 GB for the 16 distinct rows of text-to-audio, 14.9 GB for the 224 rows of a 5 s video clip); longer
     // clips keep the per-iteration GEMM of run_forward.
     constexpr size_t SMOD_TABLE_CAP = (size_t)24 << 30;   // 24 GiB
-    const int P = (c->sync_per && c->sync_lead == vh) ? c->sync_per : Ls;   // hoisting serves the all-periodic case
-    const size_t ncol = (size_t)f.depth_single * 6 * D;
-    const size_t tab_bytes = (size_t)NI * vh * P * ncol * 4;
+    const int P = ly.P;
+    const size_t tab_bytes = (size_t)NI * ly.smod_step * 4;
     // ... and only where the weight stream is what the per-iteration GEMM costs (a few distinct rows: the 8-periodic empty sync
     // features).  With the 224 dense rows of a video clip the batched GEMM costs what the 50 small ones do (18.3 vs 19 ms).
     bool hoist = f.depth_single > 0 && vh * P <= 64 && tab_bytes <= SMOD_TABLE_CAP;
@@ -757,30 +801,27 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
       const size_t held = c->smod_tab.bytes + c->svec_tab.bytes;
       if (tab_bytes + svec_bytes > held && (tab_bytes + svec_bytes - held) > free_b / 2) hoist = false;
     }
-    const void* old_tab = c->smod_tab.p;
     if (hoist && (grow(c->smod_tab, tab_bytes) != 0 || grow(c->svec_tab, svec_bytes) != 0)) {
       hipGetLastError();     // allocation failed: not an error - the per-iteration GEMM of run_forward is still there
       hoist = false;
     }
     if (!hoist && (c->smod_tab.p || c->svec_tab.p)) {   // a plan that does not hoist gives the tables back
       HIPTRY(hipStreamSynchronize(st));
-      if (c->smod_tab.p) hipFree(c->smod_tab.p);
-      if (c->svec_tab.p) hipFree(c->svec_tab.p);
-      c->smod_tab = DevBuf{};
-      c->svec_tab = DevBuf{};
+      release(c->smod_tab);
+      release(c->svec_tab);
     }
-    if (c->graph_exec && hoist != c->smod_hoisted) ctx_drop_graph(c);
-    c->smod_hoisted = false;
     if (hoist) {
-      if (c->graph_exec && old_tab != c->smod_tab.p) ctx_drop_graph(c);   // captured kernels hold the table's address
       for (int it = 0; it < NI; ++it)
-        TRY(launch_rows_add_act(c->sync_tok, rb_vec(c->vec_table + (size_t)it * D, 0, nullptr), vh * Ls, D, 1,
+        TRY(launch_rows_add_act(c->buf.sync_tok, rb_vec(c->buf.vec_table + (size_t)it * D, 0, nullptr), vh * Ls, D, 1,
                                 (char*)c->svec_tab.p + (size_t)it * vh * Ls * D * es, T, st));
-      GemmArgs gm = gemm_plain(c->svec_tab.p, NI * vh * P, c->fw.smod, c->smod_tab.p, (long)ncol);
+      GemmArgs gm = gemm_plain(c->svec_tab.p, NI * vh * P, c->fw.smod, c->smod_tab.p, ly.smod_ld);
       gm.segV = P; gm.segS = Ls;     // virtual rows: row r of the product is token r % P of (iteration, half) r / P
       TRY(launch_gemm(gm, T, EPI_STORE_F32, 0, st));
-      c->smod_hoisted = true;
     }
+    // the table the blocks read: hoisted, or run_forward's of this iteration with the leading halves' 8 rows packed
+    ly.hoisted = hoist;
+    ly.mod_per = (ly.allper || !hoist) ? ly.per : 0;
+    ly.mod_lead = ly.allper ? -1 : ly.lead;
   }
   {
     // the plan's table must be the nearest-exact map the kernels compute in their addressing
@@ -858,13 +899,12 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const int ncfg = pl.ncfg, clips = pl.clips, La = pl.La, Lv = pl.Lv, Ls = pl.Ls, Lt = pl.Lt, NI = pl.n_iter;
   const int Bc = ncfg * clips, M = Bc * La, Mv = Bc * Lv, S = La + Lv;
-  // conditioning layout (foley_prepare_sets): batch row b reads text slot b / tdiv and visual half b / vdiv - clips for the
-  // per-half layout, 1 for the per-row one
-  const int th = c->txt_rows ? Bc : ncfg, vh = c->vis_rows ? Bc : ncfg, tdiv = Bc / th, vdiv = Bc / vh;
+  const RunLayout& ly = c->layout;
+  const int th = ly.th, vh = ly.vh, lead = ly.lead;
   const bool bf = foley_is_half(T);   // 16-bit throughput mode (bf16 or fp16 operands): transposed V, fused head split
   const size_t es = esize(T);
-  const int Sp = (S + 31) & ~31, Lap = (La + 31) & ~31;  // V^T row pitches (bf16 attention)
-  const int* sp = c->step_ctr;
+  const int* sp = c->buf.step_ctr;
+  void* const qkv_dst[3] = {c->buf.Q, c->buf.K, c->buf.V};
   // algorithmic work of one launch (profile labels): dense contraction FLOPs, operand + result bytes
   auto gf = [](double m, double n, double k) { return 2.0 * m * n * k; };
   auto gb = [&](double m, double n, double k, double out_es) { return (m * k + n * k) * (double)es + m * n * out_es; };
@@ -875,39 +915,36 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   // and every single block's modulation GEMM (hifi_foley.py:366).  They depend on the iteration only, are
   // identical for every clip of a CFG half, and - add_sync being an up-sampling of the Ls sync tokens - have
   // only Ls distinct rows per half: M = ncfg*Ls (224 instead of 500 at 5 s).
-  if (!c->smod_hoisted) {
-    // distinct rows only: 8 per 8-periodic half (the leading sync_lead halves), Ls per dense half - packed back to back, which
-    // is the row order of the modulation table (RowBcast::dense_from / dense_base)
-    const int lead = c->sync_per ? c->sync_lead : 0, R = lead * c->sync_per + (vh - lead) * Ls;
-    if (c->vis_rows && lead > 1)   // per-row layout: the leading halves' rows were packed by foley_prepare_sets - one launch
-      TRY(launch_rows_add_act(c->sync_lead_rows, rb_vec(c->vec_table, D, sp), lead * c->sync_per, D, 1, c->svec, T, st));
+  if (!ly.hoisted) {
+    // distinct rows only: 8 per 8-periodic half (the leading halves), Ls per dense half - packed back to back (RunLayout::R)
+    if (ly.v_rows && lead > 1)   // per-row layout: the leading halves' rows were packed by foley_prepare_sets - one launch
+      TRY(launch_rows_add_act(c->buf.sync_lead_rows, rb_vec(c->buf.vec_table, D, sp), lead * ly.per, D, 1, c->buf.svec, T, st));
     else
       for (int h = 0; h < lead; ++h)
-        TRY(launch_rows_add_act(c->sync_tok + (size_t)h * Ls * D, rb_vec(c->vec_table, D, sp), c->sync_per, D, 1,
-                                (char*)c->svec + (size_t)h * c->sync_per * D * es, T, st));
+        TRY(launch_rows_add_act(c->buf.sync_tok + (size_t)h * Ls * D, rb_vec(c->buf.vec_table, D, sp), ly.per, D, 1,
+                                (char*)c->buf.svec + (size_t)h * ly.per * D * es, T, st));
     if (lead < vh)
-      TRY(launch_rows_add_act(c->sync_tok + (size_t)lead * Ls * D, rb_vec(c->vec_table, D, sp), (vh - lead) * Ls, D, 1,
-                              (char*)c->svec + (size_t)lead * c->sync_per * D * es, T, st));
+      TRY(launch_rows_add_act(c->buf.sync_tok + (size_t)lead * Ls * D, rb_vec(c->buf.vec_table, D, sp), (vh - lead) * Ls, D, 1,
+                              (char*)c->buf.svec + (size_t)lead * ly.per * D * es, T, st));
     if (f.depth_single > 0) {
-      // one GEMM for all blocks: [R, D] x [n_single*6D, D]^T -> smod [R, n_single*6D]
-      const double n = (double)f.depth_single * 6 * D;
-      GemmArgs gm = krot(gemm_plain(c->svec, R, W.smod, c->smod, (long)f.depth_single * 6 * D));
-      PROF("single.modulation (all blocks, one GEMM)", gf(R, n, D), gb(R, n, D, 4), launch_gemm(gm, T, EPI_STORE_F32, 0, st));
+      const double n = (double)ly.smod_ld;   // one GEMM for all blocks: [R, D] x [n_single*6D, D]^T -> smod [R, n_single*6D]
+      GemmArgs gm = krot(gemm_plain(c->buf.svec, ly.R, W.smod, c->buf.smod, ly.smod_ld));
+      PROF("single.modulation (all blocks, one GEMM)", gf(ly.R, n, D), gb(ly.R, n, D, 4), launch_gemm(gm, T, EPI_STORE_F32, 0, st));
     }
   }
 
   // audio_embedder (conv k=1 == linear over the transposed latents) + add_sync (hifi_foley.py:768, 838-839)
   {
-    GemmArgs g = krot(gemm_plain(c->xin, M, W.audio_in, c->audio, D));
-    g.rb = rb_up(c->sync_tok, D, vdiv * La, La, Ls);
+    GemmArgs g = krot(gemm_plain(c->buf.xin, M, W.audio_in, c->buf.audio, D));
+    g.rb = rb_up(c->buf.sync_tok, D, ly.vdiv * La, La, Ls);
     PROF("audio_embedder", gf(M, D, C), gb(M, D, C, 4), launch_gemm(g, T, EPI_STORE_F32, 0, st));
   }
   // visual stream starts from the step-invariant projection, replicated per clip (one gather launch); per-row layout: every
   // batch row gathers its own set's rows of the distinct projections
-  if (c->vis_rows)
-    TRY(launch_gather_rows(c->v_cond0, c->rep_idx, Bc * Lv, 1, c->vis_src * Lv, D, c->vcond, st));
+  if (ly.v_rows)
+    TRY(launch_gather_rows(c->buf.v_cond0, c->buf.rep_idx, Bc * Lv, 1, c->vis_src * Lv, D, c->buf.vcond, st));
   else
-    TRY(launch_gather_rows(c->v_cond0, c->rep_idx, clips * Lv, ncfg, Lv, D, c->vcond, st));
+    TRY(launch_gather_rows(c->buf.v_cond0, c->buf.rep_idx, clips * Lv, ncfg, Lv, D, c->buf.vcond, st));
 
   // residual updates left pending by deferred split-K GEMMs, per stream (audio, visual); the next
   // LayerNorm of that stream applies them
@@ -925,11 +962,11 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   for (int blk = 0; blk < f.depth_triple; ++blk) {
     const TripleW& w = W.t[blk];
     auto tb = [&](int s, int chunk) {
-      return rb_vec(c->modtab + ((size_t)(blk * 2 + s) * NI) * 9 * D + (size_t)chunk * D, 9L * D, sp);
+      return rb_vec(c->buf.modtab + ((size_t)(blk * 2 + s) * NI) * 9 * D + (size_t)chunk * D, 9L * D, sp);
     };
-    struct Stream { float* x; void* xn; float* qkv; void* att; void* hid; int rows, L, tok_off; const int* pos; };
-    Stream ss[2] = {{c->audio, c->xn_a, c->qkv_a, c->att_a, c->hid_a, M, La, Lv, pl.pos_audio_self},
-                    {c->vcond, c->xn_v, c->qkv_v, c->att_v, c->hid_v, Mv, Lv, 0, pl.pos_visual_self}};
+    struct Stream { float* x; void* xn; float* qkv; void* att; void* hid; int rows, L, tok_off; };
+    Stream ss[2] = {{c->buf.audio, c->buf.xn_a, c->buf.qkv_a, c->buf.att_a, c->buf.hid_a, M, La, Lv},
+                    {c->buf.vcond, c->buf.xn_v, c->buf.qkv_v, c->buf.att_v, c->buf.hid_v, Mv, Lv, 0}};
     // Both streams go through the same sequence of ops with their own weights; each op is ONE
     // launch covering the audio problem and the (much smaller) visual problem.
     auto ln2 = [&](int c_shift, int c_scale) -> int {
@@ -944,41 +981,31 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
       GemmArgs g1 = krot(gemm_plain(from_hid ? ss[1].hid : ss[1].att, ss[1].rows, lv, ss[1].x, D));
       g0.rb = tb(0, c_gate);
       g1.rb = tb(1, c_gate);
-      with_partials(g0, c->part_a);
-      with_partials(g1, c->part_v);
+      with_partials(g0, c->buf.part_a);
+      with_partials(g1, c->buf.part_v);
       int ks = 1;
       PROF(label, gf(M + Mv, la.N, la.K), gb(M + Mv, la.N, la.K, 4) + (double)la.N * la.K * es,
            launch_gemm_pair(g0, g1, T, EPI_GATE_RES, st, &ks));
       if (ks > 1) {
-        pend[0] = LnPending{c->part_a, ks, g0.partial_stride, la.b, g0.rb, slab_half};
-        pend[1] = LnPending{c->part_v, ks, g1.partial_stride, lv.b, g1.rb, slab_half};
+        pend[0] = LnPending{c->buf.part_a, ks, g0.partial_stride, la.b, g0.rb, slab_half};
+        pend[1] = LnPending{c->buf.part_v, ks, g1.partial_stride, lv.b, g1.rb, slab_half};
       }
       return 0;
     };
-    auto split_args = [&](int s, int nK, const void* gq, const void* gk, const int* pos) {
-      Stream& z = ss[s];
-      QkvSplitArgs q{};
-      q.qkv = z.qkv; q.M = z.rows; q.L = z.L; q.H = H; q.nK = nK;
-      q.gain[0] = (const float*)gq; q.gain[1] = (const float*)gk;
-      q.pos[0] = pos; q.pos[1] = nK > 1 ? pos : nullptr;
-      q.dst[0] = c->Q; q.dst[1] = c->K; q.dst[2] = c->V;
-      q.out_dtype = T; q.vt_pitch = (bf && nK == 3) ? Sp : 0;
-      q.S_tot = S; q.tok_off = z.tok_off; q.eps = 1e-6f; q.cos_tab = pl.rope_cos; q.sin_tab = pl.rope_sin;
-      const int k = pos == pl.pos_audio_self ? 0 : (pos == pl.pos_visual_self ? 1 : (pos == pl.pos_linear ? 2 : -1));
-      for (int i = 0; i < 2 && k >= 0; ++i)
-        if (q.pos[i]) { q.rcos[i] = c->rot_cos[k]; q.rsin[i] = c->rot_sin[k]; }
-      return q;
+    auto split_args = [&](int s, int nK, const float* gq, const float* gk, int rot) {   // of stream s into the joint Q/K/V
+      return qkv_split_args(c, ss[s].qkv, ss[s].rows, ss[s].L, nK, gq, gk, rot, true, qkv_dst, S, ss[s].tok_off,
+                            (bf && nK == 3) ? ly.Sp : 0, 1e-6f);
     };
     // 1. joint self attention (hifi_foley.py:215-269)
     {
       TRY(ln2(0, 1));
       GemmArgs g0 = krot(gemm_plain(ss[0].xn, ss[0].rows, w.qkv[0], ss[0].qkv, 3 * D));
       GemmArgs g1 = krot(gemm_plain(ss[1].xn, ss[1].rows, w.qkv[1], ss[1].qkv, 3 * D));
-      g0.qs = split_args(0, 3, w.qn[0], w.kn[0], ss[0].pos);
-      g1.qs = split_args(1, 3, w.qn[1], w.kn[1], ss[1].pos);
+      g0.qs = split_args(0, 3, w.qn[0], w.kn[0], 0);
+      g1.qs = split_args(1, 3, w.qn[1], w.kn[1], 1);
       PROF("triple.qkv GEMM + RMSNorm/RoPE head split", gf(M + Mv, 3 * D, D), gb(M + Mv, 3 * D, D, es) + 3.0 * D * D * es,
            launch_gemm_pair(g0, g1, T, EPI_QKV_SPLIT, st));   // head split fused into the projection
-      AttnArgs a{c->Q, c->K, c->V, Bc, H, S, S, 1, c->att_v, c->att_a, Lv, T, bf ? Sp : 0};
+      AttnArgs a{c->buf.Q, c->buf.K, c->buf.V, Bc, H, S, S, 1, c->buf.att_v, c->buf.att_a, Lv, T, bf ? ly.Sp : 0};
       PROF("triple.self attention", af(Bc, S, S), ab(Bc, S, S), launch_attention(a, T, st));
       TRY(gated2("triple.self proj GEMM (gated residual)", w.proj[0], w.proj[1], false, 2));
     }
@@ -987,9 +1014,9 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
       TRY(ln2(3, 4));
       GemmArgs g0 = krot(gemm_plain(ss[0].xn, ss[0].rows, w.cq[0], ss[0].qkv, D));
       GemmArgs g1 = krot(gemm_plain(ss[1].xn, ss[1].rows, w.cq[1], ss[1].qkv, D));
-      g0.qs = split_args(0, 1, w.cqn[0], nullptr, pl.pos_linear);
-      g1.qs = split_args(1, 1, w.cqn[1], nullptr, pl.pos_linear);
-      const int Ltp = (Lt + 31) & ~31;
+      g0.qs = split_args(0, 1, w.cqn[0], nullptr, 2);
+      g1.qs = split_args(1, 1, w.cqn[1], nullptr, 2);
+      const int Ltp = ly.Ltp, tdiv = ly.tdiv;
       const size_t offk = (size_t)blk * th * H * Lt * 128 * es;
       const size_t offv = (size_t)blk * th * H * (bf ? Ltp : Lt) * 128 * es;
       // 16-bit modes: the projection may run the attention against the <= 96 cached text keys in its epilogue (small grids:
@@ -998,14 +1025,14 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
       if (bf && Lt <= 96 && Ltp >= 96) {
         for (int s = 0; s < 2; ++s) {
           QkvSplitArgs& q = s ? g1.qs : g0.qs;
-          q.attn_k = (char*)c->txt_k + offk; q.attn_vt = (char*)c->txt_v + offv; q.attn_out = ss[s].att;
+          q.attn_k = (char*)c->buf.txt_k + offk; q.attn_vt = (char*)c->buf.txt_v + offv; q.attn_out = ss[s].att;
           q.attn_skv = Lt; q.attn_pitch = Ltp; q.attn_bdiv = tdiv; q.attn_fused = &fused;   // gemm_plan.h: <= 2 sets per tile
         }
       }
       PROF("triple.cross q GEMM + head split (+ cross attention on small grids)", gf(M + Mv, D, D),
            gb(M + Mv, D, D, es) + 1.0 * D * D * es, launch_gemm_pair(g0, g1, T, EPI_QKV_SPLIT, st));
       if (!fused) {
-        AttnArgs a{c->Q, (char*)c->txt_k + offk, (char*)c->txt_v + offv, Bc, H, S, Lt, tdiv, c->att_v, c->att_a, Lv,
+        AttnArgs a{c->buf.Q, (char*)c->buf.txt_k + offk, (char*)c->buf.txt_v + offv, Bc, H, S, Lt, tdiv, c->buf.att_v, c->buf.att_a, Lv,
                    T, bf ? Ltp : 0};
         PROF("triple.cross attention", af(Bc, S, Lt), ab(Bc, S, Lt), launch_attention(a, T, st));
       }
@@ -1024,83 +1051,78 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   const int Hc = f.conv_hidden;
   for (int blk = 0; blk < f.depth_single; ++blk) {
     const SingleW& w = W.s[blk];
-    const float* smod_b = (c->smod_hoisted ? (const float*)c->smod_tab.p : c->smod) + (size_t)blk * 6 * D;   // column block of the fused table
-    // table layout per iteration: every half periodic (8 rows each) | the leading halves periodic, the others dense (the
-    // per-iteration GEMM only - a hoisted table that is not all-periodic is dense) | every half dense
-    const bool allper = c->sync_per && c->sync_lead == vh;
-    const int per_eff = (allper || !c->smod_hoisted) ? c->sync_per : 0;
+    const float* smod_b = (ly.hoisted ? (const float*)c->smod_tab.p : c->buf.smod) + (size_t)blk * 6 * D;   // column block of the fused table
+    // table layout per iteration (RunLayout): every half periodic (8 rows each) | the leading halves periodic, the others dense
+    // (the per-iteration GEMM only) | every half dense
     auto sm = [&](int chunk) {
-      RowBcast r = rb_up(smod_b + (size_t)chunk * D, 6L * D * f.depth_single, vdiv * La, La, Ls, per_eff, allper ? -1 : c->sync_lead);
-      if (c->smod_hoisted) {   // the table of every iteration: this iteration's rows start at step * vh*P*ld
+      RowBcast r = rb_up(smod_b + (size_t)chunk * D, ly.smod_ld, ly.vdiv * La, La, Ls, ly.mod_per, ly.mod_lead);
+      if (ly.hoisted) {   // the table of every iteration: this iteration's rows start at step * smod_step
         r.step_ptr = sp;
-        r.step_stride = (long)vh * (allper ? c->sync_per : Ls) * 6L * D * f.depth_single;
+        r.step_stride = ly.smod_step;
       }
       return r;
     };
     PROF("single.layernorm+modulate (+pending split-K sum)", 0.0, ln_bytes_s,
-         launch_ln_mod_pending(c->audio, M, D, 1e-5f, sm(0), sm(1), c->xn_a, T, pend[0], st));
+         launch_ln_mod_pending(c->buf.audio, M, D, 1e-5f, sm(0), sm(1), c->buf.xn_a, T, pend[0], st));
     pend[0] = LnPending{};
-    GemmArgs gq = krot(gemm_plain(c->xn_a, M, w.qkv, c->qkv_a, 3 * D));
-    QkvSplitArgs q{};
-    q.qkv = c->qkv_a; q.M = M; q.L = La; q.H = H; q.nK = 3;
-    q.gain[0] = w.qn; q.gain[1] = w.kn;
-    q.pos[0] = pl.pos_linear; q.pos[1] = pl.pos_linear;
-    q.dst[0] = c->Q; q.dst[1] = c->K; q.dst[2] = c->V;
-    q.out_dtype = T; q.vt_pitch = bf ? Lap : 0;
-    q.S_tot = La; q.tok_off = 0; q.eps = 1.1920928955078125e-07f;  // nn.RMSNorm(eps=None) -> finfo(fp32).eps
-    q.cos_tab = pl.rope_cos; q.sin_tab = pl.rope_sin;
-    q.rcos[0] = q.rcos[1] = c->rot_cos[2]; q.rsin[0] = q.rsin[1] = c->rot_sin[2];
-    gq.qs = q;
+    GemmArgs gq = krot(gemm_plain(c->buf.xn_a, M, w.qkv, c->buf.qkv_a, 3 * D));
+    gq.qs = qkv_split_args(c, c->buf.qkv_a, M, La, 3, w.qn, w.kn, 2, true, qkv_dst, La, 0, bf ? ly.Lap : 0,
+                           1.1920928955078125e-07f);  // nn.RMSNorm(eps=None) -> finfo(fp32).eps
     PROF("single.qkv GEMM + RMSNorm/RoPE head split", gf(M, 3 * D, D), gb(M, 3 * D, D, es), launch_gemm(gq, T, EPI_QKV_SPLIT, 0, st));
     {
-      AttnArgs a{c->Q, c->K, c->V, Bc, H, La, La, 1, c->att_a, c->att_a, 0, T, bf ? Lap : 0};
+      AttnArgs a{c->buf.Q, c->buf.K, c->buf.V, Bc, H, La, La, 1, c->buf.att_a, c->buf.att_a, 0, T, bf ? ly.Lap : 0};
       PROF("single.self attention", af(Bc, La, La), ab(Bc, La, La), launch_attention(a, T, st));
     }
     {
-      GemmArgs g = krot(gemm_conv(c->att_a, M, La, D, 3, 1, w.lin1, c->audio, D));
+      GemmArgs g = krot(gemm_conv(c->buf.att_a, M, La, D, 3, 1, w.lin1, c->buf.audio, D));
       g.rb = sm(2);
-      with_partials(g, c->part_a);
+      with_partials(g, c->buf.part_a);
       int ks = 1;
       PROF("single.linear1 conv3 GEMM (gated residual)", gf(M, D, 3 * D), gb(M, D, 3 * D, 4), launch_gemm(g, T, EPI_GATE_RES, 0, st, &ks));
-      if (ks > 1) pend[0] = LnPending{c->part_a, ks, g.partial_stride, w.lin1.b, g.rb, slab_half};
+      if (ks > 1) pend[0] = LnPending{c->buf.part_a, ks, g.partial_stride, w.lin1.b, g.rb, slab_half};
     }
     PROF("single.layernorm+modulate (+pending split-K sum)", 0.0, ln_bytes_s,
-         launch_ln_mod_pending(c->audio, M, D, 1e-5f, sm(3), sm(4), c->xn_a, T, pend[0], st));
+         launch_ln_mod_pending(c->buf.audio, M, D, 1e-5f, sm(3), sm(4), c->buf.xn_a, T, pend[0], st));
     pend[0] = LnPending{};
     PROF("single.w1/w3 conv3 GEMM + SiLU gate", gf(M, 2 * Hc, 3 * D), gb(M, 2 * Hc, 3 * D, es) - (double)M * Hc * es,
-         launch_gemm(krot(gemm_conv(c->xn_a, M, La, D, 3, 1, w.w13, c->hid_a, Hc)), T, EPI_SILUGATE_T, 0, st));
+         launch_gemm(krot(gemm_conv(c->buf.xn_a, M, La, D, 3, 1, w.w13, c->buf.hid_a, Hc)), T, EPI_SILUGATE_T, 0, st));
     {
-      GemmArgs g = krot(gemm_conv(c->hid_a, M, La, Hc, 3, 1, w.w2, c->audio, D));
+      GemmArgs g = krot(gemm_conv(c->buf.hid_a, M, La, Hc, 3, 1, w.w2, c->buf.audio, D));
       g.rb = sm(5);
-      with_partials(g, c->part_a);
+      with_partials(g, c->buf.part_a);
       int ks = 1;
       PROF("single.w2 conv3 GEMM (gated residual)", gf(M, D, 3 * Hc), gb(M, D, 3 * Hc, 4), launch_gemm(g, T, EPI_GATE_RES, 0, st, &ks));
-      if (ks > 1) pend[0] = LnPending{c->part_a, ks, g.partial_stride, w.w2.b, g.rb, slab_half};
+      if (ks > 1) pend[0] = LnPending{c->buf.part_a, ks, g.partial_stride, w.w2.b, g.rb, slab_half};
     }
   }
 
   // FinalLayer1D: adaLN is a no-op with 3-D conditioning => linear(LayerNorm(x))
   {
     PROF("final.layernorm", 0.0, ln_bytes_s,
-         launch_ln_mod_pending(c->audio, M, D, 1e-6f, rb_none(), rb_none(), c->xn_a, T, pend[0], st));
-    PROF("final.linear", gf(M, C, D), gb(M, C, D, 4), launch_gemm(krot(gemm_plain(c->xn_a, M, W.fin, c->pred, C)), T, EPI_STORE_F32, 0, st));
+         launch_ln_mod_pending(c->buf.audio, M, D, 1e-6f, rb_none(), rb_none(), c->buf.xn_a, T, pend[0], st));
+    PROF("final.linear", gf(M, C, D), gb(M, C, D, 4), launch_gemm(krot(gemm_plain(c->buf.xn_a, M, W.fin, c->buf.pred, C)), T, EPI_STORE_F32, 0, st));
   }
   return 0;
 }
 
-extern "C" int foley_dit_forward(foley_ctx* c, const float* latents, int iter, float* out_rows, void* stream_v) {
-  if (!c || !latents || !out_rows) return FAIL(FOLEY_ERR_INVALID, "null argument");
+// One eager forward of `latents` at loop iteration `iter` (foley_dit_forward, foley_profile_forward): the prediction is in buf.pred
+static int forward_at(foley_ctx* c, const float* latents, int iter, hipStream_t st) {
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_prepare has not been called");
   if (iter < 0 || iter >= c->plan.n_iter) return FAIL(FOLEY_ERR_INVALID, "iteration out of range");
-  hipStream_t st = (hipStream_t)stream_v;
   HIPTRY(hipSetDevice(c->device));
   const foley_plan& pl = c->plan;
-  const int C = c->cfg.latent_dim;
-  HIPTRY(hipMemcpyAsync(c->step_ctr, &iter, sizeof(int), hipMemcpyHostToDevice, st));
+  HIPTRY(hipMemcpyAsync(c->buf.step_ctr, &iter, sizeof(int), hipMemcpyHostToDevice, st));
   HIPTRY(hipStreamSynchronize(st));  // `iter` lives on the caller's stack
-  TRY(launch_latent_rows(latents, pl.clips, C, pl.La, pl.ncfg, c->xin, c->cfg.compute_dtype, st));
-  TRY(run_forward(c, st));
-  HIPTRY(hipMemcpyAsync(out_rows, c->pred, (size_t)pl.ncfg * pl.clips * pl.La * C * 4, hipMemcpyDeviceToDevice, st));
+  TRY(launch_latent_rows(latents, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->buf.xin, c->cfg.compute_dtype, st));
+  return run_forward(c, st);
+}
+
+extern "C" int foley_dit_forward(foley_ctx* c, const float* latents, int iter, float* out_rows, void* stream_v) {
+  if (!c || !latents || !out_rows) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream_v;
+  TRY(forward_at(c, latents, iter, st));
+  const foley_plan& pl = c->plan;
+  HIPTRY(hipMemcpyAsync(out_rows, c->buf.pred, (size_t)pl.ncfg * pl.clips * pl.La * c->cfg.latent_dim * 4, hipMemcpyDeviceToDevice, st));
   return 0;
 }
 
@@ -1113,15 +1135,8 @@ extern "C" int foley_dit_forward(foley_ctx* c, const float* latents, int iter, f
 extern "C" int foley_profile_forward(foley_ctx* c, const float* latents, int iter, int repeats, foley_prof_entry* out,
                                      int cap, int* n_out, float* bracket_ms, void* stream_v) {
   if (!c || !latents || !out || !n_out || cap < 1 || repeats < 1) return FAIL(FOLEY_ERR_INVALID, "bad argument");
-  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_prepare has not been called");
-  if (iter < 0 || iter >= c->plan.n_iter) return FAIL(FOLEY_ERR_INVALID, "iteration out of range");
   hipStream_t st = (hipStream_t)stream_v;
-  HIPTRY(hipSetDevice(c->device));
-  const foley_plan& pl = c->plan;
-  HIPTRY(hipMemcpyAsync(c->step_ctr, &iter, sizeof(int), hipMemcpyHostToDevice, st));
-  HIPTRY(hipStreamSynchronize(st));
-  TRY(launch_latent_rows(latents, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->xin, c->cfg.compute_dtype, st));
-  TRY(run_forward(c, st));   // warm: code objects loaded, caches in their steady state
+  TRY(forward_at(c, latents, iter, st));   // warm: code objects loaded, caches in their steady state
   c->prof.recs.clear();
   c->prof.used = 0;
   c->prof.on = true;
@@ -1182,10 +1197,10 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
   const foley_plan& pl = c->plan;
   TRY(run_forward(c, st));
   StepArgs s{};
-  s.pred = c->pred; s.x = c->x_cur; s.x_saved = c->x_saved; s.d_acc = c->d_acc;
+  s.pred = c->buf.pred; s.x = c->buf.x_cur; s.x_saved = c->buf.x_saved; s.d_acc = c->buf.d_acc;
   s.clips = pl.clips; s.C = c->cfg.latent_dim; s.L = pl.La; s.ncfg = pl.ncfg;
-  s.guidance = pl.guidance; s.coef = pl.solver_coef; s.step_ptr = c->step_ctr;
-  s.rows_out = c->xin; s.rows_dtype = c->cfg.compute_dtype;
+  s.guidance = pl.guidance; s.coef = pl.solver_coef; s.step_ptr = c->buf.step_ctr;
+  s.rows_out = c->buf.xin; s.rows_dtype = c->cfg.compute_dtype;
   if (c->edit) {
     StepEditArgs e{};
     e.s = s;
@@ -1197,12 +1212,18 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
   return launch_solver_step(s, st);
 }
 
-// What a captured iteration depends on beyond the plan: plain vs edit, and the clip strides / presence of the edit operands
-// (their addresses are ctx-owned; foley_set_edit drops the graph when one moves).  A plain graph replayed for an edit run
-// would skip the blend, an edit graph replayed for a plain run would apply a stale one.
+// Plain vs edit iteration, and the clip strides / presence of the edit operands.  A plain graph replayed for an edit run would
+// skip the blend, an edit graph replayed for a plain run would apply a stale one.
 static int edit_key(const foley_ctx* c) {
   if (!c->edit) return 0;
   return 1 | (c->edit_x0_clips == 1 ? 2 : 0) | (c->edit_mask_clips ? 4 : 0) | (c->edit_mask_clips == 1 ? 8 : 0);
+}
+
+// The key of an iteration captured now (in GraphKey's member order).  The set maps are part of it for safety, not layout: the
+// tables a replay reads are rewritten in place.  The edit operands are ctx-owned copies, so their addresses stand for them.
+static GraphKey graph_key_now(const foley_ctx* c) {
+  return GraphKey{c->plan.guidance, edit_key(c), c->set_maps,   c->layout,     c->smod_tab.p,
+                  c->edit_x0.p,     c->edit_noise.p, c->edit_mask.p, c->tensor_gen, c->plan_gen};
 }
 
 extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const float* noise, const float* mask, int mask_clips,
@@ -1223,11 +1244,9 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
   HIPTRY(hipSetDevice(c->device));
   HIPTRY(hipStreamSynchronize(st));   // the buffers may be in use by a previous loop on this stream
   const size_t plane = (size_t)c->cfg.latent_dim * pl.La * 4;
-  const void* old[3] = {c->edit_x0.p, c->edit_noise.p, c->edit_mask.p};
   TRY(grow(c->edit_x0, (size_t)x0_clips * plane));
   TRY(grow(c->edit_noise, (size_t)pl.clips * plane));
   if (mask) TRY(grow(c->edit_mask, (size_t)mask_clips * pl.La * 4));
-  if (old[0] != c->edit_x0.p || old[1] != c->edit_noise.p || old[2] != c->edit_mask.p) ctx_drop_graph(c);
   HIPTRY(hipMemcpyAsync(c->edit_x0.p, x0, (size_t)x0_clips * plane, hipMemcpyDeviceToDevice, st));
   HIPTRY(hipMemcpyAsync(c->edit_noise.p, noise, (size_t)pl.clips * plane, hipMemcpyDeviceToDevice, st));
   if (mask) HIPTRY(hipMemcpyAsync(c->edit_mask.p, mask, (size_t)mask_clips * pl.La * 4, hipMemcpyDeviceToDevice, st));
@@ -1245,7 +1264,8 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   HIPTRY(hipSetDevice(c->device));
   const foley_plan& pl = c->plan;
   const size_t xbytes = (size_t)pl.clips * c->cfg.latent_dim * pl.La * 4;
-  if (c->graph_exec && c->graph_key != edit_key(c)) ctx_drop_graph(c);
+  GraphKey key = graph_key_now(c);
+  if (c->graph_exec && !(c->graph_key == key)) ctx_drop_graph(c);
   if (use_graph && !c->graph_exec) {
     // Every per-iteration value is read from device memory (step counter, tables) and every
     // buffer is context-owned, so ONE captured iteration replays for the whole loop and for
@@ -1267,31 +1287,30 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
     (void)hipStreamDestroy(cs);
     if (rc != 0) return rc;
     if (e != hipSuccess) return FAIL(FOLEY_ERR_HIP, hipGetErrorString(e));
-    c->graph_guidance = pl.guidance;
-    c->graph_key = edit_key(c);
+    c->graph_key = std::move(key);
   }
   c->abort_req.store(0, std::memory_order_relaxed);   // a request left over from before this loop is not for it
   HIPTRY(hipEventRecord(c->ev0, st));
-  HIPTRY(hipMemcpyAsync(c->x_cur, latents, xbytes, hipMemcpyDeviceToDevice, st));
-  HIPTRY(hipMemsetAsync(c->step_ctr, 0, sizeof(int), st));
-  TRY(launch_latent_rows(c->x_cur, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->xin, c->cfg.compute_dtype, st));
+  HIPTRY(hipMemcpyAsync(c->buf.x_cur, latents, xbytes, hipMemcpyDeviceToDevice, st));
+  HIPTRY(hipMemsetAsync(c->buf.step_ctr, 0, sizeof(int), st));
+  TRY(launch_latent_rows(c->buf.x_cur, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->buf.xin, c->cfg.compute_dtype, st));
   for (int it = 0; it < pl.n_iter; ++it) {
     if (use_graph) HIPTRY(hipGraphLaunch(c->graph_exec, st));
     else TRY(run_iteration(c, st));
     if (cb) {
-      HIPTRY(hipMemcpyAsync(latents, c->x_cur, xbytes, hipMemcpyDeviceToDevice, st));
+      HIPTRY(hipMemcpyAsync(latents, c->buf.x_cur, xbytes, hipMemcpyDeviceToDevice, st));
       HIPTRY(hipStreamSynchronize(st));
       cb(it + 1, pl.n_iter, user);
     }
     if (c->abort_req.exchange(0, std::memory_order_acq_rel)) {   // latents hold the state after iteration it + 1
       if (!cb) {
-        HIPTRY(hipMemcpyAsync(latents, c->x_cur, xbytes, hipMemcpyDeviceToDevice, st));
+        HIPTRY(hipMemcpyAsync(latents, c->buf.x_cur, xbytes, hipMemcpyDeviceToDevice, st));
         HIPTRY(hipStreamSynchronize(st));
       }
       return FAIL(FOLEY_ERR_ABORTED, "sampling loop aborted by foley_abort()");
     }
   }
-  HIPTRY(hipMemcpyAsync(latents, c->x_cur, xbytes, hipMemcpyDeviceToDevice, st));
+  HIPTRY(hipMemcpyAsync(latents, c->buf.x_cur, xbytes, hipMemcpyDeviceToDevice, st));
   HIPTRY(hipEventRecord(c->ev1, st));
   c->timed = true;
   return 0;
@@ -1307,6 +1326,34 @@ extern "C" int foley_abort(foley_ctx* c) {
 // Activations are kept time-major [clip, T, C] so that every conv is a GEMM over contiguous
 // channel vectors; weight-norm is folded at pack time; each snake is evaluated once, in the
 // epilogue of the op that produces its input.  (dac.py:28-44, 98-149, 280-303)
+// activation buffers of `act_bytes` each and the latent-rate scratch, grown while nothing on `st` reads them
+static int dac_grow(foley_ctx* c, size_t act_bytes, size_t z_bytes, hipStream_t st) {
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  HIPTRY(hipStreamSynchronize(st));
+  TRY(grow(c->dacP, act_bytes));
+  TRY(grow(c->dacQ, act_bytes));
+  TRY(grow(c->dacR, act_bytes));
+  return grow(c->dacZ, z_bytes);
+}
+
+// Residual unit `u` (dac.py:28-44) over `clips` segments of T rows, C channels: conv7 of dilation d with its snake (S_in -> S_alt),
+// then the 1x1 with the residual add into the trunk X and the snake of whatever consumes the unit's output next (-> S_in)
+static int dac_res_unit(foley_ctx* c, const std::string& u, const std::string& next_alpha, int clips, int T, int C, int d,
+                        float* S_in, float* S_alt, float* X, hipStream_t st) {
+  Lin c7, c1;
+  const void *a2, *an;
+  TRY(get_lin(c, u + "c7", FOLEY_F32, C, 7 * C, true, &c7));
+  TRY(get_lin(c, u + "c1", FOLEY_F32, C, C, true, &c1));
+  TRY(get_tensor(c, u + "a2", FOLEY_F32, {C}, &a2));
+  TRY(get_tensor(c, next_alpha, FOLEY_F32, {C}, &an));
+  GemmArgs g = gemm_conv(S_in, clips * T, T, C, 7, d, c7, nullptr, C);
+  g.out1 = S_alt; g.alpha = (const float*)a2; g.alphaC = C;
+  TRY(launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st));
+  g = gemm_plain(S_alt, clips * T, c1, X, C);
+  g.res = X; g.out1 = S_in; g.alpha = (const float*)an; g.alphaC = C;
+  return launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st);
+}
+
 extern "C" int foley_dac_decode(foley_ctx* c, const float* latents, int clips, int T, float* wave, void* stream_v) {
   if (!c || !latents || !wave || clips < 1 || T < 1) return FAIL(FOLEY_ERR_INVALID, "bad argument");
   hipStream_t st = (hipStream_t)stream_v;
@@ -1315,26 +1362,15 @@ extern "C" int foley_dac_decode(foley_ctx* c, const float* latents, int clips, i
   const int L = f.latent_dim, NR = f.dac_n_rates;
   // largest activation
   size_t maxel = (size_t)T * f.dac_dim;
-  {
-    long t = T;
-    int ch = f.dac_dim;
-    for (int i = 0; i < NR; ++i) {
-      t *= f.dac_rates[i];
-      ch /= 2;
-      maxel = std::max(maxel, (size_t)t * ch);
-    }
+  for (long i = 0, t = T, ch = f.dac_dim; i < NR; ++i) {
+    t *= f.dac_rates[i];
+    ch /= 2;
+    maxel = std::max(maxel, (size_t)t * ch);
   }
-  {
-    std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
-    HIPTRY(hipStreamSynchronize(st));
-    TRY(grow(c->dacP, maxel * clips * 4));
-    TRY(grow(c->dacQ, maxel * clips * 4));
-    TRY(grow(c->dacR, maxel * clips * 4));
-    TRY(grow(c->dacZ, (size_t)clips * T * L * 4 * 2));
-  }
-  float *P = (float*)c->dacP.p, *Q = (float*)c->dacQ.p, *R = (float*)c->dacR.p;
-  float* Z0 = (float*)c->dacZ.p;
-  float* Z1 = Z0 + (size_t)clips * T * L;
+  TRY(dac_grow(c, maxel * clips * 4, (size_t)clips * T * L * 4 * 2, st));
+  // snake-activated input of the next op, residual trunk, the other snake buffer
+  float *S_in = (float*)c->dacP.p, *X = (float*)c->dacQ.p, *S_alt = (float*)c->dacR.p;
+  float *Z0 = (float*)c->dacZ.p, *Z1 = Z0 + (size_t)clips * T * L;
   HIPTRY(hipEventRecord(c->ev0, st));
 
   TRY(launch_latent_rows(latents, clips, L, T, 1, Z0, FOLEY_F32, st));
@@ -1346,12 +1382,9 @@ extern "C" int foley_dac_decode(foley_ctx* c, const float* latents, int clips, i
   TRY(get_tensor(c, "dac.0.alpha0", FOLEY_F32, {f.dac_dim}, &al));
   {
     GemmArgs g = gemm_conv(Z1, clips * T, T, L, 7, 1, cin, nullptr, f.dac_dim);
-    g.out1 = P; g.alpha = (const float*)al; g.alphaC = f.dac_dim;
+    g.out1 = S_in; g.alpha = (const float*)al; g.alphaC = f.dac_dim;
     TRY(launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st));
   }
-  float* S_in = P;   // snake-activated input of the next op
-  float* X = Q;      // residual trunk
-  float* S_alt = R;  // the other snake buffer
   int Tin = T, Cin = f.dac_dim;
   for (int i = 0; i < NR; ++i) {
     const int s = f.dac_rates[i], Cout = Cin / 2, Tout = Tin * s, pad = (s + 1) / 2;
@@ -1372,27 +1405,10 @@ extern "C" int foley_dac_decode(foley_ctx* c, const float* latents, int clips, i
     }
     std::swap(S_in, S_alt);  // S_in now holds snake(x) for unit 0
     for (int j = 0; j < 3; ++j) {
-      const int d = f.dac_dilations[j];
-      const std::string u = p + std::to_string(j) + ".";
-      Lin c7, c1;
-      const void *a2, *an;
-      TRY(get_lin(c, u + "c7", FOLEY_F32, Cout, 7 * Cout, true, &c7));
-      TRY(get_lin(c, u + "c1", FOLEY_F32, Cout, Cout, true, &c1));
-      TRY(get_tensor(c, u + "a2", FOLEY_F32, {Cout}, &a2));
       // alpha of whatever consumes this unit's output next
       std::string nxt = (j < 2) ? p + std::to_string(j + 1) + ".a1"
                                 : (i + 1 < NR ? "dac." + std::to_string(i + 1) + ".alpha0" : std::string("dac.out.alpha"));
-      TRY(get_tensor(c, nxt, FOLEY_F32, {Cout}, &an));
-      {
-        GemmArgs g = gemm_conv(S_in, clips * Tout, Tout, Cout, 7, d, c7, nullptr, Cout);
-        g.out1 = S_alt; g.alpha = (const float*)a2; g.alphaC = Cout;
-        TRY(launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st));
-      }
-      {
-        GemmArgs g = gemm_plain(S_alt, clips * Tout, c1, X, Cout);
-        g.res = X; g.out1 = S_in; g.alpha = (const float*)an; g.alphaC = Cout;
-        TRY(launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st));
-      }
+      TRY(dac_res_unit(c, p + std::to_string(j) + ".", nxt, clips, Tout, Cout, f.dac_dilations[j], S_in, S_alt, X, st));
     }
     Tin = Tout;
     Cin = Cout;
@@ -1424,26 +1440,14 @@ extern "C" int foley_dac_encode(foley_ctx* c, const float* wave, int clips, int 
   const foley_config& f = c->cfg;
   const int L = f.latent_dim;
   size_t maxel = 0;
-  {
-    long t = T;
-    int ch = enc_dim;
-    for (int i = 0; i <= n_rates; ++i) {
-      maxel = std::max(maxel, (size_t)t * ch);
-      if (i < n_rates) { t /= rates[i]; ch *= 2; }
-    }
+  for (long i = 0, t = T, ch = enc_dim; i <= n_rates; ++i) {
+    maxel = std::max(maxel, (size_t)t * ch);
+    if (i < n_rates) { t /= rates[i]; ch *= 2; }
   }
   const int Tz = (int)(T / hop);
-  {
-    std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
-    HIPTRY(hipStreamSynchronize(st));
-    TRY(grow(c->dacP, maxel * clips * 4));
-    TRY(grow(c->dacQ, maxel * clips * 4));
-    TRY(grow(c->dacR, maxel * clips * 4));
-    TRY(grow(c->dacZ, (size_t)clips * Tz * L * 4 * 3));
-  }
+  TRY(dac_grow(c, maxel * clips * 4, (size_t)clips * Tz * L * 4 * 3, st));
   float *S_in = (float*)c->dacP.p, *X = (float*)c->dacQ.p, *S_alt = (float*)c->dacR.p;
-  float* Z0 = (float*)c->dacZ.p;
-  float* Z1 = Z0 + (size_t)clips * Tz * L;
+  float *Z0 = (float*)c->dacZ.p, *Z1 = Z0 + (size_t)clips * Tz * L;
   HIPTRY(hipEventRecord(c->ev0, st));
 
   int Tin = T, C = enc_dim;
@@ -1458,25 +1462,9 @@ extern "C" int foley_dac_encode(foley_ctx* c, const float* wave, int clips, int 
     const int s = rates[i], Cout = 2 * C, Tout = Tin / s, pad = (s + 1) / 2;
     const std::string p = "enc." + std::to_string(i) + ".";
     for (int j = 0; j < 3; ++j) {
-      const int d = f.dac_dilations[j];
-      const std::string u = p + std::to_string(j) + ".";
-      Lin c7, c1;
-      const void *a2, *an;
-      TRY(get_lin(c, u + "c7", FOLEY_F32, C, 7 * C, true, &c7));
-      TRY(get_lin(c, u + "c1", FOLEY_F32, C, C, true, &c1));
-      TRY(get_tensor(c, u + "a2", FOLEY_F32, {C}, &a2));
       // alpha of whatever consumes this unit's output next: the next unit, or the snake before the strided conv
-      TRY(get_tensor(c, j < 2 ? p + std::to_string(j + 1) + ".a1" : p + "alpha", FOLEY_F32, {C}, &an));
-      {
-        GemmArgs g = gemm_conv(S_in, clips * Tin, Tin, C, 7, d, c7, nullptr, C);
-        g.out1 = S_alt; g.alpha = (const float*)a2; g.alphaC = C;
-        TRY(launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st));
-      }
-      {
-        GemmArgs g = gemm_plain(S_alt, clips * Tin, c1, X, C);
-        g.res = X; g.out1 = S_in; g.alpha = (const float*)an; g.alphaC = C;
-        TRY(launch_gemm(g, FOLEY_F32, EPI_DAC, 0, st));
-      }
+      TRY(dac_res_unit(c, p + std::to_string(j) + ".", j < 2 ? p + std::to_string(j + 1) + ".a1" : p + "alpha", clips, Tin, C,
+                       f.dac_dilations[j], S_in, S_alt, X, st));
     }
     {
       // strided conv: output row q of a clip reads source rows q*s - pad + j, j < 2s  (dac.py:55-61)

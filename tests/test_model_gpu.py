@@ -956,8 +956,9 @@ def test_interrupt_from_the_progress_callback(tiny):
 
 
 def test_zero_depth_single_joins_side_stream(dev):
-    """depth_single == 0: the side stream forked by the forward must still be joined (graph capture
-    would fail otherwise, eager mode would race) - ADVICE r1."""
+    """depth_single == 0: the forward has no single-stream blocks and skips their modulation GEMM (it runs in line on the
+    caller's stream; an early version forked a side stream for it, which had to be joined here too): a captured loop equals
+    the eager one bit for bit and both match the oracle."""
     c = C.DiTConfig(name="triple-only", depth_triple=1, depth_single=0, hidden=256, heads=2)
     sd = synth.synth_dit_state_dict(c)
     model = sampler.FoleyModel(c, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
@@ -977,6 +978,55 @@ def test_zero_depth_single_joins_side_stream(dev):
         ref = O.sample_latents(sd, c.heads, noise, cond["text"], cond["uncond_text"], cond["clip"], cond["sync"], 4, 4.5,
                                "euler")
     assert rel_err(outs[0], ref) < 1e-4
+
+
+def _graph_vs_eager(model, dac, cond, dur, noise):
+    """(graph, eager) latents of one 6-step CFG run of `cond` on the shared context."""
+    vis = {"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}
+    txt = {"text_feat": cond["text"], "uncond_text_feat": cond["uncond_text"]}
+    return [sampler.denoise_process_with_generator(vis, txt, dur, model, dac, 4.5, 6, 1, "euler", noise=noise, use_graph=g,
+                                                   return_latents=True)[2].cpu().clone() for g in (True, False)]
+
+
+def test_graph_replay_across_text_and_video_at_one_shape(tiny):
+    """One context, use_graph=True, one shape (2 s, CFG 4.5): text-to-audio -> video -> text-to-audio -> video.  The two differ
+    in what the captured iteration launches - text-to-audio has both halves' sync tokens 8-periodic and reads the modulation
+    table foley_prepare hoisted, a video clip has one periodic and one dense half and runs the modulation GEMM in the loop -
+    so a replay of the other one's graph would be wrong.  Every graph run equals the eager run of the same inputs bit for
+    bit, and the second round equals the first bit for bit."""
+    sd, _dsd, model, dac = tiny
+    dur = 2.0
+    noise = torch.randn(1, 128, int(dur * 50), generator=torch.Generator().manual_seed(21))
+    conds = [synth.synth_conditioning(C.TINY, dur, t2a=t2a, sd=sd) for t2a in (True, False)]
+    first = {}
+    for k in (0, 1, 0, 1):
+        got, want = _graph_vs_eager(model, dac, conds[k], dur, noise)
+        assert torch.equal(got, want) and bool(torch.isfinite(got).all()), k
+        assert torch.equal(got, first.setdefault(k, got)), k
+    assert rel_err(first[0], first[1]) > 1e-2
+
+
+def test_graph_replay_after_weight_reregistration(tiny):
+    """One context, use_graph=True, one plan: the final projection's weight registered at its own address -> a scaled copy at
+    another address -> the first again -> the copy again.  The captured kernels hold the address that was registered at
+    capture, so each move must end in a new capture: every graph run equals the eager run under the same registration bit
+    for bit, the second round equals the first, and the two weights give different latents."""
+    sd, _dsd, model, dac = tiny
+    cond = synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd)
+    noise = torch.randn(1, 128, 50, generator=torch.Generator().manual_seed(22))
+    w0 = model.ctx._keep["final.w"]
+    weights = [w0, (0.5 * w0).contiguous()]
+    assert weights[1].data_ptr() != w0.data_ptr()
+    first = {}
+    try:
+        for k in (0, 1, 0, 1):
+            model.ctx.set_tensor("final.w", weights[k])
+            got, want = _graph_vs_eager(model, dac, cond, 1.0, noise)
+            assert torch.equal(got, want) and bool(torch.isfinite(got).all()), k
+            assert torch.equal(got, first.setdefault(k, got)), k
+    finally:
+        model.ctx.set_tensor("final.w", w0)
+    assert rel_err(first[0], first[1]) > 1e-2
 
 
 def test_profile_forward_brackets(tiny):
