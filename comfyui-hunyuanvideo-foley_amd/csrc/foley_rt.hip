@@ -194,12 +194,14 @@ struct GraphKey {
   RunLayout layout;
   const void* smod_tab = nullptr;   // the hoisted table (null: the per-iteration GEMM)
   const void *edit_x0 = nullptr, *edit_noise = nullptr, *edit_mask = nullptr;
+  int n_win = 0, Ltot = 0;          // windows state (foley_set_windows; 0: none): the step kernel and its grid
+  const void *win_starts = nullptr, *win_weights = nullptr;
   uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
   uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
   bool operator==(const GraphKey& o) const {
     return guidance == o.guidance && edit == o.edit && set_maps == o.set_maps && layout == o.layout && smod_tab == o.smod_tab &&
-           edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && tensor_gen == o.tensor_gen &&
-           plan_gen == o.plan_gen;
+           edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && n_win == o.n_win && Ltot == o.Ltot &&
+           win_starts == o.win_starts && win_weights == o.win_weights && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
   }
 };
 
@@ -227,6 +229,10 @@ struct foley_ctx {
   bool edit = false;
   DevBuf edit_x0, edit_noise, edit_mask;
   int edit_x0_clips = 1, edit_mask_clips = 0;   // mask clips 0: no mask (all ones)
+  // windows state (foley_set_windows; cleared by foley_prepare): ctx-owned copies of the starts and the blend weights
+  int n_win = 0, win_Ltot = 0;      // n_win 0: the clips are independent
+  DevBuf win_starts, win_weights;
+  std::vector<int32_t> win_starts_host;   // the source of the asynchronous copy stays alive with the context
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -431,7 +437,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   ctx_free_plan(c);
-  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask}) release(*b);
+  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights}) release(*b);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   for (auto e : c->prof.pool) hipEventDestroy(e);
@@ -574,6 +580,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   if (!reuse) ctx_free_plan(c);
   c->prepared = false;
   c->edit = false;                  // a plan without foley_set_edit is a plain run
+  c->n_win = 0;                     // and one without foley_set_windows has independent clips
   RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
   c->vis_src = n_vis;
   const int th = ly.th, vh = ly.vh;
@@ -1209,6 +1216,13 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
     e.x0_clips = c->edit_x0_clips; e.mask_clips = c->edit_mask_clips;
     return launch_solver_step_edit(e, st);
   }
+  if (c->n_win) {
+    StepWinArgs w{};
+    w.s = s;
+    w.n_win = c->n_win; w.Ltot = c->win_Ltot;
+    w.starts = (const int*)c->win_starts.p; w.weights = (const float*)c->win_weights.p;
+    return launch_solver_step_windows(w, st);
+  }
   return launch_solver_step(s, st);
 }
 
@@ -1220,10 +1234,14 @@ static int edit_key(const foley_ctx* c) {
 }
 
 // The key of an iteration captured now (in GraphKey's member order).  The set maps are part of it for safety, not layout: the
-// tables a replay reads are rewritten in place.  The edit operands are ctx-owned copies, so their addresses stand for them.
+// tables a replay reads are rewritten in place.  The edit operands are ctx-owned copies, so their addresses stand for them; so do
+// those of the windows tables (new starts with the same n_win and total length only rewrite what a replay reads).
 static GraphKey graph_key_now(const foley_ctx* c) {
+  const bool win = c->n_win > 0;
   return GraphKey{c->plan.guidance, edit_key(c), c->set_maps,   c->layout,     c->smod_tab.p,
-                  c->edit_x0.p,     c->edit_noise.p, c->edit_mask.p, c->tensor_gen, c->plan_gen};
+                  c->edit_x0.p,     c->edit_noise.p, c->edit_mask.p,
+                  c->n_win,         win ? c->win_Ltot : 0, win ? c->win_starts.p : nullptr, win ? c->win_weights.p : nullptr,
+                  c->tensor_gen,    c->plan_gen};
 }
 
 extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const float* noise, const float* mask, int mask_clips,
@@ -1235,6 +1253,7 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
     return 0;
   }
   if (!x0 || !noise) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0 and noise are required (all three null clears the edit state)");
+  if (c->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: the run has windows (foley_set_windows); editing a long clip is not supported");
   const foley_plan& pl = c->plan;
   if (x0_clips != 1 && x0_clips != pl.clips) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0_clips must be 1 or the plan's clips");
   if (mask && mask_clips != 1 && mask_clips != pl.clips)
@@ -1253,6 +1272,36 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
   c->edit = true;
   c->edit_x0_clips = x0_clips;
   c->edit_mask_clips = mask ? mask_clips : 0;
+  return 0;
+}
+
+extern "C" int foley_set_windows(foley_ctx* c, int n_win, const int32_t* starts, const float* weights, void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_windows: foley_prepare has not been called");
+  if (n_win <= 1 || !starts || !weights) {
+    c->n_win = 0;
+    return 0;
+  }
+  if (c->edit) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the run is an edit run (foley_set_edit); editing a long clip is not supported");
+  const foley_plan& pl = c->plan;
+  if (pl.clips % n_win != 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the plan's clips must be a multiple of n_win");
+  if (starts[0] != 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: starts[0] must be 0");
+  for (int k = 1; k < n_win; ++k) {
+    if (starts[k] <= starts[k - 1]) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: starts must ascend from 0");
+    if (starts[k] > starts[k - 1] + pl.La) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: gap between consecutive windows");
+  }
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the tables may be in use by a previous loop on this stream
+  TRY(grow(c->win_starts, (size_t)n_win * 4));
+  TRY(grow(c->win_weights, (size_t)n_win * pl.La * 4));
+  c->win_starts_host.assign(starts, starts + n_win);
+  HIPTRY(hipMemcpyAsync(c->win_starts.p, c->win_starts_host.data(), (size_t)n_win * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipMemcpyAsync(c->win_weights.p, weights, (size_t)n_win * pl.La * 4, hipMemcpyDeviceToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));   // win_starts_host may be rewritten by the next call
+  c->n_win = n_win;
+  c->win_Ltot = starts[n_win - 1] + pl.La;
   return 0;
 }
 
@@ -1728,6 +1777,21 @@ extern "C" int foley_op_solver_step_edit(const float* pred, float* x, float* x_s
   e.s = StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
   e.x0 = x0; e.noise = noise; e.mask = mask; e.x0_clips = x0_clips; e.mask_clips = mask_clips;
   return launch_solver_step_edit(e, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_solver_step_windows(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
+                                            int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
+                                            int rows_dtype, int n_win, const int32_t* starts, const float* weights, int Ltot,
+                                            void* stream) {
+  StepWinArgs w{};
+  w.s = StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
+  w.n_win = n_win; w.Ltot = Ltot; w.starts = starts; w.weights = weights;
+  return launch_solver_step_windows(w, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int32_t* starts,
+                                       const float* weights, float* out, void* stream) {
+  return launch_windows_stitch(x, clips, n_win, C, L, Ltot, starts, weights, out, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma,

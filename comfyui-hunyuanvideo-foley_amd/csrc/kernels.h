@@ -226,6 +226,19 @@ struct StepEditArgs {
   int x0_clips, mask_clips;
 };
 int launch_solver_step_edit(const StepEditArgs& a, hipStream_t st);
+// Windows form of the same step (long clips): clip v*n_win + k is window k of variation v and covers the global frames
+// [starts[k], starts[k] + L); after a row flagged STEP_BLEND every frame is replaced in all the windows that cover it by
+// sum_k weights[k][g - starts[k]] * x_k (fp32, window order), and their next input rows are staged from that value.
+struct StepWinArgs {
+  StepArgs s;            // s.clips = variations * n_win, s.L = frames per window
+  int n_win, Ltot;       // Ltot = starts[n_win - 1] + L
+  const int* starts;     // [n_win] device, ascending from 0
+  const float* weights;  // [n_win, L] device; the weights of every global frame sum to 1, a singly covered frame has 1.0f
+};
+int launch_solver_step_windows(const StepWinArgs& w, hipStream_t st);
+// x [variations*n_win, C, L] -> out [variations, C, Ltot]: the same weighted mean (windows that agree on a frame: that value as it is)
+int launch_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int* starts, const float* weights,
+                          float* out, hipStream_t st);
 // out [clips, C, L] = sigma*noise + (1-sigma)*x0 (x0 clip stride 0 when x0_clips == 1): the flow-match path's start state
 int launch_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma, float* out,
                     hipStream_t st);

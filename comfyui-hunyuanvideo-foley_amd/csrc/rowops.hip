@@ -590,6 +590,145 @@ __global__ __launch_bounds__(256) void solver_step_edit_kernel(const StepEditArg
   }
 }
 
+// Windows form (long clips): the clips of one variation are overlapping windows of ONE long clip - clip v*n_win + k covers the
+// global frames [starts[k], starts[k] + L) of variation v - and the step is indexed by GLOBAL frame: a thread owns (g, c) and
+// does, for every window that covers g, that element's plain update (the expressions of solver_step_kernel).  On rows flagged
+// STEP_BLEND (the iterations that end a solver step) the covering windows' new values are replaced in all of them by
+//   xb = sum_k weights[k][g - starts[k]] * xn_k      (fp32, in window order; the weights of a frame sum to 1)
+// and the next model input rows of every covering window are staged from xb.  A frame that one window covers has weight 1.0f
+// and a single term: it keeps its xn bit for bit.  Rows without the flag (intermediate stages) leave every window its own xn.
+// Every (clip, c, l) element belongs to exactly one thread, so no window reads what another thread wrote.  Any table of starts is
+// memory-safe: all accesses are indexed by (clip < clips, c < C, 0 <= l < L).
+template <typename OutT>
+__global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinArgs w) {
+  __shared__ float tile[32][33];
+  const StepArgs& a = w.s;
+  const int it = *a.step_ptr;
+  const float* cf = a.coef + (long)it * 8;
+  const float w_new = cf[0], w_acc = cf[1], dt = cf[2], w_store = cf[3];
+  const int flags = (int)cf[4];
+  const bool blend = (flags & STEP_BLEND) != 0;
+  const int b0 = blockIdx.z * w.n_win;
+  const int g0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const long rows = (long)a.clips * a.L;
+  float xb[4] = {0.f, 0.f, 0.f, 0.f};
+  int ncov = 0;
+  for (int k = 0; k < w.n_win; ++k) {
+    const int s0 = w.starts[k];
+    if (s0 >= g0 + 32 || s0 + a.L <= g0) continue;   // the window misses this tile (uniform over the block)
+    const int b = b0 + k;
+    // phase 1: read pred rows [l][c] (coalesced over c) and transpose through LDS
+    for (int i = ty; i < 32; i += 8) {
+      const int l = g0 + i - s0, c = c0 + tx;
+      float v = 0.f;
+      if (l >= 0 && l < a.L && c < a.C) {
+        const long r = (long)b * a.L + l;
+        if (a.ncfg == 2) {
+          const float u = a.pred[r * a.C + c], cnd = a.pred[(rows + r) * a.C + c];
+          v = u + a.guidance * (cnd - u);
+        } else {
+          v = a.pred[r * a.C + c];
+        }
+      }
+      tile[i][tx] = v;
+    }
+    __syncthreads();
+    // phase 2: update x [b][c][l] (coalesced over l)
+    const int l = g0 + tx - s0;
+    const bool in = l >= 0 && l < a.L;
+    const float wk = (in && blend) ? w.weights[(long)k * a.L + l] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = ty + 8 * j;
+      const int c = c0 + i;
+      float xn = 0.f;
+      if (c < a.C && in) {
+        const long xi = ((long)b * a.C + c) * a.L + l;
+        const float v = tile[tx][i];
+        const float xc = a.x[xi];
+        float acc = 0.f;
+        if (a.d_acc) acc = (flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
+        const float deriv = (w_acc != 0.f) ? (w_new * v + w_acc * acc) : (w_new * v);
+        const float base = (flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
+        if (flags & STEP_SAVE_X) a.x_saved[xi] = xc;
+        xn = base + deriv * dt;
+        if (blend) xb[j] = (ncov == 0) ? wk * xn : xb[j] + wk * xn;
+        else a.x[xi] = xn;
+        if (a.d_acc) a.d_acc[xi] = acc + w_store * v;
+      }
+      if (!blend) tile[tx][i] = xn;
+    }
+    if (in) ++ncov;
+    __syncthreads();
+    // phase 3 (no blend): this window's next model input rows from its own xn
+    if (!blend) {
+      if (a.rows_out) {
+        for (int i = ty; i < 32; i += 8) {
+          const int lr = g0 + i - s0, c = c0 + tx;
+          if (lr >= 0 && lr < a.L && c < a.C) {
+            const OutT v = Cvt<OutT>::to(tile[i][tx]);
+            for (int g = 0; g < a.ncfg; ++g)
+              ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + lr) * a.C + c] = v;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (!blend) return;
+  // blend rows: the agreed value goes to x and to the rows of every covering window
+#pragma unroll
+  for (int j = 0; j < 4; ++j) tile[tx][ty + 8 * j] = xb[j];
+  __syncthreads();
+  for (int k = 0; k < w.n_win; ++k) {
+    const int s0 = w.starts[k];
+    if (s0 >= g0 + 32 || s0 + a.L <= g0) continue;
+    const int b = b0 + k;
+    const int l = g0 + tx - s0;
+    if (l >= 0 && l < a.L) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = c0 + ty + 8 * j;
+        if (c < a.C) a.x[((long)b * a.C + c) * a.L + l] = xb[j];
+      }
+    }
+    if (a.rows_out) {
+      for (int i = ty; i < 32; i += 8) {
+        const int lr = g0 + i - s0, c = c0 + tx;
+        if (lr >= 0 && lr < a.L && c < a.C) {
+          const OutT v = Cvt<OutT>::to(tile[i][tx]);
+          for (int g = 0; g < a.ncfg; ++g)
+            ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + lr) * a.C + c] = v;
+        }
+      }
+    }
+  }
+}
+
+// Stitch the windows of every variation into one long clip: G[v][c][g] = sum_k weights[k][g - starts[k]] * x[v*n_win + k][c][g - starts[k]]
+// over the covering windows, in window order.  Where the covering windows hold the identical bits (after a blend row: under euler
+// always) the mean of equal values is that value, and it is copied as it is.
+__global__ __launch_bounds__(256) void windows_stitch_kernel(const float* __restrict__ x, int n_win, int C, int L, int Ltot,
+                                                             const int* __restrict__ starts, const float* __restrict__ weights,
+                                                             float* __restrict__ out) {
+  const int g = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, v = blockIdx.z;
+  if (g >= Ltot) return;
+  float sum = 0.f, first = 0.f;
+  int ncov = 0;
+  bool same = true;
+  for (int k = 0; k < n_win; ++k) {
+    const int l = g - starts[k];
+    if (l < 0 || l >= L) continue;
+    const float xv = x[(((long)v * n_win + k) * C + c) * L + l];
+    const float wk = weights[(long)k * L + l];
+    if (ncov == 0) { first = xv; sum = wk * xv; }
+    else { same = same && (__float_as_uint(xv) == __float_as_uint(first)); sum = sum + wk * xv; }
+    ++ncov;
+  }
+  out[((long)v * C + c) * Ltot + g] = same ? first : sum;
+}
+
 __global__ __launch_bounds__(256) void flow_mix_kernel(const float* __restrict__ noise, const float* __restrict__ x0,
                                                        long plane, long n, int x0_per_clip, float sigma,
                                                        float* __restrict__ out) {
@@ -919,6 +1058,34 @@ int launch_solver_step_edit(const StepEditArgs& e, hipStream_t st) {
   else FOLEY_LAUNCH(solver_step_edit_kernel<float>, grid, block, 0, st, e);
   FOLEY_LAUNCH_CHECK();
   FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+static int windows_args_ok(int clips, int n_win, int L, int Ltot, const int* starts, const float* weights) {
+  return n_win >= 1 && clips >= n_win && clips % n_win == 0 && starts && weights && Ltot >= L && (long)Ltot <= (long)n_win * L;
+}
+
+int launch_solver_step_windows(const StepWinArgs& w, hipStream_t st) {
+  const StepArgs& a = w.s;
+  if (!windows_args_ok(a.clips, w.n_win, a.L, w.Ltot, w.starts, w.weights))
+    return foley_set_err("solver_step_windows: clips must be a multiple of n_win, La <= Ltot <= n_win*La, tables required", __FILE__, __LINE__);
+  dim3 grid((w.Ltot + 31) / 32, (a.C + 31) / 32, a.clips / w.n_win), block(256);
+  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(solver_step_windows_kernel<bf16_t>, grid, block, 0, st, w);
+  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(solver_step_windows_kernel<f16_t>, grid, block, 0, st, w);
+  else FOLEY_LAUNCH(solver_step_windows_kernel<float>, grid, block, 0, st, w);
+  FOLEY_LAUNCH_CHECK();
+  FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int* starts, const float* weights,
+                          float* out, hipStream_t st) {
+  if (!x || !out || C < 1 || L < 1 || !windows_args_ok(clips, n_win, L, Ltot, starts, weights))
+    return foley_set_err("windows_stitch: clips must be a multiple of n_win, La <= Ltot <= n_win*La, tables required", __FILE__, __LINE__);
+  dim3 grid((Ltot + 255) / 256, C, clips / n_win), block(256);
+  FOLEY_LAUNCH(windows_stitch_kernel, grid, block, 0, st, x, n_win, C, L, Ltot, starts, weights, out);
   FOLEY_LAUNCH_CHECK();
   return 0;
 }

@@ -121,6 +121,7 @@ _SIGNATURES = {
     "foley_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, PROGRESS_CB, C.c_void_p, C.c_void_p]),
     "foley_abort": (C.c_int, [C.c_void_p]),
     "foley_set_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_set_windows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "foley_dac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                    C.c_void_p, C.c_void_p]),
@@ -158,6 +159,11 @@ _SIGNATURES = {
     "foley_op_solver_step_edit": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                                                                C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                                                C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_solver_step_windows": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                                                  C.c_void_p]),
+    "foley_op_windows_stitch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "foley_op_flow_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                     C.c_void_p]),
     "foley_op_latent_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -425,6 +431,22 @@ class FoleyContext:
             _check(self.lib, self.lib.foley_set_edit(self._h, _ptr(x0), x0_clips, _ptr(noise), _ptr(mask), mask_clips, _stream()),
                    "foley_set_edit")
         self._edit_keep = (x0, noise, mask)     # borrowed only until the copies on the stream are done
+
+    def set_windows(self, starts, weights: Optional[torch.Tensor]):
+        """foley_set_windows after prepare(): `starts` - n_win latent-frame offsets (host ints), `weights` [n_win, La] fp32 on
+        this context's device (host/long_form.WindowPlan); the library copies both.  starts = None (or one window) clears it."""
+        with torch.cuda.device(self.device):
+            if starts is None or weights is None:
+                _check(self.lib, self.lib.foley_set_windows(self._h, 0, None, None, _stream()), "foley_set_windows")
+                return
+            starts = [int(s) for s in starts]
+            if weights.dtype != torch.float32 or weights.device != self.device or weights.dim() != 2 or weights.shape[0] != len(starts):
+                raise FoleyRuntimeError("set_windows: weights must be [n_win, La] fp32 on the context's device")
+            if getattr(self, "plan", None) is not None and weights.shape[1] != int(self.plan["La"]):
+                raise FoleyRuntimeError("set_windows: weights must have the plan's La columns")
+            weights = weights.contiguous()
+            arr = (C.c_int32 * len(starts))(*starts)
+            _check(self.lib, self.lib.foley_set_windows(self._h, len(starts), arr, _ptr(weights), _stream()), "foley_set_windows")
 
     def abort(self) -> None:
         """Ask a foley_sample running on another thread to stop after its current iteration (it raises FoleyRuntimeError)."""
@@ -787,6 +809,39 @@ def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr,
                                               float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), dt_of(rows_out),
                                               _ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips, _stream()),
            "foley_op_solver_step_edit")
+
+
+def _windows_tables(x, starts, weights):
+    clips, _c, L = x.shape
+    if starts.dtype != torch.int32 or weights.dtype != torch.float32 or tuple(weights.shape) != (starts.numel(), L):
+        raise FoleyRuntimeError("windows ops: starts [n_win] int32 and weights [n_win, L] fp32 on the device")
+    if clips % starts.numel() != 0:
+        raise FoleyRuntimeError("windows ops: clips must be a multiple of n_win")
+    return int(starts.numel())
+
+
+def op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, starts, weights, Ltot):
+    """foley_op_solver_step_windows: x [variations*n_win, C, L]; starts [n_win] int32 and weights [n_win, L] fp32 device tensors."""
+    lib = load_library()
+    clips, Cc, L = x.shape
+    n_win = _windows_tables(x, starts, weights)
+    _check(lib, lib.foley_op_solver_step_windows(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
+                                                 float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), dt_of(rows_out),
+                                                 n_win, _ptr(starts), _ptr(weights), int(Ltot), _stream()),
+           "foley_op_solver_step_windows")
+
+
+def op_windows_stitch(x: torch.Tensor, starts: torch.Tensor, weights: torch.Tensor, Ltot: int) -> torch.Tensor:
+    """foley_op_windows_stitch: x [variations*n_win, C, L] fp32 -> new [variations, C, Ltot] fp32."""
+    lib = load_library()
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise FoleyRuntimeError("op_windows_stitch: x [variations*n_win, C, L] fp32")
+    clips, Cc, L = x.shape
+    n_win = _windows_tables(x, starts, weights)
+    out = torch.empty(clips // n_win, Cc, int(Ltot), dtype=torch.float32, device=x.device)
+    _check(lib, lib.foley_op_windows_stitch(_ptr(x), clips, n_win, Cc, L, int(Ltot), _ptr(starts), _ptr(weights), _ptr(out),
+                                            _stream()), "foley_op_windows_stitch")
+    return out
 
 
 def op_flow_mix(noise: torch.Tensor, x0: torch.Tensor, sigma: float) -> torch.Tensor:

@@ -213,13 +213,21 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
                                    generator: Optional[torch.Generator] = None, use_graph: bool = True,
                                    progress: Optional[Callable[[int, int], None]] = None,
                                    return_latents: bool = False, noise: Optional[torch.Tensor] = None,
-                                   _abort_event: Optional[threading.Event] = None, edit=None):
+                                   _abort_event: Optional[threading.Event] = None, edit=None, windows=None):
     """Same contract as the reference function of this name (utils.py:125-258):
     returns (audio [bs, 1, T] fp32 on the model's device, sample_rate).
 
     edit (host/audio_edit.EditSpec: x0, strength, mask): audio-to-audio / span regeneration - the suffix of the plain run's
     iterations that `strength` selects, started from the source latents x0 noised to that point, with the kept frames of the
-    mask held on the source's forward-noised path (foley_set_edit).  The noise is drawn exactly as for a plain run."""
+    mask held on the source's forward-noised path (foley_set_edit).  The noise is drawn exactly as for a plain run.
+
+    windows (host/long_form.WindowPlan): a long clip as one batch of overlapping windows - see _denoise_windows.  A plan of
+    one window takes the plain path exactly; `windows` together with `edit` is refused."""
+    if windows is not None and windows.n_win > 1:
+        if edit is not None:
+            raise ValueError("windows= and edit= together: editing a long clip is not supported")
+        return _denoise_windows(visual_feats, text_feats, model, dac, guidance_scale, num_inference_steps, batch_size, sampler,
+                                windows, generator, use_graph, progress, return_latents, noise, _abort_event)
     cfg = model.cfg
     La = int(audio_len_in_s * cfg.frame_rate)
     if noise is None:
@@ -247,6 +255,55 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     sr = dac.sample_rate if dac is not None else model.dac_cfg.sample_rate
     if return_latents:
         return audio, sr, latents
+    return audio, sr
+
+
+def window_rows(t: torch.Tensor, variations: int, n_win: int, what: str) -> torch.Tensor:
+    """A conditioning tensor of a windowed run -> 1 row (shared) or variations*n_win rows (clip v*n_win + k): it carries 1 row,
+    n_win rows (one per window, repeated for every variation) or variations*n_win rows."""
+    if t.dim() != 3 or t.shape[0] not in (1, n_win, variations * n_win):
+        raise ValueError(f"{what} has shape {tuple(t.shape)}: a windowed run takes 1 row, n_win ({n_win}) rows or "
+                         f"variations*n_win ({variations * n_win}) rows of [tokens, channels]")
+    if t.shape[0] == n_win and variations > 1:
+        return t.repeat(variations, 1, 1)
+    return t
+
+
+def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC, guidance_scale, num_inference_steps,
+                     variations, sampler, windows, generator, use_graph, progress, return_latents, noise, _abort_event):
+    """One long clip per variation as a batch of variations*n_win coupled windows (clip v*n_win + k = window k of variation v).
+    The noise is drawn ONCE as [variations, C, Ltot] - draw_noise, the same generator and dtype rule as a plain run - and every
+    window takes its slice, so overlapping frames start equal.  The plan carries the blend rows (edit_i0 = 0 tables); after every
+    solver step the library replaces the frames several windows cover by their weighted mean (foley_set_windows).  After the loop
+    the windows are stitched and decoded in ONE dac_decode of [variations, C, Ltot]; return_latents gives the stitched latents.
+    The length of the run is the plan's (Ltot), not audio_len_in_s.  denoise_process_multi does not shard such a run: the windows
+    of a variation are coupled."""
+    cfg = model.cfg
+    n_win, La, Ltot = windows.n_win, windows.La, windows.Ltot
+    windows.check_extent(variations)
+    clips = variations * n_win
+    vis = {k: window_rows(visual_feats[k], variations, n_win, k) for k in ("siglip2_feat", "syncformer_feat")}
+    txt = {k: window_rows(text_feats[k], variations, n_win, k) for k in ("text_feat", "uncond_text_feat")}
+    if noise is None:
+        noise = draw_noise(variations, cfg.latent_dim, Ltot, model.dtype, generator)
+    if tuple(noise.shape) != (variations, cfg.latent_dim, Ltot):
+        raise ValueError(f"noise of a windowed run is [variations, C, Ltot] = {(variations, cfg.latent_dim, Ltot)}, got {tuple(noise.shape)}")
+    noise = noise.to(device=model.device, dtype=torch.float32)
+    latents = torch.stack([noise[v, :, s:s + La] for v in range(variations) for s in windows.starts]).contiguous()
+    plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0)
+    model.attach_dac(dac)
+    model.ctx.prepare(plan)
+    weights = windows.weights.to(model.device)
+    model.ctx.set_windows(windows.starts, weights)
+    if _abort_event is not None and _abort_event.is_set():
+        raise FoleyRuntimeError("sampling aborted: another replica failed")
+    model.ctx.sample(latents, use_graph=use_graph, progress=progress)
+    starts = torch.tensor(windows.starts, dtype=torch.int32, device=model.device)
+    stitched = runtime.op_windows_stitch(latents, starts, weights, Ltot)
+    audio = model.ctx.dac_decode(stitched)
+    sr = dac.sample_rate if dac is not None else model.dac_cfg.sample_rate
+    if return_latents:
+        return audio, sr, stitched
     return audio, sr
 
 
@@ -343,7 +400,8 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     clip inside a larger shard: single-clip forwards rotate the K origin of their small-grid GEMMs per M tile (K-origin
     rotation, gemm.hip g_gemm_krot_ok), a different but deterministic summation order (tests/test_pairs_gpu.py pins how
     far it moves a result).  `edit` as for denoise_process_with_generator: per-clip source latents and masks are sharded with
-    the noise.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
+    the noise.  A windowed run (denoise_process_with_generator's `windows`) is not sharded here: the windows of one variation
+    are coupled after every step, so it runs on one device.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
     from .distributed import shard_range
     if not replicas:
         raise FoleyRuntimeError("no replicas")

@@ -323,7 +323,7 @@ class HunyuanFoleySampler:
     def generate_audio(self, hunyuan_model, hunyuan_deps, frame_rate, duration, prompt, negative_prompt, cfg_scale,
                        steps, sampler, batch_size, seed, force_offload, image=None, torch_compile_cfg=None,
                        block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1,
-                       prompts=None, negative_prompts=None, images=None):
+                       prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -337,7 +337,15 @@ class HunyuanFoleySampler:
         Audio editing (keyword-only, not sockets; host/audio_edit.py): `audio` (an AUDIO dict, batch 1 or batch_size) is
         re-sampled from part-way down the schedule - `strength` in (0, 1] selects how far (1.0: from pure noise) - and
         `regenerate` [(start_s, end_s), ...] limits the change to those spans (crossfade_s linear ramps at their edges; the
-        rest of the clip keeps the source).  A duration past the end of `audio` extends it (strength 1.0 only)."""
+        rest of the clip keeps the source).  A duration past the end of `audio` extends it (strength 1.0 only).
+
+        Long clips (keyword-only, not sockets; host/long_form.py): with `window_s` (whole seconds; None: off) and a duration
+        beyond it, the clip is generated as overlapping windows of window_s seconds - at least `window_overlap_s` seconds shared
+        by neighbours - that run as ONE batch and are blended after every solver step, then decoded as one waveform of the whole
+        length.  Every window sees its own slice of the video (text-to-audio: the learned empty rows); one prompt and one negative
+        prompt serve all windows.  `duration` may exceed the widget's 60 s here; for video the total follows the frames, cut to
+        whole seconds.  batch_size stays the number of variations.  The run takes the single-device path (the windows of a clip
+        are coupled), and does not combine with audio= / regenerate= or prompts= / images= / features=."""
         model, deps = hunyuan_model, hunyuan_deps
         device = model.device
         rng = torch.Generator(device="cpu").manual_seed(seed)          # nodes.py:273
@@ -347,7 +355,22 @@ class HunyuanFoleySampler:
                 raise ValueError(f"{name} has {len(lst)} entries: one per clip, batch_size = {batch_size}")
         if features is not None and (prompts is not None or negative_prompts is not None or images is not None):
             raise ValueError("features= already holds the conditioning: pass prompts / negative_prompts / images without it")
-        if features is not None:
+        windows = None
+        if window_s is not None:
+            if audio is not None or regenerate is not None or strength != 1.0:
+                raise ValueError("window_s does not combine with audio= / strength / regenerate=: editing a long clip is not supported")
+            if features is not None or prompts is not None or negative_prompts is not None or images is not None:
+                raise ValueError("window_s does not combine with prompts= / negative_prompts= / images= / features=: one prompt "
+                                 "and one video serve all windows")
+            if float(window_s) != int(window_s) or int(window_s) < 1:
+                raise ValueError(f"window_s must be a whole number of seconds >= 1, got {window_s}")
+        if window_s is not None and duration > window_s:
+            visual, text, windows = self._window_features(image, duration, frame_rate, prompt, negative_prompt, model, deps,
+                                                          device, int(window_s), window_overlap_s, batch_size)
+            audio_len_in_s = windows.Ltot / model.cfg.frame_rate
+            if windows.n_win == 1:              # the frames gave no more than one window: an ordinary run of that length
+                windows = None
+        elif features is not None:
             visual = {k: features[k] for k in ("siglip2_feat", "syncformer_feat")}
             text = {k: features[k] for k in ("text_feat", "uncond_text_feat")}
             audio_len_in_s = features.get("audio_len_in_s", duration)
@@ -381,7 +404,12 @@ class HunyuanFoleySampler:
             pass
         progress = (lambda i, n: pbar.update_absolute(i, n)) if pbar is not None else None
         n_dev = torch.cuda.device_count() if os.environ.get("FOLEY_DATA_PARALLEL", "0") == "1" else 1
-        if batch_size > 1 and n_dev > 1 and model.arena is not None:
+        if windows is not None:                 # coupled windows: one device
+            audio, sr = _sampler.denoise_process_with_generator(
+                visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
+                num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
+                windows=windows)
+        elif batch_size > 1 and n_dev > 1 and model.arena is not None:
             # clips are independent: shard them over the node's GPUs (host/sampler.py::denoise_process_multi; the widget
             # list is the reference's, so the switch is an environment variable - INTEGRATION.md)
             devs = [model.device] + [torch.device("cuda", i) for i in range(n_dev) if i != model.device.index]
@@ -409,6 +437,37 @@ class HunyuanFoleySampler:
                                                      model_dtype=dtype)
         res = encode_text_feat([negative_prompt, prompt], deps, device, dtype)
         return visual, {"text_feat": res[1:], "uncond_text_feat": res[:1]}, audio_len_in_s
+
+    @staticmethod
+    @torch.inference_mode()
+    def _window_features(image, duration, frame_rate, prompt, negative_prompt, model, deps, device, window_s, overlap_s, variations):
+        """Conditioning of a long clip's windows (host/long_form.plan_windows): the frames are selected ONCE for the whole clip
+        and the 8 fps / 25 fps streams sliced per window at start_s*8 / start_s*25 (the starts fall on whole seconds), then
+        SigLIP2 / Synchformer run per window as _per_clip_features runs them per clip - n_win rows; text-to-audio takes the
+        learned empty rows at the window's lengths - one shared row.  CLAP runs once: one [negative, prompt] pair for all."""
+        from .host import long_form as _long
+        if image is not None:
+            _ensure_visual_encoders(deps, device, model.dtype)
+            f8, f25 = _enc.select_frames(image, duration, frame_rate, device=device if torch.device(device).type == "cuda" else None)
+            plan = _long.plan_windows(len(f25) / _enc.FPS_SYNC, window_s, overlap_s, model.cfg.frame_rate, variations)
+            W = plan.La // model.cfg.frame_rate
+            parts = []
+            for st in plan.starts:
+                s0 = st // model.cfg.frame_rate
+                v, _len = _enc.video_features(f8[s0 * _enc.FPS_SIGLIP:(s0 + W) * _enc.FPS_SIGLIP],
+                                              f25[s0 * _enc.FPS_SYNC:(s0 + W) * _enc.FPS_SYNC],
+                                              deps["siglip2_model"], deps["syncformer_model"], device, model_dtype=model.dtype)
+                parts.append(v)
+            visual = _cond_sets.stack_features(parts, ("siglip2_feat", "syncformer_feat"))
+        else:
+            plan = _long.plan_windows(duration, window_s, overlap_s, model.cfg.frame_rate, variations)
+            W = plan.La // model.cfg.frame_rate
+            clip_len = int(W * 8)
+            sync_len = int(((int(W * 25) - 16) // 8 + 1) * 8)
+            visual = {"siglip2_feat": model.get_empty_clip_sequence(bs=1, len=clip_len),
+                      "syncformer_feat": model.get_empty_sync_sequence(bs=1, len=sync_len)}
+        res = encode_text_feat([negative_prompt, prompt], deps, device, model.dtype)
+        return visual, {"text_feat": res[1:], "uncond_text_feat": res[:1]}, plan
 
     @staticmethod
     @torch.inference_mode()

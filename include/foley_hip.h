@@ -192,6 +192,26 @@ int foley_abort(foley_ctx* ctx);
 int foley_set_edit(foley_ctx* ctx, const float* x0, int x0_clips, const float* noise, const float* mask, int mask_clips,
                    void* stream);
 
+/* Long clips as overlapping windows (additive within ABI 12).  Called after foley_prepare / foley_prepare_sets: the plan's clips
+ * become `variations` = plan.clips / n_win long clips of Ltot = starts[n_win - 1] + La latent frames each.  Clip v*n_win + k is
+ * window k of variation v: it covers the global frames [starts[k], starts[k] + La) with its own conditioning row(s) and RoPE
+ * positions 0..La.  After every iteration whose solver_coef row carries FOLEY_STEP_BLEND (the iterations that end a solver step;
+ * the plan is built with those rows, as for an edit run from iteration 0), every global frame g is replaced in all the windows
+ * that cover it by one weighted mean
+ *   xb[v][c][g] = sum_k weights[k][g - starts[k]] * x[v*n_win + k][c][g - starts[k]]      (fp32, in window order)
+ * and the next model input of those windows is staged from xb, so the windows agree on their overlaps at every step.  Rows
+ * without the flag (intermediate stages of heun-2 / midpoint-2 / kutta-4) leave every window its own value.  Exactness: a frame
+ * one window covers has weight 1.0f and a single term and keeps its value bit for bit - disjoint abutting windows are the
+ * uncoupled batch exactly; all covering windows hold the identical bits after a blend row.
+ *   starts  [n_win] int32 on the HOST, ascending, starts[0] = 0, no gap (starts[k+1] <= starts[k] + La)
+ *   weights [n_win, La] fp32 on the device; the weights of every global frame sum to 1, a singly covered frame has 1.0f
+ * Both tables are copied into context-owned buffers; the captured iteration is keyed on n_win, Ltot and those buffers, so a
+ * context alternates between plain and windowed runs safely.  n_win <= 1 or a NULL table clears the state, as does foley_prepare.
+ * plan.clips % n_win != 0, starts that do not ascend from 0, a gap, or an edit state (foley_set_edit, in either call order):
+ * FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE.  foley_sample takes and returns the windows [clips, latent_dim, La];
+ * foley_op_windows_stitch makes the long clips of them. */
+int foley_set_windows(foley_ctx* ctx, int n_win, const int32_t* starts, const float* weights, void* stream);
+
 /* DAC-VAE decoder: latents [clips, latent_dim, T] fp32 -> waveform [clips, 1, T*hop] fp32. */
 int foley_dac_decode(foley_ctx* ctx, const float* latents, int clips, int T, float* wave, void* stream);
 
@@ -377,6 +397,15 @@ int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float
                               int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
                               int rows_dtype, const float* x0, int x0_clips, const float* noise, const float* mask,
                               int mask_clips, void* stream);
+/* foley_op_solver_step's windows form (see foley_set_windows): clips = variations*n_win; starts [n_win] int32 and weights
+ * [n_win, L] fp32 both on the DEVICE here; Ltot = starts[n_win - 1] + L. */
+int foley_op_solver_step_windows(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
+                                 int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
+                                 int rows_dtype, int n_win, const int32_t* starts, const float* weights, int Ltot, void* stream);
+/* x [variations*n_win, C, L] -> out [variations, C, Ltot]: the weighted mean above per global frame; where the covering windows
+ * hold the identical bits (always after a blend row) that value is copied as it is.  starts / weights on the device. */
+int foley_op_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int32_t* starts,
+                            const float* weights, float* out, void* stream);
 /* Start state of an edit run: out [clips, C, L] = sigma*noise + (1 - sigma)*x0, x0 [x0_clips, C, L] with x0_clips 1 or clips. */
 int foley_op_flow_mix(const float* noise, const float* x0, int x0_clips, int clips, int C, int L, float sigma,
                       float* out, void* stream);
