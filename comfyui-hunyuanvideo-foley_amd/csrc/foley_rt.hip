@@ -1808,3 +1808,49 @@ extern "C" int foley_op_dac_out(const float* s, const float* w, const float* bia
                                 void* stream) {
   return launch_dac_out(s, w, bias, B, T, C, out, (hipStream_t)stream);
 }
+
+// Op entries of the row kernels that a sample launches between the GEMM, LayerNorm and attention families (tests/opcheck.py holds
+// each of them to a per-element bound): argument checks, then the launcher the runtime itself calls.
+extern "C" int foley_op_rows_add_act(const float* a, const float* v, int R, int D, int act_silu, void* out, int out_dtype,
+                                     void* stream) {
+  if (!out || R < 1 || D < 1) return FAIL(FOLEY_ERR_INVALID, "rows_add_act: null output or empty problem");
+  return launch_rows_add_act(a, v ? rb_vec(v, 0, nullptr) : rb_none(), R, D, act_silu ? 1 : 0, out, out_dtype, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_add_periodic(const float* x, const float* pos, int R, int D, int period, void* out, int out_dtype,
+                                     void* stream) {
+  if (!x || !pos || !out || R < 1 || D < 1 || period < 1) return FAIL(FOLEY_ERR_INVALID, "add_periodic: null argument or empty problem");
+  return launch_add_periodic(x, pos, R, D, period, out, out_dtype, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_gather_rows(const float* src, const int32_t* idx, int n_idx, int groups, int src_rows, int D, float* out,
+                                    void* stream) {
+  if (!src || !idx || !out || n_idx < 1 || groups < 1 || src_rows < 1 || D < 1)
+    return FAIL(FOLEY_ERR_INVALID, "gather_rows: null argument or empty problem");
+  return launch_gather_rows(src, idx, n_idx, groups, src_rows, D, out, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, void* stream) {
+  if (!src || !dst || n < 1) return FAIL(FOLEY_ERR_INVALID, "cast: null argument or empty problem");
+  return launch_cast(src, src_dtype, dst, dst_dtype, n, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_rows_periodic_check(const float* x, int groups, int rows, int period, int D, int32_t* flags, void* stream) {
+  if (!x || !flags || groups < 1 || rows < 1 || period < 1 || D < 1)
+    return FAIL(FOLEY_ERR_INVALID, "rows_periodic_check: null argument or empty problem");
+  return launch_rows_periodic_check(x, groups, rows, period, D, flags, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_dac_in(const float* x, const float* w, const float* bias, const float* alpha, int B, int T, int C,
+                               float* out0, float* out1, void* stream) {
+  if (!x || !w || !bias || !alpha || !out0 || !out1 || B < 1 || T < 1 || C < 1)
+    return FAIL(FOLEY_ERR_INVALID, "dac_in: null argument or empty problem");
+  if (((uintptr_t)w | (uintptr_t)bias | (uintptr_t)alpha | (uintptr_t)out0 | (uintptr_t)out1) & 15)
+    return FAIL(FOLEY_ERR_INVALID, "dac_in: weights, bias, alpha and outputs must be 16-byte aligned");
+  return launch_dac_in(x, w, bias, alpha, B, T, C, out0, out1, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_rows_to_planes(const float* rows, int B, int T, int C, float* out, void* stream) {
+  if (!rows || !out || B < 1 || T < 1 || C < 1) return FAIL(FOLEY_ERR_INVALID, "rows_to_planes: null argument or empty problem");
+  return launch_rows_to_planes(rows, B, T, C, out, (hipStream_t)stream);
+}

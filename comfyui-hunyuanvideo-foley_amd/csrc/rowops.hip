@@ -732,10 +732,11 @@ __global__ __launch_bounds__(256) void windows_stitch_kernel(const float* __rest
 __global__ __launch_bounds__(256) void flow_mix_kernel(const float* __restrict__ noise, const float* __restrict__ x0,
                                                        long plane, long n, int x0_per_clip, float sigma,
                                                        float* __restrict__ out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float src = x0[x0_per_clip ? i : i % plane];
-  out[i] = sigma * noise[i] + (1.f - sigma) * src;
+  // grid-stride: launch_flow_mix sizes the grid with grid1d, which stops at 4096 workgroups
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float src = x0[x0_per_clip ? i : i % plane];
+    out[i] = sigma * noise[i] + (1.f - sigma) * src;
+  }
 }
 
 __global__ void step_increment_kernel(int* p) { *p = *p + 1; }

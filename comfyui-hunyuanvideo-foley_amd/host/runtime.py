@@ -170,6 +170,13 @@ _SIGNATURES = {
                                        C.c_void_p]),
     "foley_op_dac_out": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p]),
+    "foley_op_rows_add_act": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_add_periodic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_gather_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "foley_op_cast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p]),
+    "foley_op_rows_periodic_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "foley_op_dac_in": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3),
+    "foley_op_rows_to_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -792,12 +799,17 @@ def op_qkv_split(qkv, L, H, gains: Sequence, poss: Sequence, dsts: Sequence, S_t
            "foley_op_qkv_split")
 
 
+def _rows_dt(rows_out) -> int:
+    return DT_F32 if rows_out is None else dt_of(rows_out)      # rows_out None: the step stages no model input rows
+
+
 def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out):
+    """x_saved / d_acc may be None for single-stage tables (euler), rows_out None to leave the next input rows unstaged."""
     lib = load_library()
     clips, Cc, L = x.shape
     _check(lib, lib.foley_op_solver_step(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
                                          float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out),
-                                         dt_of(rows_out), _stream()), "foley_op_solver_step")
+                                         _rows_dt(rows_out), _stream()), "foley_op_solver_step")
 
 
 def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, x0, noise, mask=None):
@@ -806,7 +818,7 @@ def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr,
     clips, Cc, L = x.shape
     mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
     _check(lib, lib.foley_op_solver_step_edit(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-                                              float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), dt_of(rows_out),
+                                              float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
                                               _ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips, _stream()),
            "foley_op_solver_step_edit")
 
@@ -826,7 +838,7 @@ def op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_p
     clips, Cc, L = x.shape
     n_win = _windows_tables(x, starts, weights)
     _check(lib, lib.foley_op_solver_step_windows(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-                                                 float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), dt_of(rows_out),
+                                                 float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
                                                  n_win, _ptr(starts), _ptr(weights), int(Ltot), _stream()),
            "foley_op_solver_step_windows")
 
@@ -844,15 +856,18 @@ def op_windows_stitch(x: torch.Tensor, starts: torch.Tensor, weights: torch.Tens
     return out
 
 
-def op_flow_mix(noise: torch.Tensor, x0: torch.Tensor, sigma: float) -> torch.Tensor:
-    """foley_op_flow_mix: sigma*noise + (1 - sigma)*x0 -> new [clips, C, L] fp32; x0 [1 | clips, C, L] (1: shared)."""
+def op_flow_mix(noise: torch.Tensor, x0: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """foley_op_flow_mix: sigma*noise + (1 - sigma)*x0 -> [clips, C, L] fp32 (new, or `out`); x0 [1 | clips, C, L] (1: shared)."""
     lib = load_library()
     if noise.dtype != torch.float32 or x0.dtype != torch.float32 or noise.dim() != 3 or x0.dim() != 3:
         raise FoleyRuntimeError("op_flow_mix: noise [clips, C, L] and x0 [1 | clips, C, L] fp32")
     clips, Cc, L = noise.shape
     if tuple(x0.shape[1:]) != (Cc, L):
         raise FoleyRuntimeError(f"op_flow_mix: x0 {tuple(x0.shape)} does not match noise {tuple(noise.shape)}")
-    out = torch.empty_like(noise)
+    if out is None:
+        out = torch.empty_like(noise)
+    elif out.dtype != torch.float32 or out.shape != noise.shape:
+        raise FoleyRuntimeError("op_flow_mix: out must be fp32 of noise's shape")
     _check(lib, lib.foley_op_flow_mix(_ptr(noise), _ptr(x0), x0.shape[0], clips, Cc, L, float(sigma), _ptr(out), _stream()),
            "foley_op_flow_mix")
     return out
@@ -870,3 +885,86 @@ def op_dac_out(s, w, bias, out):
     B, T, Cc = s.shape
     _check(lib, lib.foley_op_dac_out(_ptr(s), _ptr(w), _ptr(bias), B, T, Cc, _ptr(out), _stream()),
            "foley_op_dac_out")
+
+
+def _f32(*ts):
+    for t in ts:
+        if t is not None and t.dtype != torch.float32:
+            raise FoleyRuntimeError("fp32 operand expected")
+
+
+def op_rows_add_act(a: Optional[torch.Tensor], v: Optional[torch.Tensor], out: torch.Tensor, act_silu: bool):
+    """foley_op_rows_add_act: out [R, D] (fp32 / bf16 / fp16) = act(a + v); a [R, D] fp32 or None, v [D] fp32 or None."""
+    lib = load_library()
+    R, D = out.shape
+    _f32(a, v)
+    if (a is not None and tuple(a.shape) != (R, D)) or (v is not None and v.numel() != D):
+        raise FoleyRuntimeError("op_rows_add_act: a [R, D] and v [D] must match out [R, D]")
+    _check(lib, lib.foley_op_rows_add_act(_ptr(a), _ptr(v), R, D, int(bool(act_silu)), _ptr(out), dt_of(out), _stream()),
+           "foley_op_rows_add_act")
+
+
+def op_add_periodic(x: torch.Tensor, pos: torch.Tensor, out: torch.Tensor):
+    """foley_op_add_periodic: out [R, D] = x [R, D] + pos [period, D] row r % period."""
+    lib = load_library()
+    R, D = x.shape
+    _f32(x, pos)
+    if pos.dim() != 2 or pos.shape[1] != D or tuple(out.shape) != (R, D):
+        raise FoleyRuntimeError("op_add_periodic: x [R, D], pos [period, D], out [R, D]")
+    _check(lib, lib.foley_op_add_periodic(_ptr(x), _ptr(pos), R, D, pos.shape[0], _ptr(out), dt_of(out), _stream()),
+           "foley_op_add_periodic")
+
+
+def op_gather_rows(src: torch.Tensor, idx: torch.Tensor, groups: int, out: torch.Tensor):
+    """foley_op_gather_rows: src [groups*src_rows, D] fp32, idx [n_idx] int32 in [0, src_rows) -> out [groups*n_idx, D] fp32."""
+    lib = load_library()
+    _f32(src, out)
+    n_idx, D = idx.numel(), src.shape[1]
+    if idx.dtype != torch.int32 or src.shape[0] % groups or tuple(out.shape) != (groups * n_idx, D):
+        raise FoleyRuntimeError("op_gather_rows: int32 idx, src [groups*src_rows, D], out [groups*n_idx, D]")
+    src_rows = src.shape[0] // groups
+    if int(idx.min()) < 0 or int(idx.max()) >= src_rows:
+        raise FoleyRuntimeError("op_gather_rows: index outside [0, src_rows)")
+    _check(lib, lib.foley_op_gather_rows(_ptr(src), _ptr(idx), n_idx, groups, src_rows, D, _ptr(out), _stream()),
+           "foley_op_gather_rows")
+
+
+def op_cast(src: torch.Tensor, dst: torch.Tensor):
+    """foley_op_cast: dst = src converted element by element (fp32 <-> bf16 / fp16, fp32 -> fp32)."""
+    lib = load_library()
+    if src.numel() != dst.numel():
+        raise FoleyRuntimeError("op_cast: element counts differ")
+    _check(lib, lib.foley_op_cast(_ptr(src), dt_of(src), _ptr(dst), dt_of(dst), src.numel(), _stream()), "foley_op_cast")
+
+
+def op_rows_periodic_check(x: torch.Tensor, period: int, flags: torch.Tensor):
+    """foley_op_rows_periodic_check: x [groups, rows, D] fp32; flags [groups] int32, flags[g] |= 1 when group g is not periodic."""
+    lib = load_library()
+    groups, rows, D = x.shape
+    _f32(x)
+    if flags.dtype != torch.int32 or flags.numel() < min(groups, 32):
+        raise FoleyRuntimeError("op_rows_periodic_check: int32 flags, one per group")
+    _check(lib, lib.foley_op_rows_periodic_check(_ptr(x), groups, rows, int(period), D, _ptr(flags), _stream()),
+           "foley_op_rows_periodic_check")
+
+
+def op_dac_in(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, alpha: torch.Tensor, out0: torch.Tensor, out1: torch.Tensor):
+    """foley_op_dac_in: x [B, T] fp32, w [7, C] (tap-major), bias / alpha [C] -> out0 = conv, out1 = snake(conv), both [B*T, C]."""
+    lib = load_library()
+    B, T = x.shape
+    Cc = bias.numel()
+    _f32(x, w, bias, alpha, out0, out1)
+    if w.numel() != 7 * Cc or alpha.numel() != Cc or tuple(out0.shape) != (B * T, Cc) or tuple(out1.shape) != (B * T, Cc):
+        raise FoleyRuntimeError("op_dac_in: w [7, C], bias / alpha [C], out0 / out1 [B*T, C]")
+    _check(lib, lib.foley_op_dac_in(_ptr(x), _ptr(w), _ptr(bias), _ptr(alpha), B, T, Cc, _ptr(out0), _ptr(out1), _stream()),
+           "foley_op_dac_in")
+
+
+def op_rows_to_planes(rows: torch.Tensor, B: int, out: torch.Tensor):
+    """foley_op_rows_to_planes: rows [B*T, C] fp32 -> out [B, C, T] fp32."""
+    lib = load_library()
+    _f32(rows, out)
+    Cc = rows.shape[1]
+    if rows.shape[0] % B or tuple(out.shape) != (B, Cc, rows.shape[0] // B):
+        raise FoleyRuntimeError("op_rows_to_planes: rows [B*T, C], out [B, C, T]")
+    _check(lib, lib.foley_op_rows_to_planes(_ptr(rows), B, rows.shape[0] // B, Cc, _ptr(out), _stream()), "foley_op_rows_to_planes")

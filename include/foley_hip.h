@@ -413,6 +413,26 @@ int foley_op_latent_rows(const float* x, int clips, int C, int L, int ncfg, void
                          void* stream);
 int foley_op_dac_out(const float* s, const float* w, const float* bias, int B, int T, int C, float* out,
                      void* stream);
+/* The remaining row kernels of a run, one entry each (additive: the ABI number is unchanged).  All operands on the device.
+ * rows_add_act: out(T) [R, D] = act(a + v), a [R, D] fp32 or NULL (zeros), v [D] fp32 or NULL, act_silu 0 / 1.
+ * add_periodic: out(T) [R, D] = x [R, D] + pos [period, D] row r % period.
+ * gather_rows: out [groups*n_idx, D] row (g, l) = src row g*src_rows + idx[l] (fp32).
+ * cast: n contiguous elements, fp32 <-> bf16, fp32 <-> fp16 or fp32 -> fp32; any other pair is FOLEY_ERR_INVALID.
+ * rows_periodic_check: flags[g] |= 1 when, in group g of x [groups, rows, D] (groups <= 32), some row s >= period differs from row
+ *   s - period in its BIT PATTERN (+0 and -0 differ, equal NaN patterns agree); rows <= period launches nothing.
+ * dac_in: DAC encoder input conv 1 -> C (k = 7, pad 3) over x [B, T]: out0 [B*T, C] = y, out1 = snake(y; alpha); C % 4 == 0.
+ * rows_to_planes: rows [B*T, C] -> out [B, C, T]. */
+int foley_op_rows_add_act(const float* a, const float* v, int R, int D, int act_silu, void* out, int out_dtype,
+                          void* stream);
+int foley_op_add_periodic(const float* x, const float* pos, int R, int D, int period, void* out, int out_dtype,
+                          void* stream);
+int foley_op_gather_rows(const float* src, const int32_t* idx, int n_idx, int groups, int src_rows, int D, float* out,
+                         void* stream);
+int foley_op_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, void* stream);
+int foley_op_rows_periodic_check(const float* x, int groups, int rows, int period, int D, int32_t* flags, void* stream);
+int foley_op_dac_in(const float* x, const float* w, const float* bias, const float* alpha, int B, int T, int C,
+                    float* out0, float* out1, void* stream);
+int foley_op_rows_to_planes(const float* rows, int B, int T, int C, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -312,3 +312,221 @@ def attention_ref_and_bound(q, k, v, out_dtype, p_dtype=None):
         ref[b] = (p @ vb).transpose(0, 1).reshape(Sq, H * hd)
         e[b] = ((u_p + 2 * d_s) * (p @ vb.abs())).transpose(0, 1).reshape(Sq, H * hd)
     return ref, Bound(e, out_dtype)
+
+
+# ----------------------------------------------------------------------------- bit-for-bit checks (pure data movement)
+def assert_bits_equal(got, want, what, nan_ok=False):
+    """Every element of `got` carries the bit pattern of `want` (same dtype), compared through an integer view so that NaN and
+    the sign of zero count.  nan_ok: where `want` is a NaN any NaN will do (the payload of a converted NaN is not pinned:
+    tests/weights_ref.py states the same limit).  A failure reports the count and the bounding box like assert_elementwise."""
+    got, want = got.detach().cpu().contiguous(), want.detach().cpu().contiguous()
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, tuple(got.shape), tuple(want.shape))
+    it = _INT[got.element_size()]
+    bad = got.view(it) != want.view(it)
+    if nan_ok:
+        bad &= ~(torch.isnan(got) & torch.isnan(want))
+    if bool(bad.any()):
+        cols = got.shape[-1] if got.dim() else 1
+        idx = bad.reshape(-1, cols).nonzero()
+        r0, c0 = (int(v) for v in idx.min(0).values)
+        r1, c1 = (int(v) for v in idx.max(0).values)
+        r, c = (int(v) for v in idx[0])
+        raise AssertionError(
+            f"{what}: {int(bad.sum())} of {bad.numel()} elements differ in their bits; first at (row {r}, col {c}) of "
+            f"[{bad.numel() // cols}, {cols}]: got {float(got.reshape(-1, cols)[r, c])!r} want {float(want.reshape(-1, cols)[r, c])!r}; "
+            f"offenders lie in rows [{r0}, {r1}] x cols [{c0}, {c1}]")
+
+
+def f32(v):
+    """A Python number as the fp32 value a kernel argument carries, in fp64."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+# ----------------------------------------------------------------------------- small row kernels
+def flow_mix_ref_and_bound(noise, x0, sigma):
+    """sigma * noise + (1 - sigma) * x0 (x0 [1 | clips, C, L]): three fp32 roundings beyond the exact result - 1 - sigma, and one per
+    product or their sum when the compiler contracts one product into an FMA, two products and a sum otherwise - each relative
+    to a value no larger than |sigma noise| + |(1 - sigma) x0|: 3 U32 of that."""
+    s = f32(sigma)
+    a, b = s * noise.double().cpu(), (1.0 - s) * x0.double().cpu()
+    return a + b, Bound(3 * U32 * (a.abs() + b.abs()))
+
+
+def rows_add_act_ref_and_bound(a, v, act_silu, out_dtype, dev):
+    """act(a + v), a [R, D] or None (zeros), v [D] or None.  Returns (ref64, bound): without the activation the fp32 addition is
+    correctly rounded, so the bound is None and the caller compares bits with the CPU's fp32 sum cast to out_dtype; with SiLU
+    the addition is exact to U32 |a + v|, pushed through act_bound."""
+    y = torch.zeros(1, dtype=torch.float64)
+    if a is not None:
+        y = y + a.double().cpu()
+    if v is not None:
+        y = y + v.double().cpu()
+    if not act_silu:
+        return y, None
+    e_y = U32 * y.abs() if (a is not None and v is not None) else torch.zeros_like(y)
+    return act64("silu", y), act_bound("silu", e_y, measure_a_act("silu", y, dev), out_dtype)
+
+
+def sum32_cast(a, v, out_dtype):
+    """The CPU's fp32 a + v (either may be None) cast to out_dtype: what a correctly rounded add-and-store must give bit for bit."""
+    y = a.float().cpu() if a is not None else None
+    if v is not None:
+        y = v.float().cpu() + (y if y is not None else 0.0)
+    return y.to(out_dtype)
+
+
+def measure_a_act_tanh(y64, dev):
+    """4 x the largest |PyTorch's fp32 device tanh of fp32(y) - the fp64 tanh of y| (reference against reference, as measure_a_act)."""
+    return 4.0 * float((torch.tanh(y64.float().to(dev)).double().cpu() - torch.tanh(y64)).abs().max())
+
+
+def _conv7(x, w):
+    """x [B, Cin, T], w [Cout, Cin, 7] fp64 -> [B, Cout, T], zero padding 3."""
+    return torch.nn.functional.conv1d(x, w, None, padding=3)
+
+
+def dac_out_ref_and_bound(s, w, bias, dev):
+    """tanh(bias + sum_{j < 7, c < C} w[j C + c] s[b, t + j - 3, c]), s [B, T, C], w [7 C] tap-major.  Pre-activation: 7 C products
+    summed in fp32 in any order plus the bias, (7 C + 4) U32 mag with mag = sum |s w| + |bias|; tanh has Lipschitz constant 1 and
+    its own error a_act.  Returns (ref64 [B, T], bound, a_act)."""
+    B, T, C = s.shape
+    x, ww = s.double().cpu().transpose(1, 2), w.double().cpu().view(7, C).t().reshape(1, C, 7)
+    b = bias.double().cpu().view(1, 1, 1)
+    y, mag = (_conv7(x, ww) + b)[:, 0], (_conv7(x.abs(), ww.abs()) + b.abs())[:, 0]
+    a_act = measure_a_act_tanh(y, dev)
+    return torch.tanh(y), Bound((7 * C + 4) * U32 * mag + a_act), a_act
+
+
+def dac_in_ref_and_bounds(x, w, bias, alpha, dev):
+    """DAC encoder input conv 1 -> C (k = 7): y[b, t, c] = bias[c] + sum_j w[j C + c] x[b, t + j - 3], out0 = y, out1 = snake(y).
+    Seven products and the bias in fp32: (7 + 4) U32 mag; the snake through dac_bounds.  Returns (y64, snake64, b0, b1, a_act),
+    rows [B T, C]."""
+    B, T = x.shape
+    C = bias.numel()
+    xx, ww = x.double().cpu().view(B, 1, T), w.double().cpu().view(7, C).t().reshape(C, 1, 7)
+    b = bias.double().cpu().view(1, C, 1)
+    rows = lambda t: t.transpose(1, 2).reshape(B * T, C)
+    y, mag = rows(_conv7(xx, ww) + b), rows(_conv7(xx.abs(), ww.abs()) + b.abs())
+    a_act = measure_a_act_snake(y, alpha.cpu(), dev)
+    b0, b1 = dac_bounds((7 + 4) * U32 * mag, y, None, a_act)
+    return y, snake64(y, alpha.cpu()), b0, b1, a_act
+
+
+# ----------------------------------------------------------------------------- stand-alone head split
+def rope64(x, cos, sin):
+    """x [..., 128] fp64, cos / sin broadcastable [..., 64]: the pair (2 i, 2 i + 1) rotated by angle i."""
+    x0, x1 = x[..., 0::2], x[..., 1::2]
+    return torch.stack((x0 * cos - x1 * sin, x1 * cos + x0 * sin), dim=-1).flatten(-2)
+
+
+def qkv_head_ref_and_bound(y, gain, cos, sin, eps, out_dtype):
+    """One operand of the stand-alone head split: y [n, H, 128] as given (fp32 rows of the fused projection), gain [128] or None,
+    cos / sin [n, 64] or None.  RMSNorm (when gain) then RoPE (when cos) in fp64, with head_split_bound at e_y = 0, which leaves
+        8 U32 |gain|max max|y| / rms.
+    Why 8 covers the roundings (u = 2^-24 = U32 / 2): the sum of squares is a chain of positive terms - two roundings in the lane
+    (a product and an FMA), six butterfly levels - 8 u relative, + eps 9 u; its inverse square root halves that and adds the
+    instruction's own <= 1 ulp = 2 u: 6.5 u; times y, times gain: 8.5 u on the normalised value (4.25 U32 without a rotation).  The
+    rotation multiplies by cos / sin (9.5 u on each product) and adds (+ u of the sum): <= 10.5 u (|a cos| + |b sin|) <= 10.5 u
+    sqrt(2) max(|a|, |b|) = 14.9 u = 7.4 U32 of |gain| max|y| / rms.  No gain: a rotation alone rounds two products and their sum,
+    2 u (|y0 cos| + |y1 sin|) <= U32 sqrt(2) max|y| < 2 U32 max|y|; neither: a copy (exact before the store)."""
+    y = y.double().cpu()
+    ref = y
+    if gain is not None:
+        ref = ref * torch.rsqrt(ref.pow(2).mean(-1, keepdim=True) + f32(eps)) * gain.double().cpu()
+    if cos is not None:
+        ref = rope64(ref, cos.double().cpu()[:, None], sin.double().cpu()[:, None])
+    zero = torch.zeros_like(y)
+    if gain is not None:
+        return ref, head_split_bound(zero, y, out_dtype, gain.cpu())
+    if cos is not None:
+        return ref, Bound(2 * U32 * y.abs().amax(-1, keepdim=True).expand_as(y).clone(), out_dtype)
+    return ref, Bound(zero, out_dtype)
+
+
+# ----------------------------------------------------------------------------- solver steps (one iteration, seeded from the device)
+STEP_SAVE_X, STEP_USE_SAVED, STEP_ACC_RESET, STEP_BLEND = 1, 2, 4, 8
+
+
+def solver_step_ref_and_bounds(pred, x, x_saved, d_acc, row, ncfg, guidance):
+    """ONE iteration of the solver update in fp64 from the state the device holds (x, x_saved, d_acc [clips, C, L] copied back;
+    x_saved / d_acc may be None), pred [ncfg clips L, C], row = the iteration's coefficient row.  Returns a dict of
+    (ref64, Bound) for 'x' and 'd_acc' and ref64 alone for 'x_saved' (a copy: exact), with
+        v = u + g (c - u)                    e_v = 3 U32 (|u| + |g| (|c| + |u|))          (ncfg 1: v = pred, e_v = 0)
+        deriv = w_new v + w_acc acc          e_d = |w_new| e_v + 2 U32 (|w_new v| + |w_acc acc|)
+        xn = base + deriv dt                 e_x = |dt| e_d + 2 U32 (|base| + |deriv dt|)
+        d_acc' = acc + w_store v             e_a = |w_store| e_v + 2 U32 (|acc| + |w_store v|)
+    two roundings per line whether or not the product is contracted into an FMA (U32 is twice the unit round-off)."""
+    clips, C, L = x.shape
+    w_new, w_acc, dt, w_store = (float(t) for t in row[:4].double())
+    flags = int(row[4])
+    P = pred.double().cpu().view(ncfg, clips, L, C).transpose(2, 3)
+    if ncfg == 2:
+        g = f32(guidance)
+        u, c = P[0], P[1]
+        v, e_v = u + g * (c - u), 3 * U32 * (u.abs() + abs(g) * (c.abs() + u.abs()))
+    else:
+        v, e_v = P[0], torch.zeros_like(P[0])
+    xd = x.double().cpu()
+    acc = torch.zeros_like(xd) if (d_acc is None or flags & STEP_ACC_RESET) else d_acc.double().cpu()
+    deriv = w_new * v + w_acc * acc
+    e_d = abs(w_new) * e_v + 2 * U32 * ((w_new * v).abs() + (w_acc * acc).abs())
+    base = x_saved.double().cpu() if flags & STEP_USE_SAVED else xd
+    xn = base + deriv * dt
+    e_x = abs(dt) * e_d + 2 * U32 * (base.abs() + (deriv * dt).abs())
+    out = {"x": (xn, Bound(e_x)), "flags": flags, "s_next": float(row[5].double())}
+    if d_acc is not None:
+        out["d_acc"] = (acc + w_store * v, Bound(abs(w_store) * e_v + 2 * U32 * (acc.abs() + (w_store * v).abs())))
+    if x_saved is not None:
+        out["x_saved"] = xd if flags & STEP_SAVE_X else x_saved.double().cpu()
+    return out
+
+
+def edit_blend_ref_and_bound(xn, e_x, s_next, x0, noise, mask):
+    """The edit form's blend on a STEP_BLEND row: tgt = s noise + (1 - s) x0 (three roundings, as flow_mix), then
+    m xn + (1 - m) tgt: the propagated terms |m| e_x + |1 - m| e_t plus (2 + 1) U32 (|m xn| + |(1 - m) tgt|).
+    x0 [1 | clips, C, L], noise [clips, C, L], mask [1 | clips, L] or [L] or None (all ones)."""
+    s = float(s_next)
+    a, b = s * noise.double().cpu(), (1.0 - s) * x0.double().cpu()
+    tgt, e_t = a + b, 3 * U32 * (a.abs() + b.abs())
+    m = torch.ones(1, 1, xn.shape[-1], dtype=torch.float64) if mask is None else mask.double().cpu().view(-1, 1, xn.shape[-1])
+    p, q = m * xn, (1.0 - m) * tgt
+    return p + q, Bound(m.abs() * e_x + (1.0 - m).abs() * e_t + 3 * U32 * (p.abs() + q.abs()))
+
+
+def windows_mean_ref_and_bound(xn, e_x, n_win, starts, weights):
+    """The windows form's blend: every global frame g replaced in all its covering windows by sum_k w[k][g - starts[k]] xn_k (window
+    order).  xn / e_x [variations n_win, C, L] fp64 (e_x None: the operands are exact, as in the stitch).  n covering windows:
+    the propagated sum |w_k| e_k plus (n + 1) U32 sum |w_k x_k|.  Returns (per-window ref64, per-window e, G [variations, C, Ltot],
+    e_G, coverage [Ltot])."""
+    V, C, L = xn.shape[0] // n_win, xn.shape[1], xn.shape[2]
+    Ltot = int(starts[-1]) + L
+    w = weights.double().cpu()
+    G, mag, prop = (torch.zeros(V, C, Ltot, dtype=torch.float64) for _ in range(3))
+    cov = torch.zeros(Ltot, dtype=torch.float64)
+    for k, s in enumerate(int(t) for t in starts):
+        xk = xn.reshape(V, n_win, C, L)[:, k]
+        G[..., s:s + L] += w[k] * xk
+        mag[..., s:s + L] += (w[k] * xk).abs()
+        if e_x is not None:
+            prop[..., s:s + L] += w[k].abs() * e_x.reshape(V, n_win, C, L)[:, k]
+        cov[s:s + L] += 1
+    e_G = prop + (cov + 1) * U32 * mag
+    ref = torch.stack([G[v, :, s:s + L] for v in range(V) for s in (int(t) for t in starts)])
+    e = torch.stack([e_G[v, :, s:s + L] for v in range(V) for s in (int(t) for t in starts)])
+    return ref, e, G, e_G, cov
+
+
+def rows_of(x, ncfg, rows_dtype):
+    """The next model input rows a step stages from the sample it wrote: x [clips, C, L] -> [ncfg clips L, C] in rows_dtype, the same
+    bits in every CFG copy."""
+    r = x.detach().cpu().transpose(1, 2).reshape(-1, x.shape[1]).to(rows_dtype)
+    return r.repeat(ncfg, 1)
+
+
+def periodic_flags(x, period):
+    """[groups] int32: 1 where some row s >= period of the group differs in its BIT PATTERN from row s - period (so +0.0 against
+    -0.0 differs and equal NaN patterns agree), x [groups, rows, D] fp32."""
+    xi = x.detach().cpu().contiguous().view(torch.int32)
+    if xi.shape[1] <= period:
+        return torch.zeros(xi.shape[0], dtype=torch.int32)
+    return (xi[:, period:] != xi[:, :-period]).flatten(1).any(1).to(torch.int32)

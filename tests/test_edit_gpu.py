@@ -159,6 +159,25 @@ def test_edit_loop_matches_oracle(tiny, solver, steps, strength, use_graph):
     assert rel_err(lat, _ORACLE[key]) < 1e-4
 
 
+def test_edit_loop_matches_oracle_past_the_flow_mix_grid_cap(tiny):
+    """Six clips of 30 s: batch * La = 9000 frames, 1 152 000 latent elements - more than 4096 workgroups of 256 reach without
+    striding - at strength 0.5, so the run starts from foley_op_flow_mix's output (host/sampler.py) and not from the noise.  A start
+    state whose tail was never written (the kernel before it became a grid-stride loop) does not match the oracle."""
+    sd, _dsd, model, dac, _cond, _noise, _x0 = tiny
+    dur, clips, steps = 30.0, 6, 4
+    La = C.lengths(dur)[0]
+    assert clips * La > 8192
+    cond = synth.synth_conditioning(C.TINY, dur, t2a=False, sd=sd)
+    g = torch.Generator().manual_seed(22)
+    noise, x0 = torch.randn(clips, 128, La, generator=g), 0.7 * torch.randn(1, 128, La, generator=g)
+    mask = audio_edit.build_mask(La, [(0.3 * dur, 0.6 * dur)], 0.1)
+    want = oracle_edit_latents(sd, C.TINY.heads, noise, x0, mask, cond, steps, 4.5, "euler", 0.5)
+    vis, txt = _feats(cond)
+    _a, _sr, lat = sampler.denoise_process_with_generator(vis, txt, dur, model, dac, 4.5, steps, clips, "euler", noise=noise,
+                                                          return_latents=True, edit=audio_edit.EditSpec(x0, 0.5, mask))
+    assert rel_err(lat, want) < 1e-4
+
+
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_all_ones_at_strength_1_is_the_plain_run(tiny, use_graph):
     _sd, _dsd, model, dac, cond, _noise, x0 = tiny

@@ -366,3 +366,360 @@ def test_dac_residual_and_snake_inside_and_defects_caught():
     a_next = alpha.roll(-1)
     bad1[r, 16:32] = (v32 + (1.0 / (a_next + 1e-9)) * torch.sin(a_next * v32) ** 2)[r, 16:32]
     _missed_and_caught(torch.float32, bad1, oc.snake64(v, alpha), b1, "neighbour channel's alpha", box=(r, r, 16, 31))
+
+
+# ----------------------------------------------------------------------------- row, solver and DAC edge kernels
+# fp32 CPU emulations of each expression in more than one order - with and without the product contracted into an FMA, window and
+# tap sums forward and reversed - must stay inside the bounds of opcheck.py at the shapes tests/test_rowops_elementwise_gpu.py
+# launches: this is the arbiter of each constant.  Planted defects: where an old gate exists and is a norm, the defect must pass it;
+# where the old test could not see the defect because of its SHAPE or of where it looked, the defective emulation is run at the old
+# shape through the old assertion (it passes) and at the new shape through the new check (it fails).
+STEP_SHAPES = [(2, 128, 50), (3, 128, 33), (1, 128, 1), (2, 96, 31), (2, 40, 65)]
+
+
+def _fma(a, b, c):
+    """fp32 a * b + c with one rounding (the fp64 product of two fp32 values is exact)."""
+    a, b, c = (t if torch.is_tensor(t) else torch.tensor(t, dtype=torch.float32) for t in (a, b, c))
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _f(v):
+    return torch.tensor(float(v), dtype=torch.float32)
+
+
+def _step_emul(pred, x, x_saved, d_acc, row, ncfg, g, fma):
+    """solver_step_kernel's expressions in fp32: (xn, x_saved', d_acc')."""
+    clips, C, L = x.shape
+    w_new, w_acc, dt, w_store = row[0], row[1], row[2], row[3]
+    flags = int(row[4])
+    P = pred.view(ncfg, clips, L, C).transpose(2, 3)
+    if ncfg == 2:
+        v = _fma(_f(g), P[1] - P[0], P[0]) if fma else P[0] + _f(g) * (P[1] - P[0])
+    else:
+        v = P[0]
+    acc = torch.zeros_like(x) if (d_acc is None or flags & oc.STEP_ACC_RESET) else d_acc
+    if float(w_acc) != 0:
+        deriv = _fma(w_new, v, w_acc * acc) if fma else w_new * v + w_acc * acc
+    else:
+        deriv = w_new * v
+    base = x_saved if flags & oc.STEP_USE_SAVED else x
+    xn = _fma(deriv, dt, base) if fma else base + deriv * dt
+    da = _fma(w_store, v, acc) if fma else acc + w_store * v
+    return xn, (x.clone() if flags & oc.STEP_SAVE_X else x_saved), da
+
+
+def _tables():
+    from foley_amd.host import tables
+    return tables
+
+
+@pytest.mark.parametrize("solver,steps", [("euler", 3), ("heun-2", 4), ("midpoint-2", 4), ("kutta-4", 8)])
+@pytest.mark.parametrize("ncfg", [1, 2])
+@pytest.mark.parametrize("fma", [False, True], ids=["mul_add", "fma"])
+def test_solver_step_emulations_stay_inside(solver, steps, ncfg, fma):
+    tb = _tables()
+    coef = tb.edit_solver_table(tb.sigma_grid(steps), solver, steps)
+    for si, (clips, C, L) in enumerate(STEP_SHAPES):
+        x, xs, da = _rand((clips, C, L), 200 + si), torch.zeros(clips, C, L), torch.zeros(clips, C, L)
+        x0, noise, mask = _rand((clips, C, L), 210 + si, 0.7), _rand((clips, C, L), 220 + si), torch.rand(clips, L, generator=torch.Generator().manual_seed(si))
+        for it in range(steps):
+            pred = _rand((ncfg * clips * L, C), 230 + 10 * si + it)
+            r = oc.solver_step_ref_and_bounds(pred, x, xs, da, coef[it], ncfg, 4.5)
+            xn, xs2, da2 = _step_emul(pred, x, xs, da, coef[it], ncfg, 4.5, fma)
+            assert oc.assert_elementwise(xn, *r["x"], f"x {solver} it {it}") <= 1.0
+            assert oc.assert_elementwise(da2, *r["d_acc"], f"d_acc {solver} it {it}") <= 1.0
+            assert torch.equal(xs2.double(), r["x_saved"])
+            if r["flags"] & oc.STEP_BLEND:                     # the edit form's blend on the same iteration
+                s = coef[it][5]
+                tgt = _fma(s, noise, (1.0 - s) * x0) if fma else s * noise + (1.0 - s) * x0
+                m = mask.view(clips, 1, L)
+                xb = _fma(m, xn, (1.0 - m) * tgt) if fma else m * xn + (1.0 - m) * tgt
+                ref, bound = oc.edit_blend_ref_and_bound(r["x"][0], r["x"][1].e, r["s_next"], x0, noise, mask)
+                assert oc.assert_elementwise(xb, ref, bound, f"blend {solver} it {it}") <= 1.0
+                xn = xb
+            x, xs, da = xn, xs2, da2
+
+
+def _windows_emul(xn, n_win, starts, weights, fma, reverse):
+    V, C, L = xn.shape[0] // n_win, xn.shape[1], xn.shape[2]
+    Ltot = starts[-1] + L
+    G = torch.zeros(V, C, Ltot)
+    first = torch.ones(Ltot, dtype=torch.bool)
+    order = list(range(n_win))[::-1] if reverse else list(range(n_win))
+    for k in order:
+        s, xk = starts[k], xn.view(V, n_win, C, L)[:, k]
+        cur = G[..., s:s + L]
+        add = _fma(weights[k], xk, cur) if fma else cur + weights[k] * xk
+        G[..., s:s + L] = torch.where(first[s:s + L], weights[k] * xk, add)
+        first[s:s + L] = False
+    return G
+
+
+WIN_PLANS = [([0], 50), ([0, 50], 50), ([0, 20], 50), ([0, 32, 40], 65), ([0, 10, 20], 33)]   # Ltot = L, = n_win L, an edge inside a tile / on one, three deep
+
+
+@pytest.mark.parametrize("fma", [False, True], ids=["mul_add", "fma"])
+@pytest.mark.parametrize("reverse", [False, True], ids=["window_order", "reversed"])
+def test_windows_mean_and_stitch_emulations_stay_inside(fma, reverse):
+    from foley_amd.host import long_form
+    for pi, (starts, L) in enumerate(WIN_PLANS):
+        plan = long_form.WindowPlan.from_frames(starts, L)
+        xn = _rand((2 * plan.n_win, 40, L), 300 + pi)
+        e_x = 2 * oc.U32 * xn.double().abs()
+        G32 = _windows_emul(xn, plan.n_win, starts, plan.weights, fma, reverse)
+        ref, e, G, e_G, cov = oc.windows_mean_ref_and_bound(xn.double(), None, plan.n_win, starts, plan.weights)
+        assert oc.assert_elementwise(G32, G, e_G, f"stitch {starts}") <= 1.0
+        ref2, e2, _, _, _ = oc.windows_mean_ref_and_bound(xn.double(), e_x, plan.n_win, starts, plan.weights)
+        assert bool((e2 >= e).all()) and torch.equal(ref2, ref)
+        single = cov == 1
+        assert torch.equal(G32[..., single].double(), G[..., single]), "a singly covered frame has weight 1.0 and keeps its bits"
+
+
+def test_flow_mix_emulations_stay_inside_and_unwritten_tail_caught():
+    noise, x0 = _rand((3, 128, 77), 400), _rand((1, 128, 77), 401)
+    for s in (1.0, 0.73, 0.25, 0.0):
+        ref, bound = oc.flow_mix_ref_and_bound(noise, x0, s)
+        sf = _f(s)
+        for name, got in (("mul_add", sf * noise + (1.0 - sf) * x0), ("fma_a", _fma(sf, noise, (1.0 - sf) * x0)),
+                          ("fma_b", _fma(1.0 - sf, x0, sf * noise))):
+            assert oc.assert_elementwise(got, ref, bound, f"flow_mix {name} sigma {s}") <= 1.0
+            if s in (0.0, 1.0):
+                oc.assert_bits_equal(got, (noise if s == 1.0 else x0.expand_as(noise)).contiguous(), f"flow_mix exact {s}")
+
+    def capped(noise, x0, s):      # a kernel whose grid stops at 4096 workgroups of 256: the tail keeps what the buffer held
+        out = torch.full_like(noise, float("nan"))
+        n = min(noise.numel(), 4096 * 256)
+        out.view(-1)[:n] = (_f(s) * noise + (1.0 - _f(s)) * x0).reshape(-1)[:n]
+        return out
+    got = capped(noise, x0, 0.73)                                               # the old shape: nothing to see
+    assert rel_err(got, 0.73 * noise + (1 - 0.73) * x0) < 1e-6
+    big_n, big_x0 = _rand((3, 128, 2800), 402), _rand((1, 128, 2800), 403)
+    ref, bound = oc.flow_mix_ref_and_bound(big_n, big_x0, 0.73)
+    with pytest.raises(AssertionError, match=r"26624 of 1075200 elements outside"):
+        oc.assert_elementwise(capped(big_n, big_x0, 0.73), ref, bound, "flow_mix tail")
+
+
+@pytest.mark.parametrize("odt", DT, ids=IDS)
+def test_rows_add_act_and_add_periodic_emulations(odt):
+    cpu = torch.device("cpu")
+    a, v = _rand((70, 1536), 410, 3.0), _rand((1536,), 411)
+    for aa, vv in ((a, v), (a, None), (None, v)):
+        ref, bound = oc.rows_add_act_ref_and_bound(aa, vv, True, odt, cpu)
+        y = oc.sum32_cast(aa, vv, torch.float32)
+        for name, got in (("division", y / (1.0 + torch.exp(-y))), ("torch", F.silu(y)), ("sigmoid", y * torch.sigmoid(y))):
+            assert oc.assert_elementwise(got.expand(70, 1536).to(odt), ref.expand(70, 1536), bound, f"silu {name}") <= 1.0
+        ref, bound = oc.rows_add_act_ref_and_bound(aa, vv, False, odt, cpu)
+        assert bound is None and torch.equal(oc.sum32_cast(aa, vv, odt).double(), ref.float().to(odt).double())
+    # a row that reads the NEXT row's broadcast element on one tile corner: 1 of 107 520 elements, invisible in a 6e-2 model gate
+    ref, bound = oc.rows_add_act_ref_and_bound(a, v, True, odt, cpu)
+    y = a + v
+    y[69, 1535] = a[69, 1535] + v[0]
+    _missed_and_caught(odt, F.silu(y).to(odt), ref, bound, "wrong broadcast element", gate=6e-2, box=(69, 69, 1535, 1535))
+
+
+def _dac_out_emul(s, w, bias, reverse, drop=None):
+    """dac_out_kernel in fp32: four channel quarters per output, each summed over the taps (forward or reversed), then combined.
+    drop = (b, t): the staged sample row t is missing (zero) for the 64-sample workgroup that starts at t + 1."""
+    B, T, C = s.shape
+    sp = F.pad(s, (0, 0, 3, 3))
+    out = torch.empty(B, T)
+    cq = C // 4
+    taps = list(range(7))[::-1] if reverse else list(range(7))
+    parts = []
+    for p in range(4):
+        acc = torch.zeros(B, T)
+        for j in taps:
+            for c in (range(p * cq, (p + 1) * cq) if not reverse else reversed(range(p * cq, (p + 1) * cq))):
+                acc = acc + sp[:, j:j + T, c] * w[j * C + c]
+        parts.append(acc)
+    acc = (parts[0] + parts[1]) + (parts[2] + parts[3])
+    if drop is not None:
+        b, t = drop
+        for o in range(t + 1, min(t + 4, T)):      # outputs of the next workgroup that read sample t
+            acc[b, o] -= (s[b, t] * w[(t - o + 3) * C:(t - o + 4) * C]).sum()
+    return torch.tanh(acc + bias[0])
+
+
+@pytest.mark.parametrize("T,C", [(1, 64), (3, 64), (63, 64), (64, 96), (65, 64), (300, 64), (300, 96)])
+def test_dac_out_emulations_stay_inside(T, C):
+    s, w, b = _rand((2, T, C), 420), _rand((7 * C,), 421, 0.1), _rand((1,), 422, 0.1)
+    ref, bound, a_act = oc.dac_out_ref_and_bound(s, w, b, torch.device("cpu"))
+    assert a_act < 1e-5
+    for rev in (False, True):
+        assert oc.assert_elementwise(_dac_out_emul(s, w, b, rev), ref, bound, f"dac_out T{T} C{C} reversed {rev}") <= 1.0
+
+
+def test_dac_out_halo_sample_dropped_at_a_seam_is_caught():
+    """Sample 63 of clip 1 missing from the halo of the workgroup that starts at 64: outputs 64..66 lose one tap each (~ 0.05 each).
+    fp32 only, so - as for the other fp32 defects of this file - only the catch is asserted: the 2e-6 norm gate of test_dac_out
+    does see a whole missing tap at T = 300 (the defect moves the norm by ~ 5e-3); what it never looked at are T < 64, T = 64 / 65
+    and C = 96."""
+    T, C = 300, 64
+    s, w, b = _rand((2, T, C), 420), _rand((7 * C,), 421, 0.1), _rand((1,), 422, 0.1)
+    ref, bound, _ = oc.dac_out_ref_and_bound(s, w, b, torch.device("cpu"))
+    bad = _dac_out_emul(s, w, b, False, drop=(1, 63))
+    _missed_and_caught(torch.float32, bad, ref, bound, "halo sample dropped", box=(1, 1, 64, 66))
+
+
+@pytest.mark.parametrize("T", [1, 3, 63, 64, 65, 300])
+def test_dac_in_emulations_stay_inside(T):
+    C = 64
+    x, w, b = _rand((2, T), 430), _rand((7, C), 431, 0.4), _rand((C,), 432, 0.1)
+    alpha = torch.cat((torch.tensor([1e-3, 1e-2, 0.05, 0.3]), 1 + 0.2 * _rand((C - 4,), 433).abs()))
+    y64, s64, b0, b1, a_act = oc.dac_in_ref_and_bounds(x, w, b, alpha, torch.device("cpu"))
+    xp = F.pad(x, (3, 3))
+    for fma, rev in ((True, False), (False, True)):
+        acc = b.expand(2, T, C).clone()
+        for j in (range(6, -1, -1) if rev else range(7)):
+            xv = xp[:, j:j + T, None]
+            acc = _fma(xv, w[j], acc) if fma else acc + xv * w[j]
+        y = acc.reshape(2 * T, C)
+        sn = torch.sin(alpha * y)
+        inv = 1.0 / (alpha + 1e-9)
+        snake = _fma(inv, sn * sn, y) if fma else y + inv * (sn * sn)
+        assert oc.assert_elementwise(y, y64, b0, f"dac_in out0 T{T}") <= 1.0
+        assert oc.assert_elementwise(snake, s64, b1, f"dac_in out1 T{T}") <= 1.0
+
+
+def _wave_sum(t):
+    """Butterfly over the 64 lanes (last dimension), fp32."""
+    w = 64
+    while w > 1:
+        w //= 2
+        t = t[..., :w] + t[..., w:2 * w]
+    return t
+
+
+def _qkv_emul(y, gain, cos, sin, eps, fma, butterfly):
+    """qkv_split_kernel's role (1) in fp32 on y [n, H, 128]."""
+    y0, y1 = y[..., 0::2], y[..., 1::2]
+    if gain is not None:
+        sq = _fma(y0, y0, y1 * y1) if fma else y0 * y0 + y1 * y1
+        ss = _wave_sum(sq) if butterfly else sq.sum(-1, keepdim=True)
+        rinv = torch.rsqrt(ss * (1.0 / 128.0) + _f(eps))
+        y0, y1 = y0 * rinv * gain[0::2], y1 * rinv * gain[1::2]
+    if cos is not None:
+        c, s = cos[:, None], sin[:, None]
+        z0 = _fma(y0, c, -(y1 * s)) if fma else y0 * c - y1 * s
+        z1 = _fma(y1, c, y0 * s) if fma else y1 * c + y0 * s
+        y0, y1 = z0, z1
+    return torch.stack((y0, y1), -1).flatten(-2)
+
+
+@pytest.mark.parametrize("odt", DT, ids=IDS)
+@pytest.mark.parametrize("eps", [1e-6, 1.1920928955078125e-07])
+def test_qkv_split_standalone_emulations_stay_inside(odt, eps):
+    """The constant 8 of head_split_bound's rounding term on its own (e_y = 0): every order stays inside, heads of very different
+    scale and a gain of mixed sign included."""
+    tb = _tables()
+    n, H = 77 * 2, 3
+    y = _rand((n, H, 128), 440) * torch.logspace(-3, 3, n * H).view(n, H, 1)
+    gain = (1 + 0.1 * _rand((128,), 441)) * torch.where(torch.arange(128) % 5 == 0, -1.0, 1.0)
+    cos, sin = tb.rope_table(400)
+    pos = torch.randperm(n, generator=torch.Generator().manual_seed(1)) * 2
+    for g, p in ((gain, pos), (gain, None), (None, pos), (None, None)):
+        c, s = (cos[p], sin[p]) if p is not None else (None, None)
+        ref, bound = oc.qkv_head_ref_and_bound(y, g, c, s, eps, odt)
+        worst = 0.0
+        for fma in (False, True):
+            for fly in (False, True):
+                got = _qkv_emul(y, g, c, s, eps, fma, fly).to(odt)
+                worst = max(worst, oc.assert_elementwise(got, ref, bound, f"qkv gain {g is not None} pos {p is not None} fma {fma}"))
+        assert worst <= 1.0
+    # one wrong element at a tile corner: the last pair of the last head of the last row rotated with the NEXT position's angle
+    ref, bound = oc.qkv_head_ref_and_bound(y[:, :, :], gain, cos[pos], sin[pos], eps, odt)
+    bad = _qkv_emul(y, gain, cos[pos], sin[pos], eps, False, True)
+    p2 = pos.clone()
+    p2[-1] += 1
+    bad[-1, -1, 126:] = _qkv_emul(y, gain, cos[p2], sin[p2], eps, False, True)[-1, -1, 126:]
+    if odt == torch.float32:
+        _missed_and_caught(odt, bad.to(odt).view(n * H, 128), ref.view(n * H, 128), oc.Bound(bound.e.reshape(n * H, 128), odt), "neighbour's angle",
+                           box=(n * H - 1, n * H - 1, 126, 127))
+
+
+def _vt_emul(qkv, B, L, H, nK, pitch, tok_off, dt, skip_second_half=False):
+    """Role (2) of qkv_split_kernel: V tiles of 32 tokens written transposed, 16 tokens per thread half; the destination starts as
+    zeros (what the old tests allocate)."""
+    v = qkv.view(B, L, nK, H, 128)[:, :, nK - 1].to(dt)                     # [B, L, H, 128]
+    out = torch.zeros(B, H, 128, pitch, dtype=dt)
+    for l0 in range(0, L, 32):
+        for half in range(2):
+            if skip_second_half and half == 1:
+                continue
+            lo, hi = l0 + half * 16, min(l0 + half * 16 + 16, L)
+            if lo < hi:
+                out[..., tok_off + lo:tok_off + hi] = v[:, lo:hi].permute(0, 2, 3, 1)
+    return out
+
+
+def test_vt_half_tile_not_written_passes_the_old_shape_and_fails_the_new():
+    dt = torch.bfloat16
+    for L, seen in ((11, False), (17, True), (33, True), (77, True)):
+        qkv = _rand((2 * L, 3 * 3 * 128), 450)
+        want = _vt_emul(qkv, 2, L, 3, 3, 96, 4, dt)
+        assert torch.equal(want[..., 4:4 + L], qkv.view(2, L, 3, 3, 128)[:, :, 2].permute(0, 2, 3, 1).to(dt))
+        bad = _vt_emul(qkv, 2, L, 3, 3, 96, 4, dt, skip_second_half=True)
+        if not seen:      # test_qkv_split_bf16_transposed_v's L = 11: no token ever reaches the second half
+            assert torch.equal(bad, want)
+        else:
+            with pytest.raises(AssertionError, match="differ in their bits"):
+                oc.assert_bits_equal(bad, want, f"V^T L {L}")
+
+
+def test_stale_first_cfg_copy_of_rows_passes_the_old_assertion_and_fails_the_new():
+    clips, C, L = 2, 128, 50
+    x_prev, x = _rand((clips, C, L), 460), _rand((clips, C, L), 461)
+    for dt in DT:
+        rows = oc.rows_of(x, 2, dt)
+        rows.view(2, clips, L, C)[0] = oc.rows_of(x_prev, 1, dt).view(clips, L, C)      # the unconditional half still holds the last step
+        assert rel_err(rows.view(2, clips, L, C)[-1].float(), x.transpose(1, 2)) < (2e-6 if dt == torch.float32 else 1e-2)   # all the old test looked at
+        with pytest.raises(AssertionError, match=r"rows \[0, 99\]"):
+            oc.assert_bits_equal(rows, oc.rows_of(x, 2, dt), "rows_out")
+
+
+def test_tile_corner_off_by_64_ulp_passes_the_step_gates_and_is_caught():
+    """x[1, 31, 31] - the last element of the first 32 x 32 tile - moved by 64 ulp: 8e-6 of a tensor whose norm is ~ 113, far inside
+    the 2e-6 / 1e-6 relative norm gates of test_solver_step / test_blend_step_op / test_windows_step_op."""
+    tb = _tables()
+    clips, C, L, ncfg = 2, 128, 50, 2
+    coef = tb.solver_table(tb.sigma_grid(8), "euler", 8)
+    x, pred = _rand((clips, C, L), 470), _rand((ncfg * clips * L, C), 471)
+    r = oc.solver_step_ref_and_bounds(pred, x, None, None, coef[0], ncfg, 4.5)
+    xn, _, _ = _step_emul(pred, x, None, None, coef[0], ncfg, 4.5, False)
+    bad = xn.clone()
+    bad[1, 31, 31] = (bad[1, 31, 31].view(torch.int32) + 64).view(torch.float32)
+    assert rel_err(bad, r["x"][0]) < 1e-6
+    with pytest.raises(AssertionError, match=r"1 of 12800 elements outside"):
+        oc.assert_elementwise(bad, *r["x"], "x")
+
+
+def test_periodic_flags_reference_and_a_checker_that_skips_the_last_row():
+    """opcheck.periodic_flags compares BIT PATTERNS: + 0.0 against - 0.0 differs, equal NaN patterns agree.  A checker that never
+    reaches the last row of the last group (a grid one workgroup short) misses one flipped bit there."""
+    groups, rows, D = 3, 16, 1536
+    base = _rand((groups, 8, D), 480)
+    base[1, 3, 5] = float("nan")
+    base[2, 0, 0] = 0.0
+    x = base.repeat(1, 2, 1)
+    assert oc.periodic_flags(x, 8).tolist() == [0, 0, 0]
+    z = x.clone()
+    z[2, 8, 0] = -0.0
+    assert oc.periodic_flags(z, 8).tolist() == [0, 0, 1]
+    y = x.clone()
+    y.view(torch.int32)[2, 15, D - 1] ^= 1
+    assert oc.periodic_flags(y, 8).tolist() == [0, 0, 1]
+    assert oc.periodic_flags(y[:, :8], 8).tolist() == [0, 0, 0]                 # rows <= period: nothing is compared
+    skipping = (y.view(torch.int32)[:, 8:15] != y.view(torch.int32)[:, :7]).flatten(1).any(1).to(torch.int32)
+    assert skipping.tolist() == [0, 0, 0] != oc.periodic_flags(y, 8).tolist()
+
+
+def test_assert_bits_equal_nan_and_signed_zero():
+    a = torch.tensor([[1.0, 0.0, float("nan")]])
+    oc.assert_bits_equal(a, a.clone(), "same")
+    with pytest.raises(AssertionError, match=r"\(row 0, col 1\)"):
+        oc.assert_bits_equal(torch.tensor([[1.0, -0.0, float("nan")]]), a, "signed zero")
+    other_nan = a.clone()
+    other_nan.view(torch.int32)[0, 2] ^= 1
+    with pytest.raises(AssertionError):
+        oc.assert_bits_equal(other_nan, a, "payload")
+    oc.assert_bits_equal(other_nan, a, "payload", nan_ok=True)

@@ -928,7 +928,8 @@ def test_solver_step(dev, solver, ncfg):
         v = p[0] + g * (p[1] - p[0]) if ncfg == 2 else p[0]
         xr = st.step(v, xr)
         assert rel_err(x, xr) < 2e-6, (solver, i)
-        assert rel_err(rows.view(ncfg, clips, L, C)[-1], xr.transpose(1, 2)) < 2e-6
+        for c in range(ncfg):                  # every CFG copy of the staged rows, not only the last
+            assert rel_err(rows.view(ncfg, clips, L, C)[c], xr.transpose(1, 2)) < 2e-6, (solver, i, c)
     assert int(ctr.item()) == n
 
 
