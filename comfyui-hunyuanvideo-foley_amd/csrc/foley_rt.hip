@@ -188,7 +188,7 @@ static_assert(std::has_unique_object_representations_v<RunLayout>, "RunLayout is
 // Everything a captured loop iteration depends on beyond the workspace dimensions (a change of those frees the plan and the
 // graph with it).  foley_sample compares the key of the capture with the current one; nothing else decides a graph's validity.
 struct GraphKey {
-  float guidance = 0.f;             // a launch argument of the solver step
+  float guidance = 0.f;             // a launch argument of the solver step; 0 when a schedule table replaces it (never read then)
   int edit = 0;                     // edit_key(): plain vs edit iteration, clip strides of the edit operands
   std::vector<int32_t> set_maps;    // text_of ++ vis_of (empty: foley_prepare)
   RunLayout layout;
@@ -196,12 +196,16 @@ struct GraphKey {
   const void *edit_x0 = nullptr, *edit_noise = nullptr, *edit_mask = nullptr;
   int n_win = 0, Ltot = 0;          // windows state (foley_set_windows; 0: none): the step kernel and its grid
   const void *win_starts = nullptr, *win_weights = nullptr;
+  // guidance state (foley_set_guidance): the schedule table (null: off - the scalar `guidance`) and the rescale buffers (null:
+  // off; on adds the two statistics launches, another topology).  New values of either only rewrite what a replay reads.
+  const void *guid_sched = nullptr, *guid_scale = nullptr, *guid_part = nullptr, *guid_phi = nullptr;
   uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
   uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
   bool operator==(const GraphKey& o) const {
     return guidance == o.guidance && edit == o.edit && set_maps == o.set_maps && layout == o.layout && smod_tab == o.smod_tab &&
            edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && n_win == o.n_win && Ltot == o.Ltot &&
-           win_starts == o.win_starts && win_weights == o.win_weights && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
+           win_starts == o.win_starts && win_weights == o.win_weights && guid_sched == o.guid_sched && guid_scale == o.guid_scale &&
+           guid_part == o.guid_part && guid_phi == o.guid_phi && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
   }
 };
 
@@ -225,6 +229,7 @@ struct foley_ctx {
   // one captured loop iteration and what it was captured for
   hipGraphExec_t graph_exec = nullptr;
   GraphKey graph_key;
+  uint64_t graph_captures = 0;      // iterations captured so far (foley_debug_run_state)
   // edit state (foley_set_edit; cleared by foley_prepare): ctx-owned copies of the source latents, the run's noise and the mask
   bool edit = false;
   DevBuf edit_x0, edit_noise, edit_mask;
@@ -233,6 +238,11 @@ struct foley_ctx {
   int n_win = 0, win_Ltot = 0;      // n_win 0: the clips are independent
   DevBuf win_starts, win_weights;
   std::vector<int32_t> win_starts_host;   // the source of the asynchronous copy stays alive with the context
+  // guidance state (foley_set_guidance; cleared by foley_prepare): ctx-owned schedule table [n_iter][2] followed by phi, the
+  // per-workgroup statistics and the per-clip factors
+  bool guid_sched_on = false, guid_rescale_on = false;
+  DevBuf guid_sched, guid_part, guid_scale;
+  std::vector<float> guid_host;           // [n_iter*2 + 1] source of the copy
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -437,7 +447,8 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   ctx_free_plan(c);
-  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights}) release(*b);
+  for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights, &c->guid_sched,
+                    &c->guid_part, &c->guid_scale}) release(*b);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   for (auto e : c->prof.pool) hipEventDestroy(e);
@@ -536,7 +547,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   hipStream_t st = (hipStream_t)stream_v;
   HIPTRY(hipSetDevice(c->device));
   const foley_config& f = c->cfg;
-  if (pl->ncfg < 1 || pl->ncfg > 2 || pl->clips < 1 || pl->La < 1 || pl->Lv < 1 || pl->Ls < 8 || pl->Ls % 8 ||
+  if (pl->ncfg < 1 || pl->ncfg > 3 || pl->clips < 1 || pl->La < 1 || pl->Lv < 1 || pl->Ls < 8 || pl->Ls % 8 ||
       pl->Lt < 1 || pl->n_iter < 1)
     return FAIL(FOLEY_ERR_INVALID, "bad plan dimensions");
   if (pl->rope_len < 2 * pl->La) return FAIL(FOLEY_ERR_INVALID, "rope table shorter than 2*La");
@@ -581,6 +592,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   c->prepared = false;
   c->edit = false;                  // a plan without foley_set_edit is a plain run
   c->n_win = 0;                     // and one without foley_set_windows has independent clips
+  c->guid_sched_on = c->guid_rescale_on = false;   // and one without foley_set_guidance combines with the plan's scalar
   RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
   c->vis_src = n_vis;
   const int th = ly.th, vh = ly.vh;
@@ -1208,6 +1220,12 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
   s.clips = pl.clips; s.C = c->cfg.latent_dim; s.L = pl.La; s.ncfg = pl.ncfg;
   s.guidance = pl.guidance; s.coef = pl.solver_coef; s.step_ptr = c->buf.step_ctr;
   s.rows_out = c->buf.xin; s.rows_dtype = c->cfg.compute_dtype;
+  if (c->guid_sched_on) s.sched = (const float*)c->guid_sched.p;
+  if (c->guid_rescale_on) {   // the factors of this iteration's prediction, before the step applies them (a window is a clip)
+    const float* phi = (const float*)c->guid_sched.p + 2 * (size_t)pl.n_iter;
+    TRY(launch_guidance_stats(s, (float*)c->guid_part.p, phi, 0.f, (float*)c->guid_scale.p, st));
+    s.clip_scale = (const float*)c->guid_scale.p;
+  }
   if (c->edit) {
     StepEditArgs e{};
     e.s = s;
@@ -1238,9 +1256,12 @@ static int edit_key(const foley_ctx* c) {
 // those of the windows tables (new starts with the same n_win and total length only rewrite what a replay reads).
 static GraphKey graph_key_now(const foley_ctx* c) {
   const bool win = c->n_win > 0;
-  return GraphKey{c->plan.guidance, edit_key(c), c->set_maps,   c->layout,     c->smod_tab.p,
+  return GraphKey{c->guid_sched_on ? 0.f : c->plan.guidance, edit_key(c), c->set_maps,   c->layout,     c->smod_tab.p,
                   c->edit_x0.p,     c->edit_noise.p, c->edit_mask.p,
                   c->n_win,         win ? c->win_Ltot : 0, win ? c->win_starts.p : nullptr, win ? c->win_weights.p : nullptr,
+                  c->guid_sched_on ? c->guid_sched.p : nullptr, c->guid_rescale_on ? c->guid_scale.p : nullptr,
+                  c->guid_rescale_on ? c->guid_part.p : nullptr,
+                  c->guid_rescale_on ? (const void*)((const float*)c->guid_sched.p + 2 * (size_t)c->plan.n_iter) : nullptr,
                   c->tensor_gen,    c->plan_gen};
 }
 
@@ -1305,6 +1326,51 @@ extern "C" int foley_set_windows(foley_ctx* c, int n_win, const int32_t* starts,
   return 0;
 }
 
+extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, float rescale, void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_guidance: foley_prepare has not been called");
+  if (!sched && rescale == 0.f) {   // nothing to apply: the plan's scalar guidance
+    c->guid_sched_on = c->guid_rescale_on = false;
+    return 0;
+  }
+  const foley_plan& pl = c->plan;
+  if (pl.ncfg == 1) return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: the plan has one half (ncfg 1): there is nothing to guide");
+  if (sched && n_rows != pl.n_iter)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: the schedule must have one row per iteration of the plan (n_rows == n_iter)");
+  if (!(rescale >= 0.f && rescale <= 1.f)) return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: rescale must lie in [0, 1]");
+  if (rescale > 0.f && c->cfg.latent_dim > 256)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: rescale serves at most 256 latent channels (guidance_stats_kernel)");
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the buffers may be in use by a previous loop on this stream
+  const size_t nf = 2 * (size_t)pl.n_iter + 1;
+  TRY(grow(c->guid_sched, nf * 4));
+  if (rescale > 0.f) {
+    TRY(grow(c->guid_part, (size_t)guidance_stats_floats(pl.clips, pl.La) * 4));
+    TRY(grow(c->guid_scale, (size_t)pl.clips * 4));
+  }
+  c->guid_host.assign(nf, pl.guidance);   // without a table the rows are never read
+  if (sched) std::copy(sched, sched + 2 * (size_t)pl.n_iter, c->guid_host.begin());
+  c->guid_host[nf - 1] = rescale;
+  HIPTRY(hipMemcpyAsync(c->guid_sched.p, c->guid_host.data(), nf * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));   // guid_host may be rewritten by the next call
+  c->guid_sched_on = sched != nullptr;
+  c->guid_rescale_on = rescale > 0.f;
+  return 0;
+}
+
+// Test-only (not in include/foley_hip.h): out[0] = iterations captured into a graph so far, out[1..3] = addresses of the model
+// input rows (the workspace), the schedule table and the rescale factors - what a replay of the captured iteration addresses.
+extern "C" int foley_debug_run_state(foley_ctx* c, uint64_t* out) {
+  if (!c || !out) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  out[0] = c->graph_captures;
+  out[1] = (uint64_t)(uintptr_t)c->buf.xin;
+  out[2] = (uint64_t)(uintptr_t)c->guid_sched.p;
+  out[3] = (uint64_t)(uintptr_t)c->guid_scale.p;
+  return 0;
+}
+
 extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_progress_cb cb, void* user,
                             void* stream_v) {
   if (!c || !latents) return FAIL(FOLEY_ERR_INVALID, "null argument");
@@ -1337,6 +1403,7 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
     if (rc != 0) return rc;
     if (e != hipSuccess) return FAIL(FOLEY_ERR_HIP, hipGetErrorString(e));
     c->graph_key = std::move(key);
+    ++c->graph_captures;
   }
   c->abort_req.store(0, std::memory_order_relaxed);   // a request left over from before this loop is not for it
   HIPTRY(hipEventRecord(c->ev0, st));
@@ -1787,6 +1854,54 @@ extern "C" int foley_op_solver_step_windows(const float* pred, float* x, float* 
   w.s = StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
   w.n_win = n_win; w.Ltot = Ltot; w.starts = starts; w.weights = weights;
   return launch_solver_step_windows(w, (hipStream_t)stream);
+}
+
+// The three step forms with a guidance descriptor, and the statistics behind its factors
+static StepArgs step_args_guided(const foley_guidance_desc* gd, StepArgs s) {
+  if (gd) {
+    s.sched = gd->sched;
+    s.clip_scale = gd->clip_scale;
+  }
+  return s;
+}
+
+extern "C" int foley_op_solver_step_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
+                                           int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
+                                           void* rows_out, int rows_dtype, void* stream) {
+  return launch_solver_step(step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype}),
+                            (hipStream_t)stream);
+}
+
+extern "C" int foley_op_solver_step_edit_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
+                                                int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
+                                                void* rows_out, int rows_dtype, const float* x0, int x0_clips, const float* noise,
+                                                const float* mask, int mask_clips, void* stream) {
+  StepEditArgs e{};
+  e.s = step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype});
+  e.x0 = x0; e.noise = noise; e.mask = mask; e.x0_clips = x0_clips; e.mask_clips = mask_clips;
+  return launch_solver_step_edit(e, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved,
+                                                   float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
+                                                   int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
+                                                   const float* weights, int Ltot, void* stream) {
+  StepWinArgs w{};
+  w.s = step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype});
+  w.n_win = n_win; w.Ltot = Ltot; w.starts = starts; w.weights = weights;
+  return launch_solver_step_windows(w, (hipStream_t)stream);
+}
+
+extern "C" int64_t foley_op_guidance_stats_work(int clips, int L) { return clips < 1 || L < 1 ? 0 : (int64_t)guidance_stats_floats(clips, L); }
+
+extern "C" int foley_op_guidance_stats(const foley_guidance_desc* gd, const float* pred, int clips, int C, int L, int ncfg, float guidance,
+                                       const int32_t* step_ptr, float rescale, float* work, int64_t work_floats, void* stream) {
+  if (!gd || !gd->clip_scale) return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_stats: the descriptor's clip_scale receives the factors");
+  if (clips < 1 || L < 1 || !work || work_floats < (int64_t)guidance_stats_floats(clips, L))
+    return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_stats: work buffer smaller than foley_op_guidance_stats_work(clips, L) floats");
+  StepArgs s{pred, nullptr, nullptr, nullptr, clips, C, L, ncfg, guidance, nullptr, (int*)step_ptr, nullptr, FOLEY_F32};
+  s.sched = gd->sched;
+  return launch_guidance_stats(s, work, nullptr, rescale, (float*)gd->clip_scale, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int32_t* starts,

@@ -214,8 +214,18 @@ struct StepArgs {
   int* step_ptr;       // device iteration counter (incremented by the kernel)
   void* rows_out;      // next model input rows (T), cfg-duplicated
   int rows_dtype;
+  // guidance descriptor (null: the scalar `guidance` and no factor - the plain run's arithmetic bit for bit)
+  const float* sched = nullptr;       // [n_iter][2] {g_video, g_text} per iteration, read at row *step_ptr; ncfg 2 reads column 0
+  const float* clip_scale = nullptr;  // [clips] CFG-rescale factor of this iteration (launch_guidance_stats), multiplied into v
 };
 int launch_solver_step(const StepArgs& a, hipStream_t st);
+// CFG rescale: clip_scale[b] = phi * std(last half of clip b) / std(guided v of clip b) + (1 - phi) over the clip's C x L elements
+// (1.0f when the guided std is 0), from `a.pred` at iteration *a.step_ptr with the combine of the step kernels (a.clip_scale is
+// not read).  Two launches: per-workgroup centred partial statistics into `part` (guidance_stats_floats(clips, L) floats), then
+// one wave per clip merges them in a fixed order - no atomics, repeated runs give the same bits.  phi is read from *phi_ptr when
+// that is set (a captured graph then replays with a new value), from `phi` otherwise.
+long guidance_stats_floats(int clips, int L);
+int launch_guidance_stats(const StepArgs& a, float* part, const float* phi_ptr, float phi, float* clip_scale, hipStream_t st);
 // Edit form of the same step (audio-to-audio / span regeneration): after a row flagged STEP_BLEND (8) - the iteration that
 // ends a solver step - x <- m*x + (1-m)*(s*noise + (1-s)*x0) with s = coef row column 5 (sigma_{k+1}); mask null = all ones.
 struct StepEditArgs {

@@ -456,6 +456,30 @@ __global__ __launch_bounds__(256) void latent_rows_kernel(const float* __restric
 // coefficient row {w_new, w_acc, dt, w_store, flags}; then re-stages the next model input rows.
 constexpr int STEP_SAVE_X = 1, STEP_USE_SAVED = 2, STEP_ACC_RESET = 4;
 
+// The one place where the prediction halves of a (row, channel) become the velocity the step uses.  r = b*L + l is the row inside
+// a half, `it` the loop iteration (*step_ptr).  Two halves: v = u + g (c - u); three (h0 = nothing, h1 = video only, h2 = video
+// and prompt): v = p0 + g_video (p1 - p0) + g_text (p2 - p1), left to right.  Without a schedule g = g_video = g_text = the scalar
+// `guidance` and the two-half expression is the one the step kernels always had: plain runs keep their bits.  `scale` (the CFG
+// rescale factors, or null) multiplies the result by scale[b].
+__device__ __forceinline__ float guided_value(const StepArgs& a, int it, int b, long r, int c, const float* __restrict__ scale) {
+  const long half = (long)a.clips * a.L * a.C;
+  const float* p = a.pred + r * a.C + c;
+  float v;
+  if (a.ncfg == 2) {
+    const float g = a.sched ? a.sched[2 * it] : a.guidance;
+    const float u = p[0], cnd = p[half];
+    v = u + g * (cnd - u);
+  } else if (a.ncfg == 3) {
+    const float gv = a.sched ? a.sched[2 * it] : a.guidance, gt = a.sched ? a.sched[2 * it + 1] : a.guidance;
+    const float p0 = p[0], p1 = p[half], p2 = p[2 * half];
+    v = p0 + gv * (p1 - p0) + gt * (p2 - p1);
+  } else {
+    v = p[0];
+  }
+  if (scale) v *= scale[b];
+  return v;
+}
+
 template <typename OutT>
 __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
   __shared__ float tile[32][33];
@@ -466,19 +490,12 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
   const int b = blockIdx.z;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const long rows = (long)a.clips * a.L;
   // phase 1: read pred rows [l][c] (coalesced over c) and transpose through LDS
   for (int i = ty; i < 32; i += 8) {
     const int l = l0 + i, c = c0 + tx;
     float v = 0.f;
     if (l < a.L && c < a.C) {
-      const long r = (long)b * a.L + l;
-      if (a.ncfg == 2) {
-        const float u = a.pred[r * a.C + c], cnd = a.pred[(rows + r) * a.C + c];
-        v = u + a.guidance * (cnd - u);
-      } else {
-        v = a.pred[r * a.C + c];
-      }
+      v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
     }
     tile[i][tx] = v;
   }
@@ -536,18 +553,11 @@ __global__ __launch_bounds__(256) void solver_step_edit_kernel(const StepEditArg
   const int b = blockIdx.z;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const long rows = (long)a.clips * a.L;
   for (int i = ty; i < 32; i += 8) {
     const int l = l0 + i, c = c0 + tx;
     float v = 0.f;
     if (l < a.L && c < a.C) {
-      const long r = (long)b * a.L + l;
-      if (a.ncfg == 2) {
-        const float u = a.pred[r * a.C + c], cnd = a.pred[(rows + r) * a.C + c];
-        v = u + a.guidance * (cnd - u);
-      } else {
-        v = a.pred[r * a.C + c];
-      }
+      v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
     }
     tile[i][tx] = v;
   }
@@ -611,7 +621,6 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinA
   const int b0 = blockIdx.z * w.n_win;
   const int g0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const long rows = (long)a.clips * a.L;
   float xb[4] = {0.f, 0.f, 0.f, 0.f};
   int ncov = 0;
   for (int k = 0; k < w.n_win; ++k) {
@@ -623,13 +632,7 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinA
       const int l = g0 + i - s0, c = c0 + tx;
       float v = 0.f;
       if (l >= 0 && l < a.L && c < a.C) {
-        const long r = (long)b * a.L + l;
-        if (a.ncfg == 2) {
-          const float u = a.pred[r * a.C + c], cnd = a.pred[(rows + r) * a.C + c];
-          v = u + a.guidance * (cnd - u);
-        } else {
-          v = a.pred[r * a.C + c];
-        }
+        v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
       }
       tile[i][tx] = v;
     }
@@ -737,6 +740,112 @@ __global__ __launch_bounds__(256) void flow_mix_kernel(const float* __restrict__
     const float src = x0[x0_per_clip ? i : i % plane];
     out[i] = sigma * noise[i] + (1.f - sigma) * src;
   }
+}
+
+// ------------------------------------------------------------------ CFG rescale: per-clip statistics of the guided velocity
+// clip_scale[b] = phi * s_pos / s_cfg + (1 - phi): s_pos the standard deviation (about the mean) of the last, fully conditioned
+// half over clip b's C x L elements, s_cfg that of the guided v (guided_value without a factor); 1.0f when s_cfg is 0.
+// Launch 1: a workgroup takes GS_ROWS rows of one clip, a wave GS_RW of them - a lane reads channels lane, lane + 64, ... of a
+// row, so every load of the wave is one contiguous run of the pred row - and keeps its elements in registers: the wave's sum (about
+// its first element) gives its provisional centre, the second pass over the registers the squares about it (never E[x^2] - E[x]^2).  The four waves meet
+// in LDS, thread 0 merges them in wave order with the exact pairwise formula (Chan et al., as ln_mod_wide_body does) and stores
+// the workgroup's {n, mean_v, M2_v, mean_p, M2_p}.  Launch 2: one wave per clip; lane j merges records j, j + 64, ... in
+// ascending order, lane 0 then the 64 lanes' results in lane order.  Every order is fixed and nothing is atomic: the same input
+// gives the same bits.  128 x 50 elements per clip: 2 workgroups per clip; 128 x 3000: 94.
+constexpr int GS_ROWS = 32, GS_RW = 8, GS_REC = 5;
+
+// (n, mean, M2) <- merged with (nb, mb, m2b): M2 = M2_a + M2_b + d^2 n_a n_b / n, d = mean_b - mean_a; an empty part changes nothing
+__device__ __forceinline__ void moments_merge(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
+  if (nb == 0.f) return;
+  if (n == 0.f) {
+    n = nb; mean = mb; m2 = m2b;
+    return;
+  }
+  const float nt = n + nb, d = mb - mean;
+  mean += d * (nb / nt);
+  m2 += m2b + d * d * (n * (nb / nt));
+  n = nt;
+}
+// the same for the pair of statistics that share their count (v and the last half)
+__device__ __forceinline__ void moments_merge2(float* acc, const float* rec) {
+  float n2 = acc[0];
+  moments_merge(n2, acc[3], acc[4], rec[0], rec[3], rec[4]);
+  moments_merge(acc[0], acc[1], acc[2], rec[0], rec[1], rec[2]);
+}
+
+template <int JC>
+__global__ __launch_bounds__(256) void guidance_stats_kernel(const StepArgs a, float* __restrict__ part) {
+  __shared__ float red[4][GS_REC];
+  const int it = *a.step_ptr;
+  const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int l0 = blockIdx.x * GS_ROWS + wave * GS_RW;
+  const long last = (long)(a.ncfg - 1) * a.clips * a.L * a.C;
+  float v[GS_RW][JC], p[GS_RW][JC];
+#pragma unroll
+  for (int i = 0; i < GS_RW; ++i)
+#pragma unroll
+    for (int j = 0; j < JC; ++j) {
+      const int l = l0 + i, c = lane + 64 * j;
+      const bool ok = l < a.L && c < a.C;
+      const long r = (long)b * a.L + l;
+      v[i][j] = ok ? guided_value(a, it, b, r, c, nullptr) : 0.f;
+      p[i][j] = ok ? a.pred[last + r * a.C + c] : 0.f;
+    }
+  // the sums are taken about the wave's first element: constant data then has every difference 0, its mean and M2 exact
+  const float cv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v[0][0])));
+  const float cp = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p[0][0])));
+  float sv = 0.f, sp = 0.f;
+#pragma unroll
+  for (int i = 0; i < GS_RW; ++i)
+#pragma unroll
+    for (int j = 0; j < JC; ++j) {
+      const bool ok = l0 + i < a.L && lane + 64 * j < a.C;
+      sv += ok ? v[i][j] - cv : 0.f;
+      sp += ok ? p[i][j] - cp : 0.f;
+    }
+  const int nrow = min(max(a.L - l0, 0), GS_RW);
+  const float n = (float)(nrow * a.C);   // exact in fp32
+  sv = wave_sum(sv);
+  sp = wave_sum(sp);
+  const float mv = nrow ? cv + sv / n : 0.f, mp = nrow ? cp + sp / n : 0.f;
+  float qv = 0.f, qp = 0.f;
+#pragma unroll
+  for (int i = 0; i < GS_RW; ++i)
+#pragma unroll
+    for (int j = 0; j < JC; ++j) {
+      const bool ok = l0 + i < a.L && lane + 64 * j < a.C;
+      const float dv = ok ? v[i][j] - mv : 0.f, dp = ok ? p[i][j] - mp : 0.f;
+      qv += dv * dv;
+      qp += dp * dp;
+    }
+  qv = wave_sum(qv);
+  qp = wave_sum(qp);
+  if (lane == 0) {
+    red[wave][0] = n; red[wave][1] = mv; red[wave][2] = qv; red[wave][3] = mp; red[wave][4] = qp;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float acc[GS_REC] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int w = 0; w < 4; ++w) moments_merge2(acc, red[w]);
+    float* o = part + ((long)b * gridDim.x + blockIdx.x) * GS_REC;
+    for (int k = 0; k < GS_REC; ++k) o[k] = acc[k];
+  }
+}
+
+__global__ __launch_bounds__(64) void guidance_scale_kernel(const float* __restrict__ part, int nblk, const float* __restrict__ phi_ptr,
+                                                            float phi, float* __restrict__ clip_scale) {
+  __shared__ float red[64][GS_REC];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float acc[GS_REC] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int k = lane; k < nblk; k += 64) moments_merge2(acc, part + ((long)b * nblk + k) * GS_REC);
+  for (int k = 0; k < GS_REC; ++k) red[lane][k] = acc[k];
+  __syncthreads();
+  if (lane != 0) return;
+  for (int j = 1; j < 64; ++j) moments_merge2(acc, red[j]);
+  const float ph = phi_ptr ? *phi_ptr : phi;
+  float f = 1.0f;
+  if (acc[2] > 0.f) f = ph * sqrtf(acc[4] / acc[2]) + (1.0f - ph);   // the counts cancel in the ratio of the deviations
+  clip_scale[b] = f;
 }
 
 __global__ void step_increment_kernel(int* p) { *p = *p + 1; }
@@ -1044,6 +1153,25 @@ int launch_solver_step(const StepArgs& a, hipStream_t st) {
   else FOLEY_LAUNCH(solver_step_kernel<float>, grid, block, 0, st, a);
   FOLEY_LAUNCH_CHECK();
   FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+long guidance_stats_floats(int clips, int L) { return (long)clips * ((L + GS_ROWS - 1) / GS_ROWS) * GS_REC; }
+
+int launch_guidance_stats(const StepArgs& a, float* part, const float* phi_ptr, float phi, float* clip_scale, hipStream_t st) {
+  if (!a.pred || !a.step_ptr || !part || !clip_scale || a.clips < 1 || a.clips > 65535 || a.C < 1 || a.L < 1 || a.ncfg < 1 || a.ncfg > 3)
+    return foley_set_err("guidance_stats: pred, step_ptr, work and output buffers required; 1 <= clips <= 65535, ncfg in [1, 3]", __FILE__, __LINE__);
+  if (a.C > 256) return foley_set_err("guidance_stats: at most 256 channels", __FILE__, __LINE__);
+  if ((long)a.clips * a.C * a.L >= (1L << 31) || (long)a.C * a.L >= (1L << 24))
+    return foley_set_err("guidance_stats: clip too large (C*L < 2^24 elements per clip)", __FILE__, __LINE__);
+  const int nblk = (a.L + GS_ROWS - 1) / GS_ROWS;
+  dim3 grid(nblk, a.clips), block(256);
+  if (a.C <= 64) FOLEY_LAUNCH(guidance_stats_kernel<1>, grid, block, 0, st, a, part);
+  else if (a.C <= 128) FOLEY_LAUNCH(guidance_stats_kernel<2>, grid, block, 0, st, a, part);
+  else FOLEY_LAUNCH(guidance_stats_kernel<4>, grid, block, 0, st, a, part);
+  FOLEY_LAUNCH_CHECK();
+  FOLEY_LAUNCH(guidance_scale_kernel, dim3(a.clips), dim3(64), 0, st, (const float*)part, nblk, phi_ptr, phi, clip_scale);
   FOLEY_LAUNCH_CHECK();
   return 0;
 }

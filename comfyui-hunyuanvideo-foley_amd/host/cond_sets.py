@@ -1,6 +1,7 @@
 """Per-clip conditioning: the distinct conditioning sets of a batch and the maps from batch rows to them (pure CPU logic).
 
-A batch row is (cfg half h, clip k), row b = h*clips + k, in the [uncond ; cond] order of utils.py:193-195.  Every row reads one
+A batch row is (cfg half h, clip k), row b = h*clips + k, in the [uncond ; cond] order of utils.py:193-195 - or, with separate
+video and text guidance (`three`), the three halves [negative prompt + empty rows ; negative prompt + video ; prompt + video].  Every row reads one
 text set (its prompt, or its negative prompt in the unconditional half) and one visual set (its SigLIP2 and Synchformer features
 together; the learned empty rows in the unconditional half).  Sets are de-duplicated within each cfg half by exact equality of
 their fp32 rows, so a batch whose clips share their conditioning has exactly one set per half - the plan foley_prepare takes
@@ -20,6 +21,7 @@ class CondSetsError(ValueError):
 
 # A batch whose clips differ in their visual features lays the sync rows out per batch row; the library's periodicity check of
 # those rows serves at most 32 of them (foley_prepare_sets).  Prompts alone have no such cap.
+# 16 clips under CFG, 10 with three guidance halves.
 MAX_VISUAL_ROWS = 32
 
 
@@ -62,19 +64,23 @@ def dedup(rows: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], List[int]]:
 
 
 def build(text: torch.Tensor, unc: torch.Tensor, clip: torch.Tensor, sync: torch.Tensor, empty_clip: torch.Tensor,
-          empty_sync: torch.Tensor, batch_size: int, cfg: bool) -> CondSets:
+          empty_sync: torch.Tensor, batch_size: int, cfg: bool, three: bool = False) -> CondSets:
     """text / unc [1 or batch_size, Lt, C] (padded to one Lt), clip [1 or bs, Lv, C], sync [1 or bs, Ls, C], all fp32;
-    empty_clip / empty_sync: the learned rows [C] that stand for the visual features in the unconditional half under CFG."""
+    empty_clip / empty_sync: the learned rows [C] that stand for the visual features in the unconditional half under CFG.
+    three: the halves of separate video and text guidance - the unconditional half, then the negative prompt with the clip's
+    visual features, then the conditional half; sets are still de-duplicated per half."""
+    if three and not cfg:
+        raise CondSetsError("three halves are a form of classifier-free guidance: cfg must be set")
     for t, n in ((text, "text_feat"), (unc, "uncond_text_feat"), (clip, "siglip2_feat"), (sync, "syncformer_feat")):
         batch_of(t, batch_size, n)
     if text.shape[1:] != unc.shape[1:]:
         raise CondSetsError("text_feat and uncond_text_feat must be padded to one length")
     row = lambda t, k: t[k if t.shape[0] > 1 else 0]
-    halves_t = ([[row(unc, k) for k in range(batch_size)]] if cfg else []) + [[row(text, k) for k in range(batch_size)]]
+    halves_t = ([[row(unc, k) for k in range(batch_size)]] * (2 if three else 1) if cfg else []) + [[row(text, k) for k in range(batch_size)]]
     Lv, Ls = clip.shape[1], sync.shape[1]
     e_clip = empty_clip.reshape(1, -1).to(clip).expand(Lv, -1)
     e_sync = empty_sync.reshape(1, -1).to(sync).expand(Ls, -1)
-    halves_v = ([[(e_clip, e_sync)] * batch_size] if cfg else []) + [[(row(clip, k), row(sync, k)) for k in range(batch_size)]]
+    halves_v = ([[(e_clip, e_sync)] * batch_size] if cfg else []) + [[(row(clip, k), row(sync, k)) for k in range(batch_size)]] * (2 if three else 1)
     t_sets: List[torch.Tensor] = []
     v_sets: List[Tuple[torch.Tensor, torch.Tensor]] = []
     text_of: List[int] = []
@@ -94,7 +100,7 @@ def build(text: torch.Tensor, unc: torch.Tensor, clip: torch.Tensor, sync: torch
         out.text_of = out.vis_of = None
     elif vis_of != per_half and len(vis_of) > MAX_VISUAL_ROWS:
         raise CondSetsError(f"per-clip visual features take at most {MAX_VISUAL_ROWS} batch rows ({MAX_VISUAL_ROWS // ncfg} clips"
-                            f"{' under CFG' if cfg else ''}); this batch has {len(vis_of)}: split it into smaller batches")
+                            f"{' with three guidance halves' if three else ' under CFG' if cfg else ''}); this batch has {len(vis_of)}: split it into smaller batches")
     return out
 
 

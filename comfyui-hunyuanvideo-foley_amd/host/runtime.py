@@ -92,6 +92,11 @@ class GemmDescC(C.Structure):
     ]
 
 
+class GuidanceDescC(C.Structure):
+    """foley_guidance_desc: device pointers of the schedule table [n_iter, 2] and the per-clip factors [clips] (0: absent)."""
+    _fields_ = [("sched", C.c_void_p), ("clip_scale", C.c_void_p)]
+
+
 class ProfEntryC(C.Structure):
     _fields_ = [("label", C.c_char * 80), ("calls", C.c_int32), ("total_ms", C.c_float), ("flop", C.c_double),
                 ("bytes", C.c_double), ("kernel", C.c_char * 200)]
@@ -122,6 +127,7 @@ _SIGNATURES = {
     "foley_abort": (C.c_int, [C.c_void_p]),
     "foley_set_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_set_windows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "foley_set_guidance": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p]),
     "foley_dac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                    C.c_void_p, C.c_void_p]),
@@ -164,6 +170,15 @@ _SIGNATURES = {
                                                                                   C.c_void_p]),
     "foley_op_windows_stitch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "foley_op_solver_step_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
+        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_solver_step_edit_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
+        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_solver_step_windows_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
+        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_guidance_stats_work": (C.c_int64, [C.c_int, C.c_int]),
+    "foley_op_guidance_stats": (C.c_int, [C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     "foley_op_flow_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                     C.c_void_p]),
     "foley_op_latent_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -454,6 +469,19 @@ class FoleyContext:
             weights = weights.contiguous()
             arr = (C.c_int32 * len(starts))(*starts)
             _check(self.lib, self.lib.foley_set_windows(self._h, len(starts), arr, _ptr(weights), _stream()), "foley_set_windows")
+
+    def set_guidance(self, sched: Optional[torch.Tensor], rescale: float = 0.0):
+        """foley_set_guidance after prepare(): `sched` [n_iter, 2] fp32 rows {g_video, g_text} per loop iteration (any device;
+        the library copies it from the host), `rescale` phi in [0, 1].  sched None and rescale 0 clear the state."""
+        arr, n = None, 0
+        if sched is not None:
+            t = sched.detach().to("cpu", torch.float32).contiguous()
+            if t.dim() != 2 or t.shape[1] != 2:
+                raise FoleyRuntimeError("set_guidance: the schedule is [n_iter, 2] (g_video, g_text per iteration)")
+            n = int(t.shape[0])
+            arr = (C.c_float * (2 * n))(*t.flatten().tolist())
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_set_guidance(self._h, arr, n, float(rescale), _stream()), "foley_set_guidance")
 
     def abort(self) -> None:
         """Ask a foley_sample running on another thread to stop after its current iteration (it raises FoleyRuntimeError)."""
@@ -841,6 +869,51 @@ def op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_p
                                                  float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
                                                  n_win, _ptr(starts), _ptr(weights), int(Ltot), _stream()),
            "foley_op_solver_step_windows")
+
+
+def guidance_desc(sched: Optional[torch.Tensor] = None, clip_scale: Optional[torch.Tensor] = None) -> GuidanceDescC:
+    """Descriptor of the guided op entries: sched [n_iter, 2] fp32 and clip_scale [clips] fp32 device tensors (None: absent)."""
+    for t, what in ((sched, "sched"), (clip_scale, "clip_scale")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise FoleyRuntimeError(f"guidance_desc: {what} must be a contiguous fp32 tensor")
+    if sched is not None and (sched.dim() != 2 or sched.shape[1] != 2):
+        raise FoleyRuntimeError("guidance_desc: sched is [n_iter, 2]")
+    return GuidanceDescC(_ptr(sched), _ptr(clip_scale))
+
+
+def op_solver_step_guided(gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, edit=None, windows=None):
+    """The step forms with a guidance descriptor: plain, edit=(x0, noise, mask) or windows=(starts, weights, Ltot)."""
+    lib = load_library()
+    clips, Cc, L = x.shape
+    head = (C.byref(gd) if gd is not None else None, _ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
+            float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out))
+    if edit is not None:
+        x0, noise, mask = edit
+        mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
+        _check(lib, lib.foley_op_solver_step_edit_guided(*head, _ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips, _stream()),
+               "foley_op_solver_step_edit_guided")
+    elif windows is not None:
+        starts, weights, Ltot = windows
+        n_win = _windows_tables(x, starts, weights)
+        _check(lib, lib.foley_op_solver_step_windows_guided(*head, n_win, _ptr(starts), _ptr(weights), int(Ltot), _stream()),
+               "foley_op_solver_step_windows_guided")
+    else:
+        _check(lib, lib.foley_op_solver_step_guided(*head, _stream()), "foley_op_solver_step_guided")
+
+
+def op_guidance_stats(pred, clips, L, ncfg, guidance, sched, step_ptr, rescale, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """foley_op_guidance_stats: pred [ncfg*clips*L, C] fp32 -> the rescale factors [clips] fp32 (new, or `out`)."""
+    lib = load_library()
+    if pred.dtype != torch.float32 or pred.dim() != 2 or pred.shape[0] != ncfg * clips * L:
+        raise FoleyRuntimeError("op_guidance_stats: pred [ncfg*clips*L, C] fp32")
+    if out is None:
+        out = torch.empty(clips, dtype=torch.float32, device=pred.device)
+    n = int(lib.foley_op_guidance_stats_work(clips, L))
+    work = torch.empty(max(n, 1), dtype=torch.float32, device=pred.device)
+    gd = guidance_desc(sched, out)
+    _check(lib, lib.foley_op_guidance_stats(C.byref(gd), _ptr(pred), clips, int(pred.shape[1]), L, ncfg, float(guidance),
+                                            _ptr(step_ptr), float(rescale), _ptr(work), n, _stream()), "foley_op_guidance_stats")
+    return out
 
 
 def op_windows_stitch(x: torch.Tensor, starts: torch.Tensor, weights: torch.Tensor, Ltot: int) -> torch.Tensor:

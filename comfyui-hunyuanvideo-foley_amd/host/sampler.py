@@ -8,7 +8,8 @@ tables; every FLOP of the hot path runs in the HIP library.
 from __future__ import annotations
 
 import threading
-from typing import Callable, Dict, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -143,14 +144,46 @@ def fp8_time_dtype(model):
     return torch.float8_e4m3fn if model.quantization == "fp8_e4m3fn" else torch.float8_e5m2
 
 
+@dataclass(frozen=True)
+class GuidanceSpec:
+    """How the prediction halves become one velocity, beyond the scalar `guidance_scale` (which stays the text scale and the
+    only scale of a two-half run).
+      g_video   not None: three halves - h0 negative prompt + the learned empty visual rows, h1 negative prompt + the clip's
+                visual features, h2 prompt + the same features - combined as v = p0 + g_video (p1 - p0) + g_text (p2 - p1).
+      interval  (start, end) in fractions of the loop: the scales hold on the iterations with start <= i / n_iter < end, the
+                others use (1, 1).  Every half still runs on every iteration (the run keeps its shape).
+      rescale   phi in [0, 1]: the step uses f v, f = phi std(h_last) / std(v) + (1 - phi) per clip (windows: per window)."""
+    g_video: Optional[float] = None
+    interval: Optional[Tuple[float, float]] = None
+    rescale: float = 0.0
+
+    def check(self, guidance_scale: float) -> None:
+        if not 0.0 <= float(self.rescale) <= 1.0:
+            raise ValueError(f"guidance rescale must lie in [0, 1], got {self.rescale}")
+        if self.g_video is None and not guidance_scale > 1.0 and (self.interval is not None or self.rescale > 0.0):
+            raise ValueError("a guidance interval / rescale needs guidance: guidance_scale > 1 or a video scale (g_video)")
+
+
+def apply_guidance(ctx: FoleyContext, plan: dict) -> None:
+    """foley_set_guidance with what build_plan put into the plan (after prepare, next to set_edit / set_windows)."""
+    if plan.get("guid_sched") is not None or plan.get("guid_rescale", 0.0) > 0.0:
+        ctx.set_guidance(plan.get("guid_sched"), plan.get("guid_rescale", 0.0))
+
+
 def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_feats: Dict[str, torch.Tensor],
                La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str,
-               edit_i0: Optional[int] = None) -> dict:
+               edit_i0: Optional[int] = None, guidance: Optional[GuidanceSpec] = None) -> dict:
     """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables.
     edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows.
     Each conditioning tensor has batch 1 (shared by all clips) or batch_size (one row per clip, host/cond_sets.py): the plan
-    then holds the distinct sets and the maps `text_of` / `vis_of` (None when every clip shares its conditioning)."""
+    then holds the distinct sets and the maps `text_of` / `vis_of` (None when every clip shares its conditioning).
+    guidance (GuidanceSpec): three halves when it carries a video scale, and the schedule table / rescale value that
+    apply_guidance hands to the library after prepare (`guid_sched`, `guid_rescale`)."""
     cfg, dev = model.cfg, model.device
+    if guidance is not None:
+        guidance.check(guidance_scale)
+    three = guidance is not None and guidance.g_video is not None
+    use_cfg = guidance_scale > 1.0 or three
     f32 = lambda t: t.to(device=dev, dtype=torch.float32)
     clip, sync = f32(visual_feats["siglip2_feat"]), f32(visual_feats["syncformer_feat"])
     text, unc = f32(text_feats["text_feat"]), f32(text_feats["uncond_text_feat"])
@@ -168,18 +201,22 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     text_of = vis_of = None
     if per_clip:
         sets = cond_sets.build(text, unc, clip, sync, model.empty_clip_feat, model.empty_sync_feat, batch_size,
-                               guidance_scale > 1.0)
+                               use_cfg, three)
         if sets.homogeneous:          # every clip shares its conditioning: the batch-1 plan exactly
-            h = 1 if guidance_scale > 1.0 else 0
+            h = sets.text.shape[0] - 1
             text, clip, sync = sets.text[h:h + 1], sets.clip[h:h + 1], sets.sync[h:h + 1]
             unc = sets.text[:1]
             per_clip = False
         else:
             text_in, clip_in, sync_in, text_of, vis_of = sets.text, sets.clip, sets.sync, sets.text_of, sets.vis_of
-    ncfg = 2 if guidance_scale > 1.0 else 1
+    ncfg = 3 if three else 2 if use_cfg else 1
     if per_clip:                                  # distinct sets in [uncond ; cond] order, the maps say which row reads which
         pass
-    elif guidance_scale > 1.0:                    # [uncond ; cond]  (utils.py:193-195)
+    elif three:                                   # [negative + empty rows ; negative + video ; prompt + video]
+        text_in = torch.cat([unc, unc, text])
+        clip_in = torch.cat([model.get_empty_clip_sequence(bs=1, len=Lv).float(), clip, clip])
+        sync_in = torch.cat([model.get_empty_sync_sequence(bs=1, len=Ls).float(), sync, sync])
+    elif use_cfg:                                 # [uncond ; cond]  (utils.py:193-195)
         text_in = torch.cat([unc, text])
         clip_in = torch.cat([model.get_empty_clip_sequence(bs=1, len=Lv).float(), clip])
         sync_in = torch.cat([model.get_empty_sync_sequence(bs=1, len=Ls).float(), sync])
@@ -205,6 +242,12 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
             "text": text_in.contiguous(), "clip": clip_in.contiguous(), "sync": sync_in.contiguous(),
             "text_of": text_of, "vis_of": vis_of}
     plan.update(tabs)
+    if guidance is not None and (three or guidance.interval is not None):
+        # two halves read column 0: the one scale of the run; an edit run takes the suffix of the plain run's rows
+        sched = tables.guidance_schedule(steps, guidance.g_video if three else guidance_scale, guidance_scale, guidance.interval)
+        plan["guid_sched"] = sched[edit_i0 or 0:].contiguous()
+    if guidance is not None:
+        plan["guid_rescale"] = float(guidance.rescale)
     return plan
 
 
@@ -213,7 +256,8 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
                                    generator: Optional[torch.Generator] = None, use_graph: bool = True,
                                    progress: Optional[Callable[[int, int], None]] = None,
                                    return_latents: bool = False, noise: Optional[torch.Tensor] = None,
-                                   _abort_event: Optional[threading.Event] = None, edit=None, windows=None):
+                                   _abort_event: Optional[threading.Event] = None, edit=None, windows=None,
+                                   guidance: Optional[GuidanceSpec] = None):
     """Same contract as the reference function of this name (utils.py:125-258):
     returns (audio [bs, 1, T] fp32 on the model's device, sample_rate).
 
@@ -222,28 +266,34 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     mask held on the source's forward-noised path (foley_set_edit).  The noise is drawn exactly as for a plain run.
 
     windows (host/long_form.WindowPlan): a long clip as one batch of overlapping windows - see _denoise_windows.  A plan of
-    one window takes the plain path exactly; `windows` together with `edit` is refused."""
+    one window takes the plain path exactly; `windows` together with `edit` is refused.
+
+    guidance (GuidanceSpec): separate video / text scales (three halves), a guidance interval and CFG rescale; it combines
+    with `edit` and with `windows`.  None is the plain run, bit for bit."""
     if windows is not None and windows.n_win > 1:
         if edit is not None:
             raise ValueError("windows= and edit= together: editing a long clip is not supported")
         return _denoise_windows(visual_feats, text_feats, model, dac, guidance_scale, num_inference_steps, batch_size, sampler,
-                                windows, generator, use_graph, progress, return_latents, noise, _abort_event)
+                                windows, generator, use_graph, progress, return_latents, noise, _abort_event, guidance)
     cfg = model.cfg
     La = int(audio_len_in_s * cfg.frame_rate)
     if noise is None:
         noise = draw_noise(batch_size, cfg.latent_dim, La, model.dtype, generator)
     latents = noise.to(device=model.device, dtype=torch.float32).contiguous()
     if edit is None:
-        plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler)
+        plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
+                          guidance=guidance)
         model.attach_dac(dac)
         model.ctx.prepare(plan)
+        apply_guidance(model.ctx, plan)
     else:
         k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
         x0, mask = edit.device_operands(model.device, batch_size, La)
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          edit_i0=i0)
+                          edit_i0=i0, guidance=guidance)
         model.attach_dac(dac)
         model.ctx.prepare(plan)
+        apply_guidance(model.ctx, plan)
         model.ctx.set_edit(x0, latents, mask)
         sigma0 = float(tables.sigma_grid(num_inference_steps, cfg.flow_shift)[k0])
         latents = runtime.op_flow_mix(latents, x0, sigma0)
@@ -270,7 +320,8 @@ def window_rows(t: torch.Tensor, variations: int, n_win: int, what: str) -> torc
 
 
 def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC, guidance_scale, num_inference_steps,
-                     variations, sampler, windows, generator, use_graph, progress, return_latents, noise, _abort_event):
+                     variations, sampler, windows, generator, use_graph, progress, return_latents, noise, _abort_event,
+                     guidance=None):
     """One long clip per variation as a batch of variations*n_win coupled windows (clip v*n_win + k = window k of variation v).
     The noise is drawn ONCE as [variations, C, Ltot] - draw_noise, the same generator and dtype rule as a plain run - and every
     window takes its slice, so overlapping frames start equal.  The plan carries the blend rows (edit_i0 = 0 tables); after every
@@ -290,9 +341,10 @@ def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC,
         raise ValueError(f"noise of a windowed run is [variations, C, Ltot] = {(variations, cfg.latent_dim, Ltot)}, got {tuple(noise.shape)}")
     noise = noise.to(device=model.device, dtype=torch.float32)
     latents = torch.stack([noise[v, :, s:s + La] for v in range(variations) for s in windows.starts]).contiguous()
-    plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0)
+    plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0, guidance=guidance)
     model.attach_dac(dac)
     model.ctx.prepare(plan)
+    apply_guidance(model.ctx, plan)
     weights = windows.weights.to(model.device)
     model.ctx.set_windows(windows.starts, weights)
     if _abort_event is not None and _abort_event.is_set():
@@ -387,7 +439,8 @@ def replicate(model: FoleyModel, dac: Optional[FoleyDAC], devices: Sequence) -> 
 def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Sequence, guidance_scale: float,
                           num_inference_steps: int, batch_size: int, sampler: str,
                           generator: Optional[torch.Generator] = None, use_graph: bool = True,
-                          progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None):
+                          progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None,
+                          guidance: Optional[GuidanceSpec] = None):
     """`denoise_process_with_generator` with the clips of the batch sharded over `replicas` (the pairs
     `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199 batches clips that
     share their conditioning; per-clip conditioning, host/cond_sets.py, only changes what each clip reads), so there is no
@@ -450,7 +503,7 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                     audio_len_in_s, model, dac, guidance_scale, num_inference_steps, hi - lo,
                     sampler, use_graph=use_graph, noise=noise[lo:hi], return_latents=True,
                     progress=progress if r == 0 else None, _abort_event=failed,
-                    edit=edit.shard(lo, hi, batch_size) if edit is not None else None)
+                    edit=edit.shard(lo, hi, batch_size) if edit is not None else None, guidance=guidance)
                 torch.cuda.current_stream().synchronize()
         except Exception as e:          # surfaced on the calling thread
             running[r] = False          # FIRST: a second failing (or aborted) worker must not keep the first one waiting on it

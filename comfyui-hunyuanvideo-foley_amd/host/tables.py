@@ -78,6 +78,26 @@ def solver_table(sigmas: torch.Tensor, solver: str, n_iter: int) -> torch.Tensor
     return rows
 
 
+def guidance_schedule(n_iter: int, g_video: float, g_text: float, interval=None) -> torch.Tensor:
+    """[n_iter, 2] fp32 rows {g_video, g_text} of the loop iterations (foley_set_guidance; a two-half run reads column 0).
+    interval = (start, end), 0 <= start < end <= 1: the scales hold on the iterations with start <= i / n_iter < end, the others
+    carry (1, 1) - the conditional prediction alone.  i counts loop iterations, so a multi-stage solver counts its stages, as
+    the coefficient rows do; an edit run takes the rows [i0:] of the plain run's table."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError(f"n_iter must be >= 1, got {n_iter}")
+    rows = torch.empty(n_iter, 2, dtype=torch.float32)
+    rows[:, 0], rows[:, 1] = float(g_video), float(g_text)
+    if interval is not None:
+        start, end = (float(t) for t in interval)
+        if not 0.0 <= start < end <= 1.0:
+            raise ValueError(f"guidance interval must satisfy 0 <= start < end <= 1, got ({start}, {end})")
+        for i in range(n_iter):
+            if not start <= i / n_iter < end:
+                rows[i] = 1.0
+    return rows
+
+
 def edit_start(steps: int, solver: str, strength: float):
     """(k0, i0) of an edit run at `strength`: the run is the suffix [i0, steps) of the plain run's iterations, starting from the
     source noised to sigma_{k0}.  Counted in whole solver steps (the diffusers img2img rule): n_full = steps // stages,

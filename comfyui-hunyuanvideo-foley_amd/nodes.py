@@ -323,7 +323,8 @@ class HunyuanFoleySampler:
     def generate_audio(self, hunyuan_model, hunyuan_deps, frame_rate, duration, prompt, negative_prompt, cfg_scale,
                        steps, sampler, batch_size, seed, force_offload, image=None, torch_compile_cfg=None,
                        block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1,
-                       prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0):
+                       prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0,
+                       video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -332,7 +333,7 @@ class HunyuanFoleySampler:
         (CLAP runs on each clip's [negative, prompt] pair, as for that clip alone) - and `images` - one IMAGE frame batch per clip,
         all of one resulting duration.  A list replaces its widget; the clips of the batch then differ in what they are conditioned
         on, not only in their noise.  Different videos take per-row buffers: at most 32 batch rows (16 clips under
-        CFG), and the single blocks' modulation rows grow with the clips (about 15 GB at 30 s x 8 clips under CFG).
+        CFG, 10 with video_cfg_scale), and the single blocks' modulation rows grow with the clips (about 15 GB at 30 s x 8 clips under CFG).
 
         Audio editing (keyword-only, not sockets; host/audio_edit.py): `audio` (an AUDIO dict, batch 1 or batch_size) is
         re-sampled from part-way down the schedule - `strength` in (0, 1] selects how far (1.0: from pure noise) - and
@@ -345,8 +346,24 @@ class HunyuanFoleySampler:
         length.  Every window sees its own slice of the video (text-to-audio: the learned empty rows); one prompt and one negative
         prompt serve all windows.  `duration` may exceed the widget's 60 s here; for video the total follows the frames, cut to
         whole seconds.  batch_size stays the number of variations.  The run takes the single-device path (the windows of a clip
-        are coupled), and does not combine with audio= / regenerate= or prompts= / images= / features=."""
+        are coupled), and does not combine with audio= / regenerate= or prompts= / images= / features=.
+
+        Guidance (keyword-only, not sockets; host/sampler.py::GuidanceSpec): `video_cfg_scale` - a guidance scale of its own
+        for the video features; the `cfg_scale` widget stays the prompt's scale, and the model then runs three passes per
+        iteration (nothing / video / video + prompt) instead of two.  `guidance_interval` (start, end) in fractions of the
+        loop - guidance acts on the iterations inside it, the others take the conditional prediction (every pass still runs).
+        `cfg_rescale` in [0, 1] pulls the guided prediction's spread back to the conditional one's (0: off).  They combine with
+        audio editing and long clips."""
         model, deps = hunyuan_model, hunyuan_deps
+        guidance = None
+        if video_cfg_scale is not None or guidance_interval is not None or cfg_rescale:
+            if video_cfg_scale is not None and image is None and images is None and features is None:
+                raise ValueError("video_cfg_scale needs visual input (image / images): without it the two lower guidance "
+                                 "halves are identical")
+            guidance = _sampler.GuidanceSpec(None if video_cfg_scale is None else float(video_cfg_scale),
+                                             None if guidance_interval is None else tuple(float(t) for t in guidance_interval),
+                                             float(cfg_rescale))
+            guidance.check(cfg_scale)          # refused here, before the encoders run
         device = model.device
         rng = torch.Generator(device="cpu").manual_seed(seed)          # nodes.py:273
         audio_len_in_s = duration
@@ -408,19 +425,19 @@ class HunyuanFoleySampler:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                windows=windows)
+                windows=windows, guidance=guidance)
         elif batch_size > 1 and n_dev > 1 and model.arena is not None:
             # clips are independent: shard them over the node's GPUs (host/sampler.py::denoise_process_multi; the widget
             # list is the reference's, so the switch is an environment variable - INTEGRATION.md)
             devs = [model.device] + [torch.device("cuda", i) for i in range(n_dev) if i != model.device.index]
             reps = _sampler.replicate(model, deps["dac_model"], devs[:batch_size])
             audio, sr = _sampler.denoise_process_multi(visual, text, audio_len_in_s, reps, cfg_scale, steps, batch_size,
-                                                       sampler, generator=rng, progress=progress, edit=edit)
+                                                       sampler, generator=rng, progress=progress, edit=edit, guidance=guidance)
         else:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                edit=edit)
+                edit=edit, guidance=guidance)
         waveform_batch = audio.float().cpu()
         first = {"waveform": waveform_batch[0].unsqueeze(0), "sample_rate": sr}
         return (first, {"waveform": waveform_batch, "sample_rate": sr})

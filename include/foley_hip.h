@@ -72,7 +72,8 @@ typedef struct foley_config {
 
 /* One sampling run: conditioning + host-built index/trig tables (all device pointers). */
 typedef struct foley_plan {
-  int32_t ncfg;          /* 2 with classifier-free guidance ([uncond ; cond]), else 1 (utils.py:193-199) */
+  int32_t ncfg;          /* 2 with classifier-free guidance ([uncond ; cond]), else 1 (utils.py:193-199); 3: separate video and
+                            text guidance ([nothing ; video ; video + prompt], see foley_set_guidance) */
   int32_t clips;         /* batch_size: independent clips sharing the conditioning (per clip: foley_prepare_sets) */
   int32_t La, Lv, Ls, Lt;/* audio / visual / sync / text token counts                */
   int32_t n_iter;        /* loop iterations (= steps; multi-stage solvers still do one model call per iteration) */
@@ -211,6 +212,24 @@ int foley_set_edit(foley_ctx* ctx, const float* x0, int x0_clips, const float* n
  * FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE.  foley_sample takes and returns the windows [clips, latent_dim, La];
  * foley_op_windows_stitch makes the long clips of them. */
 int foley_set_windows(foley_ctx* ctx, int n_win, const int32_t* starts, const float* weights, void* stream);
+
+/* Guidance: how the prediction halves become one velocity (additive within ABI 12).  The plan's row order is [half][clip][token].
+ *   ncfg 2  halves [uncond ; cond]:                         v = u + g (c - u)
+ *   ncfg 3  halves h0 = negative prompt + the empty visual rows, h1 = negative prompt + the clip's visual features,
+ *           h2 = prompt + the same features:                v = p0 + g_video (p1 - p0) + g_text (p2 - p1)      (fp32, left to right)
+ * Without this call g = g_video = g_text = plan.guidance for the whole run.  Called after foley_prepare / foley_prepare_sets:
+ *   sched   [n_rows, 2] fp32 on the HOST, row i = {g_video, g_text} of loop iteration i (multi-stage solvers: every stage is
+ *           an iteration); ncfg 2 reads column 0.  n_rows must equal plan.n_iter.  NULL: no table, the scalar stays.
+ *   rescale phi in [0, 1]: every iteration the step uses f v with f = phi s_pos / s_cfg + (1 - phi) per batch clip, s_pos the
+ *           standard deviation (about the mean, over the clip's latent_dim x La elements) of the last half, s_cfg that of v;
+ *           f = 1 where s_cfg is 0.  In a windowed run every window is a clip and its factor is applied before the blend.
+ *           phi > 0 adds two launches per iteration (deterministic: fixed merge order, no atomics); 0 adds none.
+ * Table and phi are copied into context-owned buffers (captured graphs never hold the caller's pointers); the captured iteration
+ * is keyed on schedule on/off, rescale on/off and those buffers, so new values of the same shape only rewrite what a replay
+ * reads.  It combines with foley_set_edit and with foley_set_windows in either order (an edit run passes the rows [i0, steps) of
+ * the plain run's table, like its solver_coef rows).  sched NULL with rescale 0 clears the state, as does foley_prepare.
+ * plan.ncfg == 1, n_rows != plan.n_iter, rescale outside [0, 1]: FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE. */
+int foley_set_guidance(foley_ctx* ctx, const float* sched, int n_rows, float rescale, void* stream);
 
 /* DAC-VAE decoder: latents [clips, latent_dim, T] fp32 -> waveform [clips, 1, T*hop] fp32. */
 int foley_dac_decode(foley_ctx* ctx, const float* latents, int clips, int T, float* wave, void* stream);
@@ -402,6 +421,31 @@ int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float
 int foley_op_solver_step_windows(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
                                  int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
                                  int rows_dtype, int n_win, const int32_t* starts, const float* weights, int Ltot, void* stream);
+/* The three step forms with a guidance descriptor (see foley_set_guidance), everything on the DEVICE: sched [n_iter, 2] read at
+ * row *step_ptr (NULL: the scalar `guidance`), clip_scale [clips] multiplied into the guided value (NULL: none).  gd NULL, or
+ * ncfg 2 with a table whose rows all hold `guidance` and no factors, gives the bits of the entries above.  ncfg 3 takes the
+ * three-term combine; rows_out is staged ncfg times. */
+typedef struct foley_guidance_desc {
+  const float* sched;
+  float* clip_scale;
+} foley_guidance_desc;
+int foley_op_solver_step_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
+                                int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
+                                void* rows_out, int rows_dtype, void* stream);
+int foley_op_solver_step_edit_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
+                                     int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
+                                     void* rows_out, int rows_dtype, const float* x0, int x0_clips, const float* noise,
+                                     const float* mask, int mask_clips, void* stream);
+int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved,
+                                        float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
+                                        int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
+                                        const float* weights, int Ltot, void* stream);
+/* The rescale factors of one iteration: gd->clip_scale[b] = rescale * s_pos / s_cfg + (1 - rescale) from pred [ncfg*clips*L, C]
+ * at iteration *step_ptr (gd->sched as above), C <= 256.  `work`: device scratch of at least foley_op_guidance_stats_work(clips, L)
+ * floats.  Two launches, bit-identical on repetition. */
+int64_t foley_op_guidance_stats_work(int clips, int L);
+int foley_op_guidance_stats(const foley_guidance_desc* gd, const float* pred, int clips, int C, int L, int ncfg, float guidance,
+                            const int32_t* step_ptr, float rescale, float* work, int64_t work_floats, void* stream);
 /* x [variations*n_win, C, L] -> out [variations, C, Ltot]: the weighted mean above per global frame; where the covering windows
  * hold the identical bits (always after a blend row) that value is copied as it is.  starts / weights on the device. */
 int foley_op_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int32_t* starts,
