@@ -1969,3 +1969,28 @@ extern "C" int foley_op_rows_to_planes(const float* rows, int B, int T, int C, f
   if (!rows || !out || B < 1 || T < 1 || C < 1) return FAIL(FOLEY_ERR_INVALID, "rows_to_planes: null argument or empty problem");
   return launch_rows_to_planes(rows, B, T, C, out, (hipStream_t)stream);
 }
+
+// The CLAP audio tower's kernels (clap_audio.hip; host/clap_score.py)
+extern "C" int foley_op_melspec_db(const float* x, int B, int N, const int32_t* starts, int n_win, const float* basis,
+                                   const int32_t* mel_lo, const int32_t* mel_len, const float* mel_w, int mel_wp, float* out,
+                                   void* stream) {
+  if (!x || !starts || !basis || !mel_lo || !mel_len || !mel_w || !out) return FAIL(FOLEY_ERR_INVALID, "melspec_db: null argument");
+  return launch_melspec_db(x, B, N, starts, n_win, basis, mel_lo, mel_len, mel_w, mel_wp, out, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_spec_patches(const float* spec, int G, int T, int F, const float* scale, const float* shift,
+                                     const int32_t* resize_idx, const float* resize_w, int Tq, int ratio, void* out, int out_dtype,
+                                     int Kp, void* stream) {
+  if (!spec || !scale || !shift || !out || (resize_idx != nullptr) != (resize_w != nullptr))
+    return FAIL(FOLEY_ERR_INVALID, "spec_patches: null argument (the resize table is index and weight together)");
+  return launch_spec_patches(spec, G, T, F, scale, shift, resize_idx, resize_w, Tq, ratio, out, out_dtype, Kp, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_window_attention(const void* qkv, int dtype, int rows, int qkv_cols, int H, int win_tokens,
+                                         const int32_t* table, int n_win, const float* bias, const float* mask, int n_mask,
+                                         void* out, int out_pitch, void* stream) {
+  if (!qkv || !table || !bias || !out) return FAIL(FOLEY_ERR_INVALID, "window_attention: null argument");
+  if (win_tokens != 64) return FAIL(FOLEY_ERR_INVALID, "window_attention: serves 64-token windows (8 x 8)");
+  if (H < 1 || qkv_cols != 3 * H * 32) return FAIL(FOLEY_ERR_INVALID, "window_attention: serves head dim 32 (qkv [rows, 3 * H * 32])");
+  return launch_window_attention(qkv, dtype, rows, H, table, n_win, bias, mask, n_mask, out, out_pitch, (hipStream_t)stream);
+}

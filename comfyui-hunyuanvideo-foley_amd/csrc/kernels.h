@@ -269,3 +269,10 @@ int launch_logmel(const float* w16, int B, int N16, const float* basis, const in
                   int mel_wp, void* patches, int out_dtype, float* mel_out, hipStream_t st);
 int launch_dac_out(const float* s, const float* w, const float* bias, int B, int T, int C, float* out,
                    hipStream_t st);
+// clap_audio.hip: the CLAP audio tower's front end and windowed attention (host/clap_score.py)
+int launch_melspec_db(const float* x, int B, int N, const int* starts, int n_win, const float* basis, const int* mel_lo,
+                      const int* mel_len, const float* mel_w, int mel_wp, float* out, hipStream_t st);
+int launch_spec_patches(const float* spec, int G, int T, int F, const float* scale, const float* shift, const int* ridx,
+                        const float* rw, int Tq, int ratio, void* out, int out_dtype, int Kp, hipStream_t st);
+int launch_window_attention(const void* qkv, int dtype, int rows, int H, const int* table, int n_win, const float* bias,
+                            const float* mask, int n_mask, void* out, int out_pitch, hipStream_t st);

@@ -192,6 +192,12 @@ _SIGNATURES = {
     "foley_op_rows_periodic_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_op_dac_in": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3),
     "foley_op_rows_to_planes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "foley_op_melspec_db": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "foley_op_spec_patches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "foley_op_window_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -766,6 +772,76 @@ def op_logmel(w16: torch.Tensor, basis: torch.Tensor, mel_lo: torch.Tensor, mel_
     _check(lib, lib.foley_op_logmel(_ptr(w16), B, N16, _ptr(basis), _ptr(mel_lo), _ptr(mel_len), _ptr(mel_w), mel_w.shape[1],
                                     _ptr(patches), dt_of(patches), _ptr(mel) if with_mel else None, _stream()), "foley_op_logmel")
     return (patches, mel) if with_mel else patches
+
+
+def op_melspec_db(x: torch.Tensor, starts: torch.Tensor, basis: torch.Tensor, mel_lo: torch.Tensor, mel_len: torch.Tensor,
+                  mel_w: torch.Tensor) -> torch.Tensor:
+    """48 kHz waveform [B, N >= 1024] fp32 -> dB-mel spectrograms [B * W, 1001, 64] fp32 of the ten-second windows that start at
+    starts [W] int32 (foley_op_melspec_db; N < 480000: one window, the extractor's repeatpad).  Tables from
+    host/clap_score.py::melspec_tables."""
+    lib = load_library()
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] < 1024 or starts.dtype != torch.int32 or starts.dim() != 1 or starts.numel() < 1:
+        raise FoleyRuntimeError("op_melspec_db: x [B, N >= 1024] fp32, starts [W] int32")
+    if basis.numel() != 2 * 1024 * 544 or basis.dtype != torch.float32 or mel_lo.numel() != 64 or mel_len.numel() != 64 or \
+            mel_lo.dtype != torch.int32 or mel_len.dtype != torch.int32 or mel_w.dim() != 2 or mel_w.shape[0] != 64 or mel_w.dtype != torch.float32:
+        raise FoleyRuntimeError("op_melspec_db: basis [2, 1024, 544] fp32, int32 mel_lo / mel_len [64], mel_w [64, pitch] fp32")
+    B, N = x.shape
+    W = starts.numel()
+    if W > 1 and N < 480000:
+        raise FoleyRuntimeError("op_melspec_db: a clip below ten seconds has one window")
+    out = torch.empty(B * W, 1001, 64, device=x.device, dtype=torch.float32)
+    _check(lib, lib.foley_op_melspec_db(_ptr(x), B, N, _ptr(starts), W, _ptr(basis), _ptr(mel_lo), _ptr(mel_len), _ptr(mel_w),
+                                        mel_w.shape[1], _ptr(out), _stream()), "foley_op_melspec_db")
+    return out
+
+
+def op_spec_patches(spec: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, resize_idx: Optional[torch.Tensor],
+                    resize_w: Optional[torch.Tensor], Tq: int, ratio: int, out_dtype: torch.dtype, Kp: int) -> torch.Tensor:
+    """spec [G, T, F] fp32 -> patch matrix [G * (ratio F / 4) * (Tq / 4), Kp] in out_dtype (foley_op_spec_patches): BatchNorm affine
+    per bin, the 4-tap time resize (resize_idx int32 / resize_w fp32 [ratio * Tq, 4], or None for T == ratio * Tq), the fold of
+    reshape_mel2img and the im2col of the 4x4 patch embedding; columns [16, Kp) are zero."""
+    lib = load_library()
+    if spec.dim() != 3 or spec.dtype != torch.float32:
+        raise FoleyRuntimeError("op_spec_patches: spec [G, T, F] fp32")
+    G, T, F = spec.shape
+    if scale.numel() != F or shift.numel() != F or scale.dtype != torch.float32 or shift.dtype != torch.float32:
+        raise FoleyRuntimeError("op_spec_patches: fp32 scale / shift [F]")
+    if (resize_idx is None) != (resize_w is None):
+        raise FoleyRuntimeError("op_spec_patches: the resize table is index and weight together")
+    if resize_idx is not None and (resize_idx.dtype != torch.int32 or resize_w.dtype != torch.float32 or
+                                   tuple(resize_idx.shape) != (ratio * Tq, 4) or tuple(resize_w.shape) != (ratio * Tq, 4)):
+        raise FoleyRuntimeError("op_spec_patches: resize_idx int32 / resize_w fp32 [ratio * Tq, 4]")
+    if resize_idx is None and T != ratio * Tq:
+        raise FoleyRuntimeError("op_spec_patches: without a resize table T must equal ratio * Tq")
+    if F % 4 or Tq % 4:
+        raise FoleyRuntimeError("op_spec_patches: F and Tq must be multiples of 4")
+    out = torch.empty(G * (ratio * F // 4) * (Tq // 4), Kp, device=spec.device, dtype=out_dtype)
+    _check(lib, lib.foley_op_spec_patches(_ptr(spec), G, T, F, _ptr(scale), _ptr(shift), _ptr(resize_idx), _ptr(resize_w), Tq, ratio,
+                                          _ptr(out), dt_of(out), Kp, _stream()), "foley_op_spec_patches")
+    return out
+
+
+def op_window_attention(qkv: torch.Tensor, heads: int, table: torch.Tensor, bias: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None, win_tokens: int = 64) -> torch.Tensor:
+    """Windowed attention straight from a fused projection (foley_op_window_attention): qkv [rows, 3 * heads * 32], table
+    [n_win, 64] int32 source rows, bias [heads, 64, 64] fp32, mask [nW, 64, 64] fp32 or None (window g reads mask g % nW) ->
+    out [rows, >= heads * 32] in qkv's dtype (allocated [rows, heads * 32] when None; rows no window names keep their content).
+    The library refuses any head dim but 32 and any window but 64 tokens; the table's VALUES are the caller's to check."""
+    lib = load_library()
+    if qkv.dim() != 2 or table.dim() != 2 or table.dtype != torch.int32 or table.shape[1] != win_tokens or bias.dtype != torch.float32 or \
+            tuple(bias.shape) != (heads, win_tokens, win_tokens):
+        raise FoleyRuntimeError("op_window_attention: qkv [rows, 3*H*hd], int32 table [n_win, tokens], fp32 bias [H, tokens, tokens]")
+    if mask is not None and (mask.dtype != torch.float32 or mask.dim() != 3 or tuple(mask.shape[1:]) != (win_tokens, win_tokens)):
+        raise FoleyRuntimeError("op_window_attention: fp32 mask [nW, tokens, tokens]")
+    rows = qkv.shape[0]
+    if out is None:
+        out = torch.empty(rows, heads * 32, device=qkv.device, dtype=qkv.dtype)
+    if out.dim() != 2 or out.shape[0] != rows or out.dtype != qkv.dtype or out.stride(1) != 1:
+        raise FoleyRuntimeError("op_window_attention: out [rows, >= H*32] in qkv's dtype, unit column stride")
+    _check(lib, lib.foley_op_window_attention(_ptr(qkv), dt_of(qkv), rows, qkv.shape[1], heads, win_tokens, _ptr(table), table.shape[0],
+                                              _ptr(bias), _ptr(mask), mask.shape[0] if mask is not None else 0, out.data_ptr(),
+                                              out.stride(0), _stream()), "foley_op_window_attention")
+    return out
 
 
 def op_ln_mod(x, eps, shift: Optional[RowBcastC], scale: Optional[RowBcastC], out):

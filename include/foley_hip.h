@@ -477,6 +477,31 @@ int foley_op_rows_periodic_check(const float* x, int groups, int rows, int perio
 int foley_op_dac_in(const float* x, const float* w, const float* bias, const float* alpha, int B, int T, int C,
                     float* out0, float* out1, void* stream);
 int foley_op_rows_to_planes(const float* rows, int B, int T, int C, float* out, void* stream);
+/* The CLAP audio tower's own kernels (host/clap_score.py; additive: the ABI number is unchanged).  All operands on the device.
+ * melspec_db: transformers' ClapFeatureExtractor (rand_trunc / repeatpad) for 48 kHz audio.  x [B, N >= 1024] fp32; window k of
+ *   every clip is the 480000 padded samples p -> x[starts[k] + p % seg] for p < (480000 / seg) * seg, 0 beyond, seg = min(N,
+ *   480000) (N < 480000: the extractor's repeatpad and n_win must be 1; otherwise a crop at starts[k], clamped into the clip).
+ *   Each window: STFT (n_fft 1024, periodic Hann 1024, hop 480, centred, reflect) -> |X|^2 -> 64 mel triangles -> 10 log10(max(mel,
+ *   1e-10)) (a value at the floor is exactly -100): out [B * n_win, 1001, 64] fp32, window-minor.  Tables (host/clap_score.py):
+ *   basis [2][1024][544] fp32 = Hann(m) * cos / -sin(2 pi k m / 1024), bins k >= 513 zero; mel c = sum_{k < mel_len[c]}
+ *   |X|^2[mel_lo[c] + k] * mel_w[c * mel_wp + k] (int32 [64], fp32 [64, mel_wp]).
+ * spec_patches: spec [G, T, F] fp32 -> the im2col matrix of the 4x4 / stride 4 patch embedding over reshape_mel2img's image:
+ *   v[to, f] = sum_{j < 4} resize_w[to, j] * (spec[resize_idx[to, j], f] * scale[f] + shift[f]) for to < ratio * Tq (BatchNorm2d
+ *   in eval mode folded to one affine per bin, then the bicubic resize along time; both tables NULL: no resize, T = ratio * Tq),
+ *   img[r * F + f, t] = v[r * Tq + t, f], out [G * (ratio F / 4) * (Tq / 4), Kp] in out_dtype (f32 / bf16 / f16): row
+ *   (g, h, w) column kh * 4 + kw = img[4 h + kh, 4 w + kw], columns [16, Kp) zero.  F a multiple of 4 up to 256, Tq of 4, Kp >= 16.
+ * window_attention: Swin's windowed attention for 64-token windows at head dim 32, anything else is FOLEY_ERR_INVALID.  qkv
+ *   [rows, qkv_cols = 3 * H * 32] (f32 / bf16 / f16; q | k | v, head-major), table [n_win, 64] int32 = the source row of every
+ *   window token (roll, then partition), bias [H, 64, 64] fp32 (query-major), mask [n_mask, 64, 64] fp32 or NULL, window g reads
+ *   mask g % n_mask.  scores = q . k / sqrt(32) + bias + mask in fp32 (a mask value is added as a number: masked keys are not
+ *   skipped), softmax over the 64 keys, times v; query t of window g goes to out row table[g, t] (out [rows, out_pitch] in qkv's
+ *   dtype, columns h * 32 .. of each head; out_pitch >= H * 32, a multiple of 8).  No atomics, one fixed summation order. */
+int foley_op_melspec_db(const float* x, int B, int N, const int32_t* starts, int n_win, const float* basis, const int32_t* mel_lo,
+                        const int32_t* mel_len, const float* mel_w, int mel_wp, float* out, void* stream);
+int foley_op_spec_patches(const float* spec, int G, int T, int F, const float* scale, const float* shift, const int32_t* resize_idx,
+                          const float* resize_w, int Tq, int ratio, void* out, int out_dtype, int Kp, void* stream);
+int foley_op_window_attention(const void* qkv, int dtype, int rows, int qkv_cols, int H, int win_tokens, const int32_t* table,
+                              int n_win, const float* bias, const float* mask, int n_mask, void* out, int out_pitch, void* stream);
 
 #ifdef __cplusplus
 }
