@@ -199,13 +199,16 @@ struct GraphKey {
   // guidance state (foley_set_guidance): the schedule table (null: off - the scalar `guidance`) and the rescale buffers (null:
   // off; on adds the two statistics launches, another topology).  New values of either only rewrite what a replay reads.
   const void *guid_sched = nullptr, *guid_scale = nullptr, *guid_part = nullptr, *guid_phi = nullptr;
+  // step cache (foley_set_step_cache): the residual and probe buffers (null: off - the one straight-line iteration; on: the three
+  // graphs head / full body / skip body).  Mode, threshold and skip list are host decisions between replays: not part of the key.
+  const void *sc_delta = nullptr, *sc_mprev = nullptr;
   uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
   uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
   bool operator==(const GraphKey& o) const {
     return guidance == o.guidance && edit == o.edit && set_maps == o.set_maps && layout == o.layout && smod_tab == o.smod_tab &&
            edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && n_win == o.n_win && Ltot == o.Ltot &&
            win_starts == o.win_starts && win_weights == o.win_weights && guid_sched == o.guid_sched && guid_scale == o.guid_scale &&
-           guid_part == o.guid_part && guid_phi == o.guid_phi && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
+           guid_part == o.guid_part && guid_phi == o.guid_phi && sc_delta == o.sc_delta && sc_mprev == o.sc_mprev && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
   }
 };
 
@@ -243,6 +246,19 @@ struct foley_ctx {
   bool guid_sched_on = false, guid_rescale_on = false;
   DevBuf guid_sched, guid_part, guid_scale;
   std::vector<float> guid_host;           // [n_iter*2 + 1] source of the copy
+  // step cache state (foley_set_step_cache; cleared by foley_prepare): the policy's parameters, the ctx-owned residual / probe
+  // buffers, the pinned read-back of the per-row change measure and the report of the last loop
+  int sc_mode = 0;                        // 0 off, FOLEY_STEP_CACHE_SCHEDULE, FOLEY_STEP_CACHE_THRESHOLD
+  std::vector<uint8_t> sc_skip;           // schedule mode: [n_iter]
+  double sc_threshold = 0.0;
+  std::vector<double> sc_poly;            // highest degree first (empty: identity)
+  int sc_lo = 0, sc_hi = 0, sc_maxc = 0;  // iterations [lo, hi) may skip; longest run of skips (0: no cap)
+  DevBuf sc_delta, sc_mprev, sc_part, sc_rel;
+  float* sc_rel_host = nullptr;           // pinned, sc_rel_cap floats
+  int sc_rel_cap = 0;
+  std::vector<float> sc_rep_rel;          // [n_iter] of the last loop (-1: not measured)
+  std::vector<int32_t> sc_rep_skip;
+  hipGraphExec_t graph_head = nullptr, graph_skip = nullptr;   // with graph_exec (the full body) the three graphs of a cached loop
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -277,6 +293,11 @@ static void ctx_drop_graph(foley_ctx* c) {
     hipGraphExecDestroy(c->graph_exec);
     c->graph_exec = nullptr;
   }
+  for (hipGraphExec_t* g : {&c->graph_head, &c->graph_skip})
+    if (*g) {
+      hipGraphExecDestroy(*g);
+      *g = nullptr;
+    }
 }
 
 static void ctx_free_plan(foley_ctx* c) {
@@ -448,7 +469,8 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   hipSetDevice(c->device);
   ctx_free_plan(c);
   for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights, &c->guid_sched,
-                    &c->guid_part, &c->guid_scale}) release(*b);
+                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel}) release(*b);
+  if (c->sc_rel_host) (void)hipHostFree(c->sc_rel_host);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   for (auto e : c->prof.pool) hipEventDestroy(e);
@@ -593,6 +615,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   c->edit = false;                  // a plan without foley_set_edit is a plain run
   c->n_win = 0;                     // and one without foley_set_windows has independent clips
   c->guid_sched_on = c->guid_rescale_on = false;   // and one without foley_set_guidance combines with the plan's scalar
+  c->sc_mode = 0;                   // and one without foley_set_step_cache runs every block on every iteration
   RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
   c->vis_src = n_vis;
   const int th = ly.th, vh = ly.vh;
@@ -904,7 +927,14 @@ static int prof_end(foley_ctx* c, hipStream_t st) {
 // of the forward.  Round 1 overlapped it with the two-stream blocks on a side stream; with the faster block
 // kernels of round 2 its 5184 workgroups only steal CUs from them (A/B in one box: 448.5 -> 439.5 ms per
 // 50-iteration loop at bs=1, 1753 -> 1741 ms at bs=8).
-static int run_forward(foley_ctx* c, hipStream_t st) {
+// `part` (step cache): FWD_ALL is the straight line - the launches below in their order, whenever the cache is off.  Under the
+// cache an iteration is FWD_HEAD (audio_embedder, then the probe of the first block's modulated input), and
+// either FWD_BODY (everything else; foley_sample then takes delta = aN - a0) or, on a skipped iteration, audio += delta and
+// FWD_FINAL (final.layernorm + final.linear, nothing pending).  The single blocks' per-iteration modulation section belongs to the
+// body; without two-stream blocks the probe reads its table, so it then runs in the head.
+enum FwdPart { FWD_ALL = 0, FWD_HEAD, FWD_BODY, FWD_FINAL };
+
+static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
   const foley_config& f = c->cfg;
   const foley_plan& pl = c->plan;
   const ForwardW& W = c->fw;
@@ -934,7 +964,9 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   // and every single block's modulation GEMM (hifi_foley.py:366).  They depend on the iteration only, are
   // identical for every clip of a CFG half, and - add_sync being an up-sampling of the Ls sync tokens - have
   // only Ls distinct rows per half: M = ncfg*Ls (224 instead of 500 at 5 s).
-  if (!ly.hoisted) {
+  // which piece the single blocks' modulation section runs in: the body - or the head, when the probe reads its table
+  const FwdPart smod_part = f.depth_triple == 0 ? FWD_HEAD : FWD_BODY;
+  if (!ly.hoisted && (part == FWD_ALL || part == smod_part)) {
     // distinct rows only: 8 per 8-periodic half (the leading halves), Ls per dense half - packed back to back (RunLayout::R)
     if (ly.v_rows && lead > 1)   // per-row layout: the leading halves' rows were packed by foley_prepare_sets - one launch
       TRY(launch_rows_add_act(c->buf.sync_lead_rows, rb_vec(c->buf.vec_table, D, sp), lead * ly.per, D, 1, c->buf.svec, T, st));
@@ -953,11 +985,39 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   }
 
   // audio_embedder (conv k=1 == linear over the transposed latents) + add_sync (hifi_foley.py:768, 838-839)
-  {
+  if (part == FWD_ALL || part == FWD_HEAD) {
     GemmArgs g = krot(gemm_plain(c->buf.xin, M, W.audio_in, c->buf.audio, D));
     g.rb = rb_up(c->buf.sync_tok, D, ly.vdiv * La, La, Ls);
     PROF("audio_embedder", gf(M, D, C), gb(M, D, C, 4), launch_gemm(g, T, EPI_STORE_F32, 0, st));
   }
+  // the single blocks' modulation rows (RunLayout): every half periodic (8 rows each) | the leading halves periodic, the others
+  // dense (the per-iteration GEMM only) | every half dense
+  auto sm_of = [&](int blk, int chunk) {
+    const float* smod_b = (ly.hoisted ? (const float*)c->smod_tab.p : c->buf.smod) + (size_t)blk * 6 * D;   // column block of the fused table
+    RowBcast r = rb_up(smod_b + (size_t)chunk * D, ly.smod_ld, ly.vdiv * La, La, Ls, ly.mod_per, ly.mod_lead);
+    if (ly.hoisted) {   // the table of every iteration: this iteration's rows start at step * smod_step
+      r.step_ptr = sp;
+      r.step_stride = ly.smod_step;
+    }
+    return r;
+  };
+  if (part == FWD_HEAD) {
+    // step cache probe: exactly the eps and operands the first block's first LayerNorm gets below
+    const bool tri = f.depth_triple > 0;
+    auto tb0 = [&](int chunk) { return rb_vec(c->buf.modtab + (size_t)chunk * D, 9L * D, sp); };
+    TRY(launch_cache_probe(c->buf.audio, Bc, La, D, tri ? 1e-6f : 1e-5f, tri ? tb0(0) : sm_of(0, 0), tri ? tb0(1) : sm_of(0, 1),
+                           (float*)c->sc_mprev.p, (float*)c->sc_part.p, (float*)c->sc_rel.p, st));
+    return 0;
+  }
+  // FinalLayer1D: adaLN is a no-op with 3-D conditioning => linear(LayerNorm(x)); the LayerNorm applies what the last
+  // gated-residual GEMM left pending
+  auto final_layer = [&](const LnPending& pending) -> int {
+    PROF("final.layernorm", 0.0, (double)M * D * (4 + 4 + es),
+         launch_ln_mod_pending(c->buf.audio, M, D, 1e-6f, rb_none(), rb_none(), c->buf.xn_a, T, pending, st));
+    PROF("final.linear", gf(M, C, D), gb(M, C, D, 4), launch_gemm(krot(gemm_plain(c->buf.xn_a, M, W.fin, c->buf.pred, C)), T, EPI_STORE_F32, 0, st));
+    return 0;
+  };
+  if (part == FWD_FINAL) return final_layer(LnPending{});
   // visual stream starts from the step-invariant projection, replicated per clip (one gather launch); per-row layout: every
   // batch row gathers its own set's rows of the distinct projections
   if (ly.v_rows)
@@ -1070,17 +1130,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
   const int Hc = f.conv_hidden;
   for (int blk = 0; blk < f.depth_single; ++blk) {
     const SingleW& w = W.s[blk];
-    const float* smod_b = (ly.hoisted ? (const float*)c->smod_tab.p : c->buf.smod) + (size_t)blk * 6 * D;   // column block of the fused table
-    // table layout per iteration (RunLayout): every half periodic (8 rows each) | the leading halves periodic, the others dense
-    // (the per-iteration GEMM only) | every half dense
-    auto sm = [&](int chunk) {
-      RowBcast r = rb_up(smod_b + (size_t)chunk * D, ly.smod_ld, ly.vdiv * La, La, Ls, ly.mod_per, ly.mod_lead);
-      if (ly.hoisted) {   // the table of every iteration: this iteration's rows start at step * smod_step
-        r.step_ptr = sp;
-        r.step_stride = ly.smod_step;
-      }
-      return r;
-    };
+    auto sm = [&](int chunk) { return sm_of(blk, chunk); };
     PROF("single.layernorm+modulate (+pending split-K sum)", 0.0, ln_bytes_s,
          launch_ln_mod_pending(c->buf.audio, M, D, 1e-5f, sm(0), sm(1), c->buf.xn_a, T, pend[0], st));
     pend[0] = LnPending{};
@@ -1115,13 +1165,7 @@ static int run_forward(foley_ctx* c, hipStream_t st) {
     }
   }
 
-  // FinalLayer1D: adaLN is a no-op with 3-D conditioning => linear(LayerNorm(x))
-  {
-    PROF("final.layernorm", 0.0, ln_bytes_s,
-         launch_ln_mod_pending(c->buf.audio, M, D, 1e-6f, rb_none(), rb_none(), c->buf.xn_a, T, pend[0], st));
-    PROF("final.linear", gf(M, C, D), gb(M, C, D, 4), launch_gemm(krot(gemm_plain(c->buf.xn_a, M, W.fin, c->buf.pred, C)), T, EPI_STORE_F32, 0, st));
-  }
-  return 0;
+  return final_layer(pend[0]);
 }
 
 // One eager forward of `latents` at loop iteration `iter` (foley_dit_forward, foley_profile_forward): the prediction is in buf.pred
@@ -1212,9 +1256,10 @@ extern "C" int foley_profile_forward(foley_ctx* c, const float* latents, int ite
 }
 
 // --------------------------------------------------------------------------- sampler loop
-static int run_iteration(foley_ctx* c, hipStream_t st) {
+// The solver update of the prediction in buf.pred (guided / edit / windows form by the context's state): shared by the plain
+// iteration and the two bodies of a cached one.
+static int run_step(foley_ctx* c, hipStream_t st) {
   const foley_plan& pl = c->plan;
-  TRY(run_forward(c, st));
   StepArgs s{};
   s.pred = c->buf.pred; s.x = c->buf.x_cur; s.x_saved = c->buf.x_saved; s.d_acc = c->buf.d_acc;
   s.clips = pl.clips; s.C = c->cfg.latent_dim; s.L = pl.La; s.ncfg = pl.ncfg;
@@ -1244,6 +1289,63 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
   return launch_solver_step(s, st);
 }
 
+static int run_iteration(foley_ctx* c, hipStream_t st) {
+  TRY(run_forward(c, st));
+  return run_step(c, st);
+}
+
+// The three pieces of an iteration under the step cache (each a linear captured graph): the head, the full body (a copy of a0 into
+// the residual buffer - only now, the head runs before the decision and a skip needs the old delta -, the blocks, then delta =
+// aN - a0 over that copy: the final LayerNorm has written the finished stream back) and the skip body.
+enum { SC_HEAD = 0, SC_FULL = 1, SC_SKIP = 2 };
+static int run_cached_piece(foley_ctx* c, int piece, hipStream_t st) {
+  const long n = (long)c->plan.ncfg * c->plan.clips * c->plan.La * c->cfg.hidden;
+  if (piece == SC_HEAD) return run_forward(c, st, FWD_HEAD);
+  if (piece == SC_FULL) {
+    TRY(launch_cast(c->buf.audio, FOLEY_F32, c->sc_delta.p, FOLEY_F32, n, st));
+    TRY(run_forward(c, st, FWD_BODY));
+    TRY(launch_cache_delta(c->buf.audio, (float*)c->sc_delta.p, n, st));
+    return run_step(c, st);
+  }
+  TRY(launch_cache_apply(c->buf.audio, (const float*)c->sc_delta.p, n, st));
+  TRY(run_forward(c, st, FWD_FINAL));
+  return run_step(c, st);
+}
+
+// The skip policy of one loop (host/step_cache.py states the same machine in Python): iteration 0, the last one and any without a
+// valid delta are full; schedule mode skips the listed iterations; threshold mode adds poly(rel) to `acc` on every measured
+// iteration and skips while acc < threshold, inside [lo, hi) and below the cap on consecutive skips; a full iteration resets acc.
+struct StepCachePolicy {
+  double acc = 0.0;
+  int run = 0;
+  bool have_delta = false;
+  bool decide(const foley_ctx* c, int i, int n, float rel) {
+    const bool forced = i == 0 || i == n - 1 || !have_delta;
+    bool skip = false;
+    if (c->sc_mode == FOLEY_STEP_CACHE_SCHEDULE) {
+      skip = !forced && c->sc_skip[i] != 0;
+    } else {
+      if (i > 0) {
+        double v = (double)rel;
+        if (!c->sc_poly.empty()) {
+          v = 0.0;
+          for (double k : c->sc_poly) v = v * (double)rel + k;
+        }
+        acc += v;
+      }
+      skip = !forced && acc < c->sc_threshold && i >= c->sc_lo && i < c->sc_hi && (c->sc_maxc <= 0 || run < c->sc_maxc);
+    }
+    if (skip) {
+      ++run;
+    } else {
+      acc = 0.0;
+      run = 0;
+      have_delta = true;
+    }
+    return skip;
+  }
+};
+
 // Plain vs edit iteration, and the clip strides / presence of the edit operands.  A plain graph replayed for an edit run would
 // skip the blend, an edit graph replayed for a plain run would apply a stale one.
 static int edit_key(const foley_ctx* c) {
@@ -1262,6 +1364,7 @@ static GraphKey graph_key_now(const foley_ctx* c) {
                   c->guid_sched_on ? c->guid_sched.p : nullptr, c->guid_rescale_on ? c->guid_scale.p : nullptr,
                   c->guid_rescale_on ? c->guid_part.p : nullptr,
                   c->guid_rescale_on ? (const void*)((const float*)c->guid_sched.p + 2 * (size_t)c->plan.n_iter) : nullptr,
+                  c->sc_mode ? c->sc_delta.p : nullptr, c->sc_mode ? c->sc_mprev.p : nullptr,
                   c->tensor_gen,    c->plan_gen};
 }
 
@@ -1360,6 +1463,69 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
   return 0;
 }
 
+extern "C" int foley_set_step_cache(foley_ctx* c, int mode, const uint8_t* skip, int n_skip, double threshold, const double* poly,
+                                    int n_poly, const int32_t* interval, int max_consecutive, void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_step_cache: foley_prepare has not been called");
+  if (mode == 0) {
+    c->sc_mode = 0;
+    c->sc_rep_rel.clear();
+    c->sc_rep_skip.clear();
+    return 0;
+  }
+  const foley_plan& pl = c->plan;
+  if (mode != FOLEY_STEP_CACHE_SCHEDULE && mode != FOLEY_STEP_CACHE_THRESHOLD)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: mode must be 0 (off), 1 (schedule) or 2 (threshold)");
+  if (mode == FOLEY_STEP_CACHE_SCHEDULE && (!skip || n_skip != pl.n_iter))
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: the skip list must have one entry per iteration of the plan (n_skip == n_iter)");
+  if (mode == FOLEY_STEP_CACHE_THRESHOLD && !(threshold >= 0.0 && std::isfinite(threshold)))
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: the threshold must be finite and >= 0");
+  if (n_poly < 0 || (n_poly > 0 && !poly)) return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: bad polynomial");
+  for (int k = 0; k < n_poly; ++k)
+    if (!std::isfinite(poly[k])) return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: polynomial coefficients must be finite");
+  if (interval && (interval[0] < 0 || interval[1] < interval[0] || interval[1] > pl.n_iter))
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: the interval is a range of iterations inside [0, n_iter]");
+  if (max_consecutive < 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: max_consecutive must be >= 0 (0: no cap)");
+  if (c->cfg.depth_triple + c->cfg.depth_single < 1) return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: the model has no blocks to skip");
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the buffers may be in use by a previous loop on this stream
+  const int Bc = pl.ncfg * pl.clips;
+  const size_t bytes = (size_t)Bc * pl.La * c->cfg.hidden * 4;
+  TRY(grow(c->sc_delta, bytes));
+  TRY(grow(c->sc_mprev, bytes));
+  TRY(grow(c->sc_part, (size_t)cache_probe_floats(Bc, pl.La) * 4));
+  TRY(grow(c->sc_rel, (size_t)Bc * 4));
+  if (c->sc_rel_cap < Bc) {
+    if (c->sc_rel_host) (void)hipHostFree(c->sc_rel_host);
+    c->sc_rel_host = nullptr;
+    c->sc_rel_cap = 0;
+    HIPTRY(hipHostMalloc((void**)&c->sc_rel_host, (size_t)Bc * 4, hipHostMallocDefault));
+    c->sc_rel_cap = Bc;
+  }
+  c->sc_skip.clear();
+  if (mode == FOLEY_STEP_CACHE_SCHEDULE) c->sc_skip.assign(skip, skip + n_skip);
+  c->sc_threshold = threshold;
+  c->sc_poly.assign(poly, poly + n_poly);
+  c->sc_lo = interval ? interval[0] : 0;
+  c->sc_hi = interval ? interval[1] : pl.n_iter;
+  c->sc_maxc = max_consecutive;
+  c->sc_rep_rel.clear();
+  c->sc_rep_skip.clear();
+  c->sc_mode = mode;
+  return 0;
+}
+
+extern "C" int foley_step_cache_report(foley_ctx* c, float* rel, int32_t* skipped, int n) {
+  if (!c || !rel || !skipped) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  if (c->sc_rep_skip.empty() || n != (int)c->sc_rep_skip.size())
+    return FAIL(FOLEY_ERR_STATE, "foley_step_cache_report: no cached loop of n iterations has run since foley_set_step_cache");
+  std::copy(c->sc_rep_rel.begin(), c->sc_rep_rel.end(), rel);
+  std::copy(c->sc_rep_skip.begin(), c->sc_rep_skip.end(), skipped);
+  return 0;
+}
+
 // Test-only (not in include/foley_hip.h): out[0] = iterations captured into a graph so far, out[1..3] = addresses of the model
 // input rows (the workspace), the schedule table and the rescale factors - what a replay of the captured iteration addresses.
 extern "C" int foley_debug_run_state(foley_ctx* c, uint64_t* out) {
@@ -1380,26 +1546,33 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   const foley_plan& pl = c->plan;
   const size_t xbytes = (size_t)pl.clips * c->cfg.latent_dim * pl.La * 4;
   GraphKey key = graph_key_now(c);
+  const bool cached = c->sc_mode != 0;
   if (c->graph_exec && !(c->graph_key == key)) ctx_drop_graph(c);
   if (use_graph && !c->graph_exec) {
     // Every per-iteration value is read from device memory (step counter, tables) and every
     // buffer is context-owned, so ONE captured iteration replays for the whole loop and for
     // later runs of the same shape.
+    // Under the step cache the iteration is three such graphs (head, full body, skip body); the host picks a body per iteration.
     std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
     hipStream_t cs;
     HIPTRY(hipStreamSynchronize(st));
     HIPTRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    hipGraph_t graph = nullptr;
-    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+    hipGraphExec_t* const slots[3] = {&c->graph_head, &c->graph_exec, &c->graph_skip};
     int rc = 0;
-    if (e == hipSuccess) {
-      rc = run_iteration(c, cs);
-      hipError_t e2 = hipStreamEndCapture(cs, &graph);
-      if (e == hipSuccess) e = e2;
+    hipError_t e = hipSuccess;
+    for (int piece = cached ? SC_HEAD : SC_FULL; piece <= (cached ? SC_SKIP : SC_FULL) && rc == 0 && e == hipSuccess; ++piece) {
+      hipGraph_t graph = nullptr;
+      e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+      if (e == hipSuccess) {
+        rc = cached ? run_cached_piece(c, piece, cs) : run_iteration(c, cs);
+        hipError_t e2 = hipStreamEndCapture(cs, &graph);
+        if (e == hipSuccess) e = e2;
+      }
+      if (e == hipSuccess && rc == 0) e = hipGraphInstantiate(slots[piece], graph, nullptr, nullptr, 0);
+      if (graph) (void)hipGraphDestroy(graph);
     }
-    if (e == hipSuccess && rc == 0) e = hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0);
-    if (graph) (void)hipGraphDestroy(graph);
     (void)hipStreamDestroy(cs);
+    if (rc != 0 || e != hipSuccess) ctx_drop_graph(c);   // never a partial set
     if (rc != 0) return rc;
     if (e != hipSuccess) return FAIL(FOLEY_ERR_HIP, hipGetErrorString(e));
     c->graph_key = std::move(key);
@@ -1410,8 +1583,34 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   HIPTRY(hipMemcpyAsync(c->buf.x_cur, latents, xbytes, hipMemcpyDeviceToDevice, st));
   HIPTRY(hipMemsetAsync(c->buf.step_ctr, 0, sizeof(int), st));
   TRY(launch_latent_rows(c->buf.x_cur, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->buf.xin, c->cfg.compute_dtype, st));
+  StepCachePolicy policy;
+  if (cached) {
+    c->sc_rep_rel.assign(pl.n_iter, -1.f);
+    c->sc_rep_skip.assign(pl.n_iter, 0);
+  }
+  auto piece = [&](int which) -> int {
+    if (use_graph) HIPTRY(hipGraphLaunch(which == SC_HEAD ? c->graph_head : which == SC_FULL ? c->graph_exec : c->graph_skip, st));
+    else TRY(run_cached_piece(c, which, st));
+    return 0;
+  };
   for (int it = 0; it < pl.n_iter; ++it) {
-    if (use_graph) HIPTRY(hipGraphLaunch(c->graph_exec, st));
+    if (cached) {
+      TRY(piece(SC_HEAD));
+      float rel = -1.f;
+      if (c->sc_mode == FOLEY_STEP_CACHE_THRESHOLD) {   // the one read-back and synchronisation per iteration; schedule mode has none
+        const int Bc = pl.ncfg * pl.clips;
+        HIPTRY(hipMemcpyAsync(c->sc_rel_host, c->sc_rel.p, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
+        HIPTRY(hipStreamSynchronize(st));
+        if (it > 0) {   // iteration 0 has no previous m: not measured
+          rel = c->sc_rel_host[0];
+          for (int b = 1; b < Bc; ++b) rel = c->sc_rel_host[b] > rel ? c->sc_rel_host[b] : rel;   // one decision for the context
+          c->sc_rep_rel[it] = rel;
+        }
+      }
+      const bool skip = policy.decide(c, it, pl.n_iter, rel);
+      c->sc_rep_skip[it] = skip ? 1 : 0;
+      TRY(piece(skip ? SC_SKIP : SC_FULL));
+    } else if (use_graph) HIPTRY(hipGraphLaunch(c->graph_exec, st));
     else TRY(run_iteration(c, st));
     if (cb) {
       HIPTRY(hipMemcpyAsync(latents, c->buf.x_cur, xbytes, hipMemcpyDeviceToDevice, st));
@@ -1890,6 +2089,25 @@ extern "C" int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd
   w.s = step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype});
   w.n_win = n_win; w.Ltot = Ltot; w.starts = starts; w.weights = weights;
   return launch_solver_step_windows(w, (hipStream_t)stream);
+}
+
+extern "C" int64_t foley_op_cache_probe_work(int Bc, int La) { return Bc < 1 || La < 1 ? 0 : (int64_t)cache_probe_floats(Bc, La); }
+
+extern "C" int foley_op_cache_probe(const float* a0, int Bc, int La, int D, float eps, const foley_rowbcast* shift,
+                                    const foley_rowbcast* scale, float* m_prev, float* work, int64_t work_floats, float* rel,
+                                    void* stream) {
+  if (Bc < 1 || La < 1 || work_floats < (int64_t)cache_probe_floats(Bc, La))
+    return FAIL(FOLEY_ERR_INVALID, "foley_op_cache_probe: work is smaller than foley_op_cache_probe_work(Bc, La)");
+  TRY(launch_cache_probe(a0, Bc, La, D, eps, to_rb(shift), to_rb(scale), m_prev, work, rel, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int foley_op_cache_delta(const float* aN, float* delta, int64_t n, void* stream) {
+  TRY(launch_cache_delta(aN, delta, (long)n, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int foley_op_cache_apply(float* audio, const float* delta, int64_t n, void* stream) {
+  TRY(launch_cache_apply(audio, delta, (long)n, (hipStream_t)stream));
+  return 0;
 }
 
 extern "C" int64_t foley_op_guidance_stats_work(int clips, int L) { return clips < 1 || L < 1 ? 0 : (int64_t)guidance_stats_floats(clips, L); }

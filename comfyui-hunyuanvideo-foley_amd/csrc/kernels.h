@@ -226,6 +226,16 @@ int launch_solver_step(const StepArgs& a, hipStream_t st);
 // that is set (a captured graph then replays with a new value), from `phi` otherwise.
 long guidance_stats_floats(int clips, int L);
 int launch_guidance_stats(const StepArgs& a, float* part, const float* phi_ptr, float phi, float* clip_scale, hipStream_t st);
+// Step cache (foley_set_step_cache).  Probe: per row of a0 [Bc*La, D] the first block's modulated input m = LayerNorm(a0; eps) *
+// (1 + scale) + shift in fp32; m replaces m_prev [Bc*La, D] in place and rel[b] = sum|m - m_prev| /
+// sum|m_prev| over batch row b's La x D elements (0 when the denominator is 0).  Two launches: per-workgroup records into `part`
+// (cache_probe_floats(Bc, La) floats), then one wave per batch row merges them in a fixed order - no atomics, repeated runs give
+// the same bits.  delta: delta[i] = aN[i] - delta[i] (in place over a copy of a0); apply: audio[i] += delta[i].
+long cache_probe_floats(int Bc, int La);
+int launch_cache_probe(const float* a0, int Bc, int La, int D, float eps, const RowBcast& shift, const RowBcast& scale, float* m_prev,
+                       float* part, float* rel, hipStream_t st);
+int launch_cache_delta(const float* aN, float* delta, long n, hipStream_t st);
+int launch_cache_apply(float* audio, const float* delta, long n, hipStream_t st);
 // Edit form of the same step (audio-to-audio / span regeneration): after a row flagged STEP_BLEND (8) - the iteration that
 // ends a solver step - x <- m*x + (1-m)*(s*noise + (1-s)*x0) with s = coef row column 5 (sigma_{k+1}); mask null = all ones.
 struct StepEditArgs {

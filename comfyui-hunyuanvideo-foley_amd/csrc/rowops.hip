@@ -850,6 +850,125 @@ __global__ __launch_bounds__(64) void guidance_scale_kernel(const float* __restr
 
 __global__ void step_increment_kernel(int* p) { *p = *p + 1; }
 
+// ------------------------------------------------------------------ step cache: probe, residual, re-entry
+// The step cache (foley_set_step_cache) reuses the blocks' residual aN - a0 of the last full iteration while the first block's
+// modulated input m = LayerNorm(a0; eps) * (1 + scale) + shift barely moves.  cache_probe_kernel computes m of one stream row per
+// wave exactly as ln_mod_kernel does (every load of the row - a0, shift, scale and the previous m - issued before the first
+// reduction; mean, then the squares about it: never E[x^2] - E[x]^2), adds up |m - m_prev| and |m_prev| and writes m over m_prev (the
+// lane that read an element writes it: no hazard).  It does not copy a0: the residual buffer still holds the delta a skipped
+// iteration needs when the probe runs, so the full body takes its own copy of the stream first.  The four waves of a workgroup meet in LDS and
+// thread 0 adds them in wave order into the workgroup's record {sum|m - m_prev|, sum|m_prev|}; the grid is (ceil(La / 4), Bc), so a
+// record never mixes two batch rows.  cache_rel_kernel: one wave per batch row; lane j adds records j, j + 64, ... in ascending
+// order, lane 0 the 64 lanes' sums in lane order, rel_b = sum|m - m_prev| / sum|m_prev| (0 when that is 0).  Every order is fixed
+// and nothing is atomic: the same input gives the same bits.
+constexpr int CP_ROWS = 4;   // rows (= waves) per workgroup of the probe
+
+template <int MAXV>
+__global__ __launch_bounds__(64 * CP_ROWS) void cache_probe_kernel(const float* __restrict__ a0, int La, int D, float eps,
+                                                                   const RowBcast shift, const RowBcast scale,
+                                                                   float* __restrict__ m_prev, float* __restrict__ part) {
+  __shared__ float red[CP_ROWS][2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.y, l_u = blockIdx.x * CP_ROWS + wave;
+  const bool live = l_u < La;
+  const long row = (long)b * La + (live ? l_u : La - 1);   // dead waves shadow the batch row's last row (no stores, no sums)
+  const int nv = D >> 2;
+  const f32x4* xr = (const f32x4*)(a0 + row * D);
+  const f32x4* sh = shift.p ? (const f32x4*)rb_row(shift, (int)row) : nullptr;
+  const f32x4* sc = scale.p ? (const f32x4*)rb_row(scale, (int)row) : nullptr;
+  f32x4* mp = (f32x4*)(m_prev + row * D);
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 v[MAXV], hv[MAXV], cv[MAXV], ov[MAXV];
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = min(lane + i * 64, nv - 1);   // clamped: loads stay unconditional
+    v[i] = xr[c];
+    hv[i] = sh ? sh[c] : z4;
+    cv[i] = sc ? sc[c] : z4;
+    ov[i] = mp[c];
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i)
+    if (lane + i * 64 < nv) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i)
+    if (lane + i * 64 < nv) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float d = v[i][u] - mean;
+        q += d * d;
+      }
+    }
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+  float sd = 0.f, so = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = lane + i * 64;
+    if (live && c < nv) {
+      f32x4 y;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        y[u] = (v[i][u] - mean) * rstd * (1.0f + cv[i][u]) + hv[i][u];
+        sd += fabsf(y[u] - ov[i][u]);
+        so += fabsf(ov[i][u]);
+      }
+      mp[c] = y;
+    }
+  }
+  sd = wave_sum(sd);
+  so = wave_sum(so);
+  if (lane == 0) {
+    red[wave][0] = sd;
+    red[wave][1] = so;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float td = 0.f, to = 0.f;
+    for (int w = 0; w < CP_ROWS; ++w) {
+      td += red[w][0];
+      to += red[w][1];
+    }
+    float* o = part + ((long)b * gridDim.x + blockIdx.x) * 2;
+    o[0] = td;
+    o[1] = to;
+  }
+}
+
+__global__ __launch_bounds__(64) void cache_rel_kernel(const float* __restrict__ part, int nblk, float* __restrict__ rel) {
+  __shared__ float red[64][2];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float td = 0.f, to = 0.f;
+  for (int k = lane; k < nblk; k += 64) {
+    td += part[((long)b * nblk + k) * 2];
+    to += part[((long)b * nblk + k) * 2 + 1];
+  }
+  red[lane][0] = td;
+  red[lane][1] = to;
+  __syncthreads();
+  if (lane != 0) return;
+  for (int j = 1; j < 64; ++j) {
+    td += red[j][0];
+    to += red[j][1];
+  }
+  rel[b] = to > 0.f ? td / to : 0.f;
+}
+
+// delta = aN - a0 in place over a copy of a0 (SUB), audio += delta (!SUB): plain fp32, 16-byte accesses where both pointers
+// allow them (vec), the tail (and unaligned operands) one element at a time
+template <bool SUB>
+__global__ __launch_bounds__(256) void cache_axpy_kernel(const float* __restrict__ src, float* __restrict__ dst, long n, int vec) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long)gridDim.x * blockDim.x;
+  const long n4 = vec ? n >> 2 : 0;
+  for (long i = tid; i < n4; i += nth) {
+    const f32x4 a = ((const f32x4*)src)[i], d = ((f32x4*)dst)[i];
+    ((f32x4*)dst)[i] = SUB ? a - d : d + a;
+  }
+  for (long i = n4 * 4 + tid; i < n; i += nth) dst[i] = SUB ? src[i] - dst[i] : dst[i] + src[i];
+}
+
 // ------------------------------------------------------------------ DAC output conv (64 -> 1, k=7) + tanh
 // reference: decoder.model[-2:] = WNConv1d(C, 1, 7, padding=3), nn.Tanh() (dac.py:141-146).
 // A block handles 64 consecutive samples; the (64+6) x C snake-activated rows are staged in LDS.
@@ -1175,6 +1294,40 @@ int launch_guidance_stats(const StepArgs& a, float* part, const float* phi_ptr, 
   FOLEY_LAUNCH_CHECK();
   return 0;
 }
+
+long cache_probe_floats(int Bc, int La) { return (long)Bc * ((La + CP_ROWS - 1) / CP_ROWS) * 2; }
+
+int launch_cache_probe(const float* a0, int Bc, int La, int D, float eps, const RowBcast& shift, const RowBcast& scale, float* m_prev,
+                       float* part, float* rel, hipStream_t st) {
+  if (Bc < 1 || La < 1 || D < 4 || D % 4 || D > 8 * 256) return foley_set_err("cache_probe: D must be a multiple of 4 in [4, 2048], Bc and La >= 1", __FILE__, __LINE__);
+  if (!a0 || !m_prev || !part || !rel) return foley_set_err("cache_probe: null operand", __FILE__, __LINE__);
+  for (const void* p : {(const void*)a0, (const void*)m_prev, (const void*)shift.p, (const void*)scale.p})
+    if ((uintptr_t)p & 15) return foley_set_err("cache_probe: operands must be 16-byte aligned", __FILE__, __LINE__);
+  if ((shift.p && (shift.ld % 4 || shift.step_stride % 4)) || (scale.p && (scale.ld % 4 || scale.step_stride % 4)))
+    return foley_set_err("cache_probe: shift / scale row pitch must be a multiple of 4", __FILE__, __LINE__);
+  const dim3 grid((La + CP_ROWS - 1) / CP_ROWS, Bc), block(64 * CP_ROWS);
+  const int need = (D / 4 + 63) / 64;   // float4 per lane
+  if (need <= 1) FOLEY_LAUNCH((cache_probe_kernel<1>), grid, block, 0, st, a0, La, D, eps, shift, scale, m_prev, part);
+  else if (need <= 6) FOLEY_LAUNCH((cache_probe_kernel<6>), grid, block, 0, st, a0, La, D, eps, shift, scale, m_prev, part);
+  else FOLEY_LAUNCH((cache_probe_kernel<8>), grid, block, 0, st, a0, La, D, eps, shift, scale, m_prev, part);
+  FOLEY_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cache_rel_kernel, dim3(Bc), dim3(64), 0, st, part, (int)grid.x, rel);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+static int launch_cache_axpy(bool sub, const float* src, float* dst, long n, hipStream_t st) {
+  if (n < 0 || (n > 0 && (!src || !dst))) return foley_set_err("cache_delta / cache_apply: bad operands", __FILE__, __LINE__);
+  if (n == 0) return 0;
+  const int vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+  const dim3 grid(grid1d((n + 3) / 4, 256)), block(256);
+  if (sub) FOLEY_LAUNCH((cache_axpy_kernel<true>), grid, block, 0, st, src, dst, n, vec);
+  else FOLEY_LAUNCH((cache_axpy_kernel<false>), grid, block, 0, st, src, dst, n, vec);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+int launch_cache_delta(const float* aN, float* delta, long n, hipStream_t st) { return launch_cache_axpy(true, aN, delta, n, st); }
+int launch_cache_apply(float* audio, const float* delta, long n, hipStream_t st) { return launch_cache_axpy(false, delta, audio, n, st); }
 
 int launch_solver_step_edit(const StepEditArgs& e, hipStream_t st) {
   const StepArgs& a = e.s;

@@ -128,6 +128,9 @@ _SIGNATURES = {
     "foley_set_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_set_windows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "foley_set_guidance": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p]),
+    "foley_set_step_cache": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int,
+                                       C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "foley_step_cache_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int]),
     "foley_dac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                    C.c_void_p, C.c_void_p]),
@@ -179,6 +182,11 @@ _SIGNATURES = {
     "foley_op_guidance_stats_work": (C.c_int64, [C.c_int, C.c_int]),
     "foley_op_guidance_stats": (C.c_int, [C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "foley_op_cache_probe_work": (C.c_int64, [C.c_int, C.c_int]),
+    "foley_op_cache_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(RowBcastC), C.POINTER(RowBcastC),
+                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "foley_op_cache_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "foley_op_cache_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "foley_op_flow_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                     C.c_void_p]),
     "foley_op_latent_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
@@ -488,6 +496,26 @@ class FoleyContext:
             arr = (C.c_float * (2 * n))(*t.flatten().tolist())
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.foley_set_guidance(self._h, arr, n, float(rescale), _stream()), "foley_set_guidance")
+
+    def set_step_cache(self, mode: int = 0, skip=None, threshold: float = 0.0, poly=None, interval=None, max_consecutive: int = 0):
+        """foley_set_step_cache after prepare() (host/step_cache.py states the policy): mode 0 clears; 1 = schedule with `skip`, one
+        0 / 1 entry per iteration of the prepared plan; 2 = threshold with `poly` (highest degree first, None: identity),
+        `interval` = (lo, hi) iteration indices that may skip (None: all) and `max_consecutive` (0: no cap)."""
+        arr = (C.c_uint8 * len(skip))(*[1 if v else 0 for v in skip]) if skip is not None else None
+        pol = (C.c_double * len(poly))(*[float(k) for k in poly]) if poly else None
+        itv = (C.c_int32 * 2)(int(interval[0]), int(interval[1])) if interval is not None else None
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_set_step_cache(self._h, int(mode), arr, len(skip) if skip is not None else 0, float(threshold),
+                                                           pol, len(poly) if poly else 0, itv, int(max_consecutive or 0), _stream()),
+                   "foley_set_step_cache")
+
+    def step_cache_report(self):
+        """(rel, skipped) of the last sample() under the step cache: per iteration the measured change (-1.0: not measured -
+        iteration 0, and every iteration of schedule mode) and 0 / 1."""
+        n = int(self.plan["n_iter"])
+        rel, sk = (C.c_float * n)(), (C.c_int32 * n)()
+        _check(self.lib, self.lib.foley_step_cache_report(self._h, rel, sk, n), "foley_step_cache_report")
+        return list(rel), list(sk)
 
     def abort(self) -> None:
         """Ask a foley_sample running on another thread to stop after its current iteration (it raises FoleyRuntimeError)."""
@@ -990,6 +1018,39 @@ def op_guidance_stats(pred, clips, L, ncfg, guidance, sched, step_ptr, rescale, 
     _check(lib, lib.foley_op_guidance_stats(C.byref(gd), _ptr(pred), clips, int(pred.shape[1]), L, ncfg, float(guidance),
                                             _ptr(step_ptr), float(rescale), _ptr(work), n, _stream()), "foley_op_guidance_stats")
     return out
+
+
+def op_cache_probe(a0: torch.Tensor, Bc: int, eps: float, shift: Optional[RowBcastC], scale: Optional[RowBcastC], m_prev: torch.Tensor,
+                   rel: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """foley_op_cache_probe: a0 [Bc*La, D] fp32 -> m over m_prev, the change per batch row [Bc] fp32 (new, or `rel`)."""
+    lib = load_library()
+    M, D = a0.shape
+    if a0.dtype != torch.float32 or M % Bc or m_prev.dtype != torch.float32 or m_prev.numel() != a0.numel():
+        raise FoleyRuntimeError("op_cache_probe: a0 [Bc*La, D] and m_prev of its size, fp32")
+    La = M // Bc
+    n = int(lib.foley_op_cache_probe_work(Bc, La))
+    work = torch.empty(n, dtype=torch.float32, device=a0.device)
+    rel = rel if rel is not None else torch.empty(Bc, dtype=torch.float32, device=a0.device)
+    _check(lib, lib.foley_op_cache_probe(_ptr(a0), Bc, La, D, float(eps), C.byref(shift) if shift else None,
+                                         C.byref(scale) if scale else None, m_prev.data_ptr(), _ptr(work), n,
+                                         _ptr(rel), _stream()), "foley_op_cache_probe")
+    return rel
+
+
+def op_cache_delta(aN: torch.Tensor, delta: torch.Tensor):
+    """foley_op_cache_delta: delta <- aN - delta in place (fp32, any shape; views with a pitch are not supported)."""
+    lib = load_library()
+    if aN.dtype != torch.float32 or delta.dtype != torch.float32 or aN.numel() != delta.numel():
+        raise FoleyRuntimeError("op_cache_delta: two fp32 tensors of one size")
+    _check(lib, lib.foley_op_cache_delta(_ptr(aN), _ptr(delta), aN.numel(), _stream()), "foley_op_cache_delta")
+
+
+def op_cache_apply(audio: torch.Tensor, delta: torch.Tensor):
+    """foley_op_cache_apply: audio += delta in place (fp32)."""
+    lib = load_library()
+    if audio.dtype != torch.float32 or delta.dtype != torch.float32 or audio.numel() != delta.numel():
+        raise FoleyRuntimeError("op_cache_apply: two fp32 tensors of one size")
+    _check(lib, lib.foley_op_cache_apply(_ptr(audio), _ptr(delta), audio.numel(), _stream()), "foley_op_cache_apply")
 
 
 def op_windows_stitch(x: torch.Tensor, starts: torch.Tensor, weights: torch.Tensor, Ltot: int) -> torch.Tensor:

@@ -14,9 +14,10 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import cond_sets, packers, runtime, tables
+from . import cond_sets, packers, runtime, step_cache as _sc, tables
 from .config import DAC48K, DACConfig, DiTConfig
 from .runtime import FoleyContext, FoleyRuntimeError
+from .step_cache import StepCacheSpec
 
 
 class FoleyModel:
@@ -170,16 +171,36 @@ def apply_guidance(ctx: FoleyContext, plan: dict) -> None:
         ctx.set_guidance(plan.get("guid_sched"), plan.get("guid_rescale", 0.0))
 
 
+def apply_step_cache(ctx: FoleyContext, plan: dict) -> None:
+    """foley_set_step_cache with what build_plan put into the plan (after prepare, next to apply_guidance / set_edit / set_windows)."""
+    sc = plan.get("step_cache")
+    if sc is not None:
+        ctx.set_step_cache(**sc)
+
+
+def keep_step_cache_report(ctx: FoleyContext, plan: dict) -> None:
+    """After the loop: plan["step_cache_report"] = {"rel": [...], "skipped": [...]} (the node logs it)."""
+    if plan.get("step_cache") is None:
+        return
+    rel, skipped = ctx.step_cache_report()
+    plan["step_cache_report"] = {"rel": rel, "skipped": skipped}
+
+
 def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_feats: Dict[str, torch.Tensor],
                La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str,
-               edit_i0: Optional[int] = None, guidance: Optional[GuidanceSpec] = None) -> dict:
+               edit_i0: Optional[int] = None, guidance: Optional[GuidanceSpec] = None,
+               step_cache: Optional[StepCacheSpec] = None) -> dict:
     """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables.
     edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows.
     Each conditioning tensor has batch 1 (shared by all clips) or batch_size (one row per clip, host/cond_sets.py): the plan
     then holds the distinct sets and the maps `text_of` / `vis_of` (None when every clip shares its conditioning).
     guidance (GuidanceSpec): three halves when it carries a video scale, and the schedule table / rescale value that
-    apply_guidance hands to the library after prepare (`guid_sched`, `guid_rescale`)."""
+    apply_guidance hands to the library after prepare (`guid_sched`, `guid_rescale`).
+    step_cache (StepCacheSpec, host/step_cache.py): the arguments apply_step_cache hands to the library after prepare
+    (`step_cache`); an edit run takes the rows [edit_i0, steps) of a skip list and of an interval, as of the guidance table."""
     cfg, dev = model.cfg, model.device
+    if step_cache is not None:
+        step_cache.check(int(steps))
     if guidance is not None:
         guidance.check(guidance_scale)
     three = guidance is not None and guidance.g_video is not None
@@ -248,6 +269,14 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
         plan["guid_sched"] = sched[edit_i0 or 0:].contiguous()
     if guidance is not None:
         plan["guid_rescale"] = float(guidance.rescale)
+    if step_cache is not None:
+        i0 = edit_i0 or 0
+        if step_cache.mode == _sc.MODE_SCHEDULE:
+            plan["step_cache"] = {"mode": _sc.MODE_SCHEDULE, "skip": step_cache.skip_rows(int(steps), i0)}
+        else:
+            plan["step_cache"] = {"mode": _sc.MODE_THRESHOLD, "threshold": float(step_cache.threshold), "poly": step_cache.poly,
+                                  "interval": step_cache.interval_rows(int(steps), i0),
+                                  "max_consecutive": int(step_cache.max_consecutive or 0)}
     return plan
 
 
@@ -257,7 +286,7 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
                                    progress: Optional[Callable[[int, int], None]] = None,
                                    return_latents: bool = False, noise: Optional[torch.Tensor] = None,
                                    _abort_event: Optional[threading.Event] = None, edit=None, windows=None,
-                                   guidance: Optional[GuidanceSpec] = None):
+                                   guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None):
     """Same contract as the reference function of this name (utils.py:125-258):
     returns (audio [bs, 1, T] fp32 on the model's device, sample_rate).
 
@@ -269,12 +298,16 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     one window takes the plain path exactly; `windows` together with `edit` is refused.
 
     guidance (GuidanceSpec): separate video / text scales (three halves), a guidance interval and CFG rescale; it combines
-    with `edit` and with `windows`.  None is the plain run, bit for bit."""
+    with `edit` and with `windows`.  None is the plain run, bit for bit.
+
+    step_cache (StepCacheSpec): skip the blocks on iterations whose model input barely moved (threshold mode) or on listed
+    iterations (schedule mode) and reuse their last residual; it combines with guidance, `edit` and `windows`.  The decisions of
+    the run are kept in model.ctx.plan["step_cache_report"].  None runs every block on every iteration, bit for bit."""
     if windows is not None and windows.n_win > 1:
         if edit is not None:
             raise ValueError("windows= and edit= together: editing a long clip is not supported")
         return _denoise_windows(visual_feats, text_feats, model, dac, guidance_scale, num_inference_steps, batch_size, sampler,
-                                windows, generator, use_graph, progress, return_latents, noise, _abort_event, guidance)
+                                windows, generator, use_graph, progress, return_latents, noise, _abort_event, guidance, step_cache)
     cfg = model.cfg
     La = int(audio_len_in_s * cfg.frame_rate)
     if noise is None:
@@ -282,24 +315,27 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     latents = noise.to(device=model.device, dtype=torch.float32).contiguous()
     if edit is None:
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          guidance=guidance)
+                          guidance=guidance, step_cache=step_cache)
         model.attach_dac(dac)
         model.ctx.prepare(plan)
         apply_guidance(model.ctx, plan)
+        apply_step_cache(model.ctx, plan)
     else:
         k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
         x0, mask = edit.device_operands(model.device, batch_size, La)
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          edit_i0=i0, guidance=guidance)
+                          edit_i0=i0, guidance=guidance, step_cache=step_cache)
         model.attach_dac(dac)
         model.ctx.prepare(plan)
         apply_guidance(model.ctx, plan)
+        apply_step_cache(model.ctx, plan)
         model.ctx.set_edit(x0, latents, mask)
         sigma0 = float(tables.sigma_grid(num_inference_steps, cfg.flow_shift)[k0])
         latents = runtime.op_flow_mix(latents, x0, sigma0)
     if _abort_event is not None and _abort_event.is_set():      # another replica of a data-parallel run failed meanwhile
         raise FoleyRuntimeError("sampling aborted: another replica failed")
     model.ctx.sample(latents, use_graph=use_graph, progress=progress)
+    keep_step_cache_report(model.ctx, plan)
     audio = model.ctx.dac_decode(latents)
     # (the reference's "trim to exact length" slices the size-1 channel axis: a no-op)
     sr = dac.sample_rate if dac is not None else model.dac_cfg.sample_rate
@@ -321,7 +357,7 @@ def window_rows(t: torch.Tensor, variations: int, n_win: int, what: str) -> torc
 
 def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC, guidance_scale, num_inference_steps,
                      variations, sampler, windows, generator, use_graph, progress, return_latents, noise, _abort_event,
-                     guidance=None):
+                     guidance=None, step_cache=None):
     """One long clip per variation as a batch of variations*n_win coupled windows (clip v*n_win + k = window k of variation v).
     The noise is drawn ONCE as [variations, C, Ltot] - draw_noise, the same generator and dtype rule as a plain run - and every
     window takes its slice, so overlapping frames start equal.  The plan carries the blend rows (edit_i0 = 0 tables); after every
@@ -341,15 +377,18 @@ def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC,
         raise ValueError(f"noise of a windowed run is [variations, C, Ltot] = {(variations, cfg.latent_dim, Ltot)}, got {tuple(noise.shape)}")
     noise = noise.to(device=model.device, dtype=torch.float32)
     latents = torch.stack([noise[v, :, s:s + La] for v in range(variations) for s in windows.starts]).contiguous()
-    plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0, guidance=guidance)
+    plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0, guidance=guidance,
+                      step_cache=step_cache)
     model.attach_dac(dac)
     model.ctx.prepare(plan)
     apply_guidance(model.ctx, plan)
+    apply_step_cache(model.ctx, plan)
     weights = windows.weights.to(model.device)
     model.ctx.set_windows(windows.starts, weights)
     if _abort_event is not None and _abort_event.is_set():
         raise FoleyRuntimeError("sampling aborted: another replica failed")
     model.ctx.sample(latents, use_graph=use_graph, progress=progress)
+    keep_step_cache_report(model.ctx, plan)
     starts = torch.tensor(windows.starts, dtype=torch.int32, device=model.device)
     stitched = runtime.op_windows_stitch(latents, starts, weights, Ltot)
     audio = model.ctx.dac_decode(stitched)
@@ -440,7 +479,7 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                           num_inference_steps: int, batch_size: int, sampler: str,
                           generator: Optional[torch.Generator] = None, use_graph: bool = True,
                           progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None,
-                          guidance: Optional[GuidanceSpec] = None):
+                          guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None):
     """`denoise_process_with_generator` with the clips of the batch sharded over `replicas` (the pairs
     `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199 batches clips that
     share their conditioning; per-clip conditioning, host/cond_sets.py, only changes what each clip reads), so there is no
@@ -454,7 +493,9 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     rotation, gemm.hip g_gemm_krot_ok), a different but deterministic summation order (tests/test_pairs_gpu.py pins how
     far it moves a result).  `edit` as for denoise_process_with_generator: per-clip source latents and masks are sharded with
     the noise.  A windowed run (denoise_process_with_generator's `windows`) is not sharded here: the windows of one variation
-    are coupled after every step, so it runs on one device.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
+    are coupled after every step, so it runs on one device.  `step_cache` is forwarded to every shard: a skip list gives what one GPU
+    gives; in threshold mode every shard decides from the rows it holds (the max over them), so the decisions - and with them the
+    clips - depend on the sharding.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
     from .distributed import shard_range
     if not replicas:
         raise FoleyRuntimeError("no replicas")
@@ -503,7 +544,8 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                     audio_len_in_s, model, dac, guidance_scale, num_inference_steps, hi - lo,
                     sampler, use_graph=use_graph, noise=noise[lo:hi], return_latents=True,
                     progress=progress if r == 0 else None, _abort_event=failed,
-                    edit=edit.shard(lo, hi, batch_size) if edit is not None else None, guidance=guidance)
+                    edit=edit.shard(lo, hi, batch_size) if edit is not None else None, guidance=guidance,
+                    step_cache=step_cache)
                 torch.cuda.current_stream().synchronize()
         except Exception as e:          # surfaced on the calling thread
             running[r] = False          # FIRST: a second failing (or aborted) worker must not keep the first one waiting on it

@@ -26,6 +26,14 @@ from .host import sampler as _sampler
 
 log = logging.getLogger("HunyuanVideo-Foley[MI355X]")
 
+
+def log_step_cache(models) -> None:
+    """One line per context that ran under the step cache: `skipped k of n` (its plan["step_cache_report"])."""
+    for m in models:
+        rep = (getattr(m.ctx, "plan", None) or {}).get("step_cache_report")
+        if rep is not None:
+            log.info("step cache: skipped %d of %d iterations", sum(rep["skipped"]), len(rep["skipped"]))
+
 _SOLVERS = ["euler", "heun-2", "midpoint-2", "kutta-4"]
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -324,7 +332,8 @@ class HunyuanFoleySampler:
                        steps, sampler, batch_size, seed, force_offload, image=None, torch_compile_cfg=None,
                        block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1,
                        prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0,
-                       video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0):
+                       video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0, cache_threshold=None, cache_skip=None,
+                       cache_interval=None, cache_max_consecutive=None):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -353,8 +362,27 @@ class HunyuanFoleySampler:
         iteration (nothing / video / video + prompt) instead of two.  `guidance_interval` (start, end) in fractions of the
         loop - guidance acts on the iterations inside it, the others take the conditional prediction (every pass still runs).
         `cfg_rescale` in [0, 1] pulls the guided prediction's spread back to the conditional one's (0: off).  They combine with
-        audio editing and long clips."""
+        audio editing and long clips.
+
+        Step cache (keyword-only, not sockets; host/step_cache.py::StepCacheSpec): reuse the blocks' residual on iterations
+        whose model input barely moved, instead of running the blocks.  `cache_threshold` - skip while the accumulated relative
+        change of the first block's input stays below it (uncalibrated: start near 0.2; one decision serves the whole batch, so a
+        clip's result depends on its batch), limited by `cache_interval` (start, end) in fractions of the loop and
+        `cache_max_consecutive`; or `cache_skip` - the list of iteration indices to skip.  The first and the last iteration always
+        run in full.  It combines with guidance, audio editing, per-clip conditioning and long clips; the log says how many
+        iterations were skipped."""
         model, deps = hunyuan_model, hunyuan_deps
+        step_cache = None
+        if cache_threshold is not None or cache_skip is not None:
+            if cache_threshold is not None and cache_skip is not None:
+                raise ValueError("cache_threshold and cache_skip together: choose threshold mode or a skip list")
+            step_cache = _sampler.StepCacheSpec(
+                threshold=None if cache_threshold is None else float(cache_threshold),
+                skip=None if cache_skip is None else tuple(int(i) for i in cache_skip), interval=cache_interval,
+                max_consecutive=cache_max_consecutive)
+            step_cache.check(int(steps))       # refused here, before the encoders run
+        elif cache_interval is not None or cache_max_consecutive is not None:
+            raise ValueError("cache_interval / cache_max_consecutive limit threshold mode: pass cache_threshold")
         guidance = None
         if video_cfg_scale is not None or guidance_interval is not None or cfg_rescale:
             if video_cfg_scale is not None and image is None and images is None and features is None:
@@ -421,23 +449,28 @@ class HunyuanFoleySampler:
             pass
         progress = (lambda i, n: pbar.update_absolute(i, n)) if pbar is not None else None
         n_dev = torch.cuda.device_count() if os.environ.get("FOLEY_DATA_PARALLEL", "0") == "1" else 1
+        ran_on = [model]                        # the models whose contexts ran a shard (the step cache's log line)
         if windows is not None:                 # coupled windows: one device
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                windows=windows, guidance=guidance)
+                windows=windows, guidance=guidance, step_cache=step_cache)
         elif batch_size > 1 and n_dev > 1 and model.arena is not None:
             # clips are independent: shard them over the node's GPUs (host/sampler.py::denoise_process_multi; the widget
             # list is the reference's, so the switch is an environment variable - INTEGRATION.md)
             devs = [model.device] + [torch.device("cuda", i) for i in range(n_dev) if i != model.device.index]
             reps = _sampler.replicate(model, deps["dac_model"], devs[:batch_size])
+            ran_on = [m for m, _ in reps]
             audio, sr = _sampler.denoise_process_multi(visual, text, audio_len_in_s, reps, cfg_scale, steps, batch_size,
-                                                       sampler, generator=rng, progress=progress, edit=edit, guidance=guidance)
+                                                       sampler, generator=rng, progress=progress, edit=edit, guidance=guidance,
+                                                       step_cache=step_cache)
         else:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                edit=edit, guidance=guidance)
+                edit=edit, guidance=guidance, step_cache=step_cache)
+        if step_cache is not None:
+            log_step_cache(ran_on)
         waveform_batch = audio.float().cpu()
         first = {"waveform": waveform_batch[0].unsqueeze(0), "sample_rate": sr}
         return (first, {"waveform": waveform_batch, "sample_rate": sr})

@@ -231,6 +231,36 @@ int foley_set_windows(foley_ctx* ctx, int n_win, const int32_t* starts, const fl
  * plan.ncfg == 1, n_rows != plan.n_iter, rescale outside [0, 1]: FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE. */
 int foley_set_guidance(foley_ctx* ctx, const float* sched, int n_rows, float rescale, void* stream);
 
+/* Step cache (additive within ABI 12; opt-in): reuse the blocks' residual on iterations whose model input barely moved - what
+ * DiT samplers call TeaCache / first-block cache.  For one model call of loop iteration i (multi-stage solvers: every stage is an
+ * iteration) let a0 be the audio stream after audio_embedder + add_sync, aN the stream after the last block and m the first
+ * block's modulated audio input LayerNorm(a0; eps) * (1 + scale) + shift in fp32 (the eps and modulation rows that block's first
+ * LayerNorm gets).  A FULL iteration runs the forward as ever and keeps delta = aN - a0 (fp32).  A SKIPPED iteration computes a0
+ * from the current input rows, sets the stream to a0 + delta and runs final.layernorm, final.linear and the unchanged solver step
+ * (guided / edit / windows form alike) - no modulation GEMM, no visual gather, no block.  Every iteration replaces m_prev by m and
+ * measures rel = max over the batch rows b (half x clip) of sum|m - m_prev| / sum|m_prev| over the row's La x hidden elements
+ * (0 where the denominator is 0).  Iteration 0, the last iteration and any iteration without a delta of this loop are full.
+ *   mode FOLEY_STEP_CACHE_SCHEDULE   skip exactly the iterations with skip[i] != 0 (n_skip must equal plan.n_iter; an edit run
+ *                                    passes the rows [i0, steps) of the plain run's list).  No read-back, no synchronisation.
+ *   mode FOLEY_STEP_CACHE_THRESHOLD  every iteration i >= 1 adds poly(rel) to an accumulator (poly: n_poly coefficients, highest
+ *                                    degree first; n_poly 0: the identity) and is skipped while the accumulator is < threshold;
+ *                                    a full iteration resets it to 0.  interval (NULL: everywhere): iterations [interval[0],
+ *                                    interval[1]) may skip; max_consecutive > 0 caps a run of skips.  One device-to-host copy of
+ *                                    ncfg*clips floats and one stream synchronisation per iteration; ONE decision serves the
+ *                                    whole context, so a clip's result depends on what it is batched with.
+ *   mode 0                           clears the state, as does foley_prepare.
+ * delta and m_prev ([ncfg*clips*La, hidden] fp32 each) are context-owned.  The captured iteration is keyed on cache on / off (on:
+ * three linear graphs - head, full body, skip body); mode, threshold and list are host decisions and keep the graphs.  Off, a run
+ * keeps its bits and its single graph.  n_skip != n_iter, a negative or non-finite threshold, non-finite coefficients, an interval
+ * outside [0, n_iter]: FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE.
+ * foley_step_cache_report: rel[i] (-1: not measured - iteration 0, and every iteration of schedule mode) and skipped[i] of the
+ * last foley_sample under the cache; n must equal its plan.n_iter. */
+#define FOLEY_STEP_CACHE_SCHEDULE 1
+#define FOLEY_STEP_CACHE_THRESHOLD 2
+int foley_set_step_cache(foley_ctx* ctx, int mode, const uint8_t* skip, int n_skip, double threshold, const double* poly,
+                         int n_poly, const int32_t* interval, int max_consecutive, void* stream);
+int foley_step_cache_report(foley_ctx* ctx, float* rel, int32_t* skipped, int n);
+
 /* DAC-VAE decoder: latents [clips, latent_dim, T] fp32 -> waveform [clips, 1, T*hop] fp32. */
 int foley_dac_decode(foley_ctx* ctx, const float* latents, int clips, int T, float* wave, void* stream);
 
@@ -446,6 +476,17 @@ int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const flo
 int64_t foley_op_guidance_stats_work(int clips, int L);
 int foley_op_guidance_stats(const foley_guidance_desc* gd, const float* pred, int clips, int C, int L, int ncfg, float guidance,
                             const int32_t* step_ptr, float rescale, float* work, int64_t work_floats, void* stream);
+/* The step cache's kernels (see foley_set_step_cache), all operands on the DEVICE, fp32, 16-byte aligned for the probe.
+ * cache_probe: a0 [Bc*La, D] (D a multiple of 4 up to 2048) -> m = LayerNorm(a0; eps) * (1 + scale) + shift written over m_prev
+ *   [Bc*La, D], rel[b] = sum|m - m_prev| / sum|m_prev| of batch row b (0 when the denominator is 0).
+ *   `work`: scratch of at least foley_op_cache_probe_work(Bc, La) floats.  Two launches, bit-identical on repetition.
+ * cache_delta: delta[i] = aN[i] - delta[i] for i < n (in place over a copy of a0).  cache_apply: audio[i] += delta[i]. */
+int64_t foley_op_cache_probe_work(int Bc, int La);
+int foley_op_cache_probe(const float* a0, int Bc, int La, int D, float eps, const foley_rowbcast* shift,
+                         const foley_rowbcast* scale, float* m_prev, float* work, int64_t work_floats, float* rel,
+                         void* stream);
+int foley_op_cache_delta(const float* aN, float* delta, int64_t n, void* stream);
+int foley_op_cache_apply(float* audio, const float* delta, int64_t n, void* stream);
 /* x [variations*n_win, C, L] -> out [variations, C, Ltot]: the weighted mean above per global frame; where the covering windows
  * hold the identical bits (always after a blend row) that value is copied as it is.  starts / weights on the device. */
 int foley_op_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int32_t* starts,
