@@ -607,6 +607,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   constexpr int STG = 32 * KP + HD * VP;                 // one stage: K tile + V^T tile
   constexpr int NS = HD / 16, ND = HD / 32;              // k-steps of Q K^T, 32-wide output fragments
   constexpr int CK = HD / 8, NP = HD / 64;               // 16-byte chunks per K row, staging pieces per thread and tile
+  // Head dim 64 in bf16 (the conditioning encoders): a probability travels as TWO bf16 values, its rounding and the rounding's
+  // residual, and P V runs over both.  The encoders' rows are short - 9 keys in the Synchformer's time attention - and one 8-bit
+  // probability can then carry a row's whole error (up to 2^-8 of sum p |v|, seen at 1.4 x the per-element bound of
+  // tests/opcheck.py, which allows half of that); with the residual the rounding of P drops to 2^-16.  Two more MFMAs per tile
+  // and fragment; the DiT's instances (head dim 128 / 96) and fp16 (11 bits) carry no trace of it.
+  constexpr bool PSPLIT = HD == 64 && __is_same(T, bf16_t);
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * STG];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int j = lane & 31, kh = lane >> 5;
@@ -729,12 +735,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const float m_new = fmaxf(m_run, mx * scale2);
     const float m_exp = (GRP && m_new == -INFINITY) ? 0.f : m_new;   // GRP: no visible key so far - exp2(-inf - 0) = 0, not exp2(-inf + inf)
     float ps = 0.f;
-    bf16x8 pb[2];
+    bf16x8 pb[2], pr[PSPLIT ? 2 : 1];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(s[e], scale2, -m_exp));
       ps += pv;
-      pb[e >> 3][e & 7] = to_carrier<T>(pv);
+      const __bf16 hi = to_carrier<T>(pv);
+      pb[e >> 3][e & 7] = hi;
+      if constexpr (PSPLIT) pr[e >> 3][e & 7] = (__bf16)(pv - (float)hi);   // exact difference, rounded once more
     }
     ps = xhalf_sum(ps);
     // the 64 accumulator rescales only when some query's running maximum moved (rare after the first tiles)
@@ -751,8 +759,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int d = 0; d < ND; ++d)
-        o[d] = mfma16<T>(*(const bf16x8*)(Vs + (d * 32 + j) * VP + (16 * kh + 8 * u) * 2), pb[u], o[d]);
+      for (int d = 0; d < ND; ++d) {
+        const bf16x8 vfrag = *(const bf16x8*)(Vs + (d * 32 + j) * VP + (16 * kh + 8 * u) * 2);
+        o[d] = mfma16<T>(vfrag, pb[u], o[d]);
+        if constexpr (PSPLIT) o[d] = mfma16<T>(vfrag, pr[u], o[d]);
+      }
     }   // live
     const long long cb = acct ? (long long)__builtin_readcyclecounter() : 0;
     if (t + 1 < nt) {

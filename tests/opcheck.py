@@ -17,6 +17,7 @@ Conventions
 GEMM accumulation term: e_y = (K + 4) * U32 * mag, mag = |A| @ |W|^T + |bias| - the deterministic worst case of K fp32
 additions in ANY order (split-K, K-origin rotation, atomics, tap fusion), plus the bias add and the epilogue's own roundings.
 """
+import functools
 import math
 
 import torch
@@ -158,11 +159,17 @@ def head_split_bound(e_y, y_head, out_dtype, gain=None):
     through unchanged.  Two departures from the plain '2 e_y / rms per element', both needed for the bound to be true: e_y is
     the head's LARGEST (RoPE mixes an element with its pair partner, the rms with all 128), and 8 U32 |gain| max|y| / rms covers
     the fp32 roundings of the norm, the gain and the rotation themselves (at e_y ~ 1e-3 it is four orders below the first term)."""
+    return Bound(head_split_pre_bound(e_y, y_head, gain), out_dtype)
+
+
+def head_split_pre_bound(e_y, y_head, gain=None):
+    """The part of head_split_bound BEFORE the final rounding to the output type: the bound on the fp32 value a head-split
+    epilogue holds in registers (what the fused cross attention rounds to 16 bit on chip, cross_attention_ref_and_bound)."""
     if gain is None:
-        return Bound(e_y, out_dtype)
+        return e_y
     rms = y_head.double().pow(2).mean(-1, keepdim=True).sqrt()
     g = float(gain.double().abs().max())
-    return Bound((2.0 * g * e_y.amax(-1, keepdim=True) / rms).expand_as(e_y).clone() + 8 * U32 * g * (y_head.double().abs() / rms).amax(-1, keepdim=True), out_dtype)
+    return (2.0 * g * e_y.amax(-1, keepdim=True) / rms).expand_as(e_y).clone() + 8 * U32 * g * (y_head.double().abs() / rms).amax(-1, keepdim=True)
 
 
 # ----------------------------------------------------------------------------- the check
@@ -294,7 +301,8 @@ def attention_ref_and_bound(q, k, v, out_dtype, p_dtype=None):
     in the numerator and once in the row sum; u_p the rounding of a probability to the operand type before the P V MFMA.
     Read from attention.hip: every 16-bit kernel (attn_bf16 / lds / wide / long / pair) rounds P ONCE, right after the
     exponential (to_carrier), and sums the row from the UNROUNDED fp32 values, so c_p = 1 and u_p = U16[p_dtype]; the fp32 kernel
-    rounds nothing: c_p = 1 with u_p = U32.
+    rounds nothing: c_p = 1 with u_p = U32.  (attn_bf16_wide_kernel at head dim 64 in bf16 also multiplies V with the rounding's
+    residual, so its P carries ~ 2^-16; the bound does not count on it.)
     NOT rigorous for the fp32 kernel (and, to a lesser degree, the others): the expression leaves out the Skv fp32 additions of the
     P V product and of the row sum (worst case (Skv + 4) U32 P @ |V|: 4e-4 at Skv = 3480 against 2 d_s ~ 2e-4) and the error of the
     exponential.  It holds in practice because those errors add like a random walk while d_s is a worst case (MI355X: fp32 kernel at
@@ -312,6 +320,136 @@ def attention_ref_and_bound(q, k, v, out_dtype, p_dtype=None):
         ref[b] = (p @ vb).transpose(0, 1).reshape(Sq, H * hd)
         e[b] = ((u_p + 2 * d_s) * (p @ vb.abs())).transpose(0, 1).reshape(Sq, H * hd)
     return ref, Bound(e, out_dtype)
+
+
+def grouped_attention_ref_and_bound(q, k, v, grp_q, grp_kv, out_dtype, p_dtype=None):
+    """Block-diagonal attention in fp64 from the operands as rounded: q [G, H, Sq, hd], k / v [G, H, Skv, hd]; query t of a sequence
+    sees keys [(t // grp_q) grp_kv, (t // grp_q + 1) grp_kv) only - the last group may be ragged (fewer than grp_q queries), keys
+    beyond the last group are seen by nobody.  attention_ref_and_bound applied group by group; returns ([G, Sq, H hd], Bound)."""
+    G, H, Sq, hd = q.shape
+    ref = torch.empty(G, Sq, H * hd, dtype=torch.float64)
+    e = torch.empty_like(ref)
+    for i in range((Sq + grp_q - 1) // grp_q):
+        qs, ks = slice(i * grp_q, min((i + 1) * grp_q, Sq)), slice(i * grp_kv, (i + 1) * grp_kv)
+        assert ks.stop <= k.shape[2], "every query group's keys lie inside Skv"
+        r, b = attention_ref_and_bound(q[:, :, qs], k[:, :, ks], v[:, :, ks], out_dtype, p_dtype)
+        ref[:, qs], e[:, qs] = r, b.e
+    return ref, Bound(e, out_dtype)
+
+
+def round16(x, dtype):
+    """An fp64 tensor rounded to the 16-bit `dtype` (through fp32, as torch converts), back in fp64."""
+    return x.double().float().to(dtype).double()
+
+
+def rounding_span16(x, e, dtype):
+    """For a value known to lie within `e` of the fp64 `x` and then rounded to the 16-bit `dtype`: (lo, hi), the smallest and
+    largest results the rounding can give (rounding is monotone).  e is widened by 2^-23 |x| + 1e-30 so that the fp32 step of
+    round16 cannot hide a boundary.  lo == hi: the rounded value is known exactly, whatever fp32 value the kernel held."""
+    x, e = x.double(), torch.as_tensor(e, dtype=torch.float64) + U32 * x.double().abs() + 1e-30
+    return round16(x - e, dtype), round16(x + e, dtype)
+
+
+def cross_attention_ref_and_bound(q64, e_q, k, v, sets, dtype):
+    """The cross attention fused into the q projection's head-split epilogue (gemm_common.h, EPI_QKV_ATTN), head dim 128.
+        q64   [M, H, 128] fp64: q BEFORE its rounding to the operand type, RoPE(RMSNorm(x W^T + b))
+        e_q   [M, H, 128] bound on the kernel's fp32 q against q64 (head_split_pre_bound)
+        k, v  [sets, H, Skv, 128] as rounded to the operand type `dtype`; sets [M]: the text set of each row, (row // L) // bdiv
+    Returns (ref64 [M, H 128], Bound, ambiguous share of the q elements).
+
+    The kernel rounds q to 16 bit on chip, so the reference's rounded q may differ from the kernel's.  An element is AMBIGUOUS when
+    q64 lies within e_q of a rounding boundary of the type, i.e. when round(q64 - e_q) != round(q64 + e_q) (rounding_span16).  An
+    unambiguous element is the same number in the kernel and here and adds nothing.  An ambiguous element d may land on the
+    neighbouring value, ulp16(q_d) away, and moves score j by at most ulp16(q_d) |k_jd| / sqrt(128):
+        d_s' = d_s + max_j sum_{d ambiguous} ulp16(q_d) |k_jd| / sqrt(128),       d_s as in attention_ref_and_bound
+        bound = (u_p + 2 d_s') (P @ |V|)  (+ output term),                          u_p = U16[dtype]
+    u_p enters once, read from the code: the epilogue rounds a probability ONCE, right after the exponential (to_carrier, the B
+    operand of the P V MFMA), and adds the UNROUNDED fp32 value into l_run; the accumulators are rescaled in fp32.
+    Left out, as in attention_ref_and_bound: the <= 96 fp32 additions of P V and of the row sum (worst case 100 U32 P @ |V| = 1.2e-5
+    P @ |V|, against u_p >= 2.4e-4), the error of v_exp_f32 (1 ulp of fp32), and the second order of the score error, (2 d_s')^2 / 2
+    (below 1e-6 of P @ |V| in the dyadic cases, where d_s' < 1e-3).  One ulp per ambiguous element is exact while e_q stays below
+    half an ulp - every dyadic case, where the span of the two roundings IS one ulp (asserted in test_opcheck_cpu.py).  In the
+    general form (random operands at K = 1536) the worst-case e_q reaches a few bf16 ulps; the expression then presumes that the
+    kernel's fp32 q lies within one ulp of q64, which a real accumulation (~ 1e-2 of its worst case) does by a wide margin."""
+    M, H, hd = q64.shape
+    q64, e_q = q64.double(), e_q.double().expand_as(q64)
+    lo, hi = rounding_span16(q64, e_q, dtype)
+    qr = round16(q64, dtype)
+    amb = hi != lo
+    dq = torch.where(amb, ulp16(qr, dtype), torch.zeros_like(qr))       # 0 where unambiguous
+    share = float(amb.double().mean())
+    ref = torch.empty(M, H, hd, dtype=torch.float64)
+    e = torch.empty_like(ref)
+    sets = torch.as_tensor(sets).long()
+    for t in sets.unique().tolist():
+        rows = (sets == t).nonzero().flatten()
+        kk, vv, qq, dd = k[t].double(), v[t].double(), qr[rows], dq[rows]          # [H, Skv, 128], [n, H, 128]
+        s = torch.einsum("mhd,hjd->mhj", qq, kk) / math.sqrt(hd)
+        d_s = (hd + 4) * U32 * torch.einsum("mhd,hjd->mhj", qq.abs() + dd, kk.abs()).amax(-1, keepdim=True) / math.sqrt(hd)
+        slack = torch.einsum("mhd,hjd->mhj", dd, kk.abs()).amax(-1, keepdim=True) / math.sqrt(hd)
+        p = torch.softmax(s, -1)
+        ref[rows] = torch.einsum("mhj,hjd->mhd", p, vv)
+        e[rows] = (U16[dtype] + 2 * (d_s + slack)) * torch.einsum("mhj,hjd->mhd", p, vv.abs())
+    return ref.reshape(M, H * hd), Bound(e.reshape(M, H * hd), dtype), share
+
+
+def both16(t):
+    """Round to bf16 and flush what fp16 cannot hold exactly (|x| < 2^-17): the result is exact in bf16 AND fp16."""
+    t = t.to(torch.bfloat16).float()
+    t = torch.where(t.abs() < 2.0 ** -17, torch.zeros_like(t), t)
+    assert torch.equal(t.to(torch.float16).float(), t)
+    return t
+
+
+def head_q64(y, gain, cos, sin, eps):
+    """RoPE(RMSNorm(y)) in fp64: y [M, H, 128], gain [128], cos / sin [M, 64] (the table rows of each row's position)."""
+    y = y.double()
+    q = y * torch.rsqrt(y.pow(2).mean(-1, keepdim=True) + f32(eps)) * gain.double()
+    return rope64(q, cos.double()[:, None], sin.double()[:, None])
+
+
+def cross_dyadic_case(Bc, L, H, bdiv, Skv, seed, k_scale=1.0, K=256, v_floor=0.0):
+    """Operands of a SHARP case of the fused cross attention: Bc batch rows of L tokens (M = Bc L), text set (row // L) // bdiv.
+    Everything lies on a coarse dyadic grid so that the projection is exact in fp32 in ANY order (e_y = 0) and only the roundings
+    of RMSNorm and RoPE remain before q is rounded to 16 bit; and |q| is nearly uniform, because an element is ambiguous with
+    probability ~ 2 e_q / ulp16(q) and e_q (head_split_pre_bound) is relative to the head's LARGEST element: Gaussian q (many
+    small elements, whose ulp is small) would be ambiguous in 5 % of its fp16 elements.  So:
+        A     +- a_m, a_m in {1/2, 1, 2} by row, random signs per element
+        W     one entry +- 1/2 per row, column (37 n + 11) mod K: y[m, n] = +- a_m / 2, signs random per (m, n)
+        bias  +- 1/32: two magnitudes per row, 1.29 apart at most
+        RoPE  a table of QUARTER TURNS, (cos, sin) in {(1, 0), (0, 1), (-1, 0), (0, -1)} drawn per (position, pair): the rotation
+              swaps and negates partners (different gains: a wrong partner, sign or table row shows) and never makes an element small
+        gain  1 + 0.1 N(0, 1), positions 2 l (table rows 0, 2, 4, ...)
+        K, V  N(0, k_scale^2) and N(0, 1), exact in bf16 and fp16: |q|^2 = 128, so a score is ~ N(0, k_scale^2)
+              v_floor > 0: |v| >= v_floor (sign(n) (|n| + v_floor)).  For the one-hot rows of the large-score case: there an output
+              element is ONE v value plus probabilities of ~ 1e-6, which fp16 holds as subnormals - rounded to an ABSOLUTE 2^-25, not
+              to the relative u_p of the bound.  Where that v is 0 the output is nothing but such terms and the CPU emulation
+              (test_opcheck_cpu.py, no kernel involved) lands at 1.85 of the bound; away from 0 they vanish under the output's ulp.
+    Returns a dict (fp32 tensors exact in both 16-bit types; y64, q64 [M, H, 128], e_q, sets [M])."""
+    g = torch.Generator().manual_seed(seed)
+    M, N = Bc * L, H * 128
+    sgn = lambda *shape: torch.randint(0, 2, shape, generator=g).float() * 2 - 1
+    a_m = torch.tensor([0.5, 1.0, 2.0])[torch.arange(M) % 3]
+    A = sgn(M, K) * a_m[:, None]
+    W = torch.zeros(N, K)
+    W[torch.arange(N), (37 * torch.arange(N) + 11) % K] = 0.5 * sgn(N)
+    b = sgn(N) / 32
+    gain = 1 + 0.1 * torch.randn(128, generator=g)
+    turn = torch.randint(0, 4, (2 * L + 1, 64), generator=g)
+    cos = torch.tensor([1.0, 0.0, -1.0, 0.0])[turn]
+    sin = torch.tensor([0.0, 1.0, 0.0, -1.0])[turn]
+    pos = (2 * torch.arange(L)).to(torch.int32)
+    nsets = (Bc + bdiv - 1) // bdiv
+    k = both16(torch.randn(nsets, H, Skv, 128, generator=g) * k_scale)
+    v = torch.randn(nsets, H, Skv, 128, generator=g)
+    v = both16(torch.where(v < 0, v - v_floor, v + v_floor))
+    y64 = (A.double() @ W.double().t() + b.double()).view(M, H, 128)
+    pl = pos.long().repeat(Bc)
+    q64 = head_q64(y64, gain, cos[pl], sin[pl], 1e-6)
+    e_q = head_split_pre_bound(torch.zeros_like(y64), y64, gain)
+    sets = (torch.arange(M) // L) // bdiv
+    return dict(A=A, W=W, b=b, gain=gain, cos=cos, sin=sin, pos=pos, k=k, v=v, y64=y64, q64=q64, e_q=e_q, sets=sets,
+                M=M, L=L, H=H, K=K, bdiv=bdiv, Skv=Skv)
 
 
 # ----------------------------------------------------------------------------- bit-for-bit checks (pure data movement)
@@ -530,3 +668,31 @@ def periodic_flags(x, period):
     if xi.shape[1] <= period:
         return torch.zeros(xi.shape[0], dtype=torch.int32)
     return (xi[:, period:] != xi[:, :-period]).flatten(1).any(1).to(torch.int32)
+
+
+# The GPU cases of the fused cross attention (tests/test_ops_elementwise_gpu.py); the CPU emulation of test_opcheck_cpu.py runs the
+# same operands, so that what the kernel is held to has been met by plain fp32 arithmetic first.
+# name -> (Bc batch rows, L, H, bdiv, Skv, V^T pitch, forced tile, K scale).  Text set of a row: (row // L) // bdiv.
+def _edge(Skv, pitch=96):
+    return (2, 250, 2, 1, Skv, pitch, 27, 2.0)
+
+
+CROSS_CASES = {
+    # key edges, two sets (clips 1, L 250: the tile [192, 256) straddles them): one key, tile-aligned, one past, the ragged production length, full image
+    **{f"skv{s}": _edge(s) for s in (1, 32, 33, 64, 65, 77, 95, 96)},
+    "skv77_pitch104": _edge(77, 104),
+    "straddle_small": (6, 8, 3, 3, 77, 96, 27, 2.0),          # clips 3, L 8: L bdiv = 24 < 64, M = 48 <= 2 L bdiv: 24 + 24 rows in ONE tile, 16 dead rows
+    "sets3_L64": (3, 64, 2, 1, 77, 96, 27, 2.0),              # one set per batch row (per-clip conditioning): boundaries on tile boundaries
+    "sets3_L65": (3, 65, 2, 1, 77, 96, 27, 2.0),              # tile [64, 128): its first set owns ONE row
+    "sets5_L70": (5, 70, 3, 1, 77, 96, 27, 2.0),              # boundaries at 70, 140, 210, 280: every offset class inside a tile
+    "sets3_L127": (3, 127, 2, 1, 77, 96, 27, 2.0),            # a set that ends one row before a tile does
+    "sets3_bdiv2_L40": (6, 40, 2, 2, 77, 96, 27, 2.0),        # two batch rows per set: 80 rows per set
+    "large_scores": (2, 100, 2, 1, 77, 96, 27, 15.0),         # scores near +- 40: the running maximum must be subtracted
+    "auto_plan": (2, 250, 12, 1, 77, 96, 0, 2.0),             # the bs = 1 production problem: the automatic plan must land on tile 27 and fuse
+}
+
+
+@functools.lru_cache(maxsize=4)
+def cross_case(name):
+    Bc, L, H, bdiv, Skv, _, _, ks = CROSS_CASES[name]
+    return cross_dyadic_case(Bc, L, H, bdiv, Skv, seed=8000 + 7 * L + Skv, k_scale=ks, v_floor=0.25 if ks >= 15 else 0.0)

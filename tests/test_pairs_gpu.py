@@ -404,6 +404,19 @@ class PairCase:
                 e = rel_err(a[r.to(dev)].float(), ref)
                 assert e < ATTN_TOL[dt], (i, e)
                 worst = max(worst, e)
+                if fused:
+                    # Every element as well, in the GENERAL form of opcheck.cross_attention_ref_and_bound: random operands, so the
+                    # projection carries its real accumulation bound e_y and, at K ~ 1536, nearly every bf16 element of q is ambiguous
+                    # in its on-chip rounding (the dyadic cases of test_ops_elementwise_gpu.py are the sharp ones).  The bound is then
+                    # a few per cent of P @ |V| - weak, but rigorous, and enough to catch a row served from the wrong text set or a
+                    # query that lost a key tile (errors of tens of per cent of P @ |V| on that row), which the norm gate above averages away.
+                    mag = Pi.Ad.double().cpu().abs() @ Pi.Wd.float().double().cpu().abs().t() + Pi.bd.double().cpu().abs()
+                    e_y = ((Pi.K + 4) * oc.U32 * mag).view(len(r), H, 128)
+                    q64 = _rope64(_rms64(y, Pi.gains[0].double(), 1e-6), cos, sin)
+                    e_q = oc.head_split_pre_bound(e_y, y, Pi.gains[0])
+                    ref_e, bound, share = oc.cross_attention_ref_and_bound(q64, e_q, self.tk, self.tv, sets, dt)
+                    self.ew_ratio = max(self.ew_ratio, oc.assert_elementwise(a, ref_e, bound, f"problem {i}: fused cross attention"))
+                    self.amb_share = max(getattr(self, "amb_share", 0.0), share)
         else:
             sl = b.get("slabs")
             for i, Pi in enumerate(self.p):
@@ -494,6 +507,8 @@ def test_gemm_pair(dev, case, dt):
     record_parity(f"pair_gemm.{case}.{str(dt)[6:]}", rel_err=worst[0], tile=tile, ksplit=ks)
     if pc.p[0].ew:
         record_parity(f"elementwise.pair_gemm.{case}.{str(dt)[6:]}", err_over_bound=pc.ew_ratio, tile=tile, ksplit=ks)
+    if fused:
+        record_parity(f"elementwise.pair_gemm.cross_attn.{case}.{str(dt)[6:]}", err_over_bound=pc.ew_ratio, ambiguous_share=pc.amb_share, tile=tile)
 
     if pc.epi == "gate" and ks > 1 and not pc.opts.get("slabs"):
         return          # fp32 atomics: bit-identity not defined
