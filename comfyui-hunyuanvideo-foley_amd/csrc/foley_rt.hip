@@ -202,13 +202,19 @@ struct GraphKey {
   // step cache (foley_set_step_cache): the residual and probe buffers (null: off - the one straight-line iteration; on: the three
   // graphs head / full body / skip body).  Mode, threshold and skip list are host decisions between replays: not part of the key.
   const void *sc_delta = nullptr, *sc_mprev = nullptr;
+  // prompt timeline (foley_prepare_timeline): the text sets the timeline kernel addresses (0: off - the plain cross-attention, fused
+  // into its q projection where that applies: another topology) and the ctx-owned tables.  A new timeline of the same shape only
+  // rewrites what a replay reads.
+  int tl_sets = 0;
+  const void *tl_a = nullptr, *tl_b = nullptr, *tl_alpha = nullptr;
   uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
   uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
   bool operator==(const GraphKey& o) const {
     return guidance == o.guidance && edit == o.edit && set_maps == o.set_maps && layout == o.layout && smod_tab == o.smod_tab &&
            edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && n_win == o.n_win && Ltot == o.Ltot &&
            win_starts == o.win_starts && win_weights == o.win_weights && guid_sched == o.guid_sched && guid_scale == o.guid_scale &&
-           guid_part == o.guid_part && guid_phi == o.guid_phi && sc_delta == o.sc_delta && sc_mprev == o.sc_mprev && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
+           guid_part == o.guid_part && guid_phi == o.guid_phi && sc_delta == o.sc_delta && sc_mprev == o.sc_mprev && tl_sets == o.tl_sets &&
+           tl_a == o.tl_a && tl_b == o.tl_b && tl_alpha == o.tl_alpha && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
   }
 };
 
@@ -259,6 +265,10 @@ struct foley_ctx {
   std::vector<float> sc_rep_rel;          // [n_iter] of the last loop (-1: not measured)
   std::vector<int32_t> sc_rep_skip;
   hipGraphExec_t graph_head = nullptr, graph_skip = nullptr;   // with graph_exec (the full body) the three graphs of a cached loop
+  // prompt timeline state (foley_prepare_timeline; cleared by foley_prepare / foley_prepare_sets): the number of text sets (0: off)
+  // and ctx-owned copies of the per-token tables [ncfg*clips*(Lv+La)]; ws_tl_sets: the set count the workspace was sized for
+  int tl_sets = 0, ws_tl_sets = 0;
+  DevBuf tl_a, tl_b, tl_alpha;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -307,6 +317,7 @@ static void ctx_free_plan(foley_ctx* c) {
   c->owned.clear();
   c->buf = {};
   c->layout = {};
+  c->ws_tl_sets = 0;
   c->prepared = false;
 }
 
@@ -469,7 +480,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   hipSetDevice(c->device);
   ctx_free_plan(c);
   for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights, &c->guid_sched,
-                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel}) release(*b);
+                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel, &c->tl_a, &c->tl_b, &c->tl_alpha}) release(*b);
   if (c->sc_rel_host) (void)hipHostFree(c->sc_rel_host);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
@@ -551,19 +562,37 @@ static int resolve_forward_weights(foley_ctx* c) {
 // --------------------------------------------------------------------------- prepare
 // Everything that does not depend on the latents: time embedding for every loop
 // iteration, the triple blocks' AdaLN tables, text K/V per block, cond/visual/sync embedders.
-static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, void* stream_v);
+static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, const foley_text_timeline* tl, void* stream_v);
 
 extern "C" int foley_prepare(foley_ctx* c, const foley_plan* pl, void* stream_v) {
-  return prepare_impl(c, pl, nullptr, stream_v);
+  return prepare_impl(c, pl, nullptr, nullptr, stream_v);
 }
 
 extern "C" int foley_prepare_sets(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, void* stream_v) {
-  if (!sets) return prepare_impl(c, pl, nullptr, stream_v);
+  if (!sets) return prepare_impl(c, pl, nullptr, nullptr, stream_v);
   if (!sets->text_of || !sets->vis_of) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: null set map");
-  return prepare_impl(c, pl, sets, stream_v);
+  return prepare_impl(c, pl, sets, nullptr, stream_v);
 }
 
-static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, void* stream_v) {
+// Prompt timeline: plan.text holds tl->n_text sets, cached per block without a per-row gather (th = n_text slots); every query token
+// of the cross-attention picks its one or two sets through the tables (attention_timeline.hip).  The visual side is foley_prepare's.
+extern "C" int foley_prepare_timeline(foley_ctx* c, const foley_plan* pl, const foley_text_timeline* tl, void* stream_v) {
+  if (!c || !pl || !tl) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  if (!tl->set_a || !tl->set_b || !tl->alpha) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_timeline: null table");
+  if (tl->n_text < 1 || tl->n_text > FOLEY_TIMELINE_MAX_SETS) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_timeline: n_text must be in [1, 16]");
+  if (pl->ncfg < 1 || pl->clips < 1 || pl->La < 1 || pl->Lv < 1) return FAIL(FOLEY_ERR_INVALID, "bad plan dimensions");
+  if (foley_is_half(c->cfg.compute_dtype) && pl->Lt > 96)
+    return FAIL(FOLEY_ERR_INVALID, "foley_prepare_timeline: 16-bit compute takes at most 96 text tokens per set");
+  const size_t n = (size_t)pl->ncfg * pl->clips * ((size_t)pl->Lv + pl->La);
+  for (size_t i = 0; i < n; ++i) {
+    if (tl->set_a[i] < 0 || tl->set_a[i] >= tl->n_text || tl->set_b[i] < 0 || tl->set_b[i] >= tl->n_text)
+      return FAIL(FOLEY_ERR_INVALID, "foley_prepare_timeline: set index out of range");
+    if (!(tl->alpha[i] >= 0.f && tl->alpha[i] < 1.f)) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_timeline: alpha outside [0, 1)");
+  }
+  return prepare_impl(c, pl, nullptr, tl, stream_v);
+}
+
+static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_sets* sets, const foley_text_timeline* tl, void* stream_v) {
   if (!c || !pl) return FAIL(FOLEY_ERR_INVALID, "null argument");
   std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
   hipStream_t st = (hipStream_t)stream_v;
@@ -597,6 +626,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     v_rows = !v_half;
     if (v_rows && Bc0 > 32) return FAIL(FOLEY_ERR_INVALID, "foley_prepare_sets: per-clip visual features take at most 32 batch rows");
   }
+  if (tl) n_text = tl->n_text;   // validated by foley_prepare_timeline
   const int D = f.hidden, H = f.heads, C = f.latent_dim, T = f.compute_dtype;
   const size_t es = esize(T);
   const int ncfg = pl->ncfg, clips = pl->clips, La = pl->La, Lv = pl->Lv, Ls = pl->Ls, Lt = pl->Lt;
@@ -605,24 +635,26 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   slots.sets = sets != nullptr; slots.t_rows = t_rows; slots.v_rows = v_rows;
   slots.th = t_rows ? Bc : ncfg; slots.vh = v_rows ? Bc : ncfg;
   slots.tdiv = Bc / slots.th; slots.vdiv = Bc / slots.vh;
+  if (tl) { slots.th = n_text; slots.tdiv = 1; }   // one slot per text set; the timeline kernel addresses them through its tables
   slots.Sp = pad32(S); slots.Lap = pad32(La); slots.Ltp = pad32(Lt);
   slots.smod_ld = (long)f.depth_single * 6 * D;
   HIPTRY(hipStreamSynchronize(st));
   const bool reuse = c->buf.complete() && same_dims(c->plan, *pl) && c->layout.sets == slots.sets &&
-                     c->layout.t_rows == slots.t_rows && c->layout.v_rows == slots.v_rows;
+                     c->layout.t_rows == slots.t_rows && c->layout.v_rows == slots.v_rows && c->ws_tl_sets == (tl ? n_text : 0);
   if (!reuse) ctx_free_plan(c);
   c->prepared = false;
   c->edit = false;                  // a plan without foley_set_edit is a plain run
   c->n_win = 0;                     // and one without foley_set_windows has independent clips
   c->guid_sched_on = c->guid_rescale_on = false;   // and one without foley_set_guidance combines with the plan's scalar
   c->sc_mode = 0;                   // and one without foley_set_step_cache runs every block on every iteration
+  c->tl_sets = 0;                   // and one without a timeline (foley_prepare_timeline sets it below) one text set per batch row
   RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
   c->vis_src = n_vis;
   const int th = ly.th, vh = ly.vh;
   const int hidmax = f.mlp_hidden > f.conv_hidden ? f.mlp_hidden : f.conv_hidden;
   const int Lmax = std::max(std::max(La, Lv), Lt);
   const int rl[3] = {La, Lv, Lmax};   // rows of the rotation tables rot_*[k]
-  const int rsets = sets ? Bc : ncfg;   // set maps: sized for the most sets a plan of these dimensions can carry
+  const int rsets = sets ? Bc : tl ? std::max(ncfg, n_text) : ncfg;   // set maps: sized for the most sets a plan of these dimensions can carry
   const int rmax = std::max(std::max(NI, rsets * Lt), std::max(rsets * Lv, rsets * Ls));
   // widest row any precompute stage writes into the scratch (every configurable feature width)
   const size_t tcols = std::max({D, f.sync_hidden, f.cond_dim, f.clip_dim, f.sync_dim, f.time_freq_dim});
@@ -703,6 +735,19 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     }
   }
   c->set_maps = std::move(maps);
+  c->ws_tl_sets = tl ? n_text : 0;
+  if (tl) {
+    // the per-token tables, copied while nothing on `st` reads them (synchronised above); the buffers only grow, so a timeline of
+    // the same shape keeps their addresses and with them the captured graph
+    const size_t nb = (size_t)Bc * S * 4;
+    TRY(grow(c->tl_a, nb));
+    TRY(grow(c->tl_b, nb));
+    TRY(grow(c->tl_alpha, nb));
+    HIPTRY(hipMemcpy(c->tl_a.p, tl->set_a, nb, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(c->tl_b.p, tl->set_b, nb, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(c->tl_alpha.p, tl->alpha, nb, hipMemcpyHostToDevice));
+    c->tl_sets = n_text;
+  }
   c->plan = *pl;
 #define COPYTAB(field, bytes) \
   HIPTRY(hipMemcpyAsync((void*)c->buf.field, pl->field, (bytes), hipMemcpyDeviceToDevice, st)); \
@@ -1101,7 +1146,7 @@ static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
       // 16-bit modes: the projection may run the attention against the <= 96 cached text keys in its epilogue (small grids:
       // gemm_impl.h decides and reports through attn_fused); the q tensor and the attention launch are then gone
       int fused = 0;
-      if (bf && Lt <= 96 && Ltp >= 96) {
+      if (bf && Lt <= 96 && Ltp >= 96 && !c->tl_sets) {   // a prompt timeline leaves attn_* unset: its own kernel follows
         for (int s = 0; s < 2; ++s) {
           QkvSplitArgs& q = s ? g1.qs : g0.qs;
           q.attn_k = (char*)c->buf.txt_k + offk; q.attn_vt = (char*)c->buf.txt_v + offv; q.attn_out = ss[s].att;
@@ -1110,7 +1155,11 @@ static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
       }
       PROF("triple.cross q GEMM + head split (+ cross attention on small grids)", gf(M + Mv, D, D),
            gb(M + Mv, D, D, es) + 1.0 * D * D * es, launch_gemm_pair(g0, g1, T, EPI_QKV_SPLIT, st));
-      if (!fused) {
+      if (c->tl_sets) {
+        AttnTimelineArgs ta{c->buf.Q, (char*)c->buf.txt_k + offk, (char*)c->buf.txt_v + offv, (const int*)c->tl_a.p, (const int*)c->tl_b.p,
+                            (const float*)c->tl_alpha.p, Bc, H, S, Lt, c->tl_sets, c->buf.att_v, c->buf.att_a, Lv, T, bf ? Ltp : 0};
+        PROF("triple.cross attention (prompt timeline)", 2.0 * af(Bc, S, Lt), 2.0 * ab(Bc, S, Lt), launch_attention_timeline(ta, T, st));
+      } else if (!fused) {
         AttnArgs a{c->buf.Q, (char*)c->buf.txt_k + offk, (char*)c->buf.txt_v + offv, Bc, H, S, Lt, tdiv, c->buf.att_v, c->buf.att_a, Lv,
                    T, bf ? Ltp : 0};
         PROF("triple.cross attention", af(Bc, S, Lt), ab(Bc, S, Lt), launch_attention(a, T, st));
@@ -1365,6 +1414,7 @@ static GraphKey graph_key_now(const foley_ctx* c) {
                   c->guid_rescale_on ? c->guid_part.p : nullptr,
                   c->guid_rescale_on ? (const void*)((const float*)c->guid_sched.p + 2 * (size_t)c->plan.n_iter) : nullptr,
                   c->sc_mode ? c->sc_delta.p : nullptr, c->sc_mode ? c->sc_mprev.p : nullptr,
+                  c->tl_sets,       c->tl_sets ? c->tl_a.p : nullptr, c->tl_sets ? c->tl_b.p : nullptr, c->tl_sets ? c->tl_alpha.p : nullptr,
                   c->tensor_gen,    c->plan_gen};
 }
 
@@ -1943,6 +1993,13 @@ extern "C" int foley_op_attention(const void* q, const void* k, const void* v, i
                                   int H, int Sq, int Skv, int kv_bdiv, void* outA, void* outB, int split,
                                   int out_dtype, void* stream) {
   return foley_op_attention_hd(q, k, v, in_dtype, vt_pitch, Bq, H, Sq, Skv, kv_bdiv, outA, outB, split, out_dtype, 128, stream);
+}
+
+extern "C" int foley_op_attention_timeline(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq, int H, int Sq,
+                                           int Skv, int n_sets, const int32_t* set_a, const int32_t* set_b, const float* alpha, void* outA,
+                                           void* outB, int split, int out_dtype, void* stream) {
+  AttnTimelineArgs a{q, k, v, set_a, set_b, alpha, Bq, H, Sq, Skv, n_sets, outA, outB, split, in_dtype, vt_pitch};
+  return launch_attention_timeline(a, out_dtype, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_qkv_regroup(const void* qkv, int n_rows, int dtype, int H, const int32_t* idx_q, int G, int Sq, const int32_t* idx_kv, int Skv,

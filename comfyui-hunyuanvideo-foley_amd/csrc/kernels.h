@@ -153,6 +153,28 @@ struct AttnArgs {
 };
 int launch_attention(const AttnArgs& a, int out_dtype, hipStream_t st);
 
+// Timeline attention (attention_timeline.hip; host/prompt_timeline.py states the semantics): every query (b, t) attends the key
+// set of its own time, out = (1 - alpha) * attn(q; set_a) + alpha * attn(q; set_b) - two complete softmaxes over the Skv keys of
+// one set each, blended in fp32; where alpha == 0 set_b is not read.  head dim 128.  K [n_sets, H, Skv, 128]; V [n_sets, H, Skv,
+// 128] (fp32 operands) or transposed [n_sets, H, 128, vt_pitch] (16-bit operands: Skv <= 96, vt_pitch as for launch_attention) -
+// the text sets as foley_prepare caches them per block.  set_a / set_b / alpha are DEVICE tables [Bq, Sq]; the kernels clamp the
+// set indices to [0, n_sets) before they address anything (caller tables).  Output split as AttnArgs.
+struct AttnTimelineArgs {
+  const void* q;
+  const void* k;
+  const void* v;
+  const int* set_a;
+  const int* set_b;
+  const float* alpha;
+  int Bq, H, Sq, Skv, n_sets;
+  void* outA;
+  void* outB;
+  int split;
+  int in_dtype;
+  int vt_pitch;
+};
+int launch_attention_timeline(const AttnTimelineArgs& a, int out_dtype, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------------
 // Row kernels
 // ---------------------------------------------------------------------------------------------

@@ -51,6 +51,11 @@ class CondSetsC(C.Structure):
     _fields_ = [("n_text", C.c_int32), ("n_vis", C.c_int32), ("text_of", C.POINTER(C.c_int32)), ("vis_of", C.POINTER(C.c_int32))]
 
 
+class TextTimelineC(C.Structure):
+    """foley_text_timeline: n_text sets and the HOST tables [ncfg*clips*(Lv+La)]."""
+    _fields_ = [("n_text", C.c_int32), ("set_a", C.POINTER(C.c_int32)), ("set_b", C.POINTER(C.c_int32)), ("alpha", C.POINTER(C.c_float))]
+
+
 class RowBcastC(C.Structure):
     _fields_ = [("p", C.c_void_p), ("ld", C.c_int64), ("mode", C.c_int32), ("rows_per_cfg", C.c_int32),
                 ("L", C.c_int32), ("Ls", C.c_int32), ("period", C.c_int32), ("periodic_cfgs", C.c_int32)]
@@ -122,6 +127,7 @@ _SIGNATURES = {
     "foley_bcast_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "foley_prepare": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.c_void_p]),
     "foley_prepare_sets": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.POINTER(CondSetsC), C.c_void_p]),
+    "foley_prepare_timeline": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.POINTER(TextTimelineC), C.c_void_p]),
     "foley_dit_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, PROGRESS_CB, C.c_void_p, C.c_void_p]),
     "foley_abort": (C.c_int, [C.c_void_p]),
@@ -142,6 +148,7 @@ _SIGNATURES = {
                                                                         C.c_void_p]),
     "foley_op_attention_hd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                                            C.c_void_p]),
+    "foley_op_attention_timeline": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 7 + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
     "foley_op_ln_mod_pending": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.POINTER(RowBcastC),
                                           C.POINTER(RowBcastC), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                           C.POINTER(RowBcastC), C.c_void_p]),
@@ -399,7 +406,9 @@ class FoleyContext:
     # ---- run
     def prepare(self, plan: dict):
         """plan: ncfg, clips, La, Lv, Ls, Lt, n_iter, guidance + device tensors (see foley_plan).  Per-clip conditioning
-        (host/cond_sets.py): `text_of` / `vis_of` lists of ncfg*clips set indices -> foley_prepare_sets."""
+        (host/cond_sets.py): `text_of` / `vis_of` lists of ncfg*clips set indices -> foley_prepare_sets.  A prompt timeline
+        (host/prompt_timeline.py): `timeline` = (set_a, set_b, alpha), flat host sequences of ncfg*clips*(Lv+La) entries, with
+        plan["text"] holding the text sets -> foley_prepare_timeline."""
         p = FoleyPlanC()
         for k in ("ncfg", "clips", "La", "Lv", "Ls", "Lt", "n_iter", "rope_len"):
             setattr(p, k, int(plan[k]))
@@ -408,7 +417,16 @@ class FoleyContext:
                   "pos_linear", "sync_gather", "solver_coef"):
             setattr(p, k, _ptr(plan[k]))
         with torch.cuda.device(self.device):
-            if plan.get("text_of") is None:
+            if plan.get("timeline") is not None:
+                if plan.get("text_of") is not None:
+                    raise FoleyRuntimeError("a prompt timeline does not combine with per-clip set maps")
+                sa, sb, al = plan["timeline"]
+                n = p.ncfg * p.clips * (p.Lv + p.La)
+                if not (len(sa) == len(sb) == len(al) == n):
+                    raise FoleyRuntimeError("timeline tables must have ncfg*clips*(Lv+La) entries")
+                t = TextTimelineC(int(plan["text"].shape[0]), (C.c_int32 * n)(*sa), (C.c_int32 * n)(*sb), (C.c_float * n)(*al))
+                _check(self.lib, self.lib.foley_prepare_timeline(self._h, C.byref(p), C.byref(t), _stream()), "foley_prepare_timeline")
+            elif plan.get("text_of") is None:
                 _check(self.lib, self.lib.foley_prepare(self._h, C.byref(p), _stream()), "foley_prepare")
             else:
                 n = len(plan["text_of"])
@@ -701,6 +719,26 @@ def op_attention(q, k, v, outA, outB, split: int, kv_bdiv: int = 1):
     vt_pitch = v.shape[3] if q.dtype in (torch.bfloat16, torch.float16) else 0
     _check(lib, lib.foley_op_attention_hd(_ptr(q), _ptr(k), _ptr(v), dt_of(q), vt_pitch, Bq, H, Sq, Skv, kv_bdiv,
                                           _ptr(outA), _ptr(outB), split, dt_of(outB), hd, _stream()), "foley_op_attention_hd")
+
+
+def op_attention_timeline(q, k, v, set_a, set_b, alpha, outA, outB, split: int):
+    """foley_op_attention_timeline: q [Bq,H,Sq,128]; k [n_sets,H,Skv,128]; v [n_sets,H,Skv,128] (fp32) or transposed
+    [n_sets,H,128,pitch] (bf16 / fp16, Skv <= 96); set_a / set_b int32 and alpha fp32 [Bq,Sq] on the device."""
+    lib = load_library()
+    Bq, H, Sq, hd = q.shape
+    n_sets, Skv = k.shape[0], k.shape[2]
+    half = q.dtype in (torch.bfloat16, torch.float16)
+    if hd != 128 or k.shape[1] != H or k.shape[3] != 128 or k.dtype != q.dtype or v.dtype != q.dtype or v.shape[0] != n_sets or \
+            v.shape[1] != H or (v.shape[2] != 128 if half else tuple(v.shape[2:]) != (Skv, 128)):
+        raise FoleyRuntimeError("op_attention_timeline: q [Bq,H,Sq,128], k [n_sets,H,Skv,128], v [n_sets,H,Skv,128] or transposed [n_sets,H,128,pitch]")
+    for t, dt in ((set_a, torch.int32), (set_b, torch.int32), (alpha, torch.float32)):
+        if t.dtype != dt or t.numel() != Bq * Sq or t.device != q.device:
+            raise FoleyRuntimeError("op_attention_timeline: set_a / set_b int32 and alpha fp32 of [Bq, Sq] on q's device")
+    if outA.numel() != Bq * split * H * 128 or outB.numel() != Bq * (Sq - split) * H * 128 or outA.dtype != outB.dtype:
+        raise FoleyRuntimeError("op_attention_timeline: outA [Bq*split, H*128] and outB [Bq*(Sq-split), H*128] of one dtype")
+    _check(lib, lib.foley_op_attention_timeline(_ptr(q), _ptr(k), _ptr(v), dt_of(q), v.shape[3] if half else 0, Bq, H, Sq, Skv, n_sets,
+                                                _ptr(set_a), _ptr(set_b), _ptr(alpha), _ptr(outA), _ptr(outB), split, dt_of(outB),
+                                                _stream()), "foley_op_attention_timeline")
 
 
 def op_attention_scatter(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out_rows: torch.Tensor, out: torch.Tensor,

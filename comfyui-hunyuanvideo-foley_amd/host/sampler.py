@@ -14,7 +14,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import cond_sets, packers, runtime, step_cache as _sc, tables
+from . import cond_sets, packers, prompt_timeline as _ptl, runtime, step_cache as _sc, tables
 from .config import DAC48K, DACConfig, DiTConfig
 from .runtime import FoleyContext, FoleyRuntimeError
 from .step_cache import StepCacheSpec
@@ -189,7 +189,7 @@ def keep_step_cache_report(ctx: FoleyContext, plan: dict) -> None:
 def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_feats: Dict[str, torch.Tensor],
                La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str,
                edit_i0: Optional[int] = None, guidance: Optional[GuidanceSpec] = None,
-               step_cache: Optional[StepCacheSpec] = None) -> dict:
+               step_cache: Optional[StepCacheSpec] = None, timeline=None, timeline_starts=None) -> dict:
     """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables.
     edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows.
     Each conditioning tensor has batch 1 (shared by all clips) or batch_size (one row per clip, host/cond_sets.py): the plan
@@ -197,7 +197,11 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     guidance (GuidanceSpec): three halves when it carries a video scale, and the schedule table / rescale value that
     apply_guidance hands to the library after prepare (`guid_sched`, `guid_rescale`).
     step_cache (StepCacheSpec, host/step_cache.py): the arguments apply_step_cache hands to the library after prepare
-    (`step_cache`); an edit run takes the rows [edit_i0, steps) of a skip list and of an interval, as of the guidance table."""
+    (`step_cache`); an edit run takes the rows [edit_i0, steps) of a skip list and of an interval, as of the guidance table.
+    timeline (host/prompt_timeline.Timeline): text_feats["text_feat"] holds one row per distinct prompt of the timeline, in its
+    order, and the visual features are shared (batch 1); the plan then carries the text sets [negative ; prompts...] and the
+    per-token table `timeline` that prepare hands to foley_prepare_timeline.  timeline_starts: the latent-frame starts of a
+    windowed run - clip v*n_win + k reads the timeline shifted by starts[k].  None is today's path, bit for bit."""
     cfg, dev = model.cfg, model.device
     if step_cache is not None:
         step_cache.check(int(steps))
@@ -208,6 +212,15 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     f32 = lambda t: t.to(device=dev, dtype=torch.float32)
     clip, sync = f32(visual_feats["siglip2_feat"]), f32(visual_feats["syncformer_feat"])
     text, unc = f32(text_feats["text_feat"]), f32(text_feats["uncond_text_feat"])
+    text_sets = None
+    if timeline is not None:
+        if text.dim() != 3 or text.shape[0] != len(timeline.prompts):
+            raise FoleyRuntimeError(f"timeline=: text_feat carries {tuple(text.shape)}, one row per distinct prompt of the timeline "
+                                    f"({len(timeline.prompts)}) is needed")
+        if clip.shape[0] != 1 or sync.shape[0] != 1 or unc.shape[0] != 1:
+            raise FoleyRuntimeError("timeline=: the visual features and the negative prompt are shared by the clips (batch 1); "
+                                    "a timeline does not combine with per-clip conditioning")
+        text_sets, text = text, text[:1]
     try:
         per_clip = any(cond_sets.batch_of(t, batch_size, n) > 1 for t, n in (
             (clip, "siglip2_feat"), (sync, "syncformer_feat"), (text, "text_feat"), (unc, "uncond_text_feat")))
@@ -219,6 +232,8 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     model._text_len_fixed = max(model._text_len_fixed or 0, t_fixed)
     Lt = model._text_len_fixed
     text, unc = pad_or_trim_text(text, Lt), pad_or_trim_text(unc, Lt)
+    if text_sets is not None:
+        text_sets = pad_or_trim_text(text_sets, Lt)
     text_of = vis_of = None
     if per_clip:
         sets = cond_sets.build(text, unc, clip, sync, model.empty_clip_feat, model.empty_sync_feat, batch_size,
@@ -243,6 +258,8 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
         sync_in = torch.cat([model.get_empty_sync_sequence(bs=1, len=Ls).float(), sync])
     else:
         text_in, clip_in, sync_in = text, clip, sync
+    if text_sets is not None:                     # [negative ; prompts...]: the halves below the last read set 0 (prompt_timeline.batch_table)
+        text_in = torch.cat([unc, text_sets]) if ncfg > 1 else text_sets
     fp8_time = fp8_time_dtype(model)
     # The run's tables (schedule, solver coefficients, RoPE rows, position / up-sampling maps) depend on these scalars
     # only: built once per distinct run shape and kept on the device (host-side table building is milliseconds of
@@ -263,6 +280,15 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
             "text": text_in.contiguous(), "clip": clip_in.contiguous(), "sync": sync_in.contiguous(),
             "text_of": text_of, "vis_of": vis_of}
     plan.update(tabs)
+    if timeline is not None:
+        # the per-token tables depend on the timeline and the run's shape only: kept per model, keyed on both
+        tkey = (timeline.key(), Lv, La, ncfg, batch_size, tuple(timeline_starts) if timeline_starts is not None else None)
+        tcache = model.__dict__.setdefault("_timeline_cache", {})
+        if tkey not in tcache:
+            if len(tcache) >= 16:
+                tcache.pop(next(iter(tcache)))
+            tcache[tkey] = _ptl.batch_table(timeline, Lv, La, ncfg, batch_size, timeline_starts)
+        plan["timeline"] = tcache[tkey]
     if guidance is not None and (three or guidance.interval is not None):
         # two halves read column 0: the one scale of the run; an edit run takes the suffix of the plain run's rows
         sched = tables.guidance_schedule(steps, guidance.g_video if three else guidance_scale, guidance_scale, guidance.interval)
@@ -286,7 +312,8 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
                                    progress: Optional[Callable[[int, int], None]] = None,
                                    return_latents: bool = False, noise: Optional[torch.Tensor] = None,
                                    _abort_event: Optional[threading.Event] = None, edit=None, windows=None,
-                                   guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None):
+                                   guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None,
+                                   timeline=None):
     """Same contract as the reference function of this name (utils.py:125-258):
     returns (audio [bs, 1, T] fp32 on the model's device, sample_rate).
 
@@ -302,12 +329,18 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
 
     step_cache (StepCacheSpec): skip the blocks on iterations whose model input barely moved (threshold mode) or on listed
     iterations (schedule mode) and reuse their last residual; it combines with guidance, `edit` and `windows`.  The decisions of
-    the run are kept in model.ctx.plan["step_cache_report"].  None runs every block on every iteration, bit for bit."""
+    the run are kept in model.ctx.plan["step_cache_report"].  None runs every block on every iteration, bit for bit.
+
+    timeline (host/prompt_timeline.Timeline): timed prompts - text_feats["text_feat"] holds one row per distinct prompt of the
+    timeline and every token of the cross-attention reads the text set(s) of its own time (build_plan).  It combines with `edit`,
+    `windows` (the timeline is given in the long clip's time), guidance and the step cache; the visual features are shared
+    (batch 1).  None is the plain run, bit for bit."""
     if windows is not None and windows.n_win > 1:
         if edit is not None:
             raise ValueError("windows= and edit= together: editing a long clip is not supported")
         return _denoise_windows(visual_feats, text_feats, model, dac, guidance_scale, num_inference_steps, batch_size, sampler,
-                                windows, generator, use_graph, progress, return_latents, noise, _abort_event, guidance, step_cache)
+                                windows, generator, use_graph, progress, return_latents, noise, _abort_event, guidance, step_cache,
+                                timeline)
     cfg = model.cfg
     La = int(audio_len_in_s * cfg.frame_rate)
     if noise is None:
@@ -315,7 +348,7 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     latents = noise.to(device=model.device, dtype=torch.float32).contiguous()
     if edit is None:
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          guidance=guidance, step_cache=step_cache)
+                          guidance=guidance, step_cache=step_cache, timeline=timeline)
         model.attach_dac(dac)
         model.ctx.prepare(plan)
         apply_guidance(model.ctx, plan)
@@ -324,7 +357,7 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
         k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
         x0, mask = edit.device_operands(model.device, batch_size, La)
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          edit_i0=i0, guidance=guidance, step_cache=step_cache)
+                          edit_i0=i0, guidance=guidance, step_cache=step_cache, timeline=timeline)
         model.attach_dac(dac)
         model.ctx.prepare(plan)
         apply_guidance(model.ctx, plan)
@@ -357,20 +390,26 @@ def window_rows(t: torch.Tensor, variations: int, n_win: int, what: str) -> torc
 
 def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC, guidance_scale, num_inference_steps,
                      variations, sampler, windows, generator, use_graph, progress, return_latents, noise, _abort_event,
-                     guidance=None, step_cache=None):
+                     guidance=None, step_cache=None, timeline=None):
     """One long clip per variation as a batch of variations*n_win coupled windows (clip v*n_win + k = window k of variation v).
     The noise is drawn ONCE as [variations, C, Ltot] - draw_noise, the same generator and dtype rule as a plain run - and every
     window takes its slice, so overlapping frames start equal.  The plan carries the blend rows (edit_i0 = 0 tables); after every
     solver step the library replaces the frames several windows cover by their weighted mean (foley_set_windows).  After the loop
     the windows are stitched and decoded in ONE dac_decode of [variations, C, Ltot]; return_latents gives the stitched latents.
     The length of the run is the plan's (Ltot), not audio_len_in_s.  denoise_process_multi does not shard such a run: the windows
-    of a variation are coupled."""
+    of a variation are coupled.  timeline: given in the long clip's time; window k's rows are the timeline shifted by starts[k]
+    latent frames, which lifts the "one prompt for all windows" limit - the visual features are then one shared row."""
     cfg = model.cfg
     n_win, La, Ltot = windows.n_win, windows.La, windows.Ltot
     windows.check_extent(variations)
     clips = variations * n_win
     vis = {k: window_rows(visual_feats[k], variations, n_win, k) for k in ("siglip2_feat", "syncformer_feat")}
-    txt = {k: window_rows(text_feats[k], variations, n_win, k) for k in ("text_feat", "uncond_text_feat")}
+    if timeline is not None:                      # text rows are the timeline's prompts, not windows (build_plan checks them)
+        if any(v.shape[0] != 1 for v in vis.values()):
+            raise ValueError("windows= with timeline=: the visual features are one shared row (per-window video features are not carried)")
+        txt = dict(text_feats)
+    else:
+        txt = {k: window_rows(text_feats[k], variations, n_win, k) for k in ("text_feat", "uncond_text_feat")}
     if noise is None:
         noise = draw_noise(variations, cfg.latent_dim, Ltot, model.dtype, generator)
     if tuple(noise.shape) != (variations, cfg.latent_dim, Ltot):
@@ -378,7 +417,7 @@ def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC,
     noise = noise.to(device=model.device, dtype=torch.float32)
     latents = torch.stack([noise[v, :, s:s + La] for v in range(variations) for s in windows.starts]).contiguous()
     plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0, guidance=guidance,
-                      step_cache=step_cache)
+                      step_cache=step_cache, timeline=timeline, timeline_starts=windows.starts if timeline is not None else None)
     model.attach_dac(dac)
     model.ctx.prepare(plan)
     apply_guidance(model.ctx, plan)
@@ -479,7 +518,7 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                           num_inference_steps: int, batch_size: int, sampler: str,
                           generator: Optional[torch.Generator] = None, use_graph: bool = True,
                           progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None,
-                          guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None):
+                          guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None, timeline=None):
     """`denoise_process_with_generator` with the clips of the batch sharded over `replicas` (the pairs
     `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199 batches clips that
     share their conditioning; per-clip conditioning, host/cond_sets.py, only changes what each clip reads), so there is no
@@ -495,7 +534,8 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     the noise.  A windowed run (denoise_process_with_generator's `windows`) is not sharded here: the windows of one variation
     are coupled after every step, so it runs on one device.  `step_cache` is forwarded to every shard: a skip list gives what one GPU
     gives; in threshold mode every shard decides from the rows it holds (the max over them), so the decisions - and with them the
-    clips - depend on the sharding.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
+    clips - depend on the sharding.  `timeline` (one for the whole batch) is forwarded with the prompts' text rows, unsliced: every
+    shard builds the table rows of its own clips.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
     from .distributed import shard_range
     if not replicas:
         raise FoleyRuntimeError("no replicas")
@@ -540,12 +580,13 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                     return
                 running[r] = True
                 results[r] = denoise_process_with_generator(     # per-clip conditioning travels with its clips
-                    cond_sets.shard(visual_feats, lo, hi, batch_size), cond_sets.shard(text_feats, lo, hi, batch_size),
+                    cond_sets.shard(visual_feats, lo, hi, batch_size),
+                    text_feats if timeline is not None else cond_sets.shard(text_feats, lo, hi, batch_size),
                     audio_len_in_s, model, dac, guidance_scale, num_inference_steps, hi - lo,
                     sampler, use_graph=use_graph, noise=noise[lo:hi], return_latents=True,
                     progress=progress if r == 0 else None, _abort_event=failed,
                     edit=edit.shard(lo, hi, batch_size) if edit is not None else None, guidance=guidance,
-                    step_cache=step_cache)
+                    step_cache=step_cache, timeline=timeline)
                 torch.cuda.current_stream().synchronize()
         except Exception as e:          # surfaced on the calling thread
             running[r] = False          # FIRST: a second failing (or aborted) worker must not keep the first one waiting on it

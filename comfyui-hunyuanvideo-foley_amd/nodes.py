@@ -333,7 +333,7 @@ class HunyuanFoleySampler:
                        block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1,
                        prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0,
                        video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0, cache_threshold=None, cache_skip=None,
-                       cache_interval=None, cache_max_consecutive=None):
+                       cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -370,8 +370,24 @@ class HunyuanFoleySampler:
         clip's result depends on its batch), limited by `cache_interval` (start, end) in fractions of the loop and
         `cache_max_consecutive`; or `cache_skip` - the list of iteration indices to skip.  The first and the last iteration always
         run in full.  It combines with guidance, audio editing, per-clip conditioning and long clips; the log says how many
-        iterations were skipped."""
+        iterations were skipped.
+
+        Timed prompts (keyword-only, not sockets; host/prompt_timeline.py): `prompt_timeline` [(start_s, end_s, prompt), ...] -
+        every moment of the clip reads the prompt of its own time; time no span covers takes the `prompt` widget, and
+        `prompt_crossfade_s` blends neighbouring prompts linearly across each boundary (0: hard cuts).  At most 16 distinct
+        text sets, the negative prompt included.  With `window_s` the timeline is given in the long clip's time (text-to-audio;
+        per-window video features are not carried).  It combines with audio= / regenerate=, guidance and the step cache, and
+        does not combine with prompts= / negative_prompts= / images= / features=."""
         model, deps = hunyuan_model, hunyuan_deps
+        timeline = None
+        if prompt_timeline is not None:            # refused here, before the encoders run
+            if prompts is not None or negative_prompts is not None or images is not None or features is not None:
+                raise ValueError("prompt_timeline does not combine with prompts= / negative_prompts= / images= / features=: one "
+                                 "timeline serves the whole batch")
+            if window_s is not None and duration > window_s and image is not None:
+                raise ValueError("prompt_timeline with window_s takes text-to-audio: per-window video features are not carried")
+            from .host import prompt_timeline as _ptl
+            timeline = _ptl.parse(prompt_timeline, prompt, duration, prompt_crossfade_s)
         step_cache = None
         if cache_threshold is not None or cache_skip is not None:
             if cache_threshold is not None and cache_skip is not None:
@@ -411,7 +427,8 @@ class HunyuanFoleySampler:
                 raise ValueError(f"window_s must be a whole number of seconds >= 1, got {window_s}")
         if window_s is not None and duration > window_s:
             visual, text, windows = self._window_features(image, duration, frame_rate, prompt, negative_prompt, model, deps,
-                                                          device, int(window_s), window_overlap_s, batch_size)
+                                                          device, int(window_s), window_overlap_s, batch_size,
+                                                          **({"prompt_list": list(timeline.prompts)} if timeline is not None else {}))
             audio_len_in_s = windows.Ltot / model.cfg.frame_rate
             if windows.n_win == 1:              # the frames gave no more than one window: an ordinary run of that length
                 windows = None
@@ -425,14 +442,17 @@ class HunyuanFoleySampler:
                 model, deps, device)
         elif image is not None:
             visual, text, audio_len_in_s = self._video_features(image, duration, frame_rate, prompt,
-                                                                negative_prompt, deps, device, model.dtype)
+                                                                negative_prompt, deps, device, model.dtype,
+                                                                **({"prompt_list": list(timeline.prompts)} if timeline is not None else {}))
         else:
             # text-to-audio: learned "empty" visual rows (nodes.py:326-333)
             clip_len = int(duration * 8)
             sync_len = int(((int(duration * 25) - 16) // 8 + 1) * 8)
             visual = {"siglip2_feat": model.get_empty_clip_sequence(bs=1, len=clip_len),
                       "syncformer_feat": model.get_empty_sync_sequence(bs=1, len=sync_len)}
-            res = encode_text_feat([negative_prompt, prompt], deps, device, model.dtype)
+            # a timeline: all its distinct prompts in ONE call, one row each behind the negative prompt's
+            res = encode_text_feat([negative_prompt] + (list(timeline.prompts) if timeline is not None else [prompt]), deps, device,
+                                   model.dtype)
             text = {"text_feat": res[1:], "uncond_text_feat": res[:1]}
         edit = None
         if audio is not None:
@@ -449,12 +469,13 @@ class HunyuanFoleySampler:
             pass
         progress = (lambda i, n: pbar.update_absolute(i, n)) if pbar is not None else None
         n_dev = torch.cuda.device_count() if os.environ.get("FOLEY_DATA_PARALLEL", "0") == "1" else 1
+        tl_kw = {"timeline": timeline} if timeline is not None else {}      # no timeline: the calls as they were
         ran_on = [model]                        # the models whose contexts ran a shard (the step cache's log line)
         if windows is not None:                 # coupled windows: one device
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                windows=windows, guidance=guidance, step_cache=step_cache)
+                windows=windows, guidance=guidance, step_cache=step_cache, **tl_kw)
         elif batch_size > 1 and n_dev > 1 and model.arena is not None:
             # clips are independent: shard them over the node's GPUs (host/sampler.py::denoise_process_multi; the widget
             # list is the reference's, so the switch is an environment variable - INTEGRATION.md)
@@ -463,12 +484,12 @@ class HunyuanFoleySampler:
             ran_on = [m for m, _ in reps]
             audio, sr = _sampler.denoise_process_multi(visual, text, audio_len_in_s, reps, cfg_scale, steps, batch_size,
                                                        sampler, generator=rng, progress=progress, edit=edit, guidance=guidance,
-                                                       step_cache=step_cache)
+                                                       step_cache=step_cache, **tl_kw)
         else:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                edit=edit, guidance=guidance, step_cache=step_cache)
+                edit=edit, guidance=guidance, step_cache=step_cache, **tl_kw)
         if step_cache is not None:
             log_step_cache(ran_on)
         waveform_batch = audio.float().cpu()
@@ -477,7 +498,7 @@ class HunyuanFoleySampler:
 
     @staticmethod
     @torch.inference_mode()
-    def _video_features(image, duration, frame_rate, prompt, negative_prompt, deps, device, dtype=torch.float32):
+    def _video_features(image, duration, frame_rate, prompt, negative_prompt, deps, device, dtype=torch.float32, prompt_list=None):
         """Video-to-Audio conditioning (nodes.py:290-320 + utils.py:262-292): resample the IMAGE batch to
         8 fps / 25 fps, run SigLIP2 and the Synchformer visual extractor, CLAP for the two prompts.  The
         audio length follows the sync stream: len(frames_25fps) / 25."""
@@ -485,12 +506,13 @@ class HunyuanFoleySampler:
         f8, f25 = _enc.select_frames(image, duration, frame_rate, device=device if torch.device(device).type == "cuda" else None)
         visual, audio_len_in_s = _enc.video_features(f8, f25, deps["siglip2_model"], deps["syncformer_model"], device,
                                                      model_dtype=dtype)
-        res = encode_text_feat([negative_prompt, prompt], deps, device, dtype)
+        res = encode_text_feat([negative_prompt] + (prompt_list or [prompt]), deps, device, dtype)   # prompt_list: a timeline's prompts
         return visual, {"text_feat": res[1:], "uncond_text_feat": res[:1]}, audio_len_in_s
 
     @staticmethod
     @torch.inference_mode()
-    def _window_features(image, duration, frame_rate, prompt, negative_prompt, model, deps, device, window_s, overlap_s, variations):
+    def _window_features(image, duration, frame_rate, prompt, negative_prompt, model, deps, device, window_s, overlap_s, variations,
+                         prompt_list=None):
         """Conditioning of a long clip's windows (host/long_form.plan_windows): the frames are selected ONCE for the whole clip
         and the 8 fps / 25 fps streams sliced per window at start_s*8 / start_s*25 (the starts fall on whole seconds), then
         SigLIP2 / Synchformer run per window as _per_clip_features runs them per clip - n_win rows; text-to-audio takes the
@@ -516,7 +538,7 @@ class HunyuanFoleySampler:
             sync_len = int(((int(W * 25) - 16) // 8 + 1) * 8)
             visual = {"siglip2_feat": model.get_empty_clip_sequence(bs=1, len=clip_len),
                       "syncformer_feat": model.get_empty_sync_sequence(bs=1, len=sync_len)}
-        res = encode_text_feat([negative_prompt, prompt], deps, device, model.dtype)
+        res = encode_text_feat([negative_prompt] + (prompt_list or [prompt]), deps, device, model.dtype)   # prompt_list: a timeline's prompts
         return visual, {"text_feat": res[1:], "uncond_text_feat": res[:1]}, plan
 
     @staticmethod

@@ -160,6 +160,28 @@ typedef struct foley_cond_sets {
 } foley_cond_sets;
 int foley_prepare_sets(foley_ctx* ctx, const foley_plan* plan, const foley_cond_sets* sets, void* stream);
 
+/* Timed prompts (additive within ABI 12): a prompt timeline through a per-token cross-attention.  plan.text holds n_text text
+ * sets [n_text, Lt, cond_dim], n_text in [1, 16] (FOLEY_TIMELINE_MAX_SETS), and every query token of the two-stream blocks'
+ * cross-attention - batch row b = h*clips + k, token t in [0, Lv + La): the Lv visual tokens first, then the La audio frames, the
+ * order of that attention's queries - reads
+ *     out = (1 - alpha) * attention(q; set_a) + alpha * attention(q; set_b),
+ * two complete softmaxes over the Lt keys of one set each; where alpha == 0 set_b is not read.  The three tables are HOST memory of
+ * ncfg*clips*(Lv + La) entries, read during the call and copied into context-owned buffers.  Otherwise the call is foley_prepare:
+ * the VISUAL side is shared per cfg half (plan.clip / plan.sync hold ncfg sets; per-clip visual sets are not carried here), the
+ * K / V^T of the n_text sets are cached per block without a per-row gather, and the cross-q projection does not run the fused
+ * attention epilogue: the timeline kernel is launched in its place.  A captured loop iteration is keyed on timeline on / off,
+ * n_text and the table buffers: a new timeline of the same shape rewrites the tables a replay reads and keeps the graph.
+ * foley_prepare / foley_prepare_sets clear the timeline state.  Indices outside [0, n_text), alpha outside [0, 1) (NaN included),
+ * n_text outside [1, 16] and NULL tables: FOLEY_ERR_INVALID. */
+#define FOLEY_TIMELINE_MAX_SETS 16
+typedef struct foley_text_timeline {
+  int32_t n_text;
+  const int32_t* set_a;     /* [ncfg*clips*(Lv+La)] host */
+  const int32_t* set_b;     /* [ncfg*clips*(Lv+La)] host */
+  const float* alpha;       /* [ncfg*clips*(Lv+La)] host, in [0, 1) */
+} foley_text_timeline;
+int foley_prepare_timeline(foley_ctx* ctx, const foley_plan* plan, const foley_text_timeline* timeline, void* stream);
+
 /* One DiT evaluation at loop iteration `iter` (its timestep modulation): latents [clips,C,La]
  * fp32 -> velocity rows [ncfg*clips*La, C] fp32 (row = (cfg*clips + clip)*La + l). */
 int foley_dit_forward(foley_ctx* ctx, const float* latents, int iter, float* out_rows, void* stream);
@@ -370,6 +392,12 @@ int foley_op_gemm(const foley_gemm_desc* d, void* stream);
 int foley_op_attention(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq, int H,
                        int Sq, int Skv, int kv_bdiv, void* outA, void* outB, int split, int out_dtype,
                        void* stream);
+/* The timeline cross-attention at op level (head_dim 128, every operand on the device): q [Bq,H,Sq,128]; k [n_sets,H,Skv,128];
+ * v [n_sets,H,Skv,128] (fp32 operands) or TRANSPOSED [n_sets,H,128,vt_pitch] (bf16 / fp16: Skv <= 96, vt_pitch as above); set_a,
+ * set_b int32 and alpha fp32 [Bq,Sq].  Set indices are clamped to [0, n_sets) by the kernels before they address anything. */
+int foley_op_attention_timeline(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq, int H, int Sq,
+                                int Skv, int n_sets, const int32_t* set_a, const int32_t* set_b, const float* alpha, void* outA,
+                                void* outB, int split, int out_dtype, void* stream);
 /* the same with head_dim 128, 64 (the ViT-B conditioning encoders, feature_utils.py:63-108) or 96 (the Synchformer sync head,
  * models/synchformer/synchformer.py:115-187: 8 heads x 96, scale 1/sqrt(96)): fp32 operands, or 16-bit operands through the
  * LDS-staged 128-query kernel (v transposed [B,H,head_dim,vt_pitch]) */
