@@ -2020,6 +2020,31 @@ extern "C" int foley_op_logmel(const float* w16, int B, int N16, const float* ba
   return launch_logmel(w16, B, N16, basis, mel_lo, mel_len, mel_w, mel_wp, patches, out_dtype, mel_out, (hipStream_t)stream);
 }
 
+extern "C" int foley_op_loudness_energy(const float* x, int B, int C, int N, int64_t ld, const double* T16, double* work,
+                                        int64_t work_doubles, double* e, void* stream) {
+  if (!x || !T16) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  return launch_loudness_energy(x, B, C, N, (long)ld, T16, work, work_doubles, e, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_loudness_gate(const double* e, int B, int C, int nh, double* lufs, double* gamma, double* block_lufs,
+                                      void* stream) {
+  return launch_loudness_gate(e, B, C, nh, lufs, gamma, block_lufs, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_true_peak(const float* x, int B, int C, int N, int64_t ld, const float* taps36, float* true_peak,
+                                  float* sample_peak, float* envelope, void* stream) {
+  if (!x || !taps36 || !true_peak) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  return launch_true_peak(x, B, C, N, (long)ld, taps36, true_peak, sample_peak, envelope, (hipStream_t)stream);
+}
+
+extern "C" int foley_op_loudness_apply(const float* x, int B, int C, int N, int64_t ld, const float* gain, int limiter,
+                                       double ceiling, int lookahead, const float* taps36, float* y, int64_t ldy, float* g_out,
+                                       void* stream) {
+  if (!x || !gain || !y) return FAIL(FOLEY_ERR_INVALID, "null argument");
+  return launch_loudness_apply(x, B, C, N, (long)ld, gain, limiter, ceiling, lookahead, taps36, y, (long)ldy, g_out,
+                               (hipStream_t)stream);
+}
+
 extern "C" int foley_op_resize_aa_u8(const uint8_t* in, long outer, int len_in, long inner, int len_out, const int32_t* xmin,
                                      const int32_t* xsize, const int16_t* weights, int kmax, int precision, uint8_t* out, void* stream) {
   if (!in || !xmin || !xsize || !weights || !out) return FAIL(FOLEY_ERR_INVALID, "null argument");

@@ -299,6 +299,14 @@ int launch_resample_sinc(const float* x, int B, int N, int orig, int nnew, const
                          int Nout, hipStream_t st);
 int launch_logmel(const float* w16, int B, int N16, const float* basis, const int* mel_lo, const int* mel_len, const float* mel_w,
                   int mel_wp, void* patches, int out_dtype, float* mel_out, hipStream_t st);
+// loudness.hip: the BS.1770 meter, the static gain and the look-ahead limiter (host/loudness.py); T16 / taps36 are HOST memory
+int launch_loudness_energy(const float* x, int B, int C, int N, long ld, const double* T16, double* work, int64_t work_doubles,
+                           double* e, hipStream_t st);
+int launch_loudness_gate(const double* e, int B, int C, int nh, double* lufs, double* gamma, double* block_lufs, hipStream_t st);
+int launch_true_peak(const float* x, int B, int C, int N, long ld, const float* taps36, float* tp, float* sp, float* env,
+                     hipStream_t st);
+int launch_loudness_apply(const float* x, int B, int C, int N, long ld, const float* gain, int limiter, double ceil_lin, int W,
+                          const float* taps36, float* y, long ldy, float* g_out, hipStream_t st);
 int launch_dac_out(const float* s, const float* w, const float* bias, int B, int T, int C, float* out,
                    hipStream_t st);
 // clap_audio.hip: the CLAP audio tower's front end and windowed attention (host/clap_score.py)

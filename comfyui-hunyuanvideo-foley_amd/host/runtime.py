@@ -213,6 +213,13 @@ _SIGNATURES = {
                                         C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "foley_op_window_attention": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_loudness_energy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_double), C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p]),
+    "foley_op_loudness_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "foley_op_true_peak": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "foley_op_loudness_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_double, C.c_int,
+                                          C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1216,3 +1223,87 @@ def op_rows_to_planes(rows: torch.Tensor, B: int, out: torch.Tensor):
     if rows.shape[0] % B or tuple(out.shape) != (B, Cc, rows.shape[0] // B):
         raise FoleyRuntimeError("op_rows_to_planes: rows [B*T, C], out [B, C, T]")
     _check(lib, lib.foley_op_rows_to_planes(_ptr(rows), B, rows.shape[0] // B, Cc, _ptr(out), _stream()), "foley_op_rows_to_planes")
+
+
+# ----------------------------------------------------------------------------- loudness / true peak (host/loudness.py)
+def _wave(x: torch.Tensor, what: str):
+    """x [B, C, N] fp32 on the device, C 1 or 2, rows at one pitch ld >= N (a slice of a longer buffer is fine) -> (ptr, B, C, N, ld)."""
+    if x.dim() != 3 or x.dtype != torch.float32 or x.shape[1] not in (1, 2) or x.shape[0] < 1 or x.shape[2] < 1:
+        raise FoleyRuntimeError(f"{what}: x [B, C in (1, 2), N] fp32")
+    if not x.is_cuda:
+        raise FoleyRuntimeError("libfoley_hip.so needs device tensors (got a CPU tensor)")
+    B, Cc, N = x.shape
+    ld = x.stride(1) if Cc > 1 else (x.stride(0) if B > 1 else N)
+    if x.stride(2) != 1 or ld < N or (Cc > 1 and B > 1 and x.stride(0) != Cc * ld):
+        raise FoleyRuntimeError(f"{what}: the rows of x must lie at one pitch >= N with unit sample stride")
+    return x.data_ptr(), B, Cc, N, ld
+
+
+def op_loudness_energy(x: torch.Tensor, T: torch.Tensor) -> torch.Tensor:
+    """foley_op_loudness_energy: x [B, C, N] fp32 -> K-weighted hop energies e [B, C, N // 4800] fp64.  T: the 4x4 fp64 transition
+    matrix of one 480-sample chunk (host/loudness.py::chunk_transition), a CPU tensor."""
+    lib = load_library()
+    ptr, B, Cc, N, ld = _wave(x, "op_loudness_energy")
+    if T.is_cuda or T.dtype != torch.float64 or tuple(T.shape) != (4, 4):
+        raise FoleyRuntimeError("op_loudness_energy: T is a [4, 4] fp64 CPU tensor")
+    nh = N // 4800
+    e = torch.empty(B, Cc, nh, device=x.device, dtype=torch.float64)
+    if nh:
+        work = torch.empty(B * Cc * nh * 40, device=x.device, dtype=torch.float64)
+        T16 = (C.c_double * 16)(*T.reshape(-1).tolist())
+        _check(lib, lib.foley_op_loudness_energy(ptr, B, Cc, N, ld, T16, _ptr(work), work.numel(), _ptr(e), _stream()),
+               "foley_op_loudness_energy")
+    return e
+
+
+def op_loudness_gate(e: torch.Tensor):
+    """foley_op_loudness_gate: e [B, C, nh] fp64 -> (lufs [B], gamma [B], block_lufs [B, max(nh - 3, 0)]) fp64 on the device."""
+    lib = load_library()
+    if e.dim() != 3 or e.dtype != torch.float64 or e.shape[1] not in (1, 2):
+        raise FoleyRuntimeError("op_loudness_gate: e [B, C in (1, 2), nh] fp64")
+    B, Cc, nh = e.shape
+    lufs = torch.empty(B, device=e.device, dtype=torch.float64)
+    gamma = torch.empty(B, device=e.device, dtype=torch.float64)
+    blocks = torch.empty(B, max(nh - 3, 0), device=e.device, dtype=torch.float64)
+    _check(lib, lib.foley_op_loudness_gate(_ptr(e) if nh else _ptr(lufs), B, Cc, nh, _ptr(lufs), _ptr(gamma),
+                                           _ptr(blocks) if nh > 3 else None, _stream()), "foley_op_loudness_gate")
+    return lufs, gamma, blocks
+
+
+def _taps36(taps: torch.Tensor):
+    if taps.is_cuda or taps.dtype != torch.float32 or tuple(taps.shape) != (3, 12):
+        raise FoleyRuntimeError("true-peak taps: a [3, 12] fp32 CPU tensor (host/loudness.py::true_peak_taps)")
+    return (C.c_float * 36)(*taps.reshape(-1).tolist())
+
+
+def op_true_peak(x: torch.Tensor, taps: torch.Tensor, with_sample_peak: bool = True, with_envelope: bool = False):
+    """foley_op_true_peak: x [B, C, N] fp32 -> (true_peak [B], sample_peak [B] or None, envelope [B, N] or None), linear fp32."""
+    lib = load_library()
+    ptr, B, Cc, N, ld = _wave(x, "op_true_peak")
+    tp = torch.empty(B, device=x.device, dtype=torch.float32)
+    sp = torch.empty(B, device=x.device, dtype=torch.float32) if with_sample_peak else None
+    env = torch.empty(B, N, device=x.device, dtype=torch.float32) if with_envelope else None
+    _check(lib, lib.foley_op_true_peak(ptr, B, Cc, N, ld, _taps36(taps), _ptr(tp), _ptr(sp), _ptr(env), _stream()),
+           "foley_op_true_peak")
+    return tp, sp, env
+
+
+def op_loudness_apply(x: torch.Tensor, gain: torch.Tensor, limiter: bool = False, ceiling: float = 1.0, lookahead: int = 240,
+                      taps: Optional[torch.Tensor] = None, with_gain_curve: bool = False):
+    """foley_op_loudness_apply: y = gain[b] * x (one fp32 multiply), or with `limiter` the look-ahead limiter under the linear
+    `ceiling` with `lookahead` samples; a gain of 0 copies the clip unchanged.  Returns y [B, C, N] (and g [B, N] with
+    with_gain_curve, limiter mode only)."""
+    lib = load_library()
+    ptr, B, Cc, N, ld = _wave(x, "op_loudness_apply")
+    if gain.dtype != torch.float32 or gain.numel() != B:
+        raise FoleyRuntimeError("op_loudness_apply: gain [B] fp32")
+    if limiter and taps is None:
+        raise FoleyRuntimeError("op_loudness_apply: the limiter needs the true-peak taps")
+    if with_gain_curve and not limiter:
+        raise FoleyRuntimeError("op_loudness_apply: the gain curve exists in limiter mode only")
+    y = torch.empty(B, Cc, N, device=x.device, dtype=torch.float32)
+    g = torch.empty(B, N, device=x.device, dtype=torch.float32) if with_gain_curve else None
+    _check(lib, lib.foley_op_loudness_apply(ptr, B, Cc, N, ld, _ptr(gain), int(bool(limiter)), float(ceiling), int(lookahead),
+                                            _taps36(taps) if limiter else None, _ptr(y), N, _ptr(g), _stream()),
+           "foley_op_loudness_apply")
+    return (y, g) if with_gain_curve else y

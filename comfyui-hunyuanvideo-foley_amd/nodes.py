@@ -34,6 +34,11 @@ def log_step_cache(models) -> None:
         if rep is not None:
             log.info("step cache: skipped %d of %d iterations", sum(rep["skipped"]), len(rep["skipped"]))
 
+
+def _fmt_db(t) -> str:
+    return "[" + ", ".join("%.2f" % v for v in t.tolist()) + "]"
+
+
 _SOLVERS = ["euler", "heun-2", "midpoint-2", "kutta-4"]
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 
@@ -333,7 +338,8 @@ class HunyuanFoleySampler:
                        block_swap_args=None, features=None, *, audio=None, strength=1.0, regenerate=None, crossfade_s=0.1,
                        prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0,
                        video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0, cache_threshold=None, cache_skip=None,
-                       cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25):
+                       cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25,
+                       loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -377,8 +383,20 @@ class HunyuanFoleySampler:
         `prompt_crossfade_s` blends neighbouring prompts linearly across each boundary (0: hard cuts).  At most 16 distinct
         text sets, the negative prompt included.  With `window_s` the timeline is given in the long clip's time (text-to-audio;
         per-window video features are not carried).  It combines with audio= / regenerate=, guidance and the step cache, and
-        does not combine with prompts= / negative_prompts= / images= / features=."""
+        does not combine with prompts= / negative_prompts= / images= / features=.
+
+        Loudness (keyword-only, not sockets; host/loudness.py): `loudness_lufs` (None: off) brings every clip of the batch, each
+        on its own, to that integrated loudness (ITU-R BS.1770-4; about -16 for the web, -23 for EBU R128) on the device before
+        the waveform leaves it.  `true_peak_dbtp` is the true-peak ceiling: without `peak_limiter` the gain is lowered where the
+        peak would pass it; with it the full gain is applied and a 5 ms look-ahead limiter holds the peaks under the ceiling.
+        A silent clip is returned as it is.  It combines with every other option."""
         model, deps = hunyuan_model, hunyuan_deps
+        if loudness_lufs is not None:              # refused here, before the encoders run
+            from .host import loudness as _loud
+            _loud.check_args(loudness_lufs, true_peak_dbtp, peak_limiter)
+            dac_sr = getattr(deps.get("dac_model"), "sample_rate", _loud.SAMPLE_RATE)
+            if dac_sr != _loud.SAMPLE_RATE:
+                raise ValueError(f"loudness_lufs needs a {_loud.SAMPLE_RATE} Hz decoder, this one gives {dac_sr} Hz")
         timeline = None
         if prompt_timeline is not None:            # refused here, before the encoders run
             if prompts is not None or negative_prompts is not None or images is not None or features is not None:
@@ -492,6 +510,12 @@ class HunyuanFoleySampler:
                 edit=edit, guidance=guidance, step_cache=step_cache, **tl_kw)
         if step_cache is not None:
             log_step_cache(ran_on)
+        if loudness_lufs is not None:           # on the device, each clip on its own
+            out, before, after = _loud.normalize({"waveform": audio, "sample_rate": sr}, float(loudness_lufs), float(true_peak_dbtp),
+                                                 bool(peak_limiter))
+            audio = out["waveform"]
+            log.info("loudness: %s LUFS before, gain %s dB, true peak %s dBTP after", _fmt_db(before.lufs), _fmt_db(before.gain_db),
+                     _fmt_db(after.true_peak_dbtp))
         waveform_batch = audio.float().cpu()
         first = {"waveform": waveform_batch[0].unsqueeze(0), "sample_rate": sr}
         return (first, {"waveform": waveform_batch, "sample_rate": sr})

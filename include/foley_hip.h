@@ -571,6 +571,32 @@ int foley_op_spec_patches(const float* spec, int G, int T, int F, const float* s
                           const float* resize_w, int Tq, int ratio, void* out, int out_dtype, int Kp, void* stream);
 int foley_op_window_attention(const void* qkv, int dtype, int rows, int qkv_cols, int H, int win_tokens, const int32_t* table,
                               int n_win, const float* bias, const float* mask, int n_mask, void* out, int out_pitch, void* stream);
+/* The loudness and true-peak output stage (host/loudness.py; additive: the ABI number is unchanged).  Waveforms x [B, C, N] fp32
+ * at 48 kHz on the device, C 1 or 2, row (b, c) at x + (b*C + c)*ld with ld >= N; anything else is FOLEY_ERR_INVALID.  T16 and
+ * taps36 are read on the HOST at the call.  No floating-point atomics: every entry gives the same bits on repetition.
+ * loudness_energy: the K-weighting of ITU-R BS.1770-4 (two biquads, fp64 state, zero initial state) and e [B, C, nh] fp64, the sum
+ *   of y^2 over every complete hop of 4800 samples, nh = N / 4800 (nh = 0 launches nothing).  Chunks of 480 samples run in
+ *   parallel: from zero state, then a carry pass s_{k+1} = T s_k + end_k per row (T16: the chunk's 4x4 transition matrix,
+ *   row-major fp64, over the transposed-direct-form-II state (s1, s2 of stage 1, s1, s2 of stage 2)), then from the true state.
+ *   `work`: device scratch of at least B * C * nh * 40 doubles.  Three launches.
+ * loudness_gate: e -> blocks of four hops (400 ms, 75 % overlap), z_j = sum_c sum e / 19200, l_j = -0.691 + 10 log10 z_j ->
+ *   block_lufs [B, nh - 3] fp64; gamma [B] = the relative gate (-0.691 + 10 log10 mean z over l_j > -70, minus 10); lufs [B] = the
+ *   integrated loudness over the blocks above both gates; -inf where no block passes (gamma too) or nh < 4.  One wave per clip.
+ * true_peak: p[n] = max_c max(|x[n]|, |u[4n + r]|, r = 1..3), u[4n + r] = sum_{j = -5..6} x[n + j] * taps36[(r - 1)*12 + j + 5] in
+ *   fp32 (x zero outside [0, N)); true_peak [B] = max_n p[n] (linear), sample_peak [B] (nullable) = max |x|, envelope [B, N]
+ *   (nullable) = p.
+ * loudness_apply: limiter 0: y = gain[b] * x, one fp32 multiply per sample.  limiter 1: r[n] = min(1, ceiling / (gain[b] p[n]))
+ *   (fp64, rounded down to fp32; 1 outside [0, N)), gmin[m] = min r[m .. m + lookahead], g[n] = min(r[n], (sum_{m = n -
+ *   lookahead .. n} gmin[m]) / (lookahead + 1)) in fp32 in that order, y = (gain[b] * g[n]) * x for every channel, g_out [B, N]
+ *   (nullable, limiter 1 only) = g; ceiling linear and positive, 1 <= lookahead <= 480 samples.  gain[b] == 0 copies clip b
+ *   unchanged.  y [B, C, N] with row pitch ldy >= N, not overlapping x. */
+int foley_op_loudness_energy(const float* x, int B, int C, int N, int64_t ld, const double* T16, double* work,
+                             int64_t work_doubles, double* e, void* stream);
+int foley_op_loudness_gate(const double* e, int B, int C, int nh, double* lufs, double* gamma, double* block_lufs, void* stream);
+int foley_op_true_peak(const float* x, int B, int C, int N, int64_t ld, const float* taps36, float* true_peak,
+                       float* sample_peak, float* envelope, void* stream);
+int foley_op_loudness_apply(const float* x, int B, int C, int N, int64_t ld, const float* gain, int limiter, double ceiling,
+                            int lookahead, const float* taps36, float* y, int64_t ldy, float* g_out, void* stream);
 
 #ifdef __cplusplus
 }
