@@ -127,7 +127,7 @@ int launch_resample_sinc(const float* x, int B, int N, int orig, int nnew, const
                          int Nout, hipStream_t st) {
   if (B < 1 || N < 1 || orig < 1 || nnew < 1 || ntaps < 1 || width < 0 || Nout < 1)
     return foley_set_err("resample_sinc: empty problem", __FILE__, __LINE__);
-  if ((long)Nout > ((long)N + orig - 1) / orig * nnew + nnew)
+  if ((long)Nout > ((long)N * nnew + orig - 1) / orig)       // ceil(N * new / orig): torchaudio's length, the last output x can reach
     return foley_set_err("resample_sinc: Nout exceeds the resampled length", __FILE__, __LINE__);
   FOLEY_LAUNCH(resample_sinc_kernel, dim3((Nout + 255) / 256, B), dim3(256), 0, st, x, N, orig, nnew, taps, ntaps, width, out, Nout);
   return 0;

@@ -814,24 +814,30 @@ def op_resize_aa_u8(x: torch.Tensor, axis: int, len_out: int, xmin: torch.Tensor
     return out
 
 
-def op_resample_sinc(x: torch.Tensor, orig: int, new: int, taps: torch.Tensor, width: int) -> torch.Tensor:
+def op_resample_sinc(x: torch.Tensor, orig: int, new: int, taps: torch.Tensor, width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [B, N] fp32 -> [B, ceil(N * new / orig)] fp32 (foley_op_resample_sinc; orig / new reduced by their gcd, taps [new, ntaps]
-    fp32 on the device from host/sync_score.py::sinc_resample_taps)."""
+    fp32 on the device from host/sync_score.py::sinc_resample_taps).  out: a contiguous fp32 [B, ceil(N * new / orig)] to write
+    into (allocated when None)."""
     lib = load_library()
     if x.dim() != 2 or x.dtype != torch.float32 or taps.dtype != torch.float32 or taps.dim() != 2 or taps.shape[0] != new:
         raise FoleyRuntimeError("op_resample_sinc: x [B, N] fp32, taps [new, ntaps] fp32")
     B, N = x.shape
     n_out = -(-N * new // orig)
-    out = torch.empty(B, n_out, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B, n_out, device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, n_out) or out.dtype != torch.float32:
+        raise FoleyRuntimeError("op_resample_sinc: out [B, ceil(N * new / orig)] fp32")
     _check(lib, lib.foley_op_resample_sinc(_ptr(x), B, N, orig, new, _ptr(taps), taps.shape[1], width, _ptr(out), n_out, _stream()),
            "foley_op_resample_sinc")
     return out
 
 
 def op_logmel(w16: torch.Tensor, basis: torch.Tensor, mel_lo: torch.Tensor, mel_len: torch.Tensor, mel_w: torch.Tensor,
-              out_dtype: torch.dtype = torch.float32, with_mel: bool = False):
+              out_dtype: torch.dtype = torch.float32, with_mel: bool = False, out: Optional[torch.Tensor] = None,
+              mel_out: Optional[torch.Tensor] = None):
     """16 kHz waveform [B, N16] fp32 -> AST patch matrix [B*S*72, 256] in out_dtype (foley_op_logmel), S = (N16 - 10240) // 5120 + 1;
-    with_mel: also the normalised log-mel [B*S, 128, 66] fp32.  Tables from host/sync_score.py::logmel_tables."""
+    with_mel: also the normalised log-mel [B*S, 128, 66] fp32.  Tables from host/sync_score.py::logmel_tables.  out / mel_out:
+    contiguous tensors of those shapes to write into (out's dtype replaces out_dtype; mel_out implies with_mel)."""
     lib = load_library()
     if w16.dim() != 2 or w16.dtype != torch.float32 or w16.shape[1] < 10240:
         raise FoleyRuntimeError("op_logmel: w16 [B, N16 >= 10240] fp32")
@@ -840,18 +846,21 @@ def op_logmel(w16: torch.Tensor, basis: torch.Tensor, mel_lo: torch.Tensor, mel_
         raise FoleyRuntimeError("op_logmel: basis [2, 400, 544] fp32, int32 mel_lo / mel_len [128], mel_w [128, pitch] fp32")
     B, N16 = w16.shape
     S = (N16 - 10240) // 5120 + 1
-    patches = torch.empty(B * S * 72, 256, device=w16.device, dtype=out_dtype)
-    mel = torch.empty(B * S, 128, 66, device=w16.device, dtype=torch.float32) if with_mel else None
+    with_mel = with_mel or mel_out is not None
+    patches = torch.empty(B * S * 72, 256, device=w16.device, dtype=out_dtype) if out is None else out
+    mel = torch.empty(B * S, 128, 66, device=w16.device, dtype=torch.float32) if with_mel and mel_out is None else mel_out
+    if tuple(patches.shape) != (B * S * 72, 256) or (mel is not None and (tuple(mel.shape) != (B * S, 128, 66) or mel.dtype != torch.float32)):
+        raise FoleyRuntimeError("op_logmel: out [B*S*72, 256], mel_out [B*S, 128, 66] fp32")
     _check(lib, lib.foley_op_logmel(_ptr(w16), B, N16, _ptr(basis), _ptr(mel_lo), _ptr(mel_len), _ptr(mel_w), mel_w.shape[1],
                                     _ptr(patches), dt_of(patches), _ptr(mel) if with_mel else None, _stream()), "foley_op_logmel")
     return (patches, mel) if with_mel else patches
 
 
 def op_melspec_db(x: torch.Tensor, starts: torch.Tensor, basis: torch.Tensor, mel_lo: torch.Tensor, mel_len: torch.Tensor,
-                  mel_w: torch.Tensor) -> torch.Tensor:
+                  mel_w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """48 kHz waveform [B, N >= 1024] fp32 -> dB-mel spectrograms [B * W, 1001, 64] fp32 of the ten-second windows that start at
     starts [W] int32 (foley_op_melspec_db; N < 480000: one window, the extractor's repeatpad).  Tables from
-    host/clap_score.py::melspec_tables."""
+    host/clap_score.py::melspec_tables.  out: a contiguous fp32 [B * W, 1001, 64] to write into (allocated when None)."""
     lib = load_library()
     if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] < 1024 or starts.dtype != torch.int32 or starts.dim() != 1 or starts.numel() < 1:
         raise FoleyRuntimeError("op_melspec_db: x [B, N >= 1024] fp32, starts [W] int32")
@@ -862,7 +871,10 @@ def op_melspec_db(x: torch.Tensor, starts: torch.Tensor, basis: torch.Tensor, me
     W = starts.numel()
     if W > 1 and N < 480000:
         raise FoleyRuntimeError("op_melspec_db: a clip below ten seconds has one window")
-    out = torch.empty(B * W, 1001, 64, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B * W, 1001, 64, device=x.device, dtype=torch.float32)
+    if tuple(out.shape) != (B * W, 1001, 64) or out.dtype != torch.float32:
+        raise FoleyRuntimeError("op_melspec_db: out [B * W, 1001, 64] fp32")
     _check(lib, lib.foley_op_melspec_db(_ptr(x), B, N, _ptr(starts), W, _ptr(basis), _ptr(mel_lo), _ptr(mel_len), _ptr(mel_w),
                                         mel_w.shape[1], _ptr(out), _stream()), "foley_op_melspec_db")
     return out

@@ -434,7 +434,7 @@ int foley_op_resize_aa_u8(const uint8_t* in, long outer, int len_in, long inner,
                           const int32_t* xsize, const int16_t* weights, int kmax, int precision, uint8_t* out, void* stream);
 /* Rational polyphase windowed-sinc resampling (torchaudio.functional.resample with orig / new reduced by their gcd): x [B, N]
  * fp32 -> out [B, Nout] fp32, out[b, j*new_rate + p] = sum_{t < ntaps} x[b, j*orig + t - width] * taps[p*ntaps + t] (x is zero
- * outside [0, N)), Nout = ceil(N * new_rate / orig) for torchaudio's length.  taps [new_rate, ntaps] fp32 on the device, built by
+ * outside [0, N)), Nout = ceil(N * new_rate / orig) for torchaudio's length (a larger Nout is FOLEY_ERR_INVALID).  taps [new_rate, ntaps] fp32 on the device, built by
  * the caller (host/sync_score.py::sinc_resample_taps: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; 48 kHz -> 16 kHz is
  * orig 3, new_rate 1, width 19, 41 taps).  Used by the sync scorer ahead of foley_op_logmel. */
 int foley_op_resample_sinc(const float* x, int B, int N, int orig, int new_rate, const float* taps, int ntaps, int width,

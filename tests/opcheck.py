@@ -696,3 +696,234 @@ CROSS_CASES = {
 def cross_case(name):
     Bc, L, H, bdiv, Skv, _, _, ks = CROSS_CASES[name]
     return cross_dyadic_case(Bc, L, H, bdiv, Skv, seed=8000 + 7 * L + Skv, k_scale=ks, v_floor=0.25 if ks >= 15 else 0.0)
+
+
+# ----------------------------------------------------------------------------- audio front end: resampler, log-mel, dB-mel
+# (csrc/audio.hip, csrc/clap_audio.hip).  None of the three rounds to 16 bits before its output, so every bound below is a few
+# hundred U32 of a sum of absolute products: a wrong sample, frame, bin or repeat seam lies orders of magnitude outside.
+LOGMEL_MEAN, LOGMEL_2STD, LOGMEL_FLOOR = 4.2677393, 2 * 4.5689974, 1e-6       # the AST normalisation and the log's floor
+DBMEL_FLOOR = 1e-10
+
+
+def resample_ref_and_bound(x, taps, orig, new, width):
+    """foley_op_resample_sinc in fp64 from the fp32 samples x [B, N] and taps [new, ntaps]:
+        ref[b, j new + p] = sum_t x[b, j orig + t - width] taps[p][t]          (x zero outside [0, N)), cut to ceil(N new / orig)
+    mag is the same sum over absolute values; the bound (ntaps + 2) U32 mag covers ntaps fp32 FMAs in any order.  Where mag == 0
+    (every tap of the window hangs over the clip's edge or meets a zero sample) the bound is 0: the output must be 0."""
+    x, k = x.double().cpu(), taps.double().cpu()
+    B, N = x.shape
+    ntaps = k.shape[1]
+    n_out = -(-N * new // orig)
+    J = -(-n_out // new)
+    right = max(0, (J - 1) * orig + ntaps - width - N)
+    win = torch.nn.functional.pad(x, (width, right)).unfold(1, ntaps, orig)[:, :J]          # [B, J, ntaps]
+    ref = (win @ k.t()).reshape(B, -1)[:, :n_out]
+    mag = (win.abs() @ k.abs().t()).reshape(B, -1)[:, :n_out]
+    return ref, Bound((ntaps + 2) * U32 * mag)
+
+
+def mel_dense(tables, n_bins=513):
+    """The sparse mel table (mel_lo, mel_len, mel_w) as a dense fp64 [n_bins, n_mels] matrix."""
+    lo, ln, w = tables["mel_lo"].cpu(), tables["mel_len"].cpu(), tables["mel_w"].cpu()
+    fb = torch.zeros(n_bins, lo.numel(), dtype=torch.float64)
+    for c in range(lo.numel()):
+        a, n = int(lo[c]), int(ln[c])
+        fb[a:a + n, c] = w[c, :n].double()
+    return fb
+
+
+def logmel_frames(w16):
+    """The frames foley_op_logmel stages: w16 [B, N16] -> [B S, 65, 400] (same dtype); segment s of a clip is samples [5120 s,
+    5120 s + 10240), tap m of frame f reads segment sample 160 f + m - 200, reflected at the segment's edges (no edge repeat)."""
+    B, N = w16.shape
+    nseg = (N - 10240) // 5120 + 1
+    segs = torch.stack([w16[:, s * 5120:s * 5120 + 10240] for s in range(nseg)], 1).reshape(B * nseg, 10240)
+    i = torch.arange(65)[:, None] * 160 + torch.arange(400)[None] - 200
+    i = torch.where(i < 0, -i, torch.where(i >= 10240, 2 * 10239 - i, i))
+    return segs[:, i]
+
+
+def logmel_tables():
+    from foley_amd.host import sync_score
+    return sync_score.logmel_tables("cpu")
+
+
+def logmel_emulation(w16, tables=None, dtype=torch.float64):
+    """foley_op_logmel's arithmetic on the CPU from logmel_tables: reflect-padded 400-sample frames x basis -> power -> sparse mel
+    -> log -> pad -> normalise, computed in `dtype` (fp64: the reference; fp32: the same recipe as a second fp32 implementation).
+    Returns the spectrogram [B*S, 128, 66] fp32 and the im2col patches [B*S*72, 256] in the kernel's layout."""
+    tb = tables or logmel_tables()
+    fr = logmel_frames(w16.cpu()).to(dtype)                                           # [G, 65, 400]
+    re = fr @ tb["basis"][0].cpu().to(dtype)
+    im = fr @ tb["basis"][1].cpu().to(dtype)
+    pw = (re * re + im * im)[..., :513]
+    mel = torch.log(pw @ mel_dense(tb).to(dtype) + LOGMEL_FLOOR).transpose(1, 2)      # [G, 128, 65]
+    mel = torch.nn.functional.pad(mel, (0, 1))
+    mel = ((mel + LOGMEL_MEAN) / LOGMEL_2STD).float()
+    patches = mel.unfold(1, 16, 10).unfold(2, 16, 10)                                 # [G, 12, 6, 16, 16]: (fi, ti, kf, kt)
+    return mel, patches.reshape(-1, 256)
+
+
+def _dft_mel_ref_and_error(fr, tables, ntaps):
+    """Shared chain of the two spectrogram kernels, in fp64 from the staged frames fr [G, T, ntaps] and the fp32 tables:
+        re = s @ C, im = s @ S                        e_re = (ntaps + 2) U32 (|s| @ |C|), e_im likewise: ntaps fp32 FMAs in any order
+        pw = re^2 + im^2                              e_pw = 2 |re| e_re + e_re^2 + 2 |im| e_im + e_im^2 + 3 U32 pw
+        mel[c] = sum_k w[c][k] pw[lo_c + k]           e_mel = sum_k w[c][k] e_pw[lo_c + k] + (len_c + 2) U32 mel
+    Returns (mel, e_mel) [G, T, n_mels]."""
+    fr = fr.double().cpu()
+    C, Sn = (tables["basis"].cpu()[i].double()[:, :513] for i in (0, 1))
+    re, im = fr @ C, fr @ Sn
+    a = fr.abs()
+    e_re, e_im = (ntaps + 2) * U32 * (a @ C.abs()), (ntaps + 2) * U32 * (a @ Sn.abs())
+    pw = re * re + im * im
+    e_pw = 2 * re.abs() * e_re + e_re * e_re + 2 * im.abs() * e_im + e_im * e_im + 3 * U32 * pw
+    fb = mel_dense(tables)
+    mel = pw @ fb
+    e_mel = e_pw @ fb + (tables["mel_len"].cpu().double() + 2) * U32 * mel
+    return mel, e_mel
+
+
+def logmel_ref_and_bound(w16, tables, dev="cpu"):
+    """The normalised log-mel spectrogram [B S, 128, 66] of foley_op_logmel in fp64 (logmel_emulation's recipe, unrounded) with a
+    per-element bound.  With (mel, e_mel) from _dft_mel_ref_and_error at 400 taps, m = mel + 1e-6, r = e_mel / m, L = log m,
+    v = (L + 4.2677393) / (2 * 4.5689974):
+        e_v = (r / (1 - r) + a_log + 4 U32 |L|) / 9.1379948 + U32 4.2677393 / 9.1379948 + 2 U32 |v|
+      r / (1 - r)   |log(1 +- r)| <= r / (1 - r): the relative error of m pushed through the logarithm;
+      a_log         the logarithm's own error, measured reference against reference as measure_a_act does: 4 x the largest
+                    |torch's fp32 log on `dev` of fp32(m) - the fp64 log of m| over this case's m; it also pays for the rounding of
+                    the sum mel + 1e-6 and of the constant 1e-6 (each half a U32 relative to m: the same size as the fp32(m) inside
+                    the measurement, which the factor 4 multiplies);
+      4 U32 |L|     the rounding of L + mean and of the product, relative to L;
+      the constants mean is rounded to fp32 and the sum's rounding has a share relative to it (U32 mean together); 1 / (2 std) carries
+                    two roundings (the constant, the reciprocal) and the product a third: 3 half-U32 <= 2 U32, relative to v.
+    Column 65 (the time pad) is mean / (2 std), held within 2 U32 of it (four roundings: two constants, reciprocal, product).
+    Elements with r >= 0.5 get an infinite bound (NaN still offends) and are LEFT OUT; their share of the [B S, 128, 65] computed
+    elements is returned and the caller caps it.  Returns (ref64, Bound, share, a_log, silent) - silent [B S, 65] marks the frames
+    whose 400 staged samples are all zero."""
+    fr = logmel_frames(w16.cpu())
+    mel, e_mel = _dft_mel_ref_and_error(fr, tables, 400)
+    m = mel + LOGMEL_FLOOR
+    r, L = e_mel / m, torch.log(m)
+    a_log = 4.0 * float((torch.log(m.float().to(dev)).double().cpu() - L).abs().max())
+    v = (L + LOGMEL_MEAN) / LOGMEL_2STD
+    ok = r < 0.5
+    e = (r / (1 - r.clamp_max(0.5)) + a_log + 4 * U32 * L.abs()) / LOGMEL_2STD + U32 * LOGMEL_MEAN / LOGMEL_2STD + 2 * U32 * v.abs()
+    e = torch.where(ok, e, torch.full_like(e, float("inf")))
+    pad = LOGMEL_MEAN / LOGMEL_2STD
+    ref = torch.nn.functional.pad(v.transpose(1, 2), (0, 1), value=pad)
+    e = torch.nn.functional.pad(e.transpose(1, 2), (0, 1), value=2 * U32 * pad)
+    return ref, Bound(e), float((~ok).double().mean()), a_log, (fr == 0).all(-1)
+
+
+def dbmel_frames(padded):
+    """The frames foley_op_melspec_db transforms: padded [G, 480000] (a window as the extractor pads it, or a crop) -> [G, 1001,
+    1024]: centred STFT framing, 512 samples of reflect padding (no edge repeat) on either side, hop 480."""
+    p = torch.nn.functional.pad(padded[:, None], (512, 512), mode="reflect")[:, 0]
+    return p.unfold(1, 1024, 480)
+
+
+def dbmel_ref_and_bound(padded480k, tables, dev="cpu"):
+    """foley_op_melspec_db's dB-mel spectrogram [G, 1001, 64] in fp64 from the windows as padded, with a per-element bound in dB.
+    (mel, e_mel) from _dft_mel_ref_and_error at 1024 taps (the kernel's two half-sums and their addition are one of the orders
+    (1024 + 2) U32 covers), ref = 10 log10(max(mel, 1e-10)), r = e_mel / mel:
+        e_db = 10 / ln 10 * r / (1 - r) + a_log10 + 4 U32 |ref|
+    a_log10 is measured like a_log: 4 x the largest |torch's fp32 10 log10 on `dev` of fp32(mel) - ref| over the elements above
+    the floor.  mel == 0 (a silent frame) must give -100.0 exactly (bound 0).  An element whose [mel - e_mel, mel + e_mel] contains
+    1e-10 may be -100.0 or inside the bound (`amb`, see assert_dbmel); amb elements and those with r >= 0.5 (infinite bound) are
+    LEFT OUT and their share is returned.  Returns (ref64, Bound, share, a_log10, amb)."""
+    mel, e_mel = _dft_mel_ref_and_error(dbmel_frames(padded480k.cpu()), tables, 1024)
+    ref = 10.0 * torch.log10(mel.clamp_min(DBMEL_FLOOR))
+    live = mel > DBMEL_FLOOR
+    a_log10 = 0.0
+    if bool(live.any()):
+        ml = mel[live]
+        a_log10 = 4.0 * float((10.0 * torch.log10(ml.float().to(dev)).double().cpu() - 10.0 * torch.log10(ml)).abs().max())
+    r = torch.where(mel > 0, e_mel / mel.clamp_min(1e-300), torch.zeros_like(mel))
+    ok = r < 0.5
+    e = 10.0 / math.log(10.0) * r / (1 - r.clamp_max(0.5)) + a_log10 + 4 * U32 * ref.abs()
+    e = torch.where(ok, e, torch.full_like(e, float("inf")))
+    e = torch.where(mel == 0, torch.zeros_like(e), e)
+    amb = (mel > 0) & (mel - e_mel <= DBMEL_FLOOR) & (mel + e_mel >= DBMEL_FLOOR)
+    return ref, Bound(e), float((amb | ~ok).double().mean()), a_log10, amb
+
+
+def assert_dbmel(got, ref, bound, amb, what):
+    """assert_elementwise for the dB-mel: an ambiguous element (dbmel_ref_and_bound) may also be -100.0 exactly."""
+    got = got.detach().double().cpu()
+    return assert_elementwise(torch.where(amb & (got == -100.0), ref, got), ref, bound, what)
+
+
+# The cases of tests/test_audio_front_elementwise_gpu.py; the CPU emulations of test_opcheck_cpu.py run the same operands.
+# name -> (source rate, target rate, N, clips, taps, Nout); taps / Nout None: whatever the tap builder and the length rule give
+RESAMPLE_CASES = {
+    "3to1_two_blocks": (48000, 16000, 1543, 3, 41, 515),        # two full 256-output blocks + 3
+    "3to1_shorter_than_filter": (48000, 16000, 5, 1, 41, 2),    # every tap window hangs over both edges
+    "441to160": (44100, 16000, 1340, 3, 475, 487),              # the down-sampling ratio sync_scores takes for 44.1 kHz audio
+    "147to160": (44100, 48000, 1000, 3, None, 1089),
+    "1to3": (16000, 48000, 700, 3, 15, 2100),
+    "2to3": (32000, 48000, 513, 3, None, None),
+}
+LOGMEL_CASES = {"s1": 10240, "s1_long": 15359, "s2": 15360, "s3_ragged": 10240 + 2 * 5120 + 777}      # name -> N16
+# name -> (N, clips, starts)
+DBMEL_CASES = {
+    "n1024": (1024, 1, [0]),                 # n_rep 468, tail 768 zeros
+    "n1500": (1500, 1, [0]),
+    "n158400": (158400, 1, [0]),             # 3.3 s: n_rep 3, tail 4800 zeros
+    "n479999": (479999, 1, [0]),             # n_rep 1, one zero sample that the end reflect reads
+    "n480001_starts": (480001, 1, [0, 1, 5, -3]),      # 5 and -3 are clamped to 1 and 0
+    "n158400_b2": (158400, 2, [0]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def resample_case(name):
+    """(x [B, N] fp32, taps, orig, new, width): noise of amplitude 0.1 plus unit impulses at samples 0 and N - 1, per clip."""
+    from foley_amd.host import sync_score
+    src, dst, N, B, ntaps, n_out = RESAMPLE_CASES[name]
+    taps, orig, new, width = sync_score.sinc_resample_taps(src, dst)
+    assert ntaps is None or taps.shape[1] == ntaps, (name, taps.shape)
+    assert n_out is None or -(-N * new // orig) == n_out, name
+    x = 0.1 * torch.randn(B, N, generator=torch.Generator().manual_seed(4100 + N))
+    x[:, 0] += 1.0
+    x[:, N - 1] += 1.0
+    return x, taps, orig, new, width
+
+
+@functools.lru_cache(maxsize=None)
+def logmel_case(name, B):
+    """w16 [B, N16] fp32: noise of amplitude 0.1 plus a 1 kHz tone of 0.4, different per clip, with stretches of exact zeros:
+        every clip   [4500, 5900): crosses sample 5120, where segment 1 begins (frames 30 .. 35 of segment 0 and 0 .. 3 of segment 1
+                     are silent)
+        clip 0       [0, 680): frames 0 .. 3 of segment 0 are silent and frame 3 reads sample 679 last; [9600, 10900): crosses
+                     the end of segment 0 (its end reflect) and the start of segment 2
+        clip 1       (B = 3) all zeros
+        clip 2       [0, 201): frame 0 reads samples 0 .. 200 through the reflect and no further; [10039, 10240): frame 64 of
+                     segment 0 reads 10039 .. 10239 through the end reflect and nothing before."""
+    N = LOGMEL_CASES[name]
+    gen = torch.Generator().manual_seed(5200 + N + B)
+    t = torch.arange(N, dtype=torch.float64)
+    w = 0.1 * torch.randn(B, N, generator=gen, dtype=torch.float64)
+    w += 0.4 * torch.sin(2 * math.pi * 1000.0 * t / 16000.0 + torch.arange(B, dtype=torch.float64)[:, None])
+    w = w.float()
+    w[:, 4500:5900] = 0
+    w[0, :680] = 0
+    w[0, 9600:10900] = 0
+    if B > 1:
+        w[1] = 0
+    if B > 2:
+        w[2, :201] = 0
+        w[2, 10039:10240] = 0
+    return w
+
+
+@functools.lru_cache(maxsize=None)
+def dbmel_case(name):
+    """(x [B, N] fp32 noise of amplitude 0.05, starts, windows [B W, 480000]: every window as the kernel must pad or crop it)."""
+    import clap_ref
+    N, B, starts = DBMEL_CASES[name]
+    x = 0.05 * torch.randn(B, N, generator=torch.Generator().manual_seed(6300 + N + B))
+    if N < 480000:
+        wins = torch.stack([clap_ref.repeatpad(x[b]) for b in range(B)])
+    else:
+        wins = torch.stack([x[b, s:s + 480000] for b in range(B) for s in (min(max(s, 0), N - 480000) for s in starts)])
+    return x, starts, wins

@@ -971,3 +971,277 @@ def test_assert_bits_equal_nan_and_signed_zero():
     with pytest.raises(AssertionError):
         oc.assert_bits_equal(other_nan, a, "payload")
     oc.assert_bits_equal(other_nan, a, "payload", nan_ok=True)
+
+
+# ----------------------------------------------------------------------------- audio front end (tests/test_audio_front_elementwise_gpu.py)
+# fp32 emulations of the three kernels' own summation orders on the operands of the GPU cases, and planted defects.  These kernels
+# store fp32, so their old norm gates (rel_err 1e-6 for the resampler, 1e-5 for the log-mel patches) are sharp: each test below
+# states - and asserts - whether that gate, HAD THE SHAPE BEEN RUN, would have seen the defect too.  The record is: it would, for
+# every defect here but one (a spectrogram channel that no patch reads, in a segment the old test does not look at).  What the suite lacked was the cases (a ratio with new > 1 going down, inputs shorter than the filter, one
+# segment, repeat counts above 2, a clamped start), a check of EVERY element of the spectrogram (the old one looks at frozen
+# indices on click audio, most of it on the log floor), and a look at the memory around the outputs; the per-element check adds
+# the report of where a defect lies and a gate that does not thin out as the tensor grows.
+RESAMPLE_GATE, LOGMEL_GATE = 1e-6, 1e-5          # test_sync_gpu.py / test_edit_gpu.py
+DBMEL_GATE = 4 * 4.6e-5                          # test_melspec_db_op: 4 x the restatement's distance from the extractor (dB, max-abs)
+
+
+def _resample_emul(x, taps, orig, new, width, n_out, drop_last=False, wrong_phase_at=None):
+    """resample_sinc_kernel: ntaps sequential fp32 FMAs per output.  drop_last: the bound check reads `i < N - 1`;
+    wrong_phase_at: that output takes the taps of phase (o + 1) % new."""
+    B, N = x.shape
+    o = torch.arange(n_out)
+    j = o // new
+    p = o - j * new
+    if wrong_phase_at is not None:
+        p[wrong_phase_at] = (wrong_phase_at + 1) % new
+    acc = torch.zeros(B, n_out)
+    for t in range(taps.shape[1]):
+        i = j * orig - width + t
+        ok = (i >= 0) & (i < (N - 1 if drop_last else N))
+        xv = torch.where(ok, x[:, i.clamp(0, N - 1)], torch.zeros(()))
+        acc = _fma(xv, taps[p, t], acc)
+    return acc
+
+
+@pytest.mark.parametrize("name", list(oc.RESAMPLE_CASES))
+def test_resample_emulation_stays_inside(name):
+    x, taps, orig, new, width = oc.resample_case(name)
+    ref, bound = oc.resample_ref_and_bound(x, taps, orig, new, width)
+    assert ref.shape == (x.shape[0], -(-x.shape[1] * new // orig))
+    r = oc.assert_elementwise(_resample_emul(x, taps, orig, new, width, ref.shape[1]), ref, bound, name)
+    assert r < 0.2, r
+
+
+def test_resample_reference_is_the_restated_formula_and_zero_where_nothing_is_read():
+    """The fp64 reference against test_sync_cpu's conv1d restatement of torchaudio (another formulation of the same sum), and
+    mag == 0 - bound 0, the output must be 0 - where every tap meets a zero sample."""
+    from test_sync_cpu import _resample_formula
+    x, taps, orig, new, width = oc.resample_case("441to160")
+    ref, _ = oc.resample_ref_and_bound(x, taps, orig, new, width)
+    assert rel_err(_resample_formula(x.double(), 44100, 16000), ref) < 1e-7          # taps rounded to fp32 here, fp64 there
+    z = torch.zeros(1, 300)
+    z[0, 0] = 1.0
+    t3, o, n, w = oc.resample_case("3to1_two_blocks")[1:]
+    ref, bound = oc.resample_ref_and_bound(z, t3, o, n, w)
+    dead = bound.e[0] == 0
+    assert int(dead.sum()) == 100 - 7 and bool((ref[0][dead] == 0).all())           # outputs 0 .. 6 reach sample 0 (width 19, stride 3)
+    with pytest.raises(AssertionError, match="1 of 100"):
+        bad = ref.clone()
+        bad[0, 50] = 1e-30
+        oc.assert_elementwise(bad, ref, bound, "a value where nothing may be")
+
+
+def test_resample_last_sample_dropped_is_caught():
+    """`i < N - 1`: the unit impulse at N - 1 vanishes from the outputs whose taps reach it.  The 1e-6 norm gate sees it as well
+    (rel_err 0.23 - 0.33: the impulse is most of the signal's energy); the old cases end on quiet click audio."""
+    for name in ("3to1_two_blocks", "441to160", "1to3"):
+        x, taps, orig, new, width = oc.resample_case(name)
+        ref, bound = oc.resample_ref_and_bound(x, taps, orig, new, width)
+        bad = _resample_emul(x, taps, orig, new, width, ref.shape[1], drop_last=True)
+        assert rel_err(bad, ref) > RESAMPLE_GATE                    # the norm gate would have caught it
+        with pytest.raises(AssertionError, match="outside their bound") as ei:
+            oc.assert_elementwise(bad, ref, bound, name)
+        c0 = int(re.search(r"cols \[(\d+), (\d+)\]", str(ei.value)).group(1))
+        assert c0 >= ref.shape[1] - (2 * width + orig) * new // orig - new, str(ei.value)      # offenders lie at the clip's end only
+
+
+def test_resample_wrong_phase_on_one_output_is_caught():
+    """Output o takes the taps of phase (o + 1) % new, on ONE output: impossible to see at new = 1 (the only down-sampling ratio the
+    old suite runs), 1 of 1461 elements at 441:160.  rel_err is 5.6e-2 there: the norm gate would have caught it at this shape."""
+    x, taps, orig, new, width = oc.resample_case("441to160")
+    ref, bound = oc.resample_ref_and_bound(x, taps, orig, new, width)
+    bad = _resample_emul(x, taps, orig, new, width, ref.shape[1], wrong_phase_at=torch.tensor([300]))
+    assert rel_err(bad, ref) > RESAMPLE_GATE
+    with pytest.raises(AssertionError, match=r"x cols \[300, 300\]"):
+        oc.assert_elementwise(bad, ref, bound, "phase")
+    x1, t1, o1, n1, w1 = oc.resample_case("3to1_two_blocks")       # new = 1: the defect is no defect
+    assert torch.equal(_resample_emul(x1, t1, o1, n1, w1, 515, wrong_phase_at=torch.tensor([300])), _resample_emul(x1, t1, o1, n1, w1, 515))
+
+
+def _dft_emul(fr, basis, halves):
+    """The kernels' real DFT: v_mfma_f32_32x32x2_f32 steps of two taps (exact products, one fp32 rounding per step) into an fp32
+    accumulator; halves 2: taps [0, n / 2) and [n / 2, n) run as chains of their own and are added at the end (melspec_db_kernel)."""
+    n = fr.shape[-1]
+    C, Sn = basis[0][:, :513].double(), basis[1][:, :513].double()
+    f = fr.double()
+    h = n // halves
+    re = [torch.zeros(fr.shape[:-1] + (513,)) for _ in range(halves)]
+    im = [torch.zeros(fr.shape[:-1] + (513,)) for _ in range(halves)]
+    for k in range(0, h, 2):
+        for q in range(halves):
+            s = slice(q * h + k, q * h + k + 2)
+            re[q] = (re[q].double() + f[..., s] @ C[s]).float()
+            im[q] = (im[q].double() + f[..., s] @ Sn[s]).float()
+    re, im = (t[0] if halves == 1 else t[0] + t[1] for t in (re, im))
+    return re * re + im * im
+
+
+def _mel_emul(pw, tb, lo_shift=None):
+    """mel[c] = sum_k pw[lo_c + k] w[c][k] as sequential fp32 FMAs over the table's pitch (weights beyond a triangle are 0).
+    lo_shift = (c, d): triangle c starts d bins late."""
+    lo = tb["mel_lo"].long().clone()
+    if lo_shift is not None:
+        lo[lo_shift[0]] += lo_shift[1]
+    acc = torch.zeros(pw.shape[:-1] + (lo.numel(),))
+    for k in range(int(tb["mel_len"].max())):
+        acc = _fma(pw[..., (lo + k).clamp_max(512)], tb["mel_w"][:, k], acc)
+    return acc
+
+
+def _logmel_emul(fr, tb):
+    """logmel_kernel from its staged frames fr [G, 65, 400] fp32 -> the normalised spectrogram [G, 128, 66] fp32."""
+    mel = _mel_emul(_dft_emul(fr, tb["basis"], 1), tb)
+    inv2std = _f(1.0) / (_f(2.0) * _f(4.5689974))
+    v = (torch.log(mel + _f(1e-6)) + _f(4.2677393)) * inv2std
+    return F.pad(v.transpose(1, 2), (0, 1), value=float(_f(4.2677393) * inv2std))
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("name", list(oc.LOGMEL_CASES))
+def test_logmel_emulation_stays_inside(name, B):
+    tb = oc.logmel_tables()
+    w = oc.logmel_case(name, B)
+    ref, bound, share, a_log, silent = oc.logmel_ref_and_bound(w, tb)
+    assert share <= 1e-3 and ref.shape == (B * ((w.shape[1] - 10240) // 5120 + 1), 128, 66)
+    got = _logmel_emul(oc.logmel_frames(w), tb)
+    r = oc.assert_elementwise(got, ref, bound, f"{name} B {B}")
+    assert r < 0.5, r
+    assert int(silent.sum()) >= 13
+    floor = got.transpose(1, 2)[:, :65][silent]
+    assert bool((floor == floor[0, 0]).all())                      # a silent frame: one value in all 128 channels
+    # the unrounded reference IS the emulation test_sync_cpu states, before its cast to fp32
+    assert float((oc.logmel_emulation(w, tb)[0].double() - ref).abs().max()) < 1e-6
+    # and the diffuse gate is meetable: this emulation against the fp32 matmul recipe
+    assert rel_err(got, ref) <= 4 * rel_err(oc.logmel_emulation(w, tb, torch.float32)[0], ref)
+
+
+def _logmel_defect(frames_edit=None):
+    """The s3_ragged B = 3 case, its staged frames edited by frames_edit(frames, w16): (emulated spectrogram, ref64, bound)."""
+    tb = oc.logmel_tables()
+    w = oc.logmel_case("s3_ragged", 3)
+    ref, bound, _, _, _ = oc.logmel_ref_and_bound(w, tb)
+    fr = oc.logmel_frames(w).clone()
+    if frames_edit is not None:
+        frames_edit(fr, w)
+    return _logmel_emul(fr, tb), ref, bound
+
+
+def test_logmel_edge_repeat_instead_of_reflect_is_caught():
+    """Frame 0 of ONE segment (clip 2, segment 2: it begins right after a stretch of zeros, inside noise) stages sample -i - 1 for
+    i < 0 instead of -i.  127 of its 128 elements (of 76 032) leave their bound, by up to 0.5; rel_err 6.7e-3: the 1e-5 norm gate would have caught it.  Where
+    the reflect region is silent (clip 2, segment 0: zeros [0, 201)) the defect is invisible to any check: a documented blind spot
+    of that input, which is why clip 2's later segments begin in noise."""
+    def edit(fr, w):
+        i = torch.arange(400) - 200
+        fr[8, 0] = w[2, 10240:20480][torch.where(i < 0, -i - 1, i)]
+    got, ref, bound = _logmel_defect(edit)
+    assert rel_err(got, ref) > LOGMEL_GATE
+    with pytest.raises(AssertionError, match="outside their bound") as ei:
+        oc.assert_elementwise(got.reshape(9 * 128, 66), ref.reshape(9 * 128, 66), oc.Bound(bound.e.reshape(9 * 128, 66)), "edge repeat")
+    assert re.search(r"rows \[10\d\d, 11\d\d\] x cols \[0, 0\]", str(ei.value)), str(ei.value)
+
+
+def test_logmel_frame_64_from_the_next_segment_is_caught():
+    """Frame 64 - alone in the third frame tile - of segment 0 of clip 0 read from segment 1.  rel_err 8.9e-2: the norm gate would
+    have caught it."""
+    def edit(fr, w):
+        fr[0, 64] = fr[1, 64]
+    got, ref, bound = _logmel_defect(edit)
+    assert rel_err(got, ref) > LOGMEL_GATE
+    with pytest.raises(AssertionError, match="outside their bound") as ei:
+        oc.assert_elementwise(got.reshape(9 * 128, 66), ref.reshape(9 * 128, 66), oc.Bound(bound.e.reshape(9 * 128, 66)), "frame 64")
+    assert re.search(r"rows \[\d+, 1\d\d\] x cols \[64, 64\]", str(ei.value)), str(ei.value)
+
+
+def test_logmel_patch_element_from_the_next_frame_is_caught_bit_for_bit():
+    """One patch element (fi, ti, kf, kt) carries (c, t + 1).  The GPU test compares the patches with mel_out.unfold bit for bit, so
+    any such element is reported; rel_err of the patch matrix is 5e-4 for one element of 165 888: the 1e-5 norm gate would have
+    caught this one too - unless (c, t) and (c, t + 1) are both on the log floor, where both checks pass and nothing is wrong."""
+    got, ref, _ = _logmel_defect()
+    patches = got.unfold(1, 16, 10).unfold(2, 16, 10).reshape(-1, 256).contiguous()
+    bad = patches.clone()
+    fi, ti, kf, kt, g = 7, 3, 5, 9, 7                              # clip 2, segment 1 (clip 1 is silent: every element on the floor)
+    bad[(g * 12 + fi) * 6 + ti, kf * 16 + kt] = got[g, 10 * fi + kf, 10 * ti + kt + 1]
+    assert rel_err(bad, patches) > LOGMEL_GATE
+    with pytest.raises(AssertionError, match=r"1 of \d+ elements differ in their bits; first at \(row %d, col %d\)" % ((g * 12 + fi) * 6 + ti, kf * 16 + kt)):
+        oc.assert_bits_equal(bad, patches, "patch")
+
+
+def _dbmel_tb():
+    from foley_amd.host import clap_score
+    return clap_score.melspec_tables("cpu", 0.0, 14000.0)
+
+
+def _dbmel_emul(fr, tb, lo_shift=None):
+    """melspec_db_kernel from its frames fr [G, T, 1024] fp32 -> dB [G, T, 64] fp32."""
+    mel = _mel_emul(_dft_emul(fr, tb["basis"], 2), tb, lo_shift)
+    return torch.where(mel > _f(1e-10), _f(10.0) * torch.log10(mel), _f(-100.0))
+
+
+def _distinct(wins):
+    """Rows of wins without repetitions (the clamped starts repeat a window), in order of first appearance."""
+    keep = [i for i in range(wins.shape[0]) if not any(torch.equal(wins[i], wins[j]) for j in range(i))]
+    return wins[keep]
+
+
+@pytest.mark.parametrize("name", list(oc.DBMEL_CASES))
+def test_dbmel_emulation_stays_inside(name):
+    tb = _dbmel_tb()
+    x, starts, wins = oc.dbmel_case(name)
+    wins = _distinct(wins)
+    ref, bound, share, a_log10, amb = oc.dbmel_ref_and_bound(wins, tb)
+    assert share <= 1e-3 and ref.shape == (wins.shape[0], 1001, 64)
+    fr = oc.dbmel_frames(wins)
+    got = _dbmel_emul(fr, tb)
+    r = oc.assert_dbmel(got, ref, bound, amb, name)
+    assert r < 0.5, r
+    dead = (fr == 0).all(-1)
+    assert bool((got[dead] == -100.0).all()) and bool((ref[dead] == -100.0).all())
+
+
+def test_dbmel_reference_matches_the_restatement():
+    """dbmel_ref_and_bound against clap_ref.melspec_fp32 (torch.stft in fp32) on the n1500 window: the two recipes are one."""
+    import clap_ref
+    from foley_amd.host import clap_score
+    _, _, wins = oc.dbmel_case("n1500")
+    ref, bound, _, _, _ = oc.dbmel_ref_and_bound(wins, _dbmel_tb())
+    rest = clap_ref.melspec_fp32(wins, clap_score.slaney_mel_tables(0.0, 14000.0)[0])
+    assert float((rest.double() - ref).abs().max()) < 1e-3
+
+
+def test_dbmel_seam_off_by_one_and_late_triangle_are_caught():
+    """(a) ONE frame of the n1500 window staged with the repeat seam one sample late (p % (seg + 1), the sample past the clip read
+    as 0): every sample after the first seam shifts - the frame's 64 values move by up to 0.5 dB.  (b) ONE mel triangle starts one bin
+    late in every frame: up to 1.4 dB on one column.  The old dB gate (largest distance from the extractor at most 4 x 4.6e-5 dB) would
+    have caught both HAD A CLIP BELOW 4 s BEEN RUN; its two clips have repeat counts 2 and 1."""
+    tb = _dbmel_tb()
+    x, _, wins = oc.dbmel_case("n1500")
+    ref, bound, _, _, amb = oc.dbmel_ref_and_bound(wins, tb)
+    sel = torch.arange(8, 14)
+    fr = oc.dbmel_frames(wins)[:, sel].clone()
+    clean = _dbmel_emul(fr, tb)
+    oc.assert_dbmel(clean, ref[:, sel], oc.Bound(bound.e[:, sel]), amb[:, sel], "clean")
+    p = torch.arange(1024) + 10 * 480 - 512                        # frame 10 covers padded samples [4288, 5312): seam at 4500
+    fr[0, 2] = torch.cat((x[0], torch.zeros(1)))[p % 1501]
+    bad = _dbmel_emul(fr, tb)
+    assert float((bad - ref[:, sel]).abs().max()) > DBMEL_GATE
+    with pytest.raises(AssertionError, match=r"offenders lie in rows \[2, 2\]"):
+        oc.assert_dbmel(bad[0], ref[0, sel], oc.Bound(bound.e[0, sel]), amb[0, sel], "seam")
+    late = _dbmel_emul(oc.dbmel_frames(wins)[:, sel], tb, lo_shift=(20, 1))
+    assert float((late - ref[:, sel]).abs().max()) > DBMEL_GATE
+    with pytest.raises(AssertionError, match=r"x cols \[20, 20\]"):
+        oc.assert_dbmel(late[0], ref[0, sel], oc.Bound(bound.e[0, sel]), amb[0, sel], "triangle")
+
+
+def test_logmel_channel_127_is_seen_by_no_patch_and_caught_per_element():
+    """Channels 126 and 127 of the spectrogram reach no patch (12 patches of 16 at stride 10 end at channel 125), and the old test
+    compares mel_out at three frozen segments only.  Channel 127 of ANOTHER segment shifted by one frame leaves the patch matrix
+    bit for bit as it was - the old 1e-5 norm gate on the patches reads 0 - and fails the per-element check on that one row: the
+    one planted defect here that the old gates would have MISSED at any shape."""
+    got, ref, bound = _logmel_defect()
+    bad = got.clone()
+    bad[7, 127, :64] = got[7, 127, 1:65]
+    unfold = lambda m: m.unfold(1, 16, 10).unfold(2, 16, 10).reshape(-1, 256)
+    assert rel_err(unfold(bad), unfold(got)) == 0.0 < LOGMEL_GATE
+    with pytest.raises(AssertionError, match=r"offenders lie in rows \[1023, 1023\]"):
+        oc.assert_elementwise(bad.reshape(9 * 128, 66), ref.reshape(9 * 128, 66), oc.Bound(bound.e.reshape(9 * 128, 66)), "channel 127")

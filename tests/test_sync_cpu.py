@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from conftest import ROOT, golden, rel_err
 from foley_amd.host import encoders as E, runtime as rt, sync_score as S, synth
+from opcheck import logmel_emulation as _logmel_emulation
 
 
 def _resample_formula(x, orig=48000, new=16000):
@@ -79,30 +80,6 @@ def test_mel_table_matches_transformers_mel_filter_bank():
         assert 1 <= n <= S.MEL_PITCH and lo + n <= 513
         dense[lo:lo + n, c] = tb["mel_w"][c, :n]
     assert torch.equal(dense, fb)          # every triangle is one contiguous bin range
-
-
-def _logmel_emulation(w16):
-    """foley_op_logmel's arithmetic on the CPU from logmel_tables: reflect-padded 400-sample frames x basis -> power -> sparse mel
-    -> log -> pad -> normalise.  Returns the spectrogram [B*S, 128, 66] and the im2col patches [B*S*72, 256] in the kernel's layout."""
-    tb = S.logmel_tables("cpu")
-    B, N = w16.shape
-    nseg = S.num_audio_segments(N)
-    segs = torch.stack([w16[:, s * 5120:s * 5120 + 10240] for s in range(nseg)], 1).reshape(B * nseg, 10240)
-    i = torch.arange(65)[:, None] * 160 + torch.arange(400)[None] - 200
-    i = torch.where(i < 0, -i, torch.where(i >= 10240, 2 * 10239 - i, i))
-    fr = segs[:, i].double()                                                          # [G, 65, 400]
-    re = fr @ tb["basis"][0].double()
-    im = fr @ tb["basis"][1].double()
-    pw = (re * re + im * im)[..., :513]
-    fb = torch.zeros(513, 128, dtype=torch.float64)
-    for c in range(128):
-        lo, n = int(tb["mel_lo"][c]), int(tb["mel_len"][c])
-        fb[lo:lo + n, c] = tb["mel_w"][c, :n].double()
-    mel = torch.log(pw @ fb + 1e-6).transpose(1, 2)                                   # [G, 128, 65]
-    mel = F.pad(mel, (0, 1))
-    mel = ((mel + 4.2677393) / (2 * 4.5689974)).float()
-    patches = mel.unfold(1, 16, 10).unfold(2, 16, 10)                                 # [G, 12, 6, 16, 16]: (fi, ti, kf, kt)
-    return mel, patches.reshape(-1, 256)
 
 
 def test_logmel_tables_reproduce_the_reference_spectrogram():

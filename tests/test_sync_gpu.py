@@ -7,7 +7,8 @@ import torch.nn.functional as F
 
 from conftest import golden, rel_err
 from foley_amd.host import encoders as E, encoders_hip as EH, runtime as rt, sync_score as S, synth
-from test_sync_cpu import _logmel_emulation, _resample_formula, _vfeat
+from opcheck import logmel_emulation as _logmel_emulation
+from test_sync_cpu import _resample_formula, _vfeat
 
 pytestmark = pytest.mark.gpu
 
