@@ -1321,19 +1321,14 @@ static int run_step(foley_ctx* c, hipStream_t st) {
     s.clip_scale = (const float*)c->guid_scale.p;
   }
   if (c->edit) {
-    StepEditArgs e{};
-    e.s = s;
-    e.x0 = (const float*)c->edit_x0.p; e.noise = (const float*)c->edit_noise.p;
-    e.mask = c->edit_mask_clips ? (const float*)c->edit_mask.p : nullptr;
-    e.x0_clips = c->edit_x0_clips; e.mask_clips = c->edit_mask_clips;
-    return launch_solver_step_edit(e, st);
-  }
-  if (c->n_win) {
-    StepWinArgs w{};
-    w.s = s;
-    w.n_win = c->n_win; w.Ltot = c->win_Ltot;
-    w.starts = (const int*)c->win_starts.p; w.weights = (const float*)c->win_weights.p;
-    return launch_solver_step_windows(w, st);
+    s.form = STEP_FORM_EDIT;
+    s.x0 = (const float*)c->edit_x0.p; s.noise = (const float*)c->edit_noise.p;
+    s.mask = c->edit_mask_clips ? (const float*)c->edit_mask.p : nullptr;
+    s.x0_clips = c->edit_x0_clips; s.mask_clips = c->edit_mask_clips;
+  } else if (c->n_win) {
+    s.form = STEP_FORM_WINDOWS;
+    s.n_win = c->n_win; s.Ltot = c->win_Ltot;
+    s.starts = (const int*)c->win_starts.p; s.weights = (const float*)c->win_weights.p;
   }
   return launch_solver_step(s, st);
 }
@@ -2113,32 +2108,30 @@ extern "C" int foley_op_qkv_split(const float* qkv, int M, int L, int H, int nK,
 extern "C" int foley_op_solver_step(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C,
                                     int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
                                     void* rows_out, int rows_dtype, void* stream) {
-  StepArgs s{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
-  return launch_solver_step(s, (hipStream_t)stream);
+  return foley_op_solver_step_guided(nullptr, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
 }
 
 extern "C" int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
                                          int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
                                          int rows_dtype, const float* x0, int x0_clips, const float* noise, const float* mask,
                                          int mask_clips, void* stream) {
-  StepEditArgs e{};
-  e.s = StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
-  e.x0 = x0; e.noise = noise; e.mask = mask; e.x0_clips = x0_clips; e.mask_clips = mask_clips;
-  return launch_solver_step_edit(e, (hipStream_t)stream);
+  return foley_op_solver_step_edit_guided(nullptr, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out,
+                                          rows_dtype, x0, x0_clips, noise, mask, mask_clips, stream);
 }
 
 extern "C" int foley_op_solver_step_windows(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
                                             int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
                                             int rows_dtype, int n_win, const int32_t* starts, const float* weights, int Ltot,
                                             void* stream) {
-  StepWinArgs w{};
-  w.s = StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
-  w.n_win = n_win; w.Ltot = Ltot; w.starts = starts; w.weights = weights;
-  return launch_solver_step_windows(w, (hipStream_t)stream);
+  return foley_op_solver_step_windows_guided(nullptr, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out,
+                                             rows_dtype, n_win, starts, weights, Ltot, stream);
 }
 
-// The three step forms with a guidance descriptor, and the statistics behind its factors
-static StepArgs step_args_guided(const foley_guidance_desc* gd, StepArgs s) {
+// The three step forms with a guidance descriptor (null: none - the entries above), and the statistics behind its factors.  The
+// operands every form shares:
+static StepArgs step_args(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
+                          int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out, int rows_dtype) {
+  StepArgs s{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
   if (gd) {
     s.sched = gd->sched;
     s.clip_scale = gd->clip_scale;
@@ -2149,7 +2142,7 @@ static StepArgs step_args_guided(const foley_guidance_desc* gd, StepArgs s) {
 extern "C" int foley_op_solver_step_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
                                            int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
                                            void* rows_out, int rows_dtype, void* stream) {
-  return launch_solver_step(step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype}),
+  return launch_solver_step(step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype),
                             (hipStream_t)stream);
 }
 
@@ -2157,20 +2150,20 @@ extern "C" int foley_op_solver_step_edit_guided(const foley_guidance_desc* gd, c
                                                 int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
                                                 void* rows_out, int rows_dtype, const float* x0, int x0_clips, const float* noise,
                                                 const float* mask, int mask_clips, void* stream) {
-  StepEditArgs e{};
-  e.s = step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype});
-  e.x0 = x0; e.noise = noise; e.mask = mask; e.x0_clips = x0_clips; e.mask_clips = mask_clips;
-  return launch_solver_step_edit(e, (hipStream_t)stream);
+  StepArgs s = step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
+  s.form = STEP_FORM_EDIT;
+  s.x0 = x0; s.noise = noise; s.mask = mask; s.x0_clips = x0_clips; s.mask_clips = mask_clips;
+  return launch_solver_step(s, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved,
                                                    float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
                                                    int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
                                                    const float* weights, int Ltot, void* stream) {
-  StepWinArgs w{};
-  w.s = step_args_guided(gd, StepArgs{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype});
-  w.n_win = n_win; w.Ltot = Ltot; w.starts = starts; w.weights = weights;
-  return launch_solver_step_windows(w, (hipStream_t)stream);
+  StepArgs s = step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
+  s.form = STEP_FORM_WINDOWS;
+  s.n_win = n_win; s.Ltot = Ltot; s.starts = starts; s.weights = weights;
+  return launch_solver_step(s, (hipStream_t)stream);
 }
 
 extern "C" int64_t foley_op_cache_probe_work(int Bc, int La) { return Bc < 1 || La < 1 ? 0 : (int64_t)cache_probe_floats(Bc, La); }
@@ -2199,8 +2192,7 @@ extern "C" int foley_op_guidance_stats(const foley_guidance_desc* gd, const floa
   if (!gd || !gd->clip_scale) return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_stats: the descriptor's clip_scale receives the factors");
   if (clips < 1 || L < 1 || !work || work_floats < (int64_t)guidance_stats_floats(clips, L))
     return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_stats: work buffer smaller than foley_op_guidance_stats_work(clips, L) floats");
-  StepArgs s{pred, nullptr, nullptr, nullptr, clips, C, L, ncfg, guidance, nullptr, (int*)step_ptr, nullptr, FOLEY_F32};
-  s.sched = gd->sched;
+  const StepArgs s = step_args(gd, pred, nullptr, nullptr, nullptr, clips, C, L, ncfg, guidance, nullptr, (int32_t*)step_ptr, nullptr, FOLEY_F32);
   return launch_guidance_stats(s, work, nullptr, rescale, (float*)gd->clip_scale, (hipStream_t)stream);
 }
 

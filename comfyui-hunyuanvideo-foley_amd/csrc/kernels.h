@@ -224,21 +224,38 @@ int launch_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n
 int launch_latent_rows(const float* x, int clips, int C, int L, int ncfg, void* out, int out_dtype,
                        hipStream_t st);
 
-// Solver update (CFG combine + flow-match step) and re-staging of the model input rows.
+// Solver update (CFG combine + flow-match step) and re-staging of the model input rows, in one of three forms that share the
+// update's arithmetic bit for bit:
+//   edit (audio-to-audio / span regeneration): after a row flagged STEP_BLEND (8) - the iteration that ends a solver step -
+//     x <- m*x + (1-m)*(s*noise + (1-s)*x0) with s = coef row column 5 (sigma_{k+1}); mask null = all ones.
+//   windows (long clips): clip v*n_win + k is window k of variation v and covers the global frames [starts[k], starts[k] + L);
+//     after a row flagged STEP_BLEND every frame is replaced in all the windows that cover it by
+//     sum_k weights[k][g - starts[k]] * x_k (fp32, window order), and their next input rows are staged from that value.
+enum StepForm { STEP_FORM_PLAIN, STEP_FORM_EDIT, STEP_FORM_WINDOWS };
 struct StepArgs {
   const float* pred;   // [ncfg*clips*L, C] model output rows
   float* x;            // [clips, C, L] current sample (updated in place)
   float* x_saved;      // stage-0 sample for multi-stage solvers (or null)
   float* d_acc;        // running derivative combination (or null)
-  int clips, C, L, ncfg;
+  int clips, C, L, ncfg;   // windows form: clips = variations * n_win, L = frames per window
   float guidance;
-  const float* coef;   // per-iteration [n_iter][4]: {w_new, w_acc, dt, flags}
-  int* step_ptr;       // device iteration counter (incremented by the kernel)
-  void* rows_out;      // next model input rows (T), cfg-duplicated
+  const float* coef;   // per-iteration [n_iter][8]: {w_new, w_acc, dt, w_store, flags, s_next (STEP_BLEND rows), 0, 0}
+  int* step_ptr;       // device iteration counter: the row the step reads; the one-thread launch that follows the step advances it
+  void* rows_out;      // next model input rows (T), cfg-duplicated (or null)
   int rows_dtype;
   // guidance descriptor (null: the scalar `guidance` and no factor - the plain run's arithmetic bit for bit)
   const float* sched = nullptr;       // [n_iter][2] {g_video, g_text} per iteration, read at row *step_ptr; ncfg 2 reads column 0
   const float* clip_scale = nullptr;  // [clips] CFG-rescale factor of this iteration (launch_guidance_stats), multiplied into v
+  StepForm form = STEP_FORM_PLAIN;
+  // edit form
+  const float* x0 = nullptr;     // [x0_clips, C, L] source latents (clip stride 0 when x0_clips == 1)
+  const float* noise = nullptr;  // [clips, C, L] the run's initial noise
+  const float* mask = nullptr;   // [mask_clips, L] 1 = regenerate (or null)
+  int x0_clips = 0, mask_clips = 0;
+  // windows form
+  int n_win = 0, Ltot = 0;          // Ltot = starts[n_win - 1] + L
+  const int* starts = nullptr;      // [n_win] device, ascending from 0
+  const float* weights = nullptr;   // [n_win, L] device; the weights of every global frame sum to 1, a singly covered frame has 1.0f
 };
 int launch_solver_step(const StepArgs& a, hipStream_t st);
 // CFG rescale: clip_scale[b] = phi * std(last half of clip b) / std(guided v of clip b) + (1 - phi) over the clip's C x L elements
@@ -258,26 +275,6 @@ int launch_cache_probe(const float* a0, int Bc, int La, int D, float eps, const 
                        float* part, float* rel, hipStream_t st);
 int launch_cache_delta(const float* aN, float* delta, long n, hipStream_t st);
 int launch_cache_apply(float* audio, const float* delta, long n, hipStream_t st);
-// Edit form of the same step (audio-to-audio / span regeneration): after a row flagged STEP_BLEND (8) - the iteration that
-// ends a solver step - x <- m*x + (1-m)*(s*noise + (1-s)*x0) with s = coef row column 5 (sigma_{k+1}); mask null = all ones.
-struct StepEditArgs {
-  StepArgs s;
-  const float* x0;     // [x0_clips, C, L] source latents (clip stride 0 when x0_clips == 1)
-  const float* noise;  // [clips, C, L] the run's initial noise
-  const float* mask;   // [mask_clips, L] 1 = regenerate (or null)
-  int x0_clips, mask_clips;
-};
-int launch_solver_step_edit(const StepEditArgs& a, hipStream_t st);
-// Windows form of the same step (long clips): clip v*n_win + k is window k of variation v and covers the global frames
-// [starts[k], starts[k] + L); after a row flagged STEP_BLEND every frame is replaced in all the windows that cover it by
-// sum_k weights[k][g - starts[k]] * x_k (fp32, window order), and their next input rows are staged from that value.
-struct StepWinArgs {
-  StepArgs s;            // s.clips = variations * n_win, s.L = frames per window
-  int n_win, Ltot;       // Ltot = starts[n_win - 1] + L
-  const int* starts;     // [n_win] device, ascending from 0
-  const float* weights;  // [n_win, L] device; the weights of every global frame sum to 1, a singly covered frame has 1.0f
-};
-int launch_solver_step_windows(const StepWinArgs& w, hipStream_t st);
 // x [variations*n_win, C, L] -> out [variations, C, Ltot]: the same weighted mean (windows that agree on a frame: that value as it is)
 int launch_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int* starts, const float* weights,
                           float* out, hipStream_t st);

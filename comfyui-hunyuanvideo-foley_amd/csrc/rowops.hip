@@ -454,21 +454,28 @@ __global__ __launch_bounds__(256) void latent_rows_kernel(const float* __restric
 // CFG combine (utils.py:241-243) + FlowMatchDiscreteScheduler.step (scheduling_flow_match_
 // discrete.py:262-297 and the multi-stage bookkeeping :299-373) driven by a per-iteration
 // coefficient row {w_new, w_acc, dt, w_store, flags}; then re-stages the next model input rows.
-constexpr int STEP_SAVE_X = 1, STEP_USE_SAVED = 2, STEP_ACC_RESET = 4;
+//
+// The three forms (plain, edit, windows) are built from the routines below and promise each other's bits: an all-ones mask is the
+// plain run, one window is the plain step, a null or constant guidance descriptor gives the plain arithmetic.  So the roundings
+// are written out: every routine that computes turns contraction off and names each fused multiply-add, and no form has an
+// expression of its own for a value another form computes too.
+constexpr int STEP_SAVE_X = 1, STEP_USE_SAVED = 2, STEP_ACC_RESET = 4, STEP_BLEND = 8;
 
 // The one place where the prediction halves of a (row, channel) become the velocity the step uses.  r = b*L + l is the row inside
 // a half, `it` the loop iteration (*step_ptr).  Two halves: v = u + g (c - u); three (h0 = nothing, h1 = video only, h2 = video
 // and prompt): v = p0 + g_video (p1 - p0) + g_text (p2 - p1), left to right.  Without a schedule g = g_video = g_text = the scalar
 // `guidance` and the two-half expression is the one the step kernels always had: plain runs keep their bits.  `scale` (the CFG
-// rescale factors, or null) multiplies the result by scale[b].
+// rescale factors, or null) multiplies the result by scale[b].  Two halves fuse the product into the sum; three halves round both
+// products and add them in order.
 __device__ __forceinline__ float guided_value(const StepArgs& a, int it, int b, long r, int c, const float* __restrict__ scale) {
+#pragma clang fp contract(off)
   const long half = (long)a.clips * a.L * a.C;
   const float* p = a.pred + r * a.C + c;
   float v;
   if (a.ncfg == 2) {
     const float g = a.sched ? a.sched[2 * it] : a.guidance;
     const float u = p[0], cnd = p[half];
-    v = u + g * (cnd - u);
+    v = __builtin_fmaf(g, cnd - u, u);
   } else if (a.ncfg == 3) {
     const float gv = a.sched ? a.sched[2 * it] : a.guidance, gt = a.sched ? a.sched[2 * it + 1] : a.guidance;
     const float p0 = p[0], p1 = p[half], p2 = p[2 * half];
@@ -480,55 +487,54 @@ __device__ __forceinline__ float guided_value(const StepArgs& a, int it, int b, 
   return v;
 }
 
-template <typename OutT>
-__global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
-  __shared__ float tile[32][33];
-  const int it = *a.step_ptr;
+// Row *step_ptr of the coefficient table
+struct StepCoef {
+  float w_new, w_acc, dt, w_store, s_next;
+  int flags;
+};
+__device__ __forceinline__ StepCoef step_coef(const StepArgs& a, int it) {
   const float* cf = a.coef + (long)it * 8;
-  const float w_new = cf[0], w_acc = cf[1], dt = cf[2], w_store = cf[3];
-  const int flags = (int)cf[4];
-  const int b = blockIdx.z;
-  const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  return StepCoef{cf[0], cf[1], cf[2], cf[3], cf[5], (int)cf[4]};
+}
+
+// phase 1: the guided value of clip b's rows lb .. lb + 31 (lb may be negative; rows outside [0, L) give 0), read [l][c] (coalesced
+// over c) into the tile that phase 2 reads transposed
+__device__ __forceinline__ void step_guided_tile(float (*tile)[33], const StepArgs& a, int it, int b, int lb, int c0) {
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  // phase 1: read pred rows [l][c] (coalesced over c) and transpose through LDS
   for (int i = ty; i < 32; i += 8) {
-    const int l = l0 + i, c = c0 + tx;
+    const int l = lb + i, c = c0 + tx;
     float v = 0.f;
-    if (l < a.L && c < a.C) {
-      v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
-    }
+    if (l >= 0 && l < a.L && c < a.C) v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
     tile[i][tx] = v;
   }
-  __syncthreads();
-  // phase 2: update x [b][c][l] (coalesced over l)
+}
+
+// phase 2, one element: the flow-match update of x[xi] from its velocity v.  Stores x_saved as the row's flags say and returns the
+// new x, which the caller stores blended or not, and in `acc_new` the new d_acc, which the caller stores after x where a.d_acc is
+// set: stored here, ahead of x, it costs the plain kernel 0.3 us of 7.5 (the waits fall differently).
+__device__ __forceinline__ float step_update(const StepArgs& a, const StepCoef& k, long xi, float v, float& acc_new) {
+#pragma clang fp contract(off)
+  const float xc = a.x[xi];
+  float acc = 0.f;
+  if (a.d_acc) acc = (k.flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
+  const float t = k.w_new * v;
+  const float deriv = (k.w_acc != 0.f) ? __builtin_fmaf(k.w_acc, acc, t) : t;
+  const float base = (k.flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
+  if (k.flags & STEP_SAVE_X) a.x_saved[xi] = xc;
+  acc_new = __builtin_fmaf(k.w_store, v, acc);
+  return __builtin_fmaf(deriv, k.dt, base);
+}
+
+// phase 3: the tile [l][c] as clip b's next model input rows lb .. lb + 31 (cfg-duplicated), coalesced over c; nothing without rows_out
+template <typename OutT>
+__device__ __forceinline__ void step_stage_rows(const float (*tile)[33], const StepArgs& a, int b, int lb, int c0) {
+  if (!a.rows_out) return;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
-    const int c = c0 + i, l = l0 + tx;
-    float xn = 0.f;
-    if (c < a.C && l < a.L) {
-      const long xi = ((long)b * a.C + c) * a.L + l;
-      const float v = tile[tx][i];
-      const float xc = a.x[xi];
-      float acc = 0.f;
-      if (a.d_acc) acc = (flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
-      const float deriv = (w_acc != 0.f) ? (w_new * v + w_acc * acc) : (w_new * v);
-      const float base = (flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
-      if (flags & STEP_SAVE_X) a.x_saved[xi] = xc;
-      xn = base + deriv * dt;
-      a.x[xi] = xn;
-      if (a.d_acc) a.d_acc[xi] = acc + w_store * v;
-    }
-    tile[tx][i] = xn;
-  }
-  __syncthreads();
-  // phase 3: next model input rows (cfg-duplicated), coalesced over c
-  if (a.rows_out) {
-    for (int i = ty; i < 32; i += 8) {
-      const int l = l0 + i, c = c0 + tx;
-      if (l < a.L && c < a.C) {
-        const OutT v = Cvt<OutT>::to(tile[i][tx]);
-        for (int g = 0; g < a.ncfg; ++g)
-          ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + l) * a.C + c] = v;
-      }
+    const int l = lb + i, c = c0 + tx;
+    if (l >= 0 && l < a.L && c < a.C) {
+      const OutT v = Cvt<OutT>::to(tile[i][tx]);
+      for (int g = 0; g < a.ncfg; ++g) ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + l) * a.C + c] = v;
     }
   }
 }
@@ -536,111 +542,78 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
 // Edit form (audio-to-audio / span regeneration): the same step, then - on rows flagged STEP_BLEND, the iterations that end a
 // solver step - the kept frames are pulled back onto the source's forward-noised path:
 //   x <- m*x + (1-m)*(s*noise + (1-s)*x0),  s = sigma_{k+1} (column 5 of the row), m = mask[clip][l] (1 = regenerate).
-// The blend is written as two products so that m = 1 returns x and m = 0 the target bit for bit under any contraction; the
-// un-blended update is the expression of solver_step_kernel, so an all-ones mask reproduces a plain run exactly.  Only plain
-// runs take solver_step_kernel.
-constexpr int STEP_BLEND = 8;
+// The blend is two rounded products so that m = 1 returns x and m = 0 the target bit for bit: an all-ones mask is a plain run.
+__device__ __forceinline__ float edit_blend(float xn, float m, float s, float noise, float x0) {
+#pragma clang fp contract(off)
+  const float tgt = __builtin_fmaf(1.f - s, x0, s * noise);
+  return m * xn + (1.f - m) * tgt;
+}
 
-template <typename OutT>
-__global__ __launch_bounds__(256) void solver_step_edit_kernel(const StepEditArgs e) {
+template <typename OutT, bool EDIT>
+__global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
   __shared__ float tile[32][33];
-  const StepArgs& a = e.s;
   const int it = *a.step_ptr;
-  const float* cf = a.coef + (long)it * 8;
-  const float w_new = cf[0], w_acc = cf[1], dt = cf[2], w_store = cf[3];
-  const int flags = (int)cf[4];
-  const float s_next = cf[5];
+  const StepCoef k = step_coef(a, it);
   const int b = blockIdx.z;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8) {
-    const int l = l0 + i, c = c0 + tx;
-    float v = 0.f;
-    if (l < a.L && c < a.C) {
-      v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
-    }
-    tile[i][tx] = v;
-  }
+  step_guided_tile(tile, a, it, b, l0, c0);
   __syncthreads();
-  const float* x0b = e.x0 + (e.x0_clips == 1 ? 0L : (long)b * a.C * a.L);
-  const float* mb = e.mask ? e.mask + (e.mask_clips == 1 ? 0L : (long)b * a.L) : nullptr;
+  const float* x0b = EDIT ? a.x0 + (a.x0_clips == 1 ? 0L : (long)b * a.C * a.L) : nullptr;
+  const float* mb = EDIT && a.mask ? a.mask + (a.mask_clips == 1 ? 0L : (long)b * a.L) : nullptr;
+  // phase 2: update x [b][c][l] (coalesced over l)
   for (int i = ty; i < 32; i += 8) {
     const int c = c0 + i, l = l0 + tx;
     float xn = 0.f;
     if (c < a.C && l < a.L) {
       const long xi = ((long)b * a.C + c) * a.L + l;
-      const float v = tile[tx][i];
-      const float xc = a.x[xi];
-      float acc = 0.f;
-      if (a.d_acc) acc = (flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
-      const float deriv = (w_acc != 0.f) ? (w_new * v + w_acc * acc) : (w_new * v);
-      const float base = (flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
-      if (flags & STEP_SAVE_X) a.x_saved[xi] = xc;
-      xn = base + deriv * dt;
-      if (flags & STEP_BLEND) {
-        const float m = mb ? mb[l] : 1.f;
-        const float tgt = s_next * e.noise[xi] + (1.f - s_next) * x0b[(long)c * a.L + l];
-        xn = m * xn + (1.f - m) * tgt;
-      }
+      float acc_new;
+      xn = step_update(a, k, xi, tile[tx][i], acc_new);
+      if (EDIT && (k.flags & STEP_BLEND)) xn = edit_blend(xn, mb ? mb[l] : 1.f, k.s_next, a.noise[xi], x0b[(long)c * a.L + l]);
       a.x[xi] = xn;
-      if (a.d_acc) a.d_acc[xi] = acc + w_store * v;
+      if (a.d_acc) a.d_acc[xi] = acc_new;
     }
     tile[tx][i] = xn;
   }
   __syncthreads();
-  if (a.rows_out) {
-    for (int i = ty; i < 32; i += 8) {
-      const int l = l0 + i, c = c0 + tx;
-      if (l < a.L && c < a.C) {
-        const OutT v = Cvt<OutT>::to(tile[i][tx]);
-        for (int g = 0; g < a.ncfg; ++g)
-          ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + l) * a.C + c] = v;
-      }
-    }
-  }
+  step_stage_rows<OutT>(tile, a, b, l0, c0);
 }
 
 // Windows form (long clips): the clips of one variation are overlapping windows of ONE long clip - clip v*n_win + k covers the
 // global frames [starts[k], starts[k] + L) of variation v - and the step is indexed by GLOBAL frame: a thread owns (g, c) and
-// does, for every window that covers g, that element's plain update (the expressions of solver_step_kernel).  On rows flagged
+// does, for every window that covers g, that element's update.  On rows flagged
 // STEP_BLEND (the iterations that end a solver step) the covering windows' new values are replaced in all of them by
 //   xb = sum_k weights[k][g - starts[k]] * xn_k      (fp32, in window order; the weights of a frame sum to 1)
 // and the next model input rows of every covering window are staged from xb.  A frame that one window covers has weight 1.0f
 // and a single term: it keeps its xn bit for bit.  Rows without the flag (intermediate stages) leave every window its own xn.
 // Every (clip, c, l) element belongs to exactly one thread, so no window reads what another thread wrote.  Any table of starts is
 // memory-safe: all accesses are indexed by (clip < clips, c < C, 0 <= l < L).
+__device__ __forceinline__ float windows_accumulate(bool first, float wk, float xn, float xb) {
+#pragma clang fp contract(off)
+  return first ? wk * xn : __builtin_fmaf(wk, xn, xb);
+}
+
 template <typename OutT>
-__global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinArgs w) {
+__global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepArgs a) {
   __shared__ float tile[32][33];
-  const StepArgs& a = w.s;
   const int it = *a.step_ptr;
-  const float* cf = a.coef + (long)it * 8;
-  const float w_new = cf[0], w_acc = cf[1], dt = cf[2], w_store = cf[3];
-  const int flags = (int)cf[4];
-  const bool blend = (flags & STEP_BLEND) != 0;
-  const int b0 = blockIdx.z * w.n_win;
+  const StepCoef kf = step_coef(a, it);
+  const bool blend = (kf.flags & STEP_BLEND) != 0;
+  const int b0 = blockIdx.z * a.n_win;
   const int g0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   float xb[4] = {0.f, 0.f, 0.f, 0.f};
   int ncov = 0;
-  for (int k = 0; k < w.n_win; ++k) {
-    const int s0 = w.starts[k];
+  for (int k = 0; k < a.n_win; ++k) {
+    const int s0 = a.starts[k];
     if (s0 >= g0 + 32 || s0 + a.L <= g0) continue;   // the window misses this tile (uniform over the block)
     const int b = b0 + k;
-    // phase 1: read pred rows [l][c] (coalesced over c) and transpose through LDS
-    for (int i = ty; i < 32; i += 8) {
-      const int l = g0 + i - s0, c = c0 + tx;
-      float v = 0.f;
-      if (l >= 0 && l < a.L && c < a.C) {
-        v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
-      }
-      tile[i][tx] = v;
-    }
+    step_guided_tile(tile, a, it, b, g0 - s0, c0);
     __syncthreads();
     // phase 2: update x [b][c][l] (coalesced over l)
     const int l = g0 + tx - s0;
     const bool in = l >= 0 && l < a.L;
-    const float wk = (in && blend) ? w.weights[(long)k * a.L + l] : 0.f;
+    const float wk = (in && blend) ? a.weights[(long)k * a.L + l] : 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int i = ty + 8 * j;
@@ -648,17 +621,11 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinA
       float xn = 0.f;
       if (c < a.C && in) {
         const long xi = ((long)b * a.C + c) * a.L + l;
-        const float v = tile[tx][i];
-        const float xc = a.x[xi];
-        float acc = 0.f;
-        if (a.d_acc) acc = (flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
-        const float deriv = (w_acc != 0.f) ? (w_new * v + w_acc * acc) : (w_new * v);
-        const float base = (flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
-        if (flags & STEP_SAVE_X) a.x_saved[xi] = xc;
-        xn = base + deriv * dt;
-        if (blend) xb[j] = (ncov == 0) ? wk * xn : xb[j] + wk * xn;
+        float acc_new;
+        xn = step_update(a, kf, xi, tile[tx][i], acc_new);
+        if (blend) xb[j] = windows_accumulate(ncov == 0, wk, xn, xb[j]);
         else a.x[xi] = xn;
-        if (a.d_acc) a.d_acc[xi] = acc + w_store * v;
+        if (a.d_acc) a.d_acc[xi] = acc_new;
       }
       if (!blend) tile[tx][i] = xn;
     }
@@ -666,16 +633,7 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinA
     __syncthreads();
     // phase 3 (no blend): this window's next model input rows from its own xn
     if (!blend) {
-      if (a.rows_out) {
-        for (int i = ty; i < 32; i += 8) {
-          const int lr = g0 + i - s0, c = c0 + tx;
-          if (lr >= 0 && lr < a.L && c < a.C) {
-            const OutT v = Cvt<OutT>::to(tile[i][tx]);
-            for (int g = 0; g < a.ncfg; ++g)
-              ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + lr) * a.C + c] = v;
-          }
-        }
-      }
+      step_stage_rows<OutT>(tile, a, b, g0 - s0, c0);
       __syncthreads();
     }
   }
@@ -684,8 +642,8 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinA
 #pragma unroll
   for (int j = 0; j < 4; ++j) tile[tx][ty + 8 * j] = xb[j];
   __syncthreads();
-  for (int k = 0; k < w.n_win; ++k) {
-    const int s0 = w.starts[k];
+  for (int k = 0; k < a.n_win; ++k) {
+    const int s0 = a.starts[k];
     if (s0 >= g0 + 32 || s0 + a.L <= g0) continue;
     const int b = b0 + k;
     const int l = g0 + tx - s0;
@@ -696,16 +654,7 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepWinA
         if (c < a.C) a.x[((long)b * a.C + c) * a.L + l] = xb[j];
       }
     }
-    if (a.rows_out) {
-      for (int i = ty; i < 32; i += 8) {
-        const int lr = g0 + i - s0, c = c0 + tx;
-        if (lr >= 0 && lr < a.L && c < a.C) {
-          const OutT v = Cvt<OutT>::to(tile[i][tx]);
-          for (int g = 0; g < a.ncfg; ++g)
-            ((OutT*)a.rows_out)[(((long)g * a.clips + b) * a.L + lr) * a.C + c] = v;
-        }
-      }
-    }
+    step_stage_rows<OutT>(tile, a, b, g0 - s0, c0);
   }
 }
 
@@ -1265,11 +1214,32 @@ int launch_latent_rows(const float* x, int clips, int C, int L, int ncfg, void* 
   return 0;
 }
 
+static int windows_args_ok(int clips, int n_win, int L, int Ltot, const int* starts, const float* weights) {
+  return n_win >= 1 && clips >= n_win && clips % n_win == 0 && starts && weights && Ltot >= L && (long)Ltot <= (long)n_win * L;
+}
+
+// the kernel of a.form for one rows dtype; the windows form's grid runs over global frames and variations
+template <typename OutT>
+static void launch_step_form(const StepArgs& a, hipStream_t st) {
+  const bool win = a.form == STEP_FORM_WINDOWS;
+  const dim3 grid(((win ? a.Ltot : a.L) + 31) / 32, (a.C + 31) / 32, win ? a.clips / a.n_win : a.clips), block(256);
+  if (win) FOLEY_LAUNCH(solver_step_windows_kernel<OutT>, grid, block, 0, st, a);
+  else if (a.form == STEP_FORM_EDIT) FOLEY_LAUNCH((solver_step_kernel<OutT, true>), grid, block, 0, st, a);
+  else FOLEY_LAUNCH((solver_step_kernel<OutT, false>), grid, block, 0, st, a);
+}
+
 int launch_solver_step(const StepArgs& a, hipStream_t st) {
-  dim3 grid((a.L + 31) / 32, (a.C + 31) / 32, a.clips), block(256);
-  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(solver_step_kernel<bf16_t>, grid, block, 0, st, a);
-  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(solver_step_kernel<f16_t>, grid, block, 0, st, a);
-  else FOLEY_LAUNCH(solver_step_kernel<float>, grid, block, 0, st, a);
+  if (a.form == STEP_FORM_EDIT) {
+    if (!a.x0 || !a.noise) return foley_set_err("solver_step_edit: x0 and noise are required", __FILE__, __LINE__);
+    if ((a.x0_clips != 1 && a.x0_clips != a.clips) || (a.mask && a.mask_clips != 1 && a.mask_clips != a.clips))
+      return foley_set_err("solver_step_edit: x0 / mask clip count must be 1 or clips", __FILE__, __LINE__);
+  } else if (a.form == STEP_FORM_WINDOWS) {
+    if (!windows_args_ok(a.clips, a.n_win, a.L, a.Ltot, a.starts, a.weights))
+      return foley_set_err("solver_step_windows: clips must be a multiple of n_win, La <= Ltot <= n_win*La, tables required", __FILE__, __LINE__);
+  }
+  if (a.rows_dtype == FOLEY_BF16) launch_step_form<bf16_t>(a, st);
+  else if (a.rows_dtype == FOLEY_F16) launch_step_form<f16_t>(a, st);
+  else launch_step_form<float>(a, st);
   FOLEY_LAUNCH_CHECK();
   FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
   FOLEY_LAUNCH_CHECK();
@@ -1328,39 +1298,6 @@ static int launch_cache_axpy(bool sub, const float* src, float* dst, long n, hip
 }
 int launch_cache_delta(const float* aN, float* delta, long n, hipStream_t st) { return launch_cache_axpy(true, aN, delta, n, st); }
 int launch_cache_apply(float* audio, const float* delta, long n, hipStream_t st) { return launch_cache_axpy(false, delta, audio, n, st); }
-
-int launch_solver_step_edit(const StepEditArgs& e, hipStream_t st) {
-  const StepArgs& a = e.s;
-  if (!e.x0 || !e.noise) return foley_set_err("solver_step_edit: x0 and noise are required", __FILE__, __LINE__);
-  if ((e.x0_clips != 1 && e.x0_clips != a.clips) || (e.mask && e.mask_clips != 1 && e.mask_clips != a.clips))
-    return foley_set_err("solver_step_edit: x0 / mask clip count must be 1 or clips", __FILE__, __LINE__);
-  dim3 grid((a.L + 31) / 32, (a.C + 31) / 32, a.clips), block(256);
-  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(solver_step_edit_kernel<bf16_t>, grid, block, 0, st, e);
-  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(solver_step_edit_kernel<f16_t>, grid, block, 0, st, e);
-  else FOLEY_LAUNCH(solver_step_edit_kernel<float>, grid, block, 0, st, e);
-  FOLEY_LAUNCH_CHECK();
-  FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
-  FOLEY_LAUNCH_CHECK();
-  return 0;
-}
-
-static int windows_args_ok(int clips, int n_win, int L, int Ltot, const int* starts, const float* weights) {
-  return n_win >= 1 && clips >= n_win && clips % n_win == 0 && starts && weights && Ltot >= L && (long)Ltot <= (long)n_win * L;
-}
-
-int launch_solver_step_windows(const StepWinArgs& w, hipStream_t st) {
-  const StepArgs& a = w.s;
-  if (!windows_args_ok(a.clips, w.n_win, a.L, w.Ltot, w.starts, w.weights))
-    return foley_set_err("solver_step_windows: clips must be a multiple of n_win, La <= Ltot <= n_win*La, tables required", __FILE__, __LINE__);
-  dim3 grid((w.Ltot + 31) / 32, (a.C + 31) / 32, a.clips / w.n_win), block(256);
-  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(solver_step_windows_kernel<bf16_t>, grid, block, 0, st, w);
-  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(solver_step_windows_kernel<f16_t>, grid, block, 0, st, w);
-  else FOLEY_LAUNCH(solver_step_windows_kernel<float>, grid, block, 0, st, w);
-  FOLEY_LAUNCH_CHECK();
-  FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
-  FOLEY_LAUNCH_CHECK();
-  return 0;
-}
 
 int launch_windows_stitch(const float* x, int clips, int n_win, int C, int L, int Ltot, const int* starts, const float* weights,
                           float* out, hipStream_t st) {

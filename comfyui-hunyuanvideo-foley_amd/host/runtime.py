@@ -992,24 +992,34 @@ def _rows_dt(rows_out) -> int:
     return DT_F32 if rows_out is None else dt_of(rows_out)      # rows_out None: the step stages no model input rows
 
 
-def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out):
-    """x_saved / d_acc may be None for single-stage tables (euler), rows_out None to leave the next input rows unstaged."""
+def _step_call(entry: str, gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, edit=None, windows=None):
+    """One of the six foley_op_solver_step* entries: `entry` names the symbol, gd (a descriptor or None) leads the guided ones;
+    edit = (x0, noise, mask) and windows = (starts, weights, Ltot) add their form's operands."""
     lib = load_library()
     clips, Cc, L = x.shape
-    _check(lib, lib.foley_op_solver_step(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-                                         float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out),
-                                         _rows_dt(rows_out), _stream()), "foley_op_solver_step")
+    args = [_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg, float(guidance), _ptr(coef), _ptr(step_ptr),
+            _ptr(rows_out), _rows_dt(rows_out)]
+    if entry.endswith("_guided"):
+        args.insert(0, C.byref(gd) if gd is not None else None)
+    if edit is not None:
+        x0, noise, mask = edit
+        mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
+        args += [_ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips]
+    elif windows is not None:
+        starts, weights, Ltot = windows
+        args += [_windows_tables(x, starts, weights), _ptr(starts), _ptr(weights), int(Ltot)]
+    _check(lib, getattr(lib, entry)(*args, _stream()), entry)
+
+
+def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out):
+    """x_saved / d_acc may be None for single-stage tables (euler), rows_out None to leave the next input rows unstaged."""
+    _step_call("foley_op_solver_step", None, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out)
 
 
 def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, x0, noise, mask=None):
     """foley_op_solver_step_edit: x0 [1 | clips, C, L], noise [clips, C, L], mask [1 | clips, L] or None (all ones)."""
-    lib = load_library()
-    clips, Cc, L = x.shape
-    mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
-    _check(lib, lib.foley_op_solver_step_edit(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-                                              float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
-                                              _ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips, _stream()),
-           "foley_op_solver_step_edit")
+    _step_call("foley_op_solver_step_edit", None, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
+               edit=(x0, noise, mask))
 
 
 def _windows_tables(x, starts, weights):
@@ -1023,13 +1033,8 @@ def _windows_tables(x, starts, weights):
 
 def op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, starts, weights, Ltot):
     """foley_op_solver_step_windows: x [variations*n_win, C, L]; starts [n_win] int32 and weights [n_win, L] fp32 device tensors."""
-    lib = load_library()
-    clips, Cc, L = x.shape
-    n_win = _windows_tables(x, starts, weights)
-    _check(lib, lib.foley_op_solver_step_windows(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-                                                 float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
-                                                 n_win, _ptr(starts), _ptr(weights), int(Ltot), _stream()),
-           "foley_op_solver_step_windows")
+    _step_call("foley_op_solver_step_windows", None, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
+               windows=(starts, weights, Ltot))
 
 
 def guidance_desc(sched: Optional[torch.Tensor] = None, clip_scale: Optional[torch.Tensor] = None) -> GuidanceDescC:
@@ -1044,22 +1049,9 @@ def guidance_desc(sched: Optional[torch.Tensor] = None, clip_scale: Optional[tor
 
 def op_solver_step_guided(gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, edit=None, windows=None):
     """The step forms with a guidance descriptor: plain, edit=(x0, noise, mask) or windows=(starts, weights, Ltot)."""
-    lib = load_library()
-    clips, Cc, L = x.shape
-    head = (C.byref(gd) if gd is not None else None, _ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-            float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out))
-    if edit is not None:
-        x0, noise, mask = edit
-        mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
-        _check(lib, lib.foley_op_solver_step_edit_guided(*head, _ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips, _stream()),
-               "foley_op_solver_step_edit_guided")
-    elif windows is not None:
-        starts, weights, Ltot = windows
-        n_win = _windows_tables(x, starts, weights)
-        _check(lib, lib.foley_op_solver_step_windows_guided(*head, n_win, _ptr(starts), _ptr(weights), int(Ltot), _stream()),
-               "foley_op_solver_step_windows_guided")
-    else:
-        _check(lib, lib.foley_op_solver_step_guided(*head, _stream()), "foley_op_solver_step_guided")
+    form = "_edit" if edit is not None else "_windows" if windows is not None else ""
+    _step_call(f"foley_op_solver_step{form}_guided", gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
+               edit=edit, windows=windows)
 
 
 def op_guidance_stats(pred, clips, L, ncfg, guidance, sched, step_ptr, rescale, out: Optional[torch.Tensor] = None) -> torch.Tensor:

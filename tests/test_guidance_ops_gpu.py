@@ -4,7 +4,9 @@ and guard bands (tests/opcheck.py, tests/guidance_ref.py).
 The step forms run with a guidance descriptor - a schedule table whose row changes every iteration and, on every second
 iteration, per-clip factors - for two and three halves, into guarded buffers; every element is held against the bound of the step
 with the combine's extra roundings, the staged rows bit for bit against the device's own x in all ncfg copies.  With two halves, a
-constant table and no factors the three forms must give the bits of the entries without a descriptor.  The factors are held
+constant table and no factors the three forms must give the bits of the entries without a descriptor; under a varying table with
+factors, for one to three halves, the edit form with nothing to keep and the windows form with one window must give the bits of
+the plain form.  The factors are held
 against fp64 under the any-order fp32 bound of the two centred sums; because that bound cannot see one lost element in smooth
 data, a second family of inputs carries its variance in a handful of edge elements, each worth at least ten bounds."""
 import pytest
@@ -183,6 +185,42 @@ def test_constant_schedule_keeps_the_bits(dev, clips, C, L, form, dt):
         rt.op_solver_step_guided(None, _rand((ncfg * clips * L, C), 234 + it).to(dev), *c.args[:3], ncfg, GUIDANCE, coef, c.ctr.view.view(1),
                                  c.args[3], **kw)
     oc.assert_bits_equal(c.gx.view, a.gx.view, f"{form} {dt}: null descriptor")
+
+
+# ----------------------------------------------------------------------------- the forms agree with each other under any descriptor
+@pytest.mark.parametrize("dt", ALL3)
+@pytest.mark.parametrize("ncfg", [1, 2, 3])
+@pytest.mark.parametrize("solver", list(SOLVER_ITERS))
+@pytest.mark.parametrize("clips,C,L", [(2, 40, 65), (1, 128, 1)])
+def test_forms_agree_under_a_descriptor(dev, clips, C, L, solver, ncfg, dt):
+    """With a schedule that changes every iteration and per-clip factors, the edit entry without a mask and with an all-ones mask
+    (one source clip), and the windows entry with the single window [0, L) of weight 1.0f, give the bits of the plain guided
+    entry in x, x_saved, d_acc, the staged rows and the counter: a partial tile in both axes, and the one-frame clip.  All four
+    read the table with the STEP_BLEND rows, which the plain form ignores."""
+    n = SOLVER_ITERS[solver]
+    coef, sched = tables.edit_solver_table(tables.sigma_grid(n), solver, n).to(dev), _sched(n)
+    x0, noise = _rand((1, C, L), 240, 0.7).to(dev), _rand((clips, C, L), 241).to(dev)
+    ones = torch.ones(L, dtype=torch.float32, device=dev)
+    sd, wd = torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, L, dtype=torch.float32, device=dev)
+    forms = {"plain": {}, "edit, no mask": {"edit": (x0, noise, None)}, "edit, mask of ones": {"edit": (x0, noise, ones)},
+             "one window": {"windows": (sd, wd, L)}}
+    states = {f: _StepState(dev, clips, C, L, ncfg, DTS[dt], 242) for f in forms}
+    d = _Desc(dev, sched, clips, 243)
+    for it in range(n):
+        pred = _rand((ncfg * clips * L, C), 244 + it).to(dev)
+        for f, kw in forms.items():
+            st = states[f]
+            rt.op_solver_step_guided(d.desc(it % 2 == 0), pred, *st.args[:3], ncfg, GUIDANCE, coef, st.ctr.view.view(1), st.args[3], **kw)
+        a = states["plain"]
+        assert int(a.ctr.view.item()) == it + 1
+        for f in list(forms)[1:]:
+            b = states[f]
+            for ga, gb, name in zip((a.gx, a.gs, a.ga, a.gr, a.ctr), (b.gx, b.gs, b.ga, b.gr, b.ctr), ("x", "x_saved", "d_acc", "rows_out", "counter")):
+                oc.assert_bits_equal(gb.view, ga.view, f"{f} vs plain: {solver} {clips}x{C}x{L} ncfg {ncfg} {dt} it {it} {name}")
+                gb.check(f"{f} {name}")
+        for g in (a.gx, a.gs, a.ga, a.gr, a.ctr):
+            g.check("plain")
+        d.check(sched, "forms")
 
 
 # ----------------------------------------------------------------------------- the rescale factors
