@@ -207,6 +207,10 @@ struct GraphKey {
   // rewrites what a replay reads.
   int tl_sets = 0;
   const void *tl_a = nullptr, *tl_b = nullptr, *tl_alpha = nullptr;
+  // multistep (foley_set_multistep): the velocity ring and its slot count (null / 0: off - the step kernels without history;
+  // orders 2 and 3 differ in the slot count, which the history kernel reads as a launch argument)
+  const void* ms_hist = nullptr;
+  int ms_slots = 0;
   uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
   uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
   bool operator==(const GraphKey& o) const {
@@ -214,7 +218,7 @@ struct GraphKey {
            edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && n_win == o.n_win && Ltot == o.Ltot &&
            win_starts == o.win_starts && win_weights == o.win_weights && guid_sched == o.guid_sched && guid_scale == o.guid_scale &&
            guid_part == o.guid_part && guid_phi == o.guid_phi && sc_delta == o.sc_delta && sc_mprev == o.sc_mprev && tl_sets == o.tl_sets &&
-           tl_a == o.tl_a && tl_b == o.tl_b && tl_alpha == o.tl_alpha && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
+           tl_a == o.tl_a && tl_b == o.tl_b && tl_alpha == o.tl_alpha && ms_hist == o.ms_hist && ms_slots == o.ms_slots && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
   }
 };
 
@@ -269,6 +273,10 @@ struct foley_ctx {
   // and ctx-owned copies of the per-token tables [ncfg*clips*(Lv+La)]; ws_tl_sets: the set count the workspace was sized for
   int tl_sets = 0, ws_tl_sets = 0;
   DevBuf tl_a, tl_b, tl_alpha;
+  // multistep state (foley_set_multistep; cleared by foley_prepare): the order (0: off) and the ctx-owned ring of order - 1
+  // velocity slots [clips, latent_dim, La] fp32 that the history step kernels read and feed
+  int ms_order = 0;
+  DevBuf ms_hist;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -480,7 +488,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   hipSetDevice(c->device);
   ctx_free_plan(c);
   for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights, &c->guid_sched,
-                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel, &c->tl_a, &c->tl_b, &c->tl_alpha}) release(*b);
+                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel, &c->tl_a, &c->tl_b, &c->tl_alpha, &c->ms_hist}) release(*b);
   if (c->sc_rel_host) (void)hipHostFree(c->sc_rel_host);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
@@ -647,6 +655,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   c->n_win = 0;                     // and one without foley_set_windows has independent clips
   c->guid_sched_on = c->guid_rescale_on = false;   // and one without foley_set_guidance combines with the plan's scalar
   c->sc_mode = 0;                   // and one without foley_set_step_cache runs every block on every iteration
+  c->ms_order = 0;                  // and one without foley_set_multistep is a one-step method
   c->tl_sets = 0;                   // and one without a timeline (foley_prepare_timeline sets it below) one text set per batch row
   RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
   c->vis_src = n_vis;
@@ -1330,6 +1339,10 @@ static int run_step(foley_ctx* c, hipStream_t st) {
     s.n_win = c->n_win; s.Ltot = c->win_Ltot;
     s.starts = (const int*)c->win_starts.p; s.weights = (const float*)c->win_weights.p;
   }
+  if (c->ms_order >= 2) {   // the history instantiation of the same form; a skipped (cached) iteration feeds the ring like any other
+    s.hist = (float*)c->ms_hist.p;
+    s.hist_slots = c->ms_order - 1;
+  }
   return launch_solver_step(s, st);
 }
 
@@ -1410,6 +1423,7 @@ static GraphKey graph_key_now(const foley_ctx* c) {
                   c->guid_rescale_on ? (const void*)((const float*)c->guid_sched.p + 2 * (size_t)c->plan.n_iter) : nullptr,
                   c->sc_mode ? c->sc_delta.p : nullptr, c->sc_mode ? c->sc_mprev.p : nullptr,
                   c->tl_sets,       c->tl_sets ? c->tl_a.p : nullptr, c->tl_sets ? c->tl_b.p : nullptr, c->tl_sets ? c->tl_alpha.p : nullptr,
+                  c->ms_order >= 2 ? c->ms_hist.p : nullptr, c->ms_order >= 2 ? c->ms_order - 1 : 0,
                   c->tensor_gen,    c->plan_gen};
 }
 
@@ -1505,6 +1519,24 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
   HIPTRY(hipStreamSynchronize(st));   // guid_host may be rewritten by the next call
   c->guid_sched_on = sched != nullptr;
   c->guid_rescale_on = rescale > 0.f;
+  return 0;
+}
+
+extern "C" int foley_set_multistep(foley_ctx* c, int order, void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_multistep: foley_prepare has not been called");
+  if (order == 0 || order == 1) {   // a one-step method: the step kernels without history
+    c->ms_order = 0;
+    return 0;
+  }
+  if (order != 2 && order != 3) return FAIL(FOLEY_ERR_INVALID, "foley_set_multistep: order must be 0 or 1 (off), 2 or 3");
+  const foley_plan& pl = c->plan;
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the ring may be in use by a previous loop on this stream
+  TRY(grow(c->ms_hist, (size_t)(order - 1) * pl.clips * c->cfg.latent_dim * pl.La * 4));
+  c->ms_order = order;
   return 0;
 }
 
@@ -2163,6 +2195,25 @@ extern "C" int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd
   StepArgs s = step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
   s.form = STEP_FORM_WINDOWS;
   s.n_win = n_win; s.Ltot = Ltot; s.starts = starts; s.weights = weights;
+  return launch_solver_step(s, (hipStream_t)stream);
+}
+
+// The step with a velocity history (see foley_set_multistep): one entry for the three forms, chosen by the descriptor's operands.
+extern "C" int foley_op_solver_step_hist(const foley_step_hist_desc* hd, const float* pred, float* x, float* x_saved, float* d_acc,
+                                         int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
+                                         void* rows_out, int rows_dtype, void* stream) {
+  if (!hd || !hd->hist || hd->hist_slots < 1 || hd->hist_slots > 2)
+    return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_hist: the descriptor needs the ring and 1 or 2 slots");
+  if (hd->x0 && hd->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_hist: edit and windows operands exclude each other");
+  StepArgs s = step_args(hd->guidance, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
+  s.hist = hd->hist; s.hist_slots = hd->hist_slots;
+  if (hd->x0) {
+    s.form = STEP_FORM_EDIT;
+    s.x0 = hd->x0; s.noise = hd->noise; s.mask = hd->mask; s.x0_clips = hd->x0_clips; s.mask_clips = hd->mask_clips;
+  } else if (hd->n_win) {
+    s.form = STEP_FORM_WINDOWS;
+    s.n_win = hd->n_win; s.Ltot = hd->Ltot; s.starts = hd->starts; s.weights = hd->weights;
+  }
   return launch_solver_step(s, (hipStream_t)stream);
 }
 

@@ -239,7 +239,7 @@ struct StepArgs {
   float* d_acc;        // running derivative combination (or null)
   int clips, C, L, ncfg;   // windows form: clips = variations * n_win, L = frames per window
   float guidance;
-  const float* coef;   // per-iteration [n_iter][8]: {w_new, w_acc, dt, w_store, flags, s_next (STEP_BLEND rows), 0, 0}
+  const float* coef;   // per-iteration [n_iter][8]: {w_new, w_acc, dt, w_store, flags, s_next (STEP_BLEND rows), c1, c2 (STEP_HIST rows)}
   int* step_ptr;       // device iteration counter: the row the step reads; the one-thread launch that follows the step advances it
   void* rows_out;      // next model input rows (T), cfg-duplicated (or null)
   int rows_dtype;
@@ -256,6 +256,12 @@ struct StepArgs {
   int n_win = 0, Ltot = 0;          // Ltot = starts[n_win - 1] + L
   const int* starts = nullptr;      // [n_win] device, ascending from 0
   const float* weights = nullptr;   // [n_win, L] device; the weights of every global frame sum to 1, a singly covered frame has 1.0f
+  // multistep history (null: none - the kernels without it): a ring of hist_slots (order - 1: 1 or 2) slots [clips, C, L] fp32 of
+  // the velocities of earlier iterations.  Rows flagged STEP_HIST (16) add coef columns 6 and 7 times the slots (it - 1) and
+  // (it - 2) mod hist_slots to the derivative (a zero weight reads nothing); every row stores its own velocity to slot it mod
+  // hist_slots after those reads.
+  float* hist = nullptr;
+  int hist_slots = 0;
 };
 int launch_solver_step(const StepArgs& a, hipStream_t st);
 // CFG rescale: clip_scale[b] = phi * std(last half of clip b) / std(guided v of clip b) + (1 - phi) over the clip's C x L elements

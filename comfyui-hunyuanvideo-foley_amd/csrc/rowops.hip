@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void latent_rows_kernel(const float* __restric
 // plain run, one window is the plain step, a null or constant guidance descriptor gives the plain arithmetic.  So the roundings
 // are written out: every routine that computes turns contraction off and names each fused multiply-add, and no form has an
 // expression of its own for a value another form computes too.
-constexpr int STEP_SAVE_X = 1, STEP_USE_SAVED = 2, STEP_ACC_RESET = 4, STEP_BLEND = 8;
+constexpr int STEP_SAVE_X = 1, STEP_USE_SAVED = 2, STEP_ACC_RESET = 4, STEP_BLEND = 8, STEP_HIST = 16;
 
 // The one place where the prediction halves of a (row, channel) become the velocity the step uses.  r = b*L + l is the row inside
 // a half, `it` the loop iteration (*step_ptr).  Two halves: v = u + g (c - u); three (h0 = nothing, h1 = video only, h2 = video
@@ -487,14 +487,17 @@ __device__ __forceinline__ float guided_value(const StepArgs& a, int it, int b, 
   return v;
 }
 
-// Row *step_ptr of the coefficient table
+// Row *step_ptr of the coefficient table.  c1 / c2 (columns 6 and 7, the multistep weights of v_{n-1} and v_{n-2}) are read by the
+// history instantiations only.
 struct StepCoef {
   float w_new, w_acc, dt, w_store, s_next;
   int flags;
+  float c1, c2;
 };
+template <bool HIST = false>
 __device__ __forceinline__ StepCoef step_coef(const StepArgs& a, int it) {
   const float* cf = a.coef + (long)it * 8;
-  return StepCoef{cf[0], cf[1], cf[2], cf[3], cf[5], (int)cf[4]};
+  return StepCoef{cf[0], cf[1], cf[2], cf[3], cf[5], (int)cf[4], HIST ? cf[6] : 0.f, HIST ? cf[7] : 0.f};
 }
 
 // phase 1: the guided value of clip b's rows lb .. lb + 31 (lb may be negative; rows outside [0, L) give 0), read [l][c] (coalesced
@@ -512,13 +515,30 @@ __device__ __forceinline__ void step_guided_tile(float (*tile)[33], const StepAr
 // phase 2, one element: the flow-match update of x[xi] from its velocity v.  Stores x_saved as the row's flags say and returns the
 // new x, which the caller stores blended or not, and in `acc_new` the new d_acc, which the caller stores after x where a.d_acc is
 // set: stored here, ahead of x, it costs the plain kernel 0.3 us of 7.5 (the waits fall differently).
-__device__ __forceinline__ float step_update(const StepArgs& a, const StepCoef& k, long xi, float v, float& acc_new) {
+//
+// HIST (multistep runs, foley_set_multistep): a.hist is a ring of a.hist_slots (1 or 2) slots [clips, C, L] of earlier velocities.
+// On a row flagged STEP_HIST the derivative continues  deriv = fma(c1, h1, deriv), deriv = fma(c2, h2, deriv)  with h_j the slot
+// (it - j) mod slots; a term whose weight is 0.0f is not read, so warm-up rows do not depend on what the ring holds and a row with
+// both weights zero is the plain row bit for bit.  Every row then stores v - the guided value exactly as this step used it - to
+// slot it mod slots, after the reads: with two slots v_{n-2} sits in the slot being written.  One thread owns the element in all
+// three forms, so the order inside the thread is the only ordering there is.
+template <bool HIST = false>
+__device__ __forceinline__ float step_update(const StepArgs& a, const StepCoef& k, int it, long xi, float v, float& acc_new) {
 #pragma clang fp contract(off)
   const float xc = a.x[xi];
   float acc = 0.f;
   if (a.d_acc) acc = (k.flags & STEP_ACC_RESET) ? 0.f : a.d_acc[xi];
   const float t = k.w_new * v;
-  const float deriv = (k.w_acc != 0.f) ? __builtin_fmaf(k.w_acc, acc, t) : t;
+  float deriv = (k.w_acc != 0.f) ? __builtin_fmaf(k.w_acc, acc, t) : t;
+  if (HIST) {
+    const long n = (long)a.clips * a.C * a.L;
+    const int slots = a.hist_slots;
+    if (k.flags & STEP_HIST) {
+      if (k.c1 != 0.f) deriv = __builtin_fmaf(k.c1, a.hist[(long)((it + 2 * slots - 1) % slots) * n + xi], deriv);
+      if (k.c2 != 0.f) deriv = __builtin_fmaf(k.c2, a.hist[(long)((it + 2 * slots - 2) % slots) * n + xi], deriv);
+    }
+    a.hist[(long)(it % slots) * n + xi] = v;
+  }
   const float base = (k.flags & STEP_USE_SAVED) ? a.x_saved[xi] : xc;
   if (k.flags & STEP_SAVE_X) a.x_saved[xi] = xc;
   acc_new = __builtin_fmaf(k.w_store, v, acc);
@@ -549,11 +569,11 @@ __device__ __forceinline__ float edit_blend(float xn, float m, float s, float no
   return m * xn + (1.f - m) * tgt;
 }
 
-template <typename OutT, bool EDIT>
-__global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
+template <typename OutT, bool EDIT, bool HIST>
+__device__ __forceinline__ void solver_step_body(const StepArgs& a) {
   __shared__ float tile[32][33];
   const int it = *a.step_ptr;
-  const StepCoef k = step_coef(a, it);
+  const StepCoef k = step_coef<HIST>(a, it);
   const int b = blockIdx.z;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -568,7 +588,7 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
     if (c < a.C && l < a.L) {
       const long xi = ((long)b * a.C + c) * a.L + l;
       float acc_new;
-      xn = step_update(a, k, xi, tile[tx][i], acc_new);
+      xn = step_update<HIST>(a, k, it, xi, tile[tx][i], acc_new);
       if (EDIT && (k.flags & STEP_BLEND)) xn = edit_blend(xn, mb ? mb[l] : 1.f, k.s_next, a.noise[xi], x0b[(long)c * a.L + l]);
       a.x[xi] = xn;
       if (a.d_acc) a.d_acc[xi] = acc_new;
@@ -578,6 +598,12 @@ __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) {
   __syncthreads();
   step_stage_rows<OutT>(tile, a, b, l0, c0);
 }
+
+// History is a template parameter: the kernels without it are the code they were, the multistep ones have names of their own.
+template <typename OutT, bool EDIT>
+__global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, false>(a); }
+template <typename OutT, bool EDIT>
+__global__ __launch_bounds__(256) void solver_step_hist_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, true>(a); }
 
 // Windows form (long clips): the clips of one variation are overlapping windows of ONE long clip - clip v*n_win + k covers the
 // global frames [starts[k], starts[k] + L) of variation v - and the step is indexed by GLOBAL frame: a thread owns (g, c) and
@@ -593,11 +619,11 @@ __device__ __forceinline__ float windows_accumulate(bool first, float wk, float 
   return first ? wk * xn : __builtin_fmaf(wk, xn, xb);
 }
 
-template <typename OutT>
-__global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepArgs a) {
+template <typename OutT, bool HIST>
+__device__ __forceinline__ void solver_step_windows_body(const StepArgs& a) {
   __shared__ float tile[32][33];
   const int it = *a.step_ptr;
-  const StepCoef kf = step_coef(a, it);
+  const StepCoef kf = step_coef<HIST>(a, it);
   const bool blend = (kf.flags & STEP_BLEND) != 0;
   const int b0 = blockIdx.z * a.n_win;
   const int g0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
@@ -622,7 +648,7 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepArgs
       if (c < a.C && in) {
         const long xi = ((long)b * a.C + c) * a.L + l;
         float acc_new;
-        xn = step_update(a, kf, xi, tile[tx][i], acc_new);
+        xn = step_update<HIST>(a, kf, it, xi, tile[tx][i], acc_new);
         if (blend) xb[j] = windows_accumulate(ncov == 0, wk, xn, xb[j]);
         else a.x[xi] = xn;
         if (a.d_acc) a.d_acc[xi] = acc_new;
@@ -657,6 +683,11 @@ __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepArgs
     step_stage_rows<OutT>(tile, a, b, g0 - s0, c0);
   }
 }
+
+template <typename OutT>
+__global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepArgs a) { solver_step_windows_body<OutT, false>(a); }
+template <typename OutT>
+__global__ __launch_bounds__(256) void solver_step_windows_hist_kernel(const StepArgs a) { solver_step_windows_body<OutT, true>(a); }
 
 // Stitch the windows of every variation into one long clip: G[v][c][g] = sum_k weights[k][g - starts[k]] * x[v*n_win + k][c][g - starts[k]]
 // over the covering windows, in window order.  Where the covering windows hold the identical bits (after a blend row: under euler
@@ -1223,6 +1254,12 @@ template <typename OutT>
 static void launch_step_form(const StepArgs& a, hipStream_t st) {
   const bool win = a.form == STEP_FORM_WINDOWS;
   const dim3 grid(((win ? a.Ltot : a.L) + 31) / 32, (a.C + 31) / 32, win ? a.clips / a.n_win : a.clips), block(256);
+  if (a.hist) {   // a multistep run: the history instantiation of the same form
+    if (win) FOLEY_LAUNCH(solver_step_windows_hist_kernel<OutT>, grid, block, 0, st, a);
+    else if (a.form == STEP_FORM_EDIT) FOLEY_LAUNCH((solver_step_hist_kernel<OutT, true>), grid, block, 0, st, a);
+    else FOLEY_LAUNCH((solver_step_hist_kernel<OutT, false>), grid, block, 0, st, a);
+    return;
+  }
   if (win) FOLEY_LAUNCH(solver_step_windows_kernel<OutT>, grid, block, 0, st, a);
   else if (a.form == STEP_FORM_EDIT) FOLEY_LAUNCH((solver_step_kernel<OutT, true>), grid, block, 0, st, a);
   else FOLEY_LAUNCH((solver_step_kernel<OutT, false>), grid, block, 0, st, a);
@@ -1237,6 +1274,8 @@ int launch_solver_step(const StepArgs& a, hipStream_t st) {
     if (!windows_args_ok(a.clips, a.n_win, a.L, a.Ltot, a.starts, a.weights))
       return foley_set_err("solver_step_windows: clips must be a multiple of n_win, La <= Ltot <= n_win*La, tables required", __FILE__, __LINE__);
   }
+  if ((a.hist || a.hist_slots) && (!a.hist || a.hist_slots < 1 || a.hist_slots > 2))
+    return foley_set_err("solver_step: a history ring needs its buffer and 1 or 2 slots", __FILE__, __LINE__);
   if (a.rows_dtype == FOLEY_BF16) launch_step_form<bf16_t>(a, st);
   else if (a.rows_dtype == FOLEY_F16) launch_step_form<f16_t>(a, st);
   else launch_step_form<float>(a, st);

@@ -8,6 +8,8 @@ The flow-match path is x(sigma) = sigma*noise + (1 - sigma)*x0 with sigma runnin
     sigma_{k0}*noise + (1 - sigma_{k0})*x0 (foley_op_flow_mix);
   * after every iteration that ends a solver step, pulls the frames the mask keeps (m = 0) back onto the source's
     forward-noised path: x <- m*x + (1 - m)*(sigma_{k+1}*noise + (1 - sigma_{k+1})*x0) (foley_set_edit, rowops.hip).
+With a multistep order (sampler.MultistepSpec) the suffix has no velocity history at i0: its Adams-Bashforth rows warm up from
+there (tables.edit_solver_table(..., multistep_order=)), and the ring keeps the velocities, not the blended samples.
 Under euler the last sigma is 0, so kept frames end at exactly x0; the multi-stage solvers end where the plain run ends
 (sigma > 0 for them: every loop iteration is one solver stage, the reference's quirk that SolverState reproduces).
 """

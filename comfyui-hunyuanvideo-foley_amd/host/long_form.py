@@ -3,7 +3,8 @@
 A long clip of Ltot latent frames is covered by n_win windows of La frames each, window k over the global frames
 [starts[k], starts[k] + La).  Every window is one clip of the sampler's batch - its own slice of the video, RoPE positions 0..La -
 and after every solver step the frames several windows cover are replaced in all of them by one weighted mean
-(foley_set_windows), so the windows agree on their overlaps and the stitched latent decodes to one waveform.
+(foley_set_windows), so the windows agree on their overlaps and the stitched latent decodes to one waveform.  Under a multistep
+order (sampler.MultistepSpec) every window keeps the history of its own velocities; only the samples are blended.
 
 Clip index of the batch: v * n_win + k for variation v (the node's batch_size) and window k.
 """

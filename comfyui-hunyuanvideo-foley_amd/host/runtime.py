@@ -102,6 +102,14 @@ class GuidanceDescC(C.Structure):
     _fields_ = [("sched", C.c_void_p), ("clip_scale", C.c_void_p)]
 
 
+class StepHistDescC(C.Structure):
+    """foley_step_hist_desc: the velocity ring [hist_slots, clips, C, L] and the optional operands of foley_op_solver_step_hist
+    (a guidance descriptor; x0 / noise / mask of the edit form; starts / weights of the windows form) - 0: absent."""
+    _fields_ = [("hist", C.c_void_p), ("hist_slots", C.c_int32), ("guidance", C.POINTER(GuidanceDescC)),
+                ("x0", C.c_void_p), ("x0_clips", C.c_int32), ("noise", C.c_void_p), ("mask", C.c_void_p), ("mask_clips", C.c_int32),
+                ("n_win", C.c_int32), ("starts", C.c_void_p), ("weights", C.c_void_p), ("Ltot", C.c_int32)]
+
+
 class ProfEntryC(C.Structure):
     _fields_ = [("label", C.c_char * 80), ("calls", C.c_int32), ("total_ms", C.c_float), ("flop", C.c_double),
                 ("bytes", C.c_double), ("kernel", C.c_char * 200)]
@@ -137,6 +145,7 @@ _SIGNATURES = {
     "foley_set_step_cache": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int,
                                        C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "foley_step_cache_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int]),
+    "foley_set_multistep": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "foley_dac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "foley_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                    C.c_void_p, C.c_void_p]),
@@ -186,6 +195,8 @@ _SIGNATURES = {
         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_op_solver_step_windows_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "foley_op_solver_step_hist": (C.c_int, [C.POINTER(StepHistDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
+        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_op_guidance_stats_work": (C.c_int64, [C.c_int, C.c_int]),
     "foley_op_guidance_stats": (C.c_int, [C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -533,6 +544,12 @@ class FoleyContext:
             _check(self.lib, self.lib.foley_set_step_cache(self._h, int(mode), arr, len(skip) if skip is not None else 0, float(threshold),
                                                            pol, len(poly) if poly else 0, itv, int(max_consecutive or 0), _stream()),
                    "foley_set_step_cache")
+
+    def set_multistep(self, order: int = 0):
+        """foley_set_multistep after prepare(): order 2 or 3 switches the step to its history kernel (the plan's solver_coef rows
+        carry the Adams-Bashforth weights, tables.solver_table(multistep_order=)); 0 or 1 clears the state."""
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_set_multistep(self._h, int(order), _stream()), "foley_set_multistep")
 
     def step_cache_report(self):
         """(rel, skipped) of the last sample() under the step cache: per iteration the measured change (-1.0: not measured -
@@ -1052,6 +1069,31 @@ def op_solver_step_guided(gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, ste
     form = "_edit" if edit is not None else "_windows" if windows is not None else ""
     _step_call(f"foley_op_solver_step{form}_guided", gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
                edit=edit, windows=windows)
+
+
+def op_solver_step_hist(hist, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, gd=None, edit=None, windows=None,
+                        slots: Optional[int] = None):
+    """foley_op_solver_step_hist: the step forms with a velocity ring hist [slots, clips, C, L] fp32 (slots 1 or 2, taken from
+    the tensor unless given); gd a guidance descriptor or None, edit=(x0, noise, mask) or windows=(starts, weights, Ltot)."""
+    lib = load_library()
+    clips, Cc, L = x.shape
+    if hist is not None and (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 4
+                             or tuple(hist.shape[1:]) != (clips, Cc, L)):
+        raise FoleyRuntimeError("op_solver_step_hist: hist is a contiguous fp32 tensor [slots, clips, C, L]")
+    hd = StepHistDescC()
+    hd.hist = _ptr(hist)
+    hd.hist_slots = int(slots) if slots is not None else (int(hist.shape[0]) if hist is not None else 0)
+    hd.guidance = C.pointer(gd) if gd is not None else None
+    if edit is not None:
+        x0, noise, mask = edit
+        hd.x0, hd.x0_clips, hd.noise, hd.mask = _ptr(x0), int(x0.shape[0]), _ptr(noise), _ptr(mask)
+        hd.mask_clips = (1 if mask.dim() == 1 else int(mask.shape[0])) if mask is not None else 0
+    if windows is not None:
+        starts, weights, Ltot = windows
+        hd.n_win, hd.starts, hd.weights, hd.Ltot = _windows_tables(x, starts, weights), _ptr(starts), _ptr(weights), int(Ltot)
+    _check(lib, lib.foley_op_solver_step_hist(C.byref(hd), _ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
+                                              float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
+                                              _stream()), "foley_op_solver_step_hist")
 
 
 def op_guidance_stats(pred, clips, L, ncfg, guidance, sched, step_ptr, rescale, out: Optional[torch.Tensor] = None) -> torch.Tensor:

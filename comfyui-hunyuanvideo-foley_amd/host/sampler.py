@@ -165,6 +165,34 @@ class GuidanceSpec:
             raise ValueError("a guidance interval / rescale needs guidance: guidance_scale > 1 or a video scale (g_video)")
 
 
+@dataclass(frozen=True)
+class MultistepSpec:
+    """A linear multistep solver on top of `euler`: variable-step Adams-Bashforth of `order` 2 or 3 at one model call per sigma
+    step (tables.solver_table(multistep_order=), foley_set_multistep).  The first step of a run is Euler's and the second step of
+    an order-3 run is order 2, so order 3 is a third-order local formula behind a first-order first step: globally second order,
+    with a smaller constant.  It does not combine with the multi-stage solvers."""
+    order: int = 2
+
+    def check(self, sampler: str) -> None:
+        o = self.order
+        if isinstance(o, bool) or not isinstance(o, (int, float)) or int(o) != o or int(o) not in tables.MULTISTEP_ORDERS:
+            raise ValueError(f"multistep order must be one of {list(tables.MULTISTEP_ORDERS)}, got {o!r}")
+        if sampler != "euler":
+            raise ValueError(f"a multistep order needs the euler solver (one model call per sigma step), got {sampler!r}: "
+                             "heun-2, midpoint-2 and kutta-4 do not combine with it")
+
+
+def apply_multistep(ctx: FoleyContext, plan: dict) -> None:
+    """foley_set_multistep with what build_plan put into the plan (after prepare, next to the other apply_* calls)."""
+    if plan.get("multistep_order"):
+        ctx.set_multistep(int(plan["multistep_order"]))
+
+
+def _ms_kw(multistep) -> dict:
+    """The multistep keyword for a callee, only when it is set: an unset one adds nothing to the call."""
+    return {} if multistep is None else {"multistep": multistep}
+
+
 def apply_guidance(ctx: FoleyContext, plan: dict) -> None:
     """foley_set_guidance with what build_plan put into the plan (after prepare, next to set_edit / set_windows)."""
     if plan.get("guid_sched") is not None or plan.get("guid_rescale", 0.0) > 0.0:
@@ -189,7 +217,8 @@ def keep_step_cache_report(ctx: FoleyContext, plan: dict) -> None:
 def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_feats: Dict[str, torch.Tensor],
                La: int, guidance_scale: float, steps: int, batch_size: int, sampler: str,
                edit_i0: Optional[int] = None, guidance: Optional[GuidanceSpec] = None,
-               step_cache: Optional[StepCacheSpec] = None, timeline=None, timeline_starts=None) -> dict:
+               step_cache: Optional[StepCacheSpec] = None, timeline=None, timeline_starts=None,
+               multistep: Optional[MultistepSpec] = None) -> dict:
     """Conditioning replication / padding / CFG stacking of utils.py:159-199 + the run's tables.
     edit_i0 (edit runs, host/audio_edit.py): the tables of the suffix [edit_i0, steps) with the blend rows.
     Each conditioning tensor has batch 1 (shared by all clips) or batch_size (one row per clip, host/cond_sets.py): the plan
@@ -201,8 +230,12 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     timeline (host/prompt_timeline.Timeline): text_feats["text_feat"] holds one row per distinct prompt of the timeline, in its
     order, and the visual features are shared (batch 1); the plan then carries the text sets [negative ; prompts...] and the
     per-token table `timeline` that prepare hands to foley_prepare_timeline.  timeline_starts: the latent-frame starts of a
-    windowed run - clip v*n_win + k reads the timeline shifted by starts[k].  None is today's path, bit for bit."""
+    windowed run - clip v*n_win + k reads the timeline shifted by starts[k].  None is today's path, bit for bit.
+    multistep (MultistepSpec): Adams-Bashforth rows in solver_coef (an edit run's warm-up begins at edit_i0) and the order that
+    apply_multistep hands to the library after prepare (`multistep_order`)."""
     cfg, dev = model.cfg, model.device
+    if multistep is not None:
+        multistep.check(sampler)
     if step_cache is not None:
         step_cache.check(int(steps))
     if guidance is not None:
@@ -264,12 +297,14 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     # The run's tables (schedule, solver coefficients, RoPE rows, position / up-sampling maps) depend on these scalars
     # only: built once per distinct run shape and kept on the device (host-side table building is milliseconds of
     # Python per call - more than the whole precompute on the GPU)
-    key = (La, Lv, Ls, Lt, steps, sampler, float(cfg.flow_shift), cfg.time_freq_dim, str(fp8_time), str(dev), edit_i0)
+    ms_order = int(multistep.order) if multistep is not None else None
+    key = (La, Lv, Ls, Lt, steps, sampler, ms_order, float(cfg.flow_shift), cfg.time_freq_dim, str(fp8_time), str(dev), edit_i0)
     cache = model.__dict__.setdefault("_tables_cache", {})
     tabs = cache.get(key)
     if tabs is None:
+        ms = {} if ms_order is None else {"multistep_order": ms_order, "start": edit_i0 or 0}
         tb = tables.build_tables(La, Lv, Ls, Lt, steps, sampler, cfg.flow_shift, cfg.time_freq_dim, fp8_time=fp8_time,
-                                 edit_i0=edit_i0)
+                                 edit_i0=edit_i0, **ms)
         tabs = {k: tb[k].to(dev).contiguous() for k in ("t_feat", "rope_cos", "rope_sin", "pos_audio_self", "pos_visual_self",
                                                         "pos_linear", "sync_gather", "solver_coef")}
         if len(cache) >= 16:
@@ -295,6 +330,8 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
         plan["guid_sched"] = sched[edit_i0 or 0:].contiguous()
     if guidance is not None:
         plan["guid_rescale"] = float(guidance.rescale)
+    if ms_order is not None:
+        plan["multistep_order"] = ms_order
     if step_cache is not None:
         i0 = edit_i0 or 0
         if step_cache.mode == _sc.MODE_SCHEDULE:
@@ -313,7 +350,7 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
                                    return_latents: bool = False, noise: Optional[torch.Tensor] = None,
                                    _abort_event: Optional[threading.Event] = None, edit=None, windows=None,
                                    guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None,
-                                   timeline=None):
+                                   timeline=None, multistep: Optional[MultistepSpec] = None):
     """Same contract as the reference function of this name (utils.py:125-258):
     returns (audio [bs, 1, T] fp32 on the model's device, sample_rate).
 
@@ -334,13 +371,19 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     timeline (host/prompt_timeline.Timeline): timed prompts - text_feats["text_feat"] holds one row per distinct prompt of the
     timeline and every token of the cross-attention reads the text set(s) of its own time (build_plan).  It combines with `edit`,
     `windows` (the timeline is given in the long clip's time), guidance and the step cache; the visual features are shared
-    (batch 1).  None is the plain run, bit for bit."""
+    (batch 1).  None is the plain run, bit for bit.
+
+    multistep (MultistepSpec): Adams-Bashforth order 2 or 3 on the `euler` schedule, one model call per step; it combines with
+    `edit` (the warm-up begins where the edit run does), `windows`, guidance, the step cache and a timeline.  None is the plain
+    run, bit for bit, with its single captured graph."""
+    if multistep is not None:
+        multistep.check(sampler)
     if windows is not None and windows.n_win > 1:
         if edit is not None:
             raise ValueError("windows= and edit= together: editing a long clip is not supported")
         return _denoise_windows(visual_feats, text_feats, model, dac, guidance_scale, num_inference_steps, batch_size, sampler,
                                 windows, generator, use_graph, progress, return_latents, noise, _abort_event, guidance, step_cache,
-                                timeline)
+                                timeline, **_ms_kw(multistep))
     cfg = model.cfg
     La = int(audio_len_in_s * cfg.frame_rate)
     if noise is None:
@@ -348,20 +391,22 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     latents = noise.to(device=model.device, dtype=torch.float32).contiguous()
     if edit is None:
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          guidance=guidance, step_cache=step_cache, timeline=timeline)
+                          guidance=guidance, step_cache=step_cache, timeline=timeline, **_ms_kw(multistep))
         model.attach_dac(dac)
         model.ctx.prepare(plan)
         apply_guidance(model.ctx, plan)
         apply_step_cache(model.ctx, plan)
+        apply_multistep(model.ctx, plan)
     else:
         k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
         x0, mask = edit.device_operands(model.device, batch_size, La)
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
-                          edit_i0=i0, guidance=guidance, step_cache=step_cache, timeline=timeline)
+                          edit_i0=i0, guidance=guidance, step_cache=step_cache, timeline=timeline, **_ms_kw(multistep))
         model.attach_dac(dac)
         model.ctx.prepare(plan)
         apply_guidance(model.ctx, plan)
         apply_step_cache(model.ctx, plan)
+        apply_multistep(model.ctx, plan)
         model.ctx.set_edit(x0, latents, mask)
         sigma0 = float(tables.sigma_grid(num_inference_steps, cfg.flow_shift)[k0])
         latents = runtime.op_flow_mix(latents, x0, sigma0)
@@ -390,7 +435,7 @@ def window_rows(t: torch.Tensor, variations: int, n_win: int, what: str) -> torc
 
 def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC, guidance_scale, num_inference_steps,
                      variations, sampler, windows, generator, use_graph, progress, return_latents, noise, _abort_event,
-                     guidance=None, step_cache=None, timeline=None):
+                     guidance=None, step_cache=None, timeline=None, multistep=None):
     """One long clip per variation as a batch of variations*n_win coupled windows (clip v*n_win + k = window k of variation v).
     The noise is drawn ONCE as [variations, C, Ltot] - draw_noise, the same generator and dtype rule as a plain run - and every
     window takes its slice, so overlapping frames start equal.  The plan carries the blend rows (edit_i0 = 0 tables); after every
@@ -398,7 +443,8 @@ def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC,
     the windows are stitched and decoded in ONE dac_decode of [variations, C, Ltot]; return_latents gives the stitched latents.
     The length of the run is the plan's (Ltot), not audio_len_in_s.  denoise_process_multi does not shard such a run: the windows
     of a variation are coupled.  timeline: given in the long clip's time; window k's rows are the timeline shifted by starts[k]
-    latent frames, which lifts the "one prompt for all windows" limit - the visual features are then one shared row."""
+    latent frames, which lifts the "one prompt for all windows" limit - the visual features are then one shared row.
+    multistep: every window keeps the history of its own velocities; the blend leaves them as the step used them."""
     cfg = model.cfg
     n_win, La, Ltot = windows.n_win, windows.La, windows.Ltot
     windows.check_extent(variations)
@@ -417,11 +463,13 @@ def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC,
     noise = noise.to(device=model.device, dtype=torch.float32)
     latents = torch.stack([noise[v, :, s:s + La] for v in range(variations) for s in windows.starts]).contiguous()
     plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0, guidance=guidance,
-                      step_cache=step_cache, timeline=timeline, timeline_starts=windows.starts if timeline is not None else None)
+                      step_cache=step_cache, timeline=timeline, timeline_starts=windows.starts if timeline is not None else None,
+                      **_ms_kw(multistep))
     model.attach_dac(dac)
     model.ctx.prepare(plan)
     apply_guidance(model.ctx, plan)
     apply_step_cache(model.ctx, plan)
+    apply_multistep(model.ctx, plan)
     weights = windows.weights.to(model.device)
     model.ctx.set_windows(windows.starts, weights)
     if _abort_event is not None and _abort_event.is_set():
@@ -518,7 +566,8 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                           num_inference_steps: int, batch_size: int, sampler: str,
                           generator: Optional[torch.Generator] = None, use_graph: bool = True,
                           progress: Optional[Callable[[int, int], None]] = None, return_latents: bool = False, edit=None,
-                          guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None, timeline=None):
+                          guidance: Optional[GuidanceSpec] = None, step_cache: Optional[StepCacheSpec] = None, timeline=None,
+                          multistep: Optional[MultistepSpec] = None):
     """`denoise_process_with_generator` with the clips of the batch sharded over `replicas` (the pairs
     `replicate()` returns), one host thread per GPU.  Clips are independent (reference utils.py:159-199 batches clips that
     share their conditioning; per-clip conditioning, host/cond_sets.py, only changes what each clip reads), so there is no
@@ -535,8 +584,10 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     are coupled after every step, so it runs on one device.  `step_cache` is forwarded to every shard: a skip list gives what one GPU
     gives; in threshold mode every shard decides from the rows it holds (the max over them), so the decisions - and with them the
     clips - depend on the sharding.  `timeline` (one for the whole batch) is forwarded with the prompts' text rows, unsliced: every
-    shard builds the table rows of its own clips.  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
+    shard builds the table rows of its own clips.  `multistep` is forwarded to every shard (each keeps the history of its own clips).  Returns (audio [bs, 1, T] fp32 on the first replica's device, sr)."""
     from .distributed import shard_range
+    if multistep is not None:
+        multistep.check(sampler)
     if not replicas:
         raise FoleyRuntimeError("no replicas")
     m0 = replicas[0][0]
@@ -586,7 +637,7 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
                     sampler, use_graph=use_graph, noise=noise[lo:hi], return_latents=True,
                     progress=progress if r == 0 else None, _abort_event=failed,
                     edit=edit.shard(lo, hi, batch_size) if edit is not None else None, guidance=guidance,
-                    step_cache=step_cache, timeline=timeline)
+                    step_cache=step_cache, timeline=timeline, **_ms_kw(multistep))
                 torch.cuda.current_stream().synchronize()
         except Exception as e:          # surfaced on the calling thread
             running[r] = False          # FIRST: a second failing (or aborted) worker must not keep the first one waiting on it

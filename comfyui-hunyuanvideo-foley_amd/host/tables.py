@@ -19,7 +19,9 @@ import torch
 SOLVERS = ("euler", "heun-2", "midpoint-2", "kutta-4")
 STEP_SAVE_X, STEP_USE_SAVED, STEP_ACC_RESET = 1, 2, 4
 STEP_BLEND = 8          # edit runs only (foley_set_edit): blend towards the source after this row, sigma_{k+1} in column 5
+STEP_HIST = 16          # multistep runs only (foley_set_multistep): the row adds history terms, weights in columns 6 and 7
 SOLVER_STAGES = {"euler": 1, "heun-2": 2, "midpoint-2": 2, "kutta-4": 4}
+MULTISTEP_ORDERS = (2, 3)
 
 
 def sigma_grid(steps: int, shift: float = 1.0) -> torch.Tensor:
@@ -33,16 +35,51 @@ def model_timesteps(sigmas: torch.Tensor) -> torch.Tensor:
     return (sigmas[:-1] * 1000).to(torch.float32)
 
 
-def solver_table(sigmas: torch.Tensor, solver: str, n_iter: int) -> torch.Tensor:
-    """[n_iter, 8] rows {w_new, w_acc, dt, w_store, flags, 0, 0, 0}.
+def multistep_weights(sigmas: torch.Tensor, n: int, order: int):
+    """Variable-step Adams-Bashforth weights (c_0, c_1, c_2) of the step sigma_n -> sigma_{n+1} for the velocities v_n, v_{n-1},
+    v_{n-2}: the integrals over [sigma_n, sigma_{n+1}] of the Lagrange basis polynomials on the nodes sigma_n, sigma_{n-1}
+    (, sigma_{n-2}), divided by dt = sigma_{n+1} - sigma_n.  fp64 from the fp32 grid's values; the caller rounds to fp32 once.
+    Order 1 is Euler, (1, 0, 0)."""
+    if order <= 1:
+        return 1.0, 0.0, 0.0
+    s = [float(sigmas[n - j].double()) for j in range(order)]
+    h = float(sigmas[n + 1].double()) - s[0]
+    if order == 2:                                  # closed form: r = dt / (sigma_n - sigma_{n-1})
+        r = h / (s[0] - s[1])
+        return 1.0 + r / 2, -r / 2, 0.0
+    a = [t - s[0] for t in s]                       # nodes relative to sigma_n (a[0] = 0); u runs over [0, h]
+    out = []
+    for j in range(3):
+        p, q = (a[k] for k in range(3) if k != j)   # basis j = (u - p)(u - q) / ((a_j - p)(a_j - q))
+        out.append((h * h / 3 - (p + q) * h / 2 + p * q) / ((a[j] - p) * (a[j] - q)))
+    return tuple(out)
+
+
+def solver_table(sigmas: torch.Tensor, solver: str, n_iter: int, multistep_order: Optional[int] = None,
+                 start: int = 0) -> torch.Tensor:
+    """[n_iter, 8] rows {w_new, w_acc, dt, w_store, flags, 0, c_1, c_2}.
 
     Per iteration the device computes  deriv = w_new*v + w_acc*acc ; x' = base + deriv*dt ;
     acc' = (reset ? 0 : acc) + w_store*v, with base = saved sample or current sample.
     Like the reference, every loop iteration is one solver *stage* and the sigma index only
     advances after the last stage of a step.
+
+    multistep_order (2 or 3, euler only): Adams-Bashforth rows - c_0 in column 0, c_1 and c_2 (the weights of v_{n-1} and v_{n-2},
+    multistep_weights) in columns 6 and 7, STEP_HIST on every row with a non-zero history weight; the device continues
+    deriv = fma(c_1, v_{n-1}, deriv), fma(c_2, v_{n-2}, deriv).  Warm-up takes the order the history allows: row `start` (where a
+    run that takes the suffix [start:] begins, without history) is the Euler row, the row after it carries the order-2 weights.
+    Rows before `start` are those of a run from row 0.  None gives the one-step tables, value for value.
     """
     if solver not in SOLVERS:
         raise ValueError(f"Solver {solver} not supported. Supported solvers: {list(SOLVERS)}")
+    if multistep_order is not None:
+        if solver != "euler":
+            raise ValueError(f"multistep_order needs the euler solver (one model call per sigma step), got {solver}: the "
+                             "multi-stage solvers do not combine with a velocity history")
+        if multistep_order not in MULTISTEP_ORDERS or isinstance(multistep_order, bool) or int(multistep_order) != multistep_order:
+            raise ValueError(f"multistep_order must be one of {list(MULTISTEP_ORDERS)}, got {multistep_order}")
+        if not 0 <= int(start) <= n_iter:
+            raise ValueError(f"start must lie in [0, n_iter], got {start}")
     rows = torch.zeros(n_iter, 8, dtype=torch.float32)
     idx, stage, dt = 0, 0, None
     for i in range(n_iter):
@@ -50,6 +87,12 @@ def solver_table(sigmas: torch.Tensor, solver: str, n_iter: int) -> torch.Tensor
             dt = sigmas[idx + 1] - sigmas[idx]          # fp32, like the reference
         if solver == "euler":
             rows[i, :5] = torch.tensor([1.0, 0.0, float(dt), 0.0, 0.0])
+            if multistep_order is not None:
+                have = i - (int(start) if i >= int(start) else 0)      # velocities of this run before row i
+                c = torch.tensor(multistep_weights(sigmas, idx, min(int(multistep_order), have + 1)), dtype=torch.float64).float()
+                rows[i, 0], rows[i, 6], rows[i, 7] = c[0], c[1], c[2]
+                if c[1] != 0 or c[2] != 0:
+                    rows[i, 4] = float(STEP_HIST)
             idx += 1
             continue
         if solver in ("heun-2", "midpoint-2"):
@@ -117,9 +160,11 @@ def edit_start(steps: int, solver: str, strength: float):
     return k0, k0 * stages
 
 
-def edit_solver_table(sigmas: torch.Tensor, solver: str, n_iter: int, i0: int = 0) -> torch.Tensor:
-    """Rows [i0:] of solver_table with STEP_BLEND and sigma_{k+1} (column 5) on every iteration that ends a solver step."""
-    rows = solver_table(sigmas, solver, n_iter).clone()
+def edit_solver_table(sigmas: torch.Tensor, solver: str, n_iter: int, i0: int = 0, multistep_order: Optional[int] = None) -> torch.Tensor:
+    """Rows [i0:] of solver_table with STEP_BLEND and sigma_{k+1} (column 5) on every iteration that ends a solver step.
+    multistep_order: the suffix has no history at i0, so the warm-up of its Adams-Bashforth rows begins there (start=i0)."""
+    ms = {} if multistep_order is None else {"multistep_order": multistep_order, "start": i0}
+    rows = solver_table(sigmas, solver, n_iter, **ms).clone()
     stages = SOLVER_STAGES[solver]
     for i in range(stages - 1, n_iter, stages):
         k = i // stages
@@ -165,10 +210,11 @@ def interleaved_positions(la: int, lv: int):
 
 def build_tables(la: int, lv: int, ls: int, lt: int, steps: int, solver: str, shift: float,
                  time_freq_dim: int = 256, fp8_time: Optional[torch.dtype] = None,
-                 edit_i0: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                 edit_i0: Optional[int] = None, multistep_order: Optional[int] = None, start: int = 0) -> Dict[str, torch.Tensor]:
     """fp8_time: round the sinusoid timestep features through this fp8 type (fp8-wrapped model under
     autocast, embed_layers.py:134 - golden g8).  edit_i0 (edit runs): the per-iteration tables are the rows [edit_i0:] of the
-    plain run's, the solver rows carry the blend (edit_solver_table)."""
+    plain run's, the solver rows carry the blend (edit_solver_table).  multistep_order / start: Adams-Bashforth rows
+    (solver_table); an edit run's warm-up begins at edit_i0."""
     sig = sigma_grid(steps, shift)
     ts = model_timesteps(sig)
     n_iter = steps
@@ -180,7 +226,7 @@ def build_tables(la: int, lv: int, ls: int, lt: int, steps: int, solver: str, sh
         "timesteps": ts,
         "t_feat": (timestep_features(ts, time_freq_dim) if fp8_time is None
                    else timestep_features(ts, time_freq_dim).to(fp8_time).to(torch.float32)).contiguous(),
-        "solver_coef": solver_table(sig, solver, n_iter),
+        "solver_coef": solver_table(sig, solver, n_iter, multistep_order=multistep_order, start=start),
         "rope_cos": cos, "rope_sin": sin,
         "pos_audio_self": pa.to(torch.int32), "pos_visual_self": pv.to(torch.int32),
         "pos_linear": torch.arange(max(la, lv, lt), dtype=torch.int32),
@@ -188,5 +234,5 @@ def build_tables(la: int, lv: int, ls: int, lt: int, steps: int, solver: str, sh
     }
     if edit_i0 is not None:
         out["t_feat"] = out["t_feat"][edit_i0:].contiguous()
-        out["solver_coef"] = edit_solver_table(sig, solver, n_iter, edit_i0)
+        out["solver_coef"] = edit_solver_table(sig, solver, n_iter, edit_i0, multistep_order=multistep_order)
     return out

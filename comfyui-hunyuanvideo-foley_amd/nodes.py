@@ -339,7 +339,7 @@ class HunyuanFoleySampler:
                        prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0,
                        video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0, cache_threshold=None, cache_skip=None,
                        cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25,
-                       loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False):
+                       loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False, multistep_order=None):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -389,8 +389,18 @@ class HunyuanFoleySampler:
         on its own, to that integrated loudness (ITU-R BS.1770-4; about -16 for the web, -23 for EBU R128) on the device before
         the waveform leaves it.  `true_peak_dbtp` is the true-peak ceiling: without `peak_limiter` the gain is lowered where the
         peak would pass it; with it the full gain is applied and a 5 ms look-ahead limiter holds the peaks under the ceiling.
-        A silent clip is returned as it is.  It combines with every other option."""
+        A silent clip is returned as it is.  It combines with every other option.
+
+        Multistep solver (keyword-only, not a socket; host/sampler.py::MultistepSpec): `multistep_order` 2 or 3 (None: off) with
+        the `euler` solver - Adams-Bashforth on the run's sigma grid, which reuses the velocities of the one or two steps before
+        and so reaches second order at Euler's price of one model call per step.  Order 3 is a third-order formula behind a
+        first-order first step: second order overall, with a smaller constant.  It combines with every other option and does not
+        combine with heun-2 / midpoint-2 / kutta-4."""
         model, deps = hunyuan_model, hunyuan_deps
+        ms_kw = {}
+        if multistep_order is not None:            # refused here, before the encoders run
+            _sampler.MultistepSpec(multistep_order).check(sampler)
+            ms_kw = {"multistep": _sampler.MultistepSpec(int(multistep_order))}   # unset: the calls as they were
         if loudness_lufs is not None:              # refused here, before the encoders run
             from .host import loudness as _loud
             _loud.check_args(loudness_lufs, true_peak_dbtp, peak_limiter)
@@ -493,7 +503,7 @@ class HunyuanFoleySampler:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                windows=windows, guidance=guidance, step_cache=step_cache, **tl_kw)
+                windows=windows, guidance=guidance, step_cache=step_cache, **tl_kw, **ms_kw)
         elif batch_size > 1 and n_dev > 1 and model.arena is not None:
             # clips are independent: shard them over the node's GPUs (host/sampler.py::denoise_process_multi; the widget
             # list is the reference's, so the switch is an environment variable - INTEGRATION.md)
@@ -502,12 +512,12 @@ class HunyuanFoleySampler:
             ran_on = [m for m, _ in reps]
             audio, sr = _sampler.denoise_process_multi(visual, text, audio_len_in_s, reps, cfg_scale, steps, batch_size,
                                                        sampler, generator=rng, progress=progress, edit=edit, guidance=guidance,
-                                                       step_cache=step_cache, **tl_kw)
+                                                       step_cache=step_cache, **tl_kw, **ms_kw)
         else:
             audio, sr = _sampler.denoise_process_with_generator(
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
-                edit=edit, guidance=guidance, step_cache=step_cache, **tl_kw)
+                edit=edit, guidance=guidance, step_cache=step_cache, **tl_kw, **ms_kw)
         if step_cache is not None:
             log_step_cache(ran_on)
         if loudness_lufs is not None:           # on the device, each clip on its own

@@ -283,6 +283,28 @@ int foley_set_step_cache(foley_ctx* ctx, int mode, const uint8_t* skip, int n_sk
                          int n_poly, const int32_t* interval, int max_consecutive, void* stream);
 int foley_step_cache_report(foley_ctx* ctx, float* rel, int32_t* skipped, int n);
 
+/* Multistep solvers (additive within ABI 12; opt-in): variable-step Adams-Bashforth of order 2 or 3 at one model call per sigma
+ * step.  The step reuses the velocities of the one or two iterations before it:
+ *   x_{n+1} = x_n + dt (c_0 v_n + c_1 v_{n-1} + c_2 v_{n-2})
+ * with the weights in the plan's solver_coef rows: c_0 in column 0 (w_new), c_1 in column 6, c_2 in column 7, and
+ * FOLEY_STEP_HIST in the flags (column 4) of every row with a non-zero history weight.  The rows are those of a one-stage
+ * (euler) table; the first row of a run has no history and is the Euler row, the second row of an order-3 run carries the
+ * order-2 weights (host/tables.py builds them on the run's sigma grid; an edit run restarts the warm-up at its first row).
+ * Arithmetic, fp32, contraction off:  t = c_0 v;  t = fma(c_1, v_{n-1}, t) if c_1 != 0;  t = fma(c_2, v_{n-2}, t) if c_2 != 0;
+ * x = fma(t, dt, x).  A zero weight reads nothing, so warm-up rows do not depend on what the ring holds, and a table without
+ * history weights gives the Euler run bit for bit.  v is the guided velocity exactly as the step uses it (schedule and rescale
+ * factor included); every iteration stores it to a context-owned ring of order - 1 slots [clips, latent_dim, La] fp32.
+ *   order 2 or 3   allocates the ring (grow-only) and switches the step to its history kernel
+ *   order 0 or 1   clears the state, as does foley_prepare
+ * Called after foley_prepare / foley_prepare_sets / foley_prepare_timeline; it combines with foley_set_edit, foley_set_windows,
+ * foley_set_guidance and foley_set_step_cache in any order (a skipped iteration runs the unchanged step and feeds the ring).
+ * The captured iteration is keyed on the ring and its slot count.  Order 3 is a third-order local formula behind a first-order
+ * first step: its global order is 2, with a smaller constant.  The multi-stage solvers (heun-2, midpoint-2, kutta-4) do not
+ * combine with it: their tables carry no history weights.
+ * Any other order: FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE. */
+#define FOLEY_STEP_HIST 16
+int foley_set_multistep(foley_ctx* ctx, int order, void* stream);
+
 /* DAC-VAE decoder: latents [clips, latent_dim, T] fp32 -> waveform [clips, 1, T*hop] fp32. */
 int foley_dac_decode(foley_ctx* ctx, const float* latents, int clips, int T, float* wave, void* stream);
 
@@ -498,6 +520,29 @@ int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const flo
                                         float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
                                         int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
                                         const float* weights, int Ltot, void* stream);
+/* The step with a velocity history (see foley_set_multistep), everything on the DEVICE; one entry for the three forms.
+ * hist [hist_slots, clips, C, L] fp32 with hist_slots 1 or 2: rows flagged FOLEY_STEP_HIST add coef column 6 times slot
+ * (*step_ptr - 1) mod hist_slots and column 7 times slot (*step_ptr - 2) mod hist_slots (a zero weight reads nothing); every row
+ * stores its guided velocity to slot *step_ptr mod hist_slots.  guidance: optional descriptor as above.  x0 != NULL selects the
+ * edit form (operands as foley_op_solver_step_edit), n_win != 0 the windows form (as foley_op_solver_step_windows); both: refused.
+ * A NULL ring or hist_slots outside [1, 2]: FOLEY_ERR_INVALID. */
+typedef struct foley_step_hist_desc {
+  float* hist;
+  int32_t hist_slots;
+  const foley_guidance_desc* guidance;
+  const float* x0;
+  int32_t x0_clips;
+  const float* noise;
+  const float* mask;
+  int32_t mask_clips;
+  int32_t n_win;
+  const int32_t* starts;
+  const float* weights;
+  int32_t Ltot;
+} foley_step_hist_desc;
+int foley_op_solver_step_hist(const foley_step_hist_desc* hd, const float* pred, float* x, float* x_saved, float* d_acc,
+                              int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
+                              void* rows_out, int rows_dtype, void* stream);
 /* The rescale factors of one iteration: gd->clip_scale[b] = rescale * s_pos / s_cfg + (1 - rescale) from pred [ncfg*clips*L, C]
  * at iteration *step_ptr (gd->sched as above), C <= 256.  `work`: device scratch of at least foley_op_guidance_stats_work(clips, L)
  * floats.  Two launches, bit-identical on repetition. */
