@@ -185,41 +185,60 @@ struct RunLayout {
 };
 static_assert(std::has_unique_object_representations_v<RunLayout>, "RunLayout is compared bytewise");
 
+// The option-dependent operands of one loop iteration's launches, as iter_args() derives them from the context: the ONE statement
+// of what an iteration is launched with under the current run options.  The launches and the key of the captured iteration both
+// take them from here, so an operand a foley_set_* call or foley_prepare_timeline can change is in the key because it is
+// launched.  A new option adds its operands to this record and to iter_args(), and nothing else.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-extensions"   // defaulted comparisons under -std=c++17
+struct IterArgs {
+  // the solver step, complete: the guidance scalar (0 under a schedule table, which replaces it: guided_value never reads it
+  // then), the table, the edit / windows form with its operands, the multistep ring and its slot count
+  StepArgs step{};
+  // CFG rescale: the statistics launches in front of the step - their scratch, phi behind the schedule table and the factors they
+  // write, which the step reads as step.clip_scale (all null: off - no such launches, another topology)
+  float *guid_part = nullptr, *guid_scale = nullptr;
+  const float* guid_phi = nullptr;
+  // step cache: the residual the two bodies address and the probe's buffers (all null: off - the one straight-line iteration; on:
+  // the three graphs head / full body / skip body).  Mode, threshold and skip list are host decisions between replays: not here.
+  float *sc_delta = nullptr, *sc_mprev = nullptr, *sc_part = nullptr, *sc_rel = nullptr;
+  // prompt timeline: the text sets the timeline kernel addresses (0: off - the plain cross-attention, fused into its q projection
+  // where that applies: another topology) and the ctx-owned per-token tables
+  int tl_sets = 0;
+  const int *tl_a = nullptr, *tl_b = nullptr;
+  const float* tl_alpha = nullptr;
+  bool operator==(const IterArgs&) const = default;
+};
+
 // Everything a captured loop iteration depends on beyond the workspace dimensions (a change of those frees the plan and the
-// graph with it).  foley_sample compares the key of the capture with the current one; nothing else decides a graph's validity.
+// graph with it): what it is launched with, and what is not a launch operand.  foley_sample compares the key of the capture
+// with the current one; nothing else decides a graph's validity.  New values behind an unchanged address (a schedule, a mask, a
+// timeline of the same shape) only rewrite what a replay reads.
 struct GraphKey {
-  float guidance = 0.f;             // a launch argument of the solver step; 0 when a schedule table replaces it (never read then)
-  int edit = 0;                     // edit_key(): plain vs edit iteration, clip strides of the edit operands
-  std::vector<int32_t> set_maps;    // text_of ++ vis_of (empty: foley_prepare)
+  IterArgs args;
+  std::vector<int32_t> set_maps;    // text_of ++ vis_of (empty: foley_prepare); for safety, not layout: the tables are rewritten in place
   RunLayout layout;
   const void* smod_tab = nullptr;   // the hoisted table (null: the per-iteration GEMM)
-  const void *edit_x0 = nullptr, *edit_noise = nullptr, *edit_mask = nullptr;
-  int n_win = 0, Ltot = 0;          // windows state (foley_set_windows; 0: none): the step kernel and its grid
-  const void *win_starts = nullptr, *win_weights = nullptr;
-  // guidance state (foley_set_guidance): the schedule table (null: off - the scalar `guidance`) and the rescale buffers (null:
-  // off; on adds the two statistics launches, another topology).  New values of either only rewrite what a replay reads.
-  const void *guid_sched = nullptr, *guid_scale = nullptr, *guid_part = nullptr, *guid_phi = nullptr;
-  // step cache (foley_set_step_cache): the residual and probe buffers (null: off - the one straight-line iteration; on: the three
-  // graphs head / full body / skip body).  Mode, threshold and skip list are host decisions between replays: not part of the key.
-  const void *sc_delta = nullptr, *sc_mprev = nullptr;
-  // prompt timeline (foley_prepare_timeline): the text sets the timeline kernel addresses (0: off - the plain cross-attention, fused
-  // into its q projection where that applies: another topology) and the ctx-owned tables.  A new timeline of the same shape only
-  // rewrites what a replay reads.
-  int tl_sets = 0;
-  const void *tl_a = nullptr, *tl_b = nullptr, *tl_alpha = nullptr;
-  // multistep (foley_set_multistep): the velocity ring and its slot count (null / 0: off - the step kernels without history;
-  // orders 2 and 3 differ in the slot count, which the history kernel reads as a launch argument)
-  const void* ms_hist = nullptr;
-  int ms_slots = 0;
   uint64_t tensor_gen = 0;          // bumped when a registered tensor moves (foley_set_tensor)
   uint64_t plan_gen = 0;            // bumped when the workspace is freed (ctx_free_plan)
-  bool operator==(const GraphKey& o) const {
-    return guidance == o.guidance && edit == o.edit && set_maps == o.set_maps && layout == o.layout && smod_tab == o.smod_tab &&
-           edit_x0 == o.edit_x0 && edit_noise == o.edit_noise && edit_mask == o.edit_mask && n_win == o.n_win && Ltot == o.Ltot &&
-           win_starts == o.win_starts && win_weights == o.win_weights && guid_sched == o.guid_sched && guid_scale == o.guid_scale &&
-           guid_part == o.guid_part && guid_phi == o.guid_phi && sc_delta == o.sc_delta && sc_mprev == o.sc_mprev && tl_sets == o.tl_sets &&
-           tl_a == o.tl_a && tl_b == o.tl_b && tl_alpha == o.tl_alpha && ms_hist == o.ms_hist && ms_slots == o.ms_slots && tensor_gen == o.tensor_gen && plan_gen == o.plan_gen;
-  }
+  bool operator==(const GraphKey&) const = default;
+};
+#pragma clang diagnostic pop
+
+// The option values of the prepared run: foley_prepare resets them as one value, the foley_set_* calls (and foley_prepare_timeline)
+// set their own.  Values only - the buffers they speak of are the context's, grow-only, and outlive a prepare.
+struct RunOptions {
+  bool edit = false;                      // foley_set_edit; off: a plain run
+  int edit_x0_clips = 1, edit_mask_clips = 0;   // mask clips 0: no mask (all ones)
+  int n_win = 0, win_Ltot = 0;            // foley_set_windows; n_win 0: the clips are independent
+  bool guid_sched_on = false, guid_rescale_on = false;   // foley_set_guidance; off: the plan's scalar, no factors
+  int sc_mode = 0;                        // foley_set_step_cache: 0 off, FOLEY_STEP_CACHE_SCHEDULE, FOLEY_STEP_CACHE_THRESHOLD
+  std::vector<uint8_t> sc_skip;           // schedule mode: [n_iter]
+  double sc_threshold = 0.0;
+  std::vector<double> sc_poly;            // highest degree first (empty: identity)
+  int sc_lo = 0, sc_hi = 0, sc_maxc = 0;  // iterations [lo, hi) may skip; longest run of skips (0: no cap)
+  int tl_sets = 0;                        // foley_prepare_timeline: the number of text sets (0: one text set per batch row)
+  int ms_order = 0;                       // foley_set_multistep: 0 a one-step method, 2 or 3
 };
 
 struct foley_ctx {
@@ -243,39 +262,26 @@ struct foley_ctx {
   hipGraphExec_t graph_exec = nullptr;
   GraphKey graph_key;
   uint64_t graph_captures = 0;      // iterations captured so far (foley_debug_run_state)
-  // edit state (foley_set_edit; cleared by foley_prepare): ctx-owned copies of the source latents, the run's noise and the mask
-  bool edit = false;
+  RunOptions opt;                   // what the foley_set_* calls asked for (reset by foley_prepare)
+  // ctx-owned copies behind the options, grown on demand.  Edit: the source latents, the run's noise and the mask
   DevBuf edit_x0, edit_noise, edit_mask;
-  int edit_x0_clips = 1, edit_mask_clips = 0;   // mask clips 0: no mask (all ones)
-  // windows state (foley_set_windows; cleared by foley_prepare): ctx-owned copies of the starts and the blend weights
-  int n_win = 0, win_Ltot = 0;      // n_win 0: the clips are independent
+  // windows: the starts and the blend weights
   DevBuf win_starts, win_weights;
   std::vector<int32_t> win_starts_host;   // the source of the asynchronous copy stays alive with the context
-  // guidance state (foley_set_guidance; cleared by foley_prepare): ctx-owned schedule table [n_iter][2] followed by phi, the
-  // per-workgroup statistics and the per-clip factors
-  bool guid_sched_on = false, guid_rescale_on = false;
+  // guidance: the schedule table [n_iter][2] followed by phi, the per-workgroup statistics and the per-clip factors
   DevBuf guid_sched, guid_part, guid_scale;
   std::vector<float> guid_host;           // [n_iter*2 + 1] source of the copy
-  // step cache state (foley_set_step_cache; cleared by foley_prepare): the policy's parameters, the ctx-owned residual / probe
-  // buffers, the pinned read-back of the per-row change measure and the report of the last loop
-  int sc_mode = 0;                        // 0 off, FOLEY_STEP_CACHE_SCHEDULE, FOLEY_STEP_CACHE_THRESHOLD
-  std::vector<uint8_t> sc_skip;           // schedule mode: [n_iter]
-  double sc_threshold = 0.0;
-  std::vector<double> sc_poly;            // highest degree first (empty: identity)
-  int sc_lo = 0, sc_hi = 0, sc_maxc = 0;  // iterations [lo, hi) may skip; longest run of skips (0: no cap)
+  // step cache: the residual / probe buffers, the pinned read-back of the per-row change measure and the report of the last loop
   DevBuf sc_delta, sc_mprev, sc_part, sc_rel;
   float* sc_rel_host = nullptr;           // pinned, sc_rel_cap floats
   int sc_rel_cap = 0;
   std::vector<float> sc_rep_rel;          // [n_iter] of the last loop (-1: not measured)
   std::vector<int32_t> sc_rep_skip;
   hipGraphExec_t graph_head = nullptr, graph_skip = nullptr;   // with graph_exec (the full body) the three graphs of a cached loop
-  // prompt timeline state (foley_prepare_timeline; cleared by foley_prepare / foley_prepare_sets): the number of text sets (0: off)
-  // and ctx-owned copies of the per-token tables [ncfg*clips*(Lv+La)]; ws_tl_sets: the set count the workspace was sized for
-  int tl_sets = 0, ws_tl_sets = 0;
+  // prompt timeline: the per-token tables [ncfg*clips*(Lv+La)]; ws_tl_sets: the set count the workspace was sized for
+  int ws_tl_sets = 0;
   DevBuf tl_a, tl_b, tl_alpha;
-  // multistep state (foley_set_multistep; cleared by foley_prepare): the order (0: off) and the ctx-owned ring of order - 1
-  // velocity slots [clips, latent_dim, La] fp32 that the history step kernels read and feed
-  int ms_order = 0;
+  // multistep: the ring of order - 1 velocity slots [clips, latent_dim, La] fp32 that the history step kernels read and feed
   DevBuf ms_hist;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -287,6 +293,43 @@ struct foley_ctx {
   void* wstore = nullptr;
   void (*wstore_free)(void*) = nullptr;
 };
+
+// What an iteration of the prepared run is launched with under the current options (IterArgs).  No launches; reads the context only.
+static IterArgs iter_args(const foley_ctx* c) {
+  const foley_plan& pl = c->plan;
+  const RunOptions& o = c->opt;
+  IterArgs a{StepArgs{c->buf.pred, c->buf.x_cur, c->buf.x_saved, c->buf.d_acc, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg,
+                      o.guid_sched_on ? 0.f : pl.guidance, pl.solver_coef, c->buf.step_ctr, c->buf.xin, c->cfg.compute_dtype}};
+  StepArgs& s = a.step;
+  if (o.guid_sched_on) s.sched = (const float*)c->guid_sched.p;
+  if (o.guid_rescale_on) {   // the factors of this iteration's prediction, before the step applies them (a window is a clip)
+    a.guid_part = (float*)c->guid_part.p;
+    a.guid_phi = (const float*)c->guid_sched.p + 2 * (size_t)pl.n_iter;
+    s.clip_scale = a.guid_scale = (float*)c->guid_scale.p;
+  }
+  if (o.edit) {   // the edit operands are ctx-owned copies, so their addresses stand for them; so do those of the windows tables
+    s.form = STEP_FORM_EDIT;
+    s.x0 = (const float*)c->edit_x0.p; s.noise = (const float*)c->edit_noise.p;
+    s.mask = o.edit_mask_clips ? (const float*)c->edit_mask.p : nullptr;
+    s.x0_clips = o.edit_x0_clips; s.mask_clips = o.edit_mask_clips;
+  } else if (o.n_win) {
+    s.form = STEP_FORM_WINDOWS;
+    s.n_win = o.n_win; s.Ltot = o.win_Ltot;
+    s.starts = (const int*)c->win_starts.p; s.weights = (const float*)c->win_weights.p;
+  }
+  if (o.ms_order >= 2) {   // the history instantiation of the same form; a skipped (cached) iteration feeds the ring like any other
+    s.hist = (float*)c->ms_hist.p;
+    s.hist_slots = o.ms_order - 1;
+  }
+  if (o.sc_mode) {
+    a.sc_delta = (float*)c->sc_delta.p; a.sc_mprev = (float*)c->sc_mprev.p;
+    a.sc_part = (float*)c->sc_part.p; a.sc_rel = (float*)c->sc_rel.p;
+  }
+  if (o.tl_sets) {
+    a.tl_sets = o.tl_sets; a.tl_a = (const int*)c->tl_a.p; a.tl_b = (const int*)c->tl_b.p; a.tl_alpha = (const float*)c->tl_alpha.p;
+  }
+  return a;
+}
 
 // internal hooks for weights.hip (not part of the C ABI)
 void** foley_ctx_wstore_slot(foley_ctx* c) { return &c->wstore; }
@@ -651,12 +694,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
                      c->layout.t_rows == slots.t_rows && c->layout.v_rows == slots.v_rows && c->ws_tl_sets == (tl ? n_text : 0);
   if (!reuse) ctx_free_plan(c);
   c->prepared = false;
-  c->edit = false;                  // a plan without foley_set_edit is a plain run
-  c->n_win = 0;                     // and one without foley_set_windows has independent clips
-  c->guid_sched_on = c->guid_rescale_on = false;   // and one without foley_set_guidance combines with the plan's scalar
-  c->sc_mode = 0;                   // and one without foley_set_step_cache runs every block on every iteration
-  c->ms_order = 0;                  // and one without foley_set_multistep is a one-step method
-  c->tl_sets = 0;                   // and one without a timeline (foley_prepare_timeline sets it below) one text set per batch row
+  c->opt = RunOptions{};            // a plan without foley_set_* calls is a plain run (a timeline sets its set count below)
   RunLayout& ly = (c->layout = slots);   // the sync-token part follows below; complete where `prepared` is set
   c->vis_src = n_vis;
   const int th = ly.th, vh = ly.vh;
@@ -755,7 +793,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
     HIPTRY(hipMemcpy(c->tl_a.p, tl->set_a, nb, hipMemcpyHostToDevice));
     HIPTRY(hipMemcpy(c->tl_b.p, tl->set_b, nb, hipMemcpyHostToDevice));
     HIPTRY(hipMemcpy(c->tl_alpha.p, tl->alpha, nb, hipMemcpyHostToDevice));
-    c->tl_sets = n_text;
+    c->opt.tl_sets = n_text;
   }
   c->plan = *pl;
 #define COPYTAB(field, bytes) \
@@ -1003,6 +1041,7 @@ static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
   const int ncfg = pl.ncfg, clips = pl.clips, La = pl.La, Lv = pl.Lv, Ls = pl.Ls, Lt = pl.Lt, NI = pl.n_iter;
   const int Bc = ncfg * clips, M = Bc * La, Mv = Bc * Lv, S = La + Lv;
   const RunLayout& ly = c->layout;
+  const IterArgs ia = iter_args(c);   // the probe's buffers and the timeline's tables
   const int th = ly.th, vh = ly.vh, lead = ly.lead;
   const bool bf = foley_is_half(T);   // 16-bit throughput mode (bf16 or fp16 operands): transposed V, fused head split
   const size_t es = esize(T);
@@ -1060,7 +1099,7 @@ static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
     const bool tri = f.depth_triple > 0;
     auto tb0 = [&](int chunk) { return rb_vec(c->buf.modtab + (size_t)chunk * D, 9L * D, sp); };
     TRY(launch_cache_probe(c->buf.audio, Bc, La, D, tri ? 1e-6f : 1e-5f, tri ? tb0(0) : sm_of(0, 0), tri ? tb0(1) : sm_of(0, 1),
-                           (float*)c->sc_mprev.p, (float*)c->sc_part.p, (float*)c->sc_rel.p, st));
+                           ia.sc_mprev, ia.sc_part, ia.sc_rel, st));
     return 0;
   }
   // FinalLayer1D: adaLN is a no-op with 3-D conditioning => linear(LayerNorm(x)); the LayerNorm applies what the last
@@ -1155,7 +1194,7 @@ static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
       // 16-bit modes: the projection may run the attention against the <= 96 cached text keys in its epilogue (small grids:
       // gemm_impl.h decides and reports through attn_fused); the q tensor and the attention launch are then gone
       int fused = 0;
-      if (bf && Lt <= 96 && Ltp >= 96 && !c->tl_sets) {   // a prompt timeline leaves attn_* unset: its own kernel follows
+      if (bf && Lt <= 96 && Ltp >= 96 && !ia.tl_sets) {   // a prompt timeline leaves attn_* unset: its own kernel follows
         for (int s = 0; s < 2; ++s) {
           QkvSplitArgs& q = s ? g1.qs : g0.qs;
           q.attn_k = (char*)c->buf.txt_k + offk; q.attn_vt = (char*)c->buf.txt_v + offv; q.attn_out = ss[s].att;
@@ -1164,9 +1203,9 @@ static int run_forward(foley_ctx* c, hipStream_t st, FwdPart part = FWD_ALL) {
       }
       PROF("triple.cross q GEMM + head split (+ cross attention on small grids)", gf(M + Mv, D, D),
            gb(M + Mv, D, D, es) + 1.0 * D * D * es, launch_gemm_pair(g0, g1, T, EPI_QKV_SPLIT, st));
-      if (c->tl_sets) {
-        AttnTimelineArgs ta{c->buf.Q, (char*)c->buf.txt_k + offk, (char*)c->buf.txt_v + offv, (const int*)c->tl_a.p, (const int*)c->tl_b.p,
-                            (const float*)c->tl_alpha.p, Bc, H, S, Lt, c->tl_sets, c->buf.att_v, c->buf.att_a, Lv, T, bf ? Ltp : 0};
+      if (ia.tl_sets) {
+        AttnTimelineArgs ta{c->buf.Q, (char*)c->buf.txt_k + offk, (char*)c->buf.txt_v + offv, ia.tl_a, ia.tl_b,
+                            ia.tl_alpha, Bc, H, S, Lt, ia.tl_sets, c->buf.att_v, c->buf.att_a, Lv, T, bf ? Ltp : 0};
         PROF("triple.cross attention (prompt timeline)", 2.0 * af(Bc, S, Lt), 2.0 * ab(Bc, S, Lt), launch_attention_timeline(ta, T, st));
       } else if (!fused) {
         AttnArgs a{c->buf.Q, (char*)c->buf.txt_k + offk, (char*)c->buf.txt_v + offv, Bc, H, S, Lt, tdiv, c->buf.att_v, c->buf.att_a, Lv,
@@ -1314,41 +1353,16 @@ extern "C" int foley_profile_forward(foley_ctx* c, const float* latents, int ite
 }
 
 // --------------------------------------------------------------------------- sampler loop
-// The solver update of the prediction in buf.pred (guided / edit / windows form by the context's state): shared by the plain
-// iteration and the two bodies of a cached one.
-static int run_step(foley_ctx* c, hipStream_t st) {
-  const foley_plan& pl = c->plan;
-  StepArgs s{};
-  s.pred = c->buf.pred; s.x = c->buf.x_cur; s.x_saved = c->buf.x_saved; s.d_acc = c->buf.d_acc;
-  s.clips = pl.clips; s.C = c->cfg.latent_dim; s.L = pl.La; s.ncfg = pl.ncfg;
-  s.guidance = pl.guidance; s.coef = pl.solver_coef; s.step_ptr = c->buf.step_ctr;
-  s.rows_out = c->buf.xin; s.rows_dtype = c->cfg.compute_dtype;
-  if (c->guid_sched_on) s.sched = (const float*)c->guid_sched.p;
-  if (c->guid_rescale_on) {   // the factors of this iteration's prediction, before the step applies them (a window is a clip)
-    const float* phi = (const float*)c->guid_sched.p + 2 * (size_t)pl.n_iter;
-    TRY(launch_guidance_stats(s, (float*)c->guid_part.p, phi, 0.f, (float*)c->guid_scale.p, st));
-    s.clip_scale = (const float*)c->guid_scale.p;
-  }
-  if (c->edit) {
-    s.form = STEP_FORM_EDIT;
-    s.x0 = (const float*)c->edit_x0.p; s.noise = (const float*)c->edit_noise.p;
-    s.mask = c->edit_mask_clips ? (const float*)c->edit_mask.p : nullptr;
-    s.x0_clips = c->edit_x0_clips; s.mask_clips = c->edit_mask_clips;
-  } else if (c->n_win) {
-    s.form = STEP_FORM_WINDOWS;
-    s.n_win = c->n_win; s.Ltot = c->win_Ltot;
-    s.starts = (const int*)c->win_starts.p; s.weights = (const float*)c->win_weights.p;
-  }
-  if (c->ms_order >= 2) {   // the history instantiation of the same form; a skipped (cached) iteration feeds the ring like any other
-    s.hist = (float*)c->ms_hist.p;
-    s.hist_slots = c->ms_order - 1;
-  }
-  return launch_solver_step(s, st);
+// The solver update of the prediction in buf.pred, as iter_args() states it (guided / edit / windows form, with or without
+// history), behind the statistics of CFG rescale: shared by the plain iteration and the two bodies of a cached one.
+static int run_step(const IterArgs& a, hipStream_t st) {
+  if (a.guid_scale) TRY(launch_guidance_stats(a.step, a.guid_part, a.guid_phi, 0.f, a.guid_scale, st));
+  return launch_solver_step(a.step, st);
 }
 
 static int run_iteration(foley_ctx* c, hipStream_t st) {
   TRY(run_forward(c, st));
-  return run_step(c, st);
+  return run_step(iter_args(c), st);
 }
 
 // The three pieces of an iteration under the step cache (each a linear captured graph): the head, the full body (a copy of a0 into
@@ -1357,16 +1371,17 @@ static int run_iteration(foley_ctx* c, hipStream_t st) {
 enum { SC_HEAD = 0, SC_FULL = 1, SC_SKIP = 2 };
 static int run_cached_piece(foley_ctx* c, int piece, hipStream_t st) {
   const long n = (long)c->plan.ncfg * c->plan.clips * c->plan.La * c->cfg.hidden;
+  const IterArgs a = iter_args(c);
   if (piece == SC_HEAD) return run_forward(c, st, FWD_HEAD);
   if (piece == SC_FULL) {
-    TRY(launch_cast(c->buf.audio, FOLEY_F32, c->sc_delta.p, FOLEY_F32, n, st));
+    TRY(launch_cast(c->buf.audio, FOLEY_F32, a.sc_delta, FOLEY_F32, n, st));
     TRY(run_forward(c, st, FWD_BODY));
-    TRY(launch_cache_delta(c->buf.audio, (float*)c->sc_delta.p, n, st));
-    return run_step(c, st);
+    TRY(launch_cache_delta(c->buf.audio, a.sc_delta, n, st));
+    return run_step(a, st);
   }
-  TRY(launch_cache_apply(c->buf.audio, (const float*)c->sc_delta.p, n, st));
+  TRY(launch_cache_apply(c->buf.audio, a.sc_delta, n, st));
   TRY(run_forward(c, st, FWD_FINAL));
-  return run_step(c, st);
+  return run_step(a, st);
 }
 
 // The skip policy of one loop (host/step_cache.py states the same machine in Python): iteration 0, the last one and any without a
@@ -1376,21 +1391,21 @@ struct StepCachePolicy {
   double acc = 0.0;
   int run = 0;
   bool have_delta = false;
-  bool decide(const foley_ctx* c, int i, int n, float rel) {
+  bool decide(const RunOptions& o, int i, int n, float rel) {
     const bool forced = i == 0 || i == n - 1 || !have_delta;
     bool skip = false;
-    if (c->sc_mode == FOLEY_STEP_CACHE_SCHEDULE) {
-      skip = !forced && c->sc_skip[i] != 0;
+    if (o.sc_mode == FOLEY_STEP_CACHE_SCHEDULE) {
+      skip = !forced && o.sc_skip[i] != 0;
     } else {
       if (i > 0) {
         double v = (double)rel;
-        if (!c->sc_poly.empty()) {
+        if (!o.sc_poly.empty()) {
           v = 0.0;
-          for (double k : c->sc_poly) v = v * (double)rel + k;
+          for (double k : o.sc_poly) v = v * (double)rel + k;
         }
         acc += v;
       }
-      skip = !forced && acc < c->sc_threshold && i >= c->sc_lo && i < c->sc_hi && (c->sc_maxc <= 0 || run < c->sc_maxc);
+      skip = !forced && acc < o.sc_threshold && i >= o.sc_lo && i < o.sc_hi && (o.sc_maxc <= 0 || run < o.sc_maxc);
     }
     if (skip) {
       ++run;
@@ -1403,28 +1418,9 @@ struct StepCachePolicy {
   }
 };
 
-// Plain vs edit iteration, and the clip strides / presence of the edit operands.  A plain graph replayed for an edit run would
-// skip the blend, an edit graph replayed for a plain run would apply a stale one.
-static int edit_key(const foley_ctx* c) {
-  if (!c->edit) return 0;
-  return 1 | (c->edit_x0_clips == 1 ? 2 : 0) | (c->edit_mask_clips ? 4 : 0) | (c->edit_mask_clips == 1 ? 8 : 0);
-}
-
-// The key of an iteration captured now (in GraphKey's member order).  The set maps are part of it for safety, not layout: the
-// tables a replay reads are rewritten in place.  The edit operands are ctx-owned copies, so their addresses stand for them; so do
-// those of the windows tables (new starts with the same n_win and total length only rewrite what a replay reads).
+// The key of an iteration captured now: its launch operands, and what is not one.
 static GraphKey graph_key_now(const foley_ctx* c) {
-  const bool win = c->n_win > 0;
-  return GraphKey{c->guid_sched_on ? 0.f : c->plan.guidance, edit_key(c), c->set_maps,   c->layout,     c->smod_tab.p,
-                  c->edit_x0.p,     c->edit_noise.p, c->edit_mask.p,
-                  c->n_win,         win ? c->win_Ltot : 0, win ? c->win_starts.p : nullptr, win ? c->win_weights.p : nullptr,
-                  c->guid_sched_on ? c->guid_sched.p : nullptr, c->guid_rescale_on ? c->guid_scale.p : nullptr,
-                  c->guid_rescale_on ? c->guid_part.p : nullptr,
-                  c->guid_rescale_on ? (const void*)((const float*)c->guid_sched.p + 2 * (size_t)c->plan.n_iter) : nullptr,
-                  c->sc_mode ? c->sc_delta.p : nullptr, c->sc_mode ? c->sc_mprev.p : nullptr,
-                  c->tl_sets,       c->tl_sets ? c->tl_a.p : nullptr, c->tl_sets ? c->tl_b.p : nullptr, c->tl_sets ? c->tl_alpha.p : nullptr,
-                  c->ms_order >= 2 ? c->ms_hist.p : nullptr, c->ms_order >= 2 ? c->ms_order - 1 : 0,
-                  c->tensor_gen,    c->plan_gen};
+  return GraphKey{iter_args(c), c->set_maps, c->layout, c->smod_tab.p, c->tensor_gen, c->plan_gen};
 }
 
 extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const float* noise, const float* mask, int mask_clips,
@@ -1432,11 +1428,11 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
   if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_edit: foley_prepare has not been called");
   if (!x0 && !noise && !mask) {
-    c->edit = false;
+    c->opt.edit = false;
     return 0;
   }
   if (!x0 || !noise) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0 and noise are required (all three null clears the edit state)");
-  if (c->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: the run has windows (foley_set_windows); editing a long clip is not supported");
+  if (c->opt.n_win) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: the run has windows (foley_set_windows); editing a long clip is not supported");
   const foley_plan& pl = c->plan;
   if (x0_clips != 1 && x0_clips != pl.clips) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0_clips must be 1 or the plan's clips");
   if (mask && mask_clips != 1 && mask_clips != pl.clips)
@@ -1452,9 +1448,9 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
   HIPTRY(hipMemcpyAsync(c->edit_x0.p, x0, (size_t)x0_clips * plane, hipMemcpyDeviceToDevice, st));
   HIPTRY(hipMemcpyAsync(c->edit_noise.p, noise, (size_t)pl.clips * plane, hipMemcpyDeviceToDevice, st));
   if (mask) HIPTRY(hipMemcpyAsync(c->edit_mask.p, mask, (size_t)mask_clips * pl.La * 4, hipMemcpyDeviceToDevice, st));
-  c->edit = true;
-  c->edit_x0_clips = x0_clips;
-  c->edit_mask_clips = mask ? mask_clips : 0;
+  c->opt.edit = true;
+  c->opt.edit_x0_clips = x0_clips;
+  c->opt.edit_mask_clips = mask ? mask_clips : 0;
   return 0;
 }
 
@@ -1462,10 +1458,10 @@ extern "C" int foley_set_windows(foley_ctx* c, int n_win, const int32_t* starts,
   if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_windows: foley_prepare has not been called");
   if (n_win <= 1 || !starts || !weights) {
-    c->n_win = 0;
+    c->opt.n_win = 0;
     return 0;
   }
-  if (c->edit) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the run is an edit run (foley_set_edit); editing a long clip is not supported");
+  if (c->opt.edit) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the run is an edit run (foley_set_edit); editing a long clip is not supported");
   const foley_plan& pl = c->plan;
   if (pl.clips % n_win != 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the plan's clips must be a multiple of n_win");
   if (starts[0] != 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: starts[0] must be 0");
@@ -1483,8 +1479,8 @@ extern "C" int foley_set_windows(foley_ctx* c, int n_win, const int32_t* starts,
   HIPTRY(hipMemcpyAsync(c->win_starts.p, c->win_starts_host.data(), (size_t)n_win * 4, hipMemcpyHostToDevice, st));
   HIPTRY(hipMemcpyAsync(c->win_weights.p, weights, (size_t)n_win * pl.La * 4, hipMemcpyDeviceToDevice, st));
   HIPTRY(hipStreamSynchronize(st));   // win_starts_host may be rewritten by the next call
-  c->n_win = n_win;
-  c->win_Ltot = starts[n_win - 1] + pl.La;
+  c->opt.n_win = n_win;
+  c->opt.win_Ltot = starts[n_win - 1] + pl.La;
   return 0;
 }
 
@@ -1492,7 +1488,7 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
   if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_guidance: foley_prepare has not been called");
   if (!sched && rescale == 0.f) {   // nothing to apply: the plan's scalar guidance
-    c->guid_sched_on = c->guid_rescale_on = false;
+    c->opt.guid_sched_on = c->opt.guid_rescale_on = false;
     return 0;
   }
   const foley_plan& pl = c->plan;
@@ -1517,8 +1513,8 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
   c->guid_host[nf - 1] = rescale;
   HIPTRY(hipMemcpyAsync(c->guid_sched.p, c->guid_host.data(), nf * 4, hipMemcpyHostToDevice, st));
   HIPTRY(hipStreamSynchronize(st));   // guid_host may be rewritten by the next call
-  c->guid_sched_on = sched != nullptr;
-  c->guid_rescale_on = rescale > 0.f;
+  c->opt.guid_sched_on = sched != nullptr;
+  c->opt.guid_rescale_on = rescale > 0.f;
   return 0;
 }
 
@@ -1526,7 +1522,7 @@ extern "C" int foley_set_multistep(foley_ctx* c, int order, void* stream_v) {
   if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_multistep: foley_prepare has not been called");
   if (order == 0 || order == 1) {   // a one-step method: the step kernels without history
-    c->ms_order = 0;
+    c->opt.ms_order = 0;
     return 0;
   }
   if (order != 2 && order != 3) return FAIL(FOLEY_ERR_INVALID, "foley_set_multistep: order must be 0 or 1 (off), 2 or 3");
@@ -1536,7 +1532,7 @@ extern "C" int foley_set_multistep(foley_ctx* c, int order, void* stream_v) {
   HIPTRY(hipSetDevice(c->device));
   HIPTRY(hipStreamSynchronize(st));   // the ring may be in use by a previous loop on this stream
   TRY(grow(c->ms_hist, (size_t)(order - 1) * pl.clips * c->cfg.latent_dim * pl.La * 4));
-  c->ms_order = order;
+  c->opt.ms_order = order;
   return 0;
 }
 
@@ -1545,7 +1541,7 @@ extern "C" int foley_set_step_cache(foley_ctx* c, int mode, const uint8_t* skip,
   if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_step_cache: foley_prepare has not been called");
   if (mode == 0) {
-    c->sc_mode = 0;
+    c->opt.sc_mode = 0;
     c->sc_rep_rel.clear();
     c->sc_rep_skip.clear();
     return 0;
@@ -1581,16 +1577,16 @@ extern "C" int foley_set_step_cache(foley_ctx* c, int mode, const uint8_t* skip,
     HIPTRY(hipHostMalloc((void**)&c->sc_rel_host, (size_t)Bc * 4, hipHostMallocDefault));
     c->sc_rel_cap = Bc;
   }
-  c->sc_skip.clear();
-  if (mode == FOLEY_STEP_CACHE_SCHEDULE) c->sc_skip.assign(skip, skip + n_skip);
-  c->sc_threshold = threshold;
-  c->sc_poly.assign(poly, poly + n_poly);
-  c->sc_lo = interval ? interval[0] : 0;
-  c->sc_hi = interval ? interval[1] : pl.n_iter;
-  c->sc_maxc = max_consecutive;
+  c->opt.sc_skip.clear();
+  if (mode == FOLEY_STEP_CACHE_SCHEDULE) c->opt.sc_skip.assign(skip, skip + n_skip);
+  c->opt.sc_threshold = threshold;
+  c->opt.sc_poly.assign(poly, poly + n_poly);
+  c->opt.sc_lo = interval ? interval[0] : 0;
+  c->opt.sc_hi = interval ? interval[1] : pl.n_iter;
+  c->opt.sc_maxc = max_consecutive;
   c->sc_rep_rel.clear();
   c->sc_rep_skip.clear();
-  c->sc_mode = mode;
+  c->opt.sc_mode = mode;
   return 0;
 }
 
@@ -1623,7 +1619,7 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   const foley_plan& pl = c->plan;
   const size_t xbytes = (size_t)pl.clips * c->cfg.latent_dim * pl.La * 4;
   GraphKey key = graph_key_now(c);
-  const bool cached = c->sc_mode != 0;
+  const bool cached = c->opt.sc_mode != 0;
   if (c->graph_exec && !(c->graph_key == key)) ctx_drop_graph(c);
   if (use_graph && !c->graph_exec) {
     // Every per-iteration value is read from device memory (step counter, tables) and every
@@ -1674,7 +1670,7 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
     if (cached) {
       TRY(piece(SC_HEAD));
       float rel = -1.f;
-      if (c->sc_mode == FOLEY_STEP_CACHE_THRESHOLD) {   // the one read-back and synchronisation per iteration; schedule mode has none
+      if (c->opt.sc_mode == FOLEY_STEP_CACHE_THRESHOLD) {   // the one read-back and synchronisation per iteration; schedule mode has none
         const int Bc = pl.ncfg * pl.clips;
         HIPTRY(hipMemcpyAsync(c->sc_rel_host, c->sc_rel.p, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
         HIPTRY(hipStreamSynchronize(st));
@@ -1684,7 +1680,7 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
           c->sc_rep_rel[it] = rel;
         }
       }
-      const bool skip = policy.decide(c, it, pl.n_iter, rel);
+      const bool skip = policy.decide(c->opt, it, pl.n_iter, rel);
       c->sc_rep_skip[it] = skip ? 1 : 0;
       TRY(piece(skip ? SC_SKIP : SC_FULL));
     } else if (use_graph) HIPTRY(hipGraphLaunch(c->graph_exec, st));
@@ -2171,31 +2167,46 @@ static StepArgs step_args(const foley_guidance_desc* gd, const float* pred, floa
   return s;
 }
 
+// The one builder behind the guided and history entries: a descriptor's guidance, ring (null: none) and the operands of `form`.
+static int step_launch(const foley_step_hist_desc& d, StepForm form, const float* pred, float* x, float* x_saved, float* d_acc, int clips,
+                       int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out, int rows_dtype,
+                       void* stream) {
+  StepArgs s = step_args(d.guidance, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
+  s.hist = d.hist; s.hist_slots = d.hist_slots; s.form = form;
+  if (form == STEP_FORM_EDIT) {
+    s.x0 = d.x0; s.noise = d.noise; s.mask = d.mask; s.x0_clips = d.x0_clips; s.mask_clips = d.mask_clips;
+  } else if (form == STEP_FORM_WINDOWS) {
+    s.n_win = d.n_win; s.Ltot = d.Ltot; s.starts = d.starts; s.weights = d.weights;
+  }
+  return launch_solver_step(s, (hipStream_t)stream);
+}
+
 extern "C" int foley_op_solver_step_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
                                            int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
                                            void* rows_out, int rows_dtype, void* stream) {
-  return launch_solver_step(step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype),
-                            (hipStream_t)stream);
+  foley_step_hist_desc d{};
+  d.guidance = gd;
+  return step_launch(d, STEP_FORM_PLAIN, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
 }
 
 extern "C" int foley_op_solver_step_edit_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
                                                 int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
                                                 void* rows_out, int rows_dtype, const float* x0, int x0_clips, const float* noise,
                                                 const float* mask, int mask_clips, void* stream) {
-  StepArgs s = step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
-  s.form = STEP_FORM_EDIT;
-  s.x0 = x0; s.noise = noise; s.mask = mask; s.x0_clips = x0_clips; s.mask_clips = mask_clips;
-  return launch_solver_step(s, (hipStream_t)stream);
+  foley_step_hist_desc d{};
+  d.guidance = gd;
+  d.x0 = x0; d.x0_clips = x0_clips; d.noise = noise; d.mask = mask; d.mask_clips = mask_clips;
+  return step_launch(d, STEP_FORM_EDIT, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
 }
 
 extern "C" int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved,
                                                    float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
                                                    int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
                                                    const float* weights, int Ltot, void* stream) {
-  StepArgs s = step_args(gd, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
-  s.form = STEP_FORM_WINDOWS;
-  s.n_win = n_win; s.Ltot = Ltot; s.starts = starts; s.weights = weights;
-  return launch_solver_step(s, (hipStream_t)stream);
+  foley_step_hist_desc d{};
+  d.guidance = gd;
+  d.n_win = n_win; d.starts = starts; d.weights = weights; d.Ltot = Ltot;
+  return step_launch(d, STEP_FORM_WINDOWS, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
 }
 
 // The step with a velocity history (see foley_set_multistep): one entry for the three forms, chosen by the descriptor's operands.
@@ -2205,16 +2216,8 @@ extern "C" int foley_op_solver_step_hist(const foley_step_hist_desc* hd, const f
   if (!hd || !hd->hist || hd->hist_slots < 1 || hd->hist_slots > 2)
     return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_hist: the descriptor needs the ring and 1 or 2 slots");
   if (hd->x0 && hd->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_hist: edit and windows operands exclude each other");
-  StepArgs s = step_args(hd->guidance, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
-  s.hist = hd->hist; s.hist_slots = hd->hist_slots;
-  if (hd->x0) {
-    s.form = STEP_FORM_EDIT;
-    s.x0 = hd->x0; s.noise = hd->noise; s.mask = hd->mask; s.x0_clips = hd->x0_clips; s.mask_clips = hd->mask_clips;
-  } else if (hd->n_win) {
-    s.form = STEP_FORM_WINDOWS;
-    s.n_win = hd->n_win; s.Ltot = hd->Ltot; s.starts = hd->starts; s.weights = hd->weights;
-  }
-  return launch_solver_step(s, (hipStream_t)stream);
+  return step_launch(*hd, hd->x0 ? STEP_FORM_EDIT : hd->n_win ? STEP_FORM_WINDOWS : STEP_FORM_PLAIN, pred, x, x_saved, d_acc, clips, C, L,
+                     ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
 }
 
 extern "C" int64_t foley_op_cache_probe_work(int Bc, int La) { return Bc < 1 || La < 1 ? 0 : (int64_t)cache_probe_floats(Bc, La); }

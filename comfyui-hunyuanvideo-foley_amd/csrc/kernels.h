@@ -262,6 +262,11 @@ struct StepArgs {
   // hist_slots after those reads.
   float* hist = nullptr;
   int hist_slots = 0;
+  // memberwise: the runtime keys its captured iteration on what it launches (a C++20 default, accepted under -std=c++17)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-extensions"
+  bool operator==(const StepArgs&) const = default;
+#pragma clang diagnostic pop
 };
 int launch_solver_step(const StepArgs& a, hipStream_t st);
 // CFG rescale: clip_scale[b] = phi * std(last half of clip b) / std(guided v of clip b) + (1 - phi) over the clip's C x L elements

@@ -206,6 +206,16 @@ def apply_step_cache(ctx: FoleyContext, plan: dict) -> None:
         ctx.set_step_cache(**sc)
 
 
+def prepare_run(model: "FoleyModel", dac, plan: dict) -> None:
+    """The start of every run: the DAC weights, foley_prepare of the plan, then the options build_plan put into it (set_edit /
+    set_windows follow at the caller, with their operands)."""
+    model.attach_dac(dac)
+    model.ctx.prepare(plan)
+    apply_guidance(model.ctx, plan)
+    apply_step_cache(model.ctx, plan)
+    apply_multistep(model.ctx, plan)
+
+
 def keep_step_cache_report(ctx: FoleyContext, plan: dict) -> None:
     """After the loop: plan["step_cache_report"] = {"rel": [...], "skipped": [...]} (the node logs it)."""
     if plan.get("step_cache") is None:
@@ -392,21 +402,13 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     if edit is None:
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
                           guidance=guidance, step_cache=step_cache, timeline=timeline, **_ms_kw(multistep))
-        model.attach_dac(dac)
-        model.ctx.prepare(plan)
-        apply_guidance(model.ctx, plan)
-        apply_step_cache(model.ctx, plan)
-        apply_multistep(model.ctx, plan)
+        prepare_run(model, dac, plan)
     else:
         k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
         x0, mask = edit.device_operands(model.device, batch_size, La)
         plan = build_plan(model, visual_feats, text_feats, La, guidance_scale, num_inference_steps, batch_size, sampler,
                           edit_i0=i0, guidance=guidance, step_cache=step_cache, timeline=timeline, **_ms_kw(multistep))
-        model.attach_dac(dac)
-        model.ctx.prepare(plan)
-        apply_guidance(model.ctx, plan)
-        apply_step_cache(model.ctx, plan)
-        apply_multistep(model.ctx, plan)
+        prepare_run(model, dac, plan)
         model.ctx.set_edit(x0, latents, mask)
         sigma0 = float(tables.sigma_grid(num_inference_steps, cfg.flow_shift)[k0])
         latents = runtime.op_flow_mix(latents, x0, sigma0)
@@ -465,11 +467,7 @@ def _denoise_windows(visual_feats, text_feats, model: FoleyModel, dac: FoleyDAC,
     plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, clips, sampler, edit_i0=0, guidance=guidance,
                       step_cache=step_cache, timeline=timeline, timeline_starts=windows.starts if timeline is not None else None,
                       **_ms_kw(multistep))
-    model.attach_dac(dac)
-    model.ctx.prepare(plan)
-    apply_guidance(model.ctx, plan)
-    apply_step_cache(model.ctx, plan)
-    apply_multistep(model.ctx, plan)
+    prepare_run(model, dac, plan)
     weights = windows.weights.to(model.device)
     model.ctx.set_windows(windows.starts, weights)
     if _abort_event is not None and _abort_event.is_set():

@@ -1,5 +1,6 @@
 """The prompt timeline on the HIP engine: the loop against the oracle restatement with timed text (tests/timeline_ref.py), a
-one-span timeline against the plain run, the keying of the captured graph, the refusals of foley_prepare_timeline, a bf16 run."""
+one-span timeline against the plain run, the keying of the captured graph (on the timeline state, and across runs that differ in
+several options at once), the refusals of foley_prepare_timeline, a bf16 run."""
 import ctypes
 
 import pytest
@@ -138,6 +139,52 @@ def test_graph_keyed_on_the_timeline_state(tiny):
         caps[name] = _captures(model) - c0
         assert rel_err(got, want[name]) < 1e-6, name
     assert caps["A"] >= 1 and caps["B"] == 0 and caps["plain"] >= 1, caps      # plain <-> timeline re-captures, A -> B keeps the graph
+
+
+def test_graph_keyed_across_different_options(tiny, dev):
+    """One context, use_graph=True, two clips of 1 s, 10 euler steps: plain -> two windows under multistep order 2 -> an edit with
+    a mask under a guidance schedule with rescale -> a step-cache skip list under three halves -> a timeline -> plain.  Every
+    transition swaps one set of options for another (the keying tests of the features toggle one each).  Each run captures exactly
+    once and carries the bits of the same call with use_graph=False on a context of its own: graph and eager issue the same
+    launches with the same arguments.  The last plain run carries the bits of the first."""
+    sd, _dsd, model, dac, cond, texts, unc = tiny
+    g = torch.Generator().manual_seed(12)
+    wplan = long_form.WindowPlan.from_frames([0, 30], LA)
+    n2, nw = torch.randn(2, 128, LA, generator=g), torch.randn(1, 128, wplan.Ltot, generator=g)
+    ed = audio_edit.EditSpec(0.7 * torch.randn(2, 128, LA, generator=g), 1.0, audio_edit.build_mask(LA, [(0.2, 0.5)], 0.1))
+    Guid = sampler.GuidanceSpec
+    seq = [("plain", {}),
+           ("windows, order 2", dict(bs=1, noise=nw, windows=wplan, multistep=sampler.MultistepSpec(2))),
+           ("edit, schedule, rescale", dict(edit=ed, guidance=Guid(interval=(0.2, 0.7), rescale=0.7))),
+           ("skip list, three halves", dict(scale=2.0, guidance=Guid(g_video=7.0), step_cache=sampler.StepCacheSpec(skip=(3, 6)))),
+           ("timeline", dict(tl=_timeline(*THREE))),
+           ("plain", {})]
+
+    def call(m, use_graph, tl=None, scale=CFG, bs=2, noise=n2, **kw):
+        vis, txt = _feats(cond, texts, unc, tl)
+        if tl is None:
+            txt["text_feat"] = texts[2:3]
+        return sampler.denoise_process_with_generator(vis, txt, 1.0, m, dac, scale, STEPS, bs, "euler", noise=noise, use_graph=use_graph,
+                                                      return_latents=True, timeline=tl, **kw)[2].clone()
+
+    want = {}
+    for name, kw in seq[:-1]:
+        want[name] = call(sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY), False, **kw)
+    assert want["windows, order 2"].shape == (1, 128, wplan.Ltot)
+    names = list(want)
+    for i, a in enumerate(names):
+        for b in names[i + 1:]:
+            assert want[a].shape != want[b].shape or rel_err(want[a], want[b]) > 1e-3, (a, b)
+    one = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
+    got = []
+    for name, kw in seq:
+        c0 = _captures(one)
+        got.append(call(one, True, **kw))
+        e = rel_err(got[-1], want[name])
+        print("%s: graph vs eager %.2e, captures +%d" % (name, e, _captures(one) - c0))
+        assert _captures(one) == c0 + 1, name
+        assert torch.equal(got[-1], want[name]), (name, e)
+    assert torch.equal(got[-1], got[0])
 
 
 def test_prepare_timeline_refusals(tiny):
