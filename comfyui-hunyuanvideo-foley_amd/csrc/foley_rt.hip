@@ -2133,91 +2133,18 @@ extern "C" int foley_op_qkv_split(const float* qkv, int M, int L, int H, int nK,
   return launch_qkv_split(a, (hipStream_t)stream);
 }
 
-extern "C" int foley_op_solver_step(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C,
-                                    int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                                    void* rows_out, int rows_dtype, void* stream) {
-  return foley_op_solver_step_guided(nullptr, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
-}
-
-extern "C" int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
-                                         int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
-                                         int rows_dtype, const float* x0, int x0_clips, const float* noise, const float* mask,
-                                         int mask_clips, void* stream) {
-  return foley_op_solver_step_edit_guided(nullptr, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out,
-                                          rows_dtype, x0, x0_clips, noise, mask, mask_clips, stream);
-}
-
-extern "C" int foley_op_solver_step_windows(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
-                                            int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
-                                            int rows_dtype, int n_win, const int32_t* starts, const float* weights, int Ltot,
-                                            void* stream) {
-  return foley_op_solver_step_windows_guided(nullptr, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out,
-                                             rows_dtype, n_win, starts, weights, Ltot, stream);
-}
-
-// The three step forms with a guidance descriptor (null: none - the entries above), and the statistics behind its factors.  The
-// operands every form shares:
-static StepArgs step_args(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
-                          int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out, int rows_dtype) {
-  StepArgs s{pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype};
-  if (gd) {
-    s.sched = gd->sched;
-    s.clip_scale = gd->clip_scale;
-  }
-  return s;
-}
-
-// The one builder behind the guided and history entries: a descriptor's guidance, ring (null: none) and the operands of `form`.
-static int step_launch(const foley_step_hist_desc& d, StepForm form, const float* pred, float* x, float* x_saved, float* d_acc, int clips,
-                       int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out, int rows_dtype,
-                       void* stream) {
-  StepArgs s = step_args(d.guidance, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype);
-  s.hist = d.hist; s.hist_slots = d.hist_slots; s.form = form;
-  if (form == STEP_FORM_EDIT) {
-    s.x0 = d.x0; s.noise = d.noise; s.mask = d.mask; s.x0_clips = d.x0_clips; s.mask_clips = d.mask_clips;
-  } else if (form == STEP_FORM_WINDOWS) {
-    s.n_win = d.n_win; s.Ltot = d.Ltot; s.starts = d.starts; s.weights = d.weights;
-  }
+// The solver step, one entry for every form and option: the descriptor translated into the StepArgs the sampler loop launches
+// with.  launch_solver_step checks the form's operands and the ring (a buffer with 1 or 2 slots, or neither).
+extern "C" int foley_op_solver_step(const foley_step_desc* d, void* stream) {
+  if (!d) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step: null descriptor");
+  if (d->x0 && d->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step: edit and windows operands exclude each other");
+  StepArgs s{d->pred, d->x, d->x_saved, d->d_acc, d->clips, d->C, d->L, d->ncfg, d->guidance, d->coef, d->step_ptr, d->rows_out, d->rows_dtype};
+  s.sched = d->gd.sched; s.clip_scale = d->gd.clip_scale;
+  s.form = d->x0 ? STEP_FORM_EDIT : d->n_win ? STEP_FORM_WINDOWS : STEP_FORM_PLAIN;
+  s.x0 = d->x0; s.noise = d->noise; s.mask = d->mask; s.x0_clips = d->x0_clips; s.mask_clips = d->mask_clips;
+  s.n_win = d->n_win; s.Ltot = d->Ltot; s.starts = d->starts; s.weights = d->weights;
+  s.hist = d->hist; s.hist_slots = d->hist_slots;
   return launch_solver_step(s, (hipStream_t)stream);
-}
-
-extern "C" int foley_op_solver_step_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
-                                           int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                                           void* rows_out, int rows_dtype, void* stream) {
-  foley_step_hist_desc d{};
-  d.guidance = gd;
-  return step_launch(d, STEP_FORM_PLAIN, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
-}
-
-extern "C" int foley_op_solver_step_edit_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
-                                                int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                                                void* rows_out, int rows_dtype, const float* x0, int x0_clips, const float* noise,
-                                                const float* mask, int mask_clips, void* stream) {
-  foley_step_hist_desc d{};
-  d.guidance = gd;
-  d.x0 = x0; d.x0_clips = x0_clips; d.noise = noise; d.mask = mask; d.mask_clips = mask_clips;
-  return step_launch(d, STEP_FORM_EDIT, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
-}
-
-extern "C" int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved,
-                                                   float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
-                                                   int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
-                                                   const float* weights, int Ltot, void* stream) {
-  foley_step_hist_desc d{};
-  d.guidance = gd;
-  d.n_win = n_win; d.starts = starts; d.weights = weights; d.Ltot = Ltot;
-  return step_launch(d, STEP_FORM_WINDOWS, pred, x, x_saved, d_acc, clips, C, L, ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
-}
-
-// The step with a velocity history (see foley_set_multistep): one entry for the three forms, chosen by the descriptor's operands.
-extern "C" int foley_op_solver_step_hist(const foley_step_hist_desc* hd, const float* pred, float* x, float* x_saved, float* d_acc,
-                                         int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                                         void* rows_out, int rows_dtype, void* stream) {
-  if (!hd || !hd->hist || hd->hist_slots < 1 || hd->hist_slots > 2)
-    return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_hist: the descriptor needs the ring and 1 or 2 slots");
-  if (hd->x0 && hd->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_hist: edit and windows operands exclude each other");
-  return step_launch(*hd, hd->x0 ? STEP_FORM_EDIT : hd->n_win ? STEP_FORM_WINDOWS : STEP_FORM_PLAIN, pred, x, x_saved, d_acc, clips, C, L,
-                     ncfg, guidance, coef, step_ptr, rows_out, rows_dtype, stream);
 }
 
 extern "C" int64_t foley_op_cache_probe_work(int Bc, int La) { return Bc < 1 || La < 1 ? 0 : (int64_t)cache_probe_floats(Bc, La); }
@@ -2246,7 +2173,8 @@ extern "C" int foley_op_guidance_stats(const foley_guidance_desc* gd, const floa
   if (!gd || !gd->clip_scale) return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_stats: the descriptor's clip_scale receives the factors");
   if (clips < 1 || L < 1 || !work || work_floats < (int64_t)guidance_stats_floats(clips, L))
     return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_stats: work buffer smaller than foley_op_guidance_stats_work(clips, L) floats");
-  const StepArgs s = step_args(gd, pred, nullptr, nullptr, nullptr, clips, C, L, ncfg, guidance, nullptr, (int32_t*)step_ptr, nullptr, FOLEY_F32);
+  StepArgs s{pred, nullptr, nullptr, nullptr, clips, C, L, ncfg, guidance, nullptr, (int32_t*)step_ptr, nullptr, FOLEY_F32};
+  s.sched = gd->sched; s.clip_scale = gd->clip_scale;
   return launch_guidance_stats(s, work, nullptr, rescale, (float*)gd->clip_scale, (hipStream_t)stream);
 }
 

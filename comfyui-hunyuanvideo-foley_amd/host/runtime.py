@@ -102,11 +102,14 @@ class GuidanceDescC(C.Structure):
     _fields_ = [("sched", C.c_void_p), ("clip_scale", C.c_void_p)]
 
 
-class StepHistDescC(C.Structure):
-    """foley_step_hist_desc: the velocity ring [hist_slots, clips, C, L] and the optional operands of foley_op_solver_step_hist
-    (a guidance descriptor; x0 / noise / mask of the edit form; starts / weights of the windows form) - 0: absent."""
-    _fields_ = [("hist", C.c_void_p), ("hist_slots", C.c_int32), ("guidance", C.POINTER(GuidanceDescC)),
-                ("x0", C.c_void_p), ("x0_clips", C.c_int32), ("noise", C.c_void_p), ("mask", C.c_void_p), ("mask_clips", C.c_int32),
+class StepDescC(C.Structure):
+    """foley_step_desc: every operand of foley_op_solver_step - the core ones, then the optional guidance descriptor, velocity
+    ring [hist_slots, clips, C, L], x0 / noise / mask of the edit form and starts / weights of the windows form (0: absent)."""
+    _fields_ = [("pred", C.c_void_p), ("x", C.c_void_p), ("x_saved", C.c_void_p), ("d_acc", C.c_void_p),
+                ("clips", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("ncfg", C.c_int32),
+                ("guidance", C.c_float), ("rows_dtype", C.c_int32), ("coef", C.c_void_p), ("step_ptr", C.c_void_p), ("rows_out", C.c_void_p),
+                ("gd", GuidanceDescC), ("hist", C.c_void_p), ("hist_slots", C.c_int32), ("x0_clips", C.c_int32),
+                ("x0", C.c_void_p), ("noise", C.c_void_p), ("mask", C.c_void_p), ("mask_clips", C.c_int32),
                 ("n_win", C.c_int32), ("starts", C.c_void_p), ("weights", C.c_void_p), ("Ltot", C.c_int32)]
 
 
@@ -116,7 +119,7 @@ class ProfEntryC(C.Structure):
 
 
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_int32, C.c_int32, C.c_void_p)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _SIGNATURES = {
     "foley_abi_version": (C.c_uint32, []),
@@ -179,24 +182,9 @@ _SIGNATURES = {
     "foley_op_qkv_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "foley_op_solver_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p,
-                                                                          C.c_void_p, C.c_int, C.c_void_p]),
-    "foley_op_solver_step_edit": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                                               C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                                                               C.c_void_p, C.c_int, C.c_void_p]),
-    "foley_op_solver_step_windows": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                                                  C.c_void_p]),
+    "foley_op_solver_step": (C.c_int, [C.POINTER(StepDescC), C.c_void_p]),
     "foley_op_windows_stitch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
-    "foley_op_solver_step_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
-        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "foley_op_solver_step_edit_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
-        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "foley_op_solver_step_windows_guided": (C.c_int, [C.POINTER(GuidanceDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
-        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "foley_op_solver_step_hist": (C.c_int, [C.POINTER(StepHistDescC)] + [C.c_void_p] * 4 + [C.c_int] * 4 + [
-        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_op_guidance_stats_work": (C.c_int64, [C.c_int, C.c_int]),
     "foley_op_guidance_stats": (C.c_int, [C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -1009,36 +997,6 @@ def _rows_dt(rows_out) -> int:
     return DT_F32 if rows_out is None else dt_of(rows_out)      # rows_out None: the step stages no model input rows
 
 
-def _step_call(entry: str, gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, edit=None, windows=None):
-    """One of the six foley_op_solver_step* entries: `entry` names the symbol, gd (a descriptor or None) leads the guided ones;
-    edit = (x0, noise, mask) and windows = (starts, weights, Ltot) add their form's operands."""
-    lib = load_library()
-    clips, Cc, L = x.shape
-    args = [_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg, float(guidance), _ptr(coef), _ptr(step_ptr),
-            _ptr(rows_out), _rows_dt(rows_out)]
-    if entry.endswith("_guided"):
-        args.insert(0, C.byref(gd) if gd is not None else None)
-    if edit is not None:
-        x0, noise, mask = edit
-        mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
-        args += [_ptr(x0), x0.shape[0], _ptr(noise), _ptr(mask), mask_clips]
-    elif windows is not None:
-        starts, weights, Ltot = windows
-        args += [_windows_tables(x, starts, weights), _ptr(starts), _ptr(weights), int(Ltot)]
-    _check(lib, getattr(lib, entry)(*args, _stream()), entry)
-
-
-def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out):
-    """x_saved / d_acc may be None for single-stage tables (euler), rows_out None to leave the next input rows unstaged."""
-    _step_call("foley_op_solver_step", None, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out)
-
-
-def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, x0, noise, mask=None):
-    """foley_op_solver_step_edit: x0 [1 | clips, C, L], noise [clips, C, L], mask [1 | clips, L] or None (all ones)."""
-    _step_call("foley_op_solver_step_edit", None, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
-               edit=(x0, noise, mask))
-
-
 def _windows_tables(x, starts, weights):
     clips, _c, L = x.shape
     if starts.dtype != torch.int32 or weights.dtype != torch.float32 or tuple(weights.shape) != (starts.numel(), L):
@@ -1048,14 +1006,8 @@ def _windows_tables(x, starts, weights):
     return int(starts.numel())
 
 
-def op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, starts, weights, Ltot):
-    """foley_op_solver_step_windows: x [variations*n_win, C, L]; starts [n_win] int32 and weights [n_win, L] fp32 device tensors."""
-    _step_call("foley_op_solver_step_windows", None, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
-               windows=(starts, weights, Ltot))
-
-
 def guidance_desc(sched: Optional[torch.Tensor] = None, clip_scale: Optional[torch.Tensor] = None) -> GuidanceDescC:
-    """Descriptor of the guided op entries: sched [n_iter, 2] fp32 and clip_scale [clips] fp32 device tensors (None: absent)."""
+    """Guidance descriptor of op_solver_step(gd=) and foley_op_guidance_stats: sched [n_iter, 2] fp32 and clip_scale [clips] fp32 device tensors (None: absent)."""
     for t, what in ((sched, "sched"), (clip_scale, "clip_scale")):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise FoleyRuntimeError(f"guidance_desc: {what} must be a contiguous fp32 tensor")
@@ -1064,36 +1016,49 @@ def guidance_desc(sched: Optional[torch.Tensor] = None, clip_scale: Optional[tor
     return GuidanceDescC(_ptr(sched), _ptr(clip_scale))
 
 
-def op_solver_step_guided(gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, edit=None, windows=None):
-    """The step forms with a guidance descriptor: plain, edit=(x0, noise, mask) or windows=(starts, weights, Ltot)."""
-    form = "_edit" if edit is not None else "_windows" if windows is not None else ""
-    _step_call(f"foley_op_solver_step{form}_guided", gd, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out,
-               edit=edit, windows=windows)
-
-
-def op_solver_step_hist(hist, pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, gd=None, edit=None, windows=None,
-                        slots: Optional[int] = None):
-    """foley_op_solver_step_hist: the step forms with a velocity ring hist [slots, clips, C, L] fp32 (slots 1 or 2, taken from
-    the tensor unless given); gd a guidance descriptor or None, edit=(x0, noise, mask) or windows=(starts, weights, Ltot)."""
+def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, *, gd: Optional[GuidanceDescC] = None,
+                   hist: Optional[torch.Tensor] = None, slots: Optional[int] = None, edit=None, windows=None):
+    """foley_op_solver_step: x_saved / d_acc may be None for single-stage tables (euler), rows_out None to leave the next input
+    rows unstaged.  gd: a guidance_desc; hist: a velocity ring [slots, clips, C, L] fp32 (slots 1 or 2, taken from the tensor
+    unless given).  edit=(x0 [1 | clips, C, L], noise [clips, C, L], mask [1 | clips, L] or [L] or None: all ones) selects the
+    edit form, windows=(starts [n_win] int32, weights [n_win, L] fp32, Ltot) with x [variations*n_win, C, L] the windows form."""
     lib = load_library()
     clips, Cc, L = x.shape
     if hist is not None and (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 4
                              or tuple(hist.shape[1:]) != (clips, Cc, L)):
-        raise FoleyRuntimeError("op_solver_step_hist: hist is a contiguous fp32 tensor [slots, clips, C, L]")
-    hd = StepHistDescC()
-    hd.hist = _ptr(hist)
-    hd.hist_slots = int(slots) if slots is not None else (int(hist.shape[0]) if hist is not None else 0)
-    hd.guidance = C.pointer(gd) if gd is not None else None
+        raise FoleyRuntimeError("op_solver_step: hist is a contiguous fp32 tensor [slots, clips, C, L]")
+    d = StepDescC(_ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg, float(guidance), _rows_dt(rows_out),
+                  _ptr(coef), _ptr(step_ptr), _ptr(rows_out))
+    if gd is not None:
+        d.gd = gd
+    d.hist = _ptr(hist)
+    d.hist_slots = int(slots) if slots is not None else (int(hist.shape[0]) if hist is not None else 0)
     if edit is not None:
         x0, noise, mask = edit
-        hd.x0, hd.x0_clips, hd.noise, hd.mask = _ptr(x0), int(x0.shape[0]), _ptr(noise), _ptr(mask)
-        hd.mask_clips = (1 if mask.dim() == 1 else int(mask.shape[0])) if mask is not None else 0
+        d.x0, d.x0_clips, d.noise, d.mask = _ptr(x0), int(x0.shape[0]), _ptr(noise), _ptr(mask)
+        d.mask_clips = (1 if mask.dim() == 1 else int(mask.shape[0])) if mask is not None else 0
     if windows is not None:
         starts, weights, Ltot = windows
-        hd.n_win, hd.starts, hd.weights, hd.Ltot = _windows_tables(x, starts, weights), _ptr(starts), _ptr(weights), int(Ltot)
-    _check(lib, lib.foley_op_solver_step_hist(C.byref(hd), _ptr(pred), _ptr(x), _ptr(x_saved), _ptr(d_acc), clips, Cc, L, ncfg,
-                                              float(guidance), _ptr(coef), _ptr(step_ptr), _ptr(rows_out), _rows_dt(rows_out),
-                                              _stream()), "foley_op_solver_step_hist")
+        d.n_win, d.starts, d.weights, d.Ltot = _windows_tables(x, starts, weights), _ptr(starts), _ptr(weights), int(Ltot)
+    _check(lib, lib.foley_op_solver_step(C.byref(d), _stream()), "foley_op_solver_step")
+
+
+# The four names callers used before ABI 13, kept as plain forwards so that code written against them still runs.  Options go through
+# as keywords, so a further one is added to op_solver_step alone.
+def op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, x0, noise, mask=None):
+    op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, edit=(x0, noise, mask))
+
+
+def op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, starts, weights, Ltot):
+    op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, windows=(starts, weights, Ltot))
+
+
+def op_solver_step_guided(gd, *core, **options):
+    op_solver_step(*core, gd=gd, **options)
+
+
+def op_solver_step_hist(hist, *core, **options):
+    op_solver_step(*core, hist=hist, **options)
 
 
 def op_guidance_stats(pred, clips, L, ncfg, guidance, sched, step_ptr, rescale, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FOLEY_ABI_VERSION 12   /* 12 (additions that leave every existing entry as it was, so the version stays): foley_prepare_sets, foley_op_resample_sinc, foley_op_logmel, head_dim 96 in foley_op_attention_hd (the sync scorer); 12: foley_op_qkv_regroup.n_rows / foley_op_attention_scatter.out_nrows (the caller-supplied row tables are range-checked on the device: source rows clamped, output rows outside the buffer dropped); 11: foley_op_resize_aa_u8 (the frames' antialiased uint8 resize, bit for bit), foley_op_attention_scatter, foley_rowbcast.periodic_cfgs; 10: foley_op_qkv_regroup (token regrouping of the conditioning encoders' attention); 9: foley_bcast_local (single-process grouped broadcast of the arenas); 8: foley_qkv_split_desc.attn_* (cross attention in the epilogue of its q projection), foley_abort / FOLEY_ERR_ABORTED; 7: FOLEY_DT_F16 as a compute dtype (foley_config.compute_dtype, op descriptors); 6: foley_rowbcast.Ls (mode 2: nearest-exact up-sampled operand); 5: reference-keyed loading (foley_weights_*, foley_load_tensor, foley_bcast_weights); 4: fp8 weight storage (dtype codes 3/4, foley_gemm_desc.ldw/.wfmt); 3: foley_profile_forward; 2: foley_gemm_desc gained partials / qkv / rstride; foley_op_ln_mod_pending, foley_dac_encode */
+#define FOLEY_ABI_VERSION 13   /* 13: the seven foley_op_solver_step* entries became the one foley_op_solver_step(const foley_step_desc*, stream) - the positional pred .. rows_dtype are the fields of the same names, the gd argument of the _guided entries is .gd, the x0 / x0_clips / noise / mask / mask_clips arguments of the _edit entries and n_win / starts / weights / Ltot of the _windows entries are the fields of those names (x0 != NULL / n_win != 0 select the form), foley_step_hist_desc.hist / .hist_slots are .hist / .hist_slots and its .guidance pointer is the embedded .gd; 12 (additions that leave every existing entry as it was, so the version stays): foley_prepare_sets, foley_op_resample_sinc, foley_op_logmel, head_dim 96 in foley_op_attention_hd (the sync scorer); 12: foley_op_qkv_regroup.n_rows / foley_op_attention_scatter.out_nrows (the caller-supplied row tables are range-checked on the device: source rows clamped, output rows outside the buffer dropped); 11: foley_op_resize_aa_u8 (the frames' antialiased uint8 resize, bit for bit), foley_op_attention_scatter, foley_rowbcast.periodic_cfgs; 10: foley_op_qkv_regroup (token regrouping of the conditioning encoders' attention); 9: foley_bcast_local (single-process grouped broadcast of the arenas); 8: foley_qkv_split_desc.attn_* (cross attention in the epilogue of its q projection), foley_abort / FOLEY_ERR_ABORTED; 7: FOLEY_DT_F16 as a compute dtype (foley_config.compute_dtype, op descriptors); 6: foley_rowbcast.Ls (mode 2: nearest-exact up-sampled operand); 5: reference-keyed loading (foley_weights_*, foley_load_tensor, foley_bcast_weights); 4: fp8 weight storage (dtype codes 3/4, foley_gemm_desc.ldw/.wfmt); 3: foley_profile_forward; 2: foley_gemm_desc gained partials / qkv / rstride; foley_op_ln_mod_pending, foley_dac_encode */
 
 enum foley_dtype {
   FOLEY_DT_F32 = 0, FOLEY_DT_BF16 = 1, FOLEY_DT_I32 = 2,
@@ -487,51 +487,41 @@ int foley_op_ln_mod_pending2(float* x, int M, int D, float eps, const foley_rowb
 int foley_op_qkv_split(const float* qkv, int M, int L, int H, int nK, const float* const* gain,
                        const int32_t* const* pos, void* const* dst, int out_dtype, int vt_pitch, int S_tot,
                        int tok_off, float eps, const float* cos_tab, const float* sin_tab, void* stream);
-int foley_op_solver_step(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
-                         int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
-                         int rows_dtype, void* stream);
-/* foley_op_solver_step's edit form (see foley_set_edit): the same update, then the blend after FOLEY_STEP_BLEND rows;
- * x0 [x0_clips, C, L], noise [clips, C, L], mask [mask_clips, L] or NULL (all ones); x0_clips / mask_clips 1 or clips. */
-int foley_op_solver_step_edit(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
-                              int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
-                              int rows_dtype, const float* x0, int x0_clips, const float* noise, const float* mask,
-                              int mask_clips, void* stream);
-/* foley_op_solver_step's windows form (see foley_set_windows): clips = variations*n_win; starts [n_win] int32 and weights
- * [n_win, L] fp32 both on the DEVICE here; Ltot = starts[n_win - 1] + L. */
-int foley_op_solver_step_windows(const float* pred, float* x, float* x_saved, float* d_acc, int clips, int C, int L,
-                                 int ncfg, float guidance, const float* coef, int32_t* step_ptr, void* rows_out,
-                                 int rows_dtype, int n_win, const int32_t* starts, const float* weights, int Ltot, void* stream);
-/* The three step forms with a guidance descriptor (see foley_set_guidance), everything on the DEVICE: sched [n_iter, 2] read at
- * row *step_ptr (NULL: the scalar `guidance`), clip_scale [clips] multiplied into the guided value (NULL: none).  gd NULL, or
- * ncfg 2 with a table whose rows all hold `guidance` and no factors, gives the bits of the entries above.  ncfg 3 takes the
- * three-term combine; rows_out is staged ncfg times. */
+/* Guidance descriptor (see foley_set_guidance), on the DEVICE: sched [n_iter, 2] read at row *step_ptr (NULL: the scalar
+ * `guidance`), clip_scale [clips] multiplied into the guided value (NULL: none). */
 typedef struct foley_guidance_desc {
   const float* sched;
   float* clip_scale;
 } foley_guidance_desc;
-int foley_op_solver_step_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
-                                int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                                void* rows_out, int rows_dtype, void* stream);
-int foley_op_solver_step_edit_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved, float* d_acc,
-                                     int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                                     void* rows_out, int rows_dtype, const float* x0, int x0_clips, const float* noise,
-                                     const float* mask, int mask_clips, void* stream);
-int foley_op_solver_step_windows_guided(const foley_guidance_desc* gd, const float* pred, float* x, float* x_saved,
-                                        float* d_acc, int clips, int C, int L, int ncfg, float guidance, const float* coef,
-                                        int32_t* step_ptr, void* rows_out, int rows_dtype, int n_win, const int32_t* starts,
-                                        const float* weights, int Ltot, void* stream);
-/* The step with a velocity history (see foley_set_multistep), everything on the DEVICE; one entry for the three forms.
- * hist [hist_slots, clips, C, L] fp32 with hist_slots 1 or 2: rows flagged FOLEY_STEP_HIST add coef column 6 times slot
- * (*step_ptr - 1) mod hist_slots and column 7 times slot (*step_ptr - 2) mod hist_slots (a zero weight reads nothing); every row
- * stores its guided velocity to slot *step_ptr mod hist_slots.  guidance: optional descriptor as above.  x0 != NULL selects the
- * edit form (operands as foley_op_solver_step_edit), n_win != 0 the windows form (as foley_op_solver_step_windows); both: refused.
- * A NULL ring or hist_slots outside [1, 2]: FOLEY_ERR_INVALID. */
-typedef struct foley_step_hist_desc {
+/* One solver step (CFG combine + scheduler update + staging of the next model input rows), every operand on the DEVICE; an absent
+ * operand is NULL / 0.  pred [ncfg*clips*L, C], x / x_saved / d_acc [clips, C, L] (x_saved / d_acc NULL for single-stage tables),
+ * coef [n_iter, 8] read at row *step_ptr, which a one-thread launch then advances; rows_out NULL: no rows staged, else ncfg copies.
+ * gd: both NULL, or ncfg 2 with a table whose rows all hold `guidance` and no factors, give the same bits; ncfg 3 takes the
+ *   three-term combine.
+ * hist [hist_slots, clips, C, L] fp32 (see foley_set_multistep): rows flagged FOLEY_STEP_HIST add coef column 6 times slot
+ *   (*step_ptr - 1) mod hist_slots and column 7 times slot (*step_ptr - 2) mod hist_slots (a zero weight reads nothing); every row
+ *   stores its guided velocity to slot *step_ptr mod hist_slots.  NULL with 0 slots: the kernels without history; a ring needs 1
+ *   or 2 slots and slots need a ring, anything else is FOLEY_ERR_INVALID.
+ * x0 != NULL selects the edit form (see foley_set_edit): the same update, then the blend after FOLEY_STEP_BLEND rows; x0
+ *   [x0_clips, C, L], noise [clips, C, L], mask [mask_clips, L] or NULL (all ones); x0_clips / mask_clips 1 or clips.
+ * n_win != 0 selects the windows form (see foley_set_windows): clips = variations*n_win; starts [n_win] int32 and weights
+ *   [n_win, L] fp32; Ltot = starts[n_win - 1] + L.  Both forms at once: refused. */
+typedef struct foley_step_desc {
+  const float* pred;
+  float* x;
+  float* x_saved;
+  float* d_acc;
+  int32_t clips, C, L, ncfg;
+  float guidance;
+  int32_t rows_dtype;
+  const float* coef;
+  int32_t* step_ptr;
+  void* rows_out;
+  foley_guidance_desc gd;
   float* hist;
   int32_t hist_slots;
-  const foley_guidance_desc* guidance;
-  const float* x0;
   int32_t x0_clips;
+  const float* x0;
   const float* noise;
   const float* mask;
   int32_t mask_clips;
@@ -539,10 +529,11 @@ typedef struct foley_step_hist_desc {
   const int32_t* starts;
   const float* weights;
   int32_t Ltot;
-} foley_step_hist_desc;
-int foley_op_solver_step_hist(const foley_step_hist_desc* hd, const float* pred, float* x, float* x_saved, float* d_acc,
-                              int clips, int C, int L, int ncfg, float guidance, const float* coef, int32_t* step_ptr,
-                              void* rows_out, int rows_dtype, void* stream);
+} foley_step_desc;
+#if defined(__cplusplus) && defined(__LP64__)
+static_assert(sizeof(foley_step_desc) == 168, "foley_step_desc: LP64 layout (the bindings mirror it field by field)");
+#endif
+int foley_op_solver_step(const foley_step_desc* d, void* stream);
 /* The rescale factors of one iteration: gd->clip_scale[b] = rescale * s_pos / s_cfg + (1 - rescale) from pred [ncfg*clips*L, C]
  * at iteration *step_ptr (gd->sched as above), C <= 256.  `work`: device scratch of at least foley_op_guidance_stats_work(clips, L)
  * floats.  Two launches, bit-identical on repetition. */

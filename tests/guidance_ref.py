@@ -3,9 +3,8 @@ of them, so the definition lives here.
 
 restated_loop   the sampling loop of oracle.sample_latents restated over two or three prediction halves with a per-iteration
                 schedule and the rescale factor (fp64 statistics), over O.dit_forward / O.SolverState / O.flow_sigmas.
-combine_ref     fp64 value and per-element bound of the combine; step_ref_and_bounds continues it through the solver update
-                (the lines of opcheck.solver_step_ref_and_bounds after the combine, with the combine's bound carried in).
-factor_ref      fp64 rescale factors and their bound.
+factor_ref      fp64 rescale factors and their bound, over opcheck.combine_ref (the guided value and its bound; the solver
+                update behind it is opcheck.step_ref_and_bounds).
 """
 import torch
 
@@ -65,54 +64,6 @@ def restated_loop(sd, heads, noise, text, uncond_text, clip, sync, steps, g_text
     return x
 
 
-# ----------------------------------------------------------------------------- the combine and the step behind it
-def combine_ref(pred, clips, L, ncfg, gv, gt, scale=None, e_scale=None):
-    """pred [ncfg clips L, C] -> (v [clips, C, L] fp64, e_v): the guided value and its bound from the fp32 operands.
-        two halves      v = u + g (c - u)                          e = 3 U32 (|u| + |g| (|c| + |u|))       (opcheck's term)
-        three halves    v = p0 + gv (p1 - p0) + gt (p2 - p1)       e = 3 U32 (|p0| + |gv| (|p1| + |p0|)) + 3 U32 (|a| + |gt| (|p2| + |p1|))
-                        with a = p0 + gv (p1 - p0): each added term is a difference (one rounding), a product and a sum (two
-                        roundings, fused or not) - three roundings relative to the magnitudes that enter, U32 twice the
-                        unit round-off.
-        factor          v f: one more rounding, U32 |v f|, plus the propagated |f| e and |v| e_f (e_f: the factor's own bound
-                        when the reference factor is not the device's).
-    gv / gt: the fp32 table entries as fp64 numbers; scale [clips] fp32 or None."""
-    P = pred.double().cpu().view(ncfg, clips, L, -1).transpose(2, 3)
-    if ncfg == 2:
-        u, c = P[0], P[1]
-        v, e = u + gv * (c - u), 3 * U32 * (u.abs() + abs(gv) * (c.abs() + u.abs()))
-    elif ncfg == 3:
-        p0, p1, p2 = P[0], P[1], P[2]
-        a = p0 + gv * (p1 - p0)
-        v = a + gt * (p2 - p1)
-        e = 3 * U32 * (p0.abs() + abs(gv) * (p1.abs() + p0.abs())) + 3 * U32 * (a.abs() + abs(gt) * (p2.abs() + p1.abs()))
-    else:
-        v, e = P[0], torch.zeros_like(P[0])
-    if scale is not None:
-        f = scale.double().cpu().view(-1, 1, 1)
-        ef = torch.zeros_like(f) if e_scale is None else e_scale.double().cpu().view(-1, 1, 1)
-        v, e = v * f, f.abs() * e + v.abs() * ef + U32 * (v * f).abs()
-    return v, e
-
-
-def step_ref_and_bounds(v, e_v, x, x_saved, d_acc, row):
-    """opcheck.solver_step_ref_and_bounds from the guided value on: same lines, same bounds, e_v supplied by combine_ref."""
-    w_new, w_acc, dt, w_store = (float(t) for t in row[:4].double())
-    flags = int(row[4])
-    xd = x.double().cpu()
-    acc = torch.zeros_like(xd) if (d_acc is None or flags & oc.STEP_ACC_RESET) else d_acc.double().cpu()
-    deriv = w_new * v + w_acc * acc
-    e_d = abs(w_new) * e_v + 2 * U32 * ((w_new * v).abs() + (w_acc * acc).abs())
-    base = x_saved.double().cpu() if flags & oc.STEP_USE_SAVED else xd
-    xn = base + deriv * dt
-    e_x = abs(dt) * e_d + 2 * U32 * (base.abs() + (deriv * dt).abs())
-    out = {"x": (xn, oc.Bound(e_x)), "flags": flags, "s_next": float(row[5].double())}
-    if d_acc is not None:
-        out["d_acc"] = (acc + w_store * v, oc.Bound(abs(w_store) * e_v + 2 * U32 * (acc.abs() + (w_store * v).abs())))
-    if x_saved is not None:
-        out["x_saved"] = xd if flags & oc.STEP_SAVE_X else x_saved.double().cpu()
-    return out
-
-
 # ----------------------------------------------------------------------------- the factor
 def _m2_and_bound(x, e_x):
     """x [clips, n] fp64, e_x its per-element bound -> (M2 = sum (x - mean)^2, bound) for an fp32 evaluation that centres every
@@ -134,7 +85,7 @@ def factor_ref(pred, clips, L, ncfg, gv, gt, phi, keep=None):
     limits the statistics to those elements - what a kernel that loses the others would compute.
     f = phi sqrt(M2_p / M2_v) + (1 - phi); with relative bounds r_p, r_v of the two sums the ratio of the deviations moves by at
     most (r_p + r_v) / (2 (1 - r_v)) relatively; division, square root, product and sum add 4 U32 of |phi ratio| + |1 - phi|."""
-    v, e_v = combine_ref(pred, clips, L, ncfg, gv, gt)
+    v, e_v = oc.combine_ref(pred, clips, L, ncfg, gv, gt)
     p = pred.double().cpu().view(ncfg, clips, L, -1).transpose(2, 3)[ncfg - 1]
     if keep is not None:
         sel = lambda t: torch.stack([t[b][keep[b]] for b in range(clips)])     # the same count in every clip

@@ -5,18 +5,15 @@ table_loop64         the table-driven loop in fp64 for a scalar ODE dx/dsigma = 
 rk4_reference        the same ODE by classical Runge-Kutta in fp64 (the order tests' truth).
 restated_loop        the fp32 CPU sampling loop over O.dit_forward with a velocity history, in the manner of
                      guidance_ref.restated_loop; with all history weights zero it is O.sample_latents(..., "euler").
-step_ref_and_bounds  opcheck.solver_step_ref_and_bounds continued through the history terms, from the guided value on.
+The per-element reference of one step with a history ring is opcheck.step_ref_and_bounds(..., ring, it).
 """
 import math
 
 import torch
 
 import guidance_ref as G
-import opcheck as oc
-from opcheck import U32
+from opcheck import STEP_HIST
 from oracle import foley_oracle as O
-
-STEP_HIST = 16
 
 
 # ----------------------------------------------------------------------------- scalar problems
@@ -101,38 +98,3 @@ def restated_loop(sd, heads, noise, text, uncond_text, clip, sync, steps, guidan
         x = x + deriv * dt
         hist.append(v)
     return x
-
-
-# ----------------------------------------------------------------------------- one step, element by element
-def step_ref_and_bounds(v, e_v, x, x_saved, d_acc, row, ring, it):
-    """guidance_ref.step_ref_and_bounds (opcheck.solver_step_ref_and_bounds from the guided value on) continued through the
-    history terms.  ring [slots, clips, C, L]: the device's ring as read back BEFORE the step (exact operands), `it` the iteration.
-        deriv = w_new v + w_acc acc                    e_d as there
-        deriv += c_j h_j  (flagged rows, c_j != 0)     e_d += 2 U32 (|deriv| + |c_j h_j|): the product and the sum, fused or not,
-                                                       relative to the magnitudes that enter; h_j = slot (it - j) mod slots
-        xn = base + deriv dt                           e_x = |dt| e_d + 2 U32 (|base| + |deriv dt|)
-    and the slot it mod slots receives v itself: bound e_v.  A term whose weight is zero is not read (the ring may hold NaN there).
-    Adds 'slot' (index), 'hist' ((v, Bound(e_v))) to the dict of guidance_ref.step_ref_and_bounds."""
-    w_new, w_acc, dt, w_store = (float(t) for t in row[:4].double())
-    flags = int(row[4])
-    slots = ring.shape[0]
-    xd = x.double().cpu()
-    acc = torch.zeros_like(xd) if (d_acc is None or flags & oc.STEP_ACC_RESET) else d_acc.double().cpu()
-    deriv = w_new * v + w_acc * acc
-    e_d = abs(w_new) * e_v + 2 * U32 * ((w_new * v).abs() + (w_acc * acc).abs())
-    if flags & STEP_HIST:
-        for j in (1, 2):
-            c = float(row[5 + j].double())
-            if c != 0.0:
-                term = c * ring[(it - j) % slots].double().cpu()
-                e_d = e_d + 2 * U32 * (deriv.abs() + term.abs())
-                deriv = deriv + term
-    base = x_saved.double().cpu() if flags & oc.STEP_USE_SAVED else xd
-    xn = base + deriv * dt
-    e_x = abs(dt) * e_d + 2 * U32 * (base.abs() + (deriv * dt).abs())
-    out = {"x": (xn, oc.Bound(e_x)), "flags": flags, "s_next": float(row[5].double()), "slot": it % slots, "hist": (v, oc.Bound(e_v))}
-    if d_acc is not None:
-        out["d_acc"] = (acc + w_store * v, oc.Bound(abs(w_store) * e_v + 2 * U32 * (acc.abs() + (w_store * v).abs())))
-    if x_saved is not None:
-        out["x_saved"] = xd if flags & oc.STEP_SAVE_X else x_saved.double().cpu()
-    return out

@@ -582,41 +582,81 @@ def qkv_head_ref_and_bound(y, gain, cos, sin, eps, out_dtype):
 
 
 # ----------------------------------------------------------------------------- solver steps (one iteration, seeded from the device)
-STEP_SAVE_X, STEP_USE_SAVED, STEP_ACC_RESET, STEP_BLEND = 1, 2, 4, 8
+STEP_SAVE_X, STEP_USE_SAVED, STEP_ACC_RESET, STEP_BLEND, STEP_HIST = 1, 2, 4, 8, 16
 
 
-def solver_step_ref_and_bounds(pred, x, x_saved, d_acc, row, ncfg, guidance):
-    """ONE iteration of the solver update in fp64 from the state the device holds (x, x_saved, d_acc [clips, C, L] copied back;
-    x_saved / d_acc may be None), pred [ncfg clips L, C], row = the iteration's coefficient row.  Returns a dict of
-    (ref64, Bound) for 'x' and 'd_acc' and ref64 alone for 'x_saved' (a copy: exact), with
-        v = u + g (c - u)                    e_v = 3 U32 (|u| + |g| (|c| + |u|))          (ncfg 1: v = pred, e_v = 0)
-        deriv = w_new v + w_acc acc          e_d = |w_new| e_v + 2 U32 (|w_new v| + |w_acc acc|)
-        xn = base + deriv dt                 e_x = |dt| e_d + 2 U32 (|base| + |deriv dt|)
-        d_acc' = acc + w_store v             e_a = |w_store| e_v + 2 U32 (|acc| + |w_store v|)
-    two roundings per line whether or not the product is contracted into an FMA (U32 is twice the unit round-off)."""
-    clips, C, L = x.shape
+def combine_ref(pred, clips, L, ncfg, gv, gt, scale=None, e_scale=None):
+    """pred [ncfg clips L, C] -> (v [clips, C, L] fp64, e_v): the guided value and its bound from the fp32 operands.
+        one half        v = pred                                   e = 0
+        two halves      v = u + g (c - u)                          e = 3 U32 (|u| + |g| (|c| + |u|))
+        three halves    v = p0 + gv (p1 - p0) + gt (p2 - p1)       e = 3 U32 (|p0| + |gv| (|p1| + |p0|)) + 3 U32 (|a| + |gt| (|p2| + |p1|))
+                        with a = p0 + gv (p1 - p0): each added term is a difference (one rounding), a product and a sum (two
+                        roundings, fused or not) - three roundings relative to the magnitudes that enter, U32 twice the
+                        unit round-off.
+        factor          v f: one more rounding, U32 |v f|, plus the propagated |f| e and |v| e_f (e_f: the factor's own bound
+                        when the reference factor is not the device's).
+    gv / gt: the fp32 table entries (or f32(guidance)) as fp64 numbers; scale [clips] fp32 or None."""
+    P = pred.double().cpu().view(ncfg, clips, L, -1).transpose(2, 3)
+    if ncfg == 2:
+        u, c = P[0], P[1]
+        v, e = u + gv * (c - u), 3 * U32 * (u.abs() + abs(gv) * (c.abs() + u.abs()))
+    elif ncfg == 3:
+        p0, p1, p2 = P[0], P[1], P[2]
+        a = p0 + gv * (p1 - p0)
+        v = a + gt * (p2 - p1)
+        e = 3 * U32 * (p0.abs() + abs(gv) * (p1.abs() + p0.abs())) + 3 * U32 * (a.abs() + abs(gt) * (p2.abs() + p1.abs()))
+    else:
+        v, e = P[0], torch.zeros_like(P[0])
+    if scale is not None:
+        f = scale.double().cpu().view(-1, 1, 1)
+        ef = torch.zeros_like(f) if e_scale is None else e_scale.double().cpu().view(-1, 1, 1)
+        v, e = v * f, f.abs() * e + v.abs() * ef + U32 * (v * f).abs()
+    return v, e
+
+
+def step_ref_and_bounds(v, e_v, x, x_saved, d_acc, row, ring=None, it=None):
+    """ONE iteration of the solver update in fp64 from the guided value (v, e_v of combine_ref) and the state the device holds (x,
+    x_saved, d_acc [clips, C, L] copied back; x_saved / d_acc may be None), row = the iteration's coefficient row.  Returns a dict
+    of (ref64, Bound) for 'x' and 'd_acc' and ref64 alone for 'x_saved' (a copy: exact), with
+        deriv = w_new v + w_acc acc                    e_d = |w_new| e_v + 2 U32 (|w_new v| + |w_acc acc|)
+        deriv += c_j h_j  (flagged rows, c_j != 0)     e_d += 2 U32 (|deriv| + |c_j h_j|): the product and the sum relative to
+                                                       the magnitudes that enter; h_j = slot (it - j) mod slots
+        xn = base + deriv dt                           e_x = |dt| e_d + 2 U32 (|base| + |deriv dt|)
+        d_acc' = acc + w_store v                       e_a = |w_store| e_v + 2 U32 (|acc| + |w_store v|)
+    two roundings per line whether or not the product is contracted into an FMA (U32 is twice the unit round-off).
+    ring [slots, clips, C, L] (or None: no history): the device's ring as read back BEFORE the step (exact operands), `it` the
+    iteration.  A term whose weight is zero is not read (the ring may hold NaN there); the slot it mod slots receives v itself,
+    bound e_v: with a ring the dict also has 'slot' (index) and 'hist' ((v, Bound(e_v)))."""
     w_new, w_acc, dt, w_store = (float(t) for t in row[:4].double())
     flags = int(row[4])
-    P = pred.double().cpu().view(ncfg, clips, L, C).transpose(2, 3)
-    if ncfg == 2:
-        g = f32(guidance)
-        u, c = P[0], P[1]
-        v, e_v = u + g * (c - u), 3 * U32 * (u.abs() + abs(g) * (c.abs() + u.abs()))
-    else:
-        v, e_v = P[0], torch.zeros_like(P[0])
     xd = x.double().cpu()
     acc = torch.zeros_like(xd) if (d_acc is None or flags & STEP_ACC_RESET) else d_acc.double().cpu()
     deriv = w_new * v + w_acc * acc
     e_d = abs(w_new) * e_v + 2 * U32 * ((w_new * v).abs() + (w_acc * acc).abs())
+    if ring is not None and flags & STEP_HIST:
+        for j in (1, 2):
+            c = float(row[5 + j].double())
+            if c != 0.0:
+                term = c * ring[(it - j) % ring.shape[0]].double().cpu()
+                e_d = e_d + 2 * U32 * (deriv.abs() + term.abs())
+                deriv = deriv + term
     base = x_saved.double().cpu() if flags & STEP_USE_SAVED else xd
     xn = base + deriv * dt
     e_x = abs(dt) * e_d + 2 * U32 * (base.abs() + (deriv * dt).abs())
     out = {"x": (xn, Bound(e_x)), "flags": flags, "s_next": float(row[5].double())}
+    if ring is not None:
+        out["slot"], out["hist"] = it % ring.shape[0], (v, Bound(e_v))
     if d_acc is not None:
         out["d_acc"] = (acc + w_store * v, Bound(abs(w_store) * e_v + 2 * U32 * (acc.abs() + (w_store * v).abs())))
     if x_saved is not None:
         out["x_saved"] = xd if flags & STEP_SAVE_X else x_saved.double().cpu()
     return out
+
+
+def solver_step_ref_and_bounds(pred, x, x_saved, d_acc, row, ncfg, guidance):
+    """step_ref_and_bounds behind the two-half (or one-half) combine with the scalar `guidance`, pred [ncfg clips L, C]."""
+    v, e_v = combine_ref(pred, x.shape[0], x.shape[2], ncfg, f32(guidance), f32(guidance))
+    return step_ref_and_bounds(v, e_v, x, x_saved, d_acc, row)
 
 
 def edit_blend_ref_and_bound(xn, e_x, s_next, x0, noise, mask):

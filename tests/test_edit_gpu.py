@@ -65,7 +65,7 @@ def test_blend_step_op(dev, solver, steps, rows_dtype, x0_clips, mask_kind):
         xp, xsp, dap = x.clone(), x_saved.clone(), d_acc.clone()
         step_p.fill_(it)
         rt.op_solver_step(pred, xp, xsp, dap, ncfg, guid, coef, step_p, rows_p)          # the plain step on the same state
-        rt.op_solver_step_edit(pred, x, x_saved, d_acc, ncfg, guid, coef, step, rows, x0, noise, mask)
+        rt.op_solver_step(pred, x, x_saved, d_acc, ncfg, guid, coef, step, rows, edit=(x0, noise, mask))
         torch.cuda.synchronize()
         assert int(step) == it + 1
         for got, want in zip((x, x_saved, d_acc), ref):

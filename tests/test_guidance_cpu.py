@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import guidance_ref as G
+from abi_pin import assert_abi_version
 from conftest import ROOT, rel_err
 from foley_amd import nodes
 from foley_amd.host import cond_sets, config as C, runtime as rt, sampler, synth, tables
@@ -153,11 +154,11 @@ def test_node_and_spec_refusals():
 def test_new_symbols_declared_and_exported():
     hdr = open(os.path.join(ROOT, "include", "foley_hip.h")).read()
     lib = rt.load_library()
-    for name in ("foley_set_guidance", "foley_op_solver_step_guided", "foley_op_solver_step_edit_guided",
-                 "foley_op_solver_step_windows_guided", "foley_op_guidance_stats", "foley_op_guidance_stats_work"):
+    for name in ("foley_set_guidance", "foley_op_solver_step", "foley_op_guidance_stats", "foley_op_guidance_stats_work"):
         assert re.search(r"\b(int|int64_t)\s+" + name + r"\s*\(", hdr), name
         assert name in rt.EXPORTED_SYMBOLS
         assert getattr(lib, name) is not None
-    assert "typedef struct foley_guidance_desc" in hdr
-    assert lib.foley_abi_version() == rt.ABI_VERSION == 12
+    assert "typedef struct foley_guidance_desc" in hdr and "typedef struct foley_step_desc" in hdr
+    assert re.search(r"\bfoley_guidance_desc gd;", hdr)          # the step's descriptor carries the guidance descriptor
+    assert_abi_version()
     assert lib.foley_op_guidance_stats_work(1, 50) == 2 * 5 and lib.foley_op_guidance_stats_work(8, 3000) == 8 * 94 * 5

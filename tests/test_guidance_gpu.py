@@ -6,6 +6,7 @@ import ctypes
 import pytest
 import torch
 
+from abi_pin import assert_abi_version
 import guidance_ref as G
 from conftest import rel_err
 from foley_amd.host import audio_edit, config as C, long_form, runtime as rt, sampler, synth, tables
@@ -200,7 +201,7 @@ def test_graph_keyed_on_the_guidance_state(tiny):
     s1 = state()
     _run(model, dac, conds[:1], noise, "euler", 3.5, None, True)
     assert state()[0] == s1[0] + 1
-    assert lib.foley_abi_version() == 12
+    assert_abi_version()
 
 
 def test_set_guidance_refusals(tiny, dev):

@@ -4,7 +4,7 @@ and guard bands (tests/opcheck.py, tests/guidance_ref.py).
 The step forms run with a guidance descriptor - a schedule table whose row changes every iteration and, on every second
 iteration, per-clip factors - for two and three halves, into guarded buffers; every element is held against the bound of the step
 with the combine's extra roundings, the staged rows bit for bit against the device's own x in all ncfg copies.  With two halves, a
-constant table and no factors the three forms must give the bits of the entries without a descriptor; under a varying table with
+constant table and no factors the three forms must give the bits of the calls without a descriptor; under a varying table with
 factors, for one to three halves, the edit form with nothing to keep and the windows form with one window must give the bits of
 the plain form.  The factors are held
 against fp64 under the any-order fp32 bound of the two centred sums; because that bound cannot see one lost element in smooth
@@ -16,7 +16,7 @@ import guidance_ref as G
 import opcheck as oc
 from conftest import record_parity
 from foley_amd.host import long_form, runtime as rt, tables
-from test_rowops_elementwise_gpu import ALL3, DTS, GUIDANCE, SOLVER_ITERS, STEP_SHAPES, _rand, _StepState
+from step_harness import ALL3, DTS, GUIDANCE, SOLVER_ITERS, STEP_SHAPES, StepState, _rand
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +38,10 @@ def _factors(clips, seed):
 
 
 def _guided_ref(pred, st, coef_row, sched_row, ncfg, scale):
-    x, xs, da = st.snapshot()
+    x, xs, da, _ = st.snapshot()
     clips, _, L = x.shape
-    v, e_v = G.combine_ref(pred, clips, L, ncfg, float(sched_row[0].double()), float(sched_row[1].double()), scale)
-    return G.step_ref_and_bounds(v, e_v, x, xs, da, coef_row)
+    v, e_v = oc.combine_ref(pred, clips, L, ncfg, float(sched_row[0].double()), float(sched_row[1].double()), scale)
+    return oc.step_ref_and_bounds(v, e_v, x, xs, da, coef_row)
 
 
 class _Desc:
@@ -72,7 +72,7 @@ class _Desc:
 def test_guided_step_elementwise(dev, clips, C, L, solver, ncfg, dt):
     n = SOLVER_ITERS[solver]
     coef, sched = tables.solver_table(tables.sigma_grid(n), solver, n), _sched(n)
-    st = _StepState(dev, clips, C, L, ncfg, DTS[dt], 200)
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 200)
     d = _Desc(dev, sched, clips, 201)
     cd = coef.to(dev)
     worst = 0.0
@@ -80,7 +80,7 @@ def test_guided_step_elementwise(dev, clips, C, L, solver, ncfg, dt):
         pred = _rand((ncfg * clips * L, C), 202 + it)
         with_scale = it % 2 == 1
         r = _guided_ref(pred, st, coef[it], sched[it], ncfg, d.scale if with_scale else None)
-        rt.op_solver_step_guided(d.desc(with_scale), pred.to(dev), *st.args[:3], ncfg, GUIDANCE, cd, st.ctr.view.view(1), st.args[3])
+        st.step(pred, cd, gd=d.desc(with_scale))
         what = f"guided step {solver} {clips}x{C}x{L} ncfg {ncfg} {dt} it {it}"
         worst = max(worst, st.check(it, r, *r["x"], what))
         d.check(sched, what)
@@ -100,7 +100,7 @@ def test_guided_step_edit_elementwise(dev, clips, C, L, solver, ncfg, dt):
     mask = torch.rand(clips, L, generator=torch.Generator().manual_seed(212))
     mask[:, : L // 3] = 0.0
     mask[:, L // 3: L // 2] = 1.0
-    st = _StepState(dev, clips, C, L, ncfg, DTS[dt], 213)
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 213)
     d = _Desc(dev, sched, clips, 214)
     cd, edit = coef.to(dev), (x0.to(dev), noise.to(dev), mask.to(dev))
     worst = 0.0
@@ -111,8 +111,7 @@ def test_guided_step_edit_elementwise(dev, clips, C, L, solver, ncfg, dt):
         ref, bound = r["x"]
         if r["flags"] & oc.STEP_BLEND:
             ref, bound = oc.edit_blend_ref_and_bound(ref, bound.e, r["s_next"], x0, noise, mask)
-        rt.op_solver_step_guided(d.desc(with_scale), pred.to(dev), *st.args[:3], ncfg, GUIDANCE, cd, st.ctr.view.view(1), st.args[3],
-                                 edit=edit)
+        st.step(pred, cd, gd=d.desc(with_scale), edit=edit)
         what = f"guided step_edit {solver} {clips}x{C}x{L} ncfg {ncfg} {dt} it {it}"
         worst = max(worst, st.check(it, r, ref, bound, what))
         d.check(sched, what)
@@ -131,7 +130,7 @@ def test_guided_step_windows_elementwise(dev, _clips, C, L, solver, ncfg, dt):
     starts = [0, L // 3, 2 * L // 3] if L >= 3 else [0, L, 2 * L]
     plan = long_form.WindowPlan.from_frames(starts, L)
     n_win, clips = plan.n_win, 2 * plan.n_win
-    st = _StepState(dev, clips, C, L, ncfg, DTS[dt], 220)
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 220)
     d = _Desc(dev, sched, clips, 221)
     cd, sd, wd = coef.to(dev), torch.tensor(starts, dtype=torch.int32, device=dev), plan.weights.to(dev)
     worst = 0.0
@@ -143,8 +142,7 @@ def test_guided_step_windows_elementwise(dev, _clips, C, L, solver, ncfg, dt):
         if r["flags"] & oc.STEP_BLEND:
             ref, e, _, _, _ = oc.windows_mean_ref_and_bound(ref, bound.e, n_win, starts, plan.weights)
             bound = oc.Bound(e)
-        rt.op_solver_step_guided(d.desc(with_scale), pred.to(dev), *st.args[:3], ncfg, GUIDANCE, cd, st.ctr.view.view(1), st.args[3],
-                                 windows=(sd, wd, plan.Ltot))
+        st.step(pred, cd, gd=d.desc(with_scale), windows=(sd, wd, plan.Ltot))
         what = f"guided step_windows {solver} C{C} L{L} starts {starts} ncfg {ncfg} {dt} it {it}"
         worst = max(worst, st.check(it, r, ref, bound, what))
         d.check(sched, what)
@@ -163,27 +161,26 @@ def test_constant_schedule_keeps_the_bits(dev, clips, C, L, form, dt):
     sched[:, 1] = -3.0                       # two halves read column 0 only
     starts = [0, L // 3]
     plan = long_form.WindowPlan.from_frames(starts, L)
-    kw, old = {}, rt.op_solver_step
+    kw = {}
     if form == "edit":
         x0, noise, mask = _rand((1, C, L), 230, 0.7).to(dev), _rand((clips, C, L), 231).to(dev), torch.rand(L, generator=torch.Generator().manual_seed(232)).to(dev)
-        kw, old = {"edit": (x0, noise, mask)}, lambda *a: rt.op_solver_step_edit(*a, x0, noise, mask)
+        kw = {"edit": (x0, noise, mask)}
     elif form == "windows":
         sd, wd = torch.tensor(starts, dtype=torch.int32, device=dev), plan.weights.to(dev)
-        kw, old = {"windows": (sd, wd, plan.Ltot)}, lambda *a: rt.op_solver_step_windows(*a, sd, wd, plan.Ltot)
-    a, b = _StepState(dev, clips, C, L, ncfg, DTS[dt], 233), _StepState(dev, clips, C, L, ncfg, DTS[dt], 233)
+        kw = {"windows": (sd, wd, plan.Ltot)}
+    a, b = StepState(dev, clips, C, L, ncfg, DTS[dt], 233), StepState(dev, clips, C, L, ncfg, DTS[dt], 233)
     gd = rt.guidance_desc(sched, None)
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 234 + it).to(dev)
-        old(pred, *a.args[:3], ncfg, GUIDANCE, coef, a.ctr.view.view(1), a.args[3])
-        rt.op_solver_step_guided(gd, pred, *b.args[:3], ncfg, GUIDANCE, coef, b.ctr.view.view(1), b.args[3], **kw)
+        a.step(pred, coef, **kw)                    # no guidance option at all
+        b.step(pred, coef, gd=gd, **kw)
         for ga, gb, name in zip((a.gx, a.gs, a.ga, a.gr, a.ctr), (b.gx, b.gs, b.ga, b.gr, b.ctr), ("x", "x_saved", "d_acc", "rows_out", "counter")):
             oc.assert_bits_equal(gb.view, ga.view, f"{form} {dt} it {it} {name}: descriptor with a constant table vs none")
             gb.check(f"{form} {name}")
-    # a null descriptor is the old entry as well
-    c = _StepState(dev, clips, C, L, ncfg, DTS[dt], 233)
+    # an explicit gd=None is the call without the option as well
+    c = StepState(dev, clips, C, L, ncfg, DTS[dt], 233)
     for it in range(n):
-        rt.op_solver_step_guided(None, _rand((ncfg * clips * L, C), 234 + it).to(dev), *c.args[:3], ncfg, GUIDANCE, coef, c.ctr.view.view(1),
-                                 c.args[3], **kw)
+        c.step(_rand((ncfg * clips * L, C), 234 + it).to(dev), coef, gd=None, **kw)
     oc.assert_bits_equal(c.gx.view, a.gx.view, f"{form} {dt}: null descriptor")
 
 
@@ -204,13 +201,12 @@ def test_forms_agree_under_a_descriptor(dev, clips, C, L, solver, ncfg, dt):
     sd, wd = torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, L, dtype=torch.float32, device=dev)
     forms = {"plain": {}, "edit, no mask": {"edit": (x0, noise, None)}, "edit, mask of ones": {"edit": (x0, noise, ones)},
              "one window": {"windows": (sd, wd, L)}}
-    states = {f: _StepState(dev, clips, C, L, ncfg, DTS[dt], 242) for f in forms}
+    states = {f: StepState(dev, clips, C, L, ncfg, DTS[dt], 242) for f in forms}
     d = _Desc(dev, sched, clips, 243)
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 244 + it).to(dev)
         for f, kw in forms.items():
-            st = states[f]
-            rt.op_solver_step_guided(d.desc(it % 2 == 0), pred, *st.args[:3], ncfg, GUIDANCE, coef, st.ctr.view.view(1), st.args[3], **kw)
+            states[f].step(pred, coef, gd=d.desc(it % 2 == 0), **kw)
         a = states["plain"]
         assert int(a.ctr.view.item()) == it + 1
         for f in list(forms)[1:]:

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from abi_pin import assert_abi_version
 from conftest import ROOT, golden, rel_err
 from foley_amd.host import config as C, packers, runtime as rt, sampler, synth, tables
 from oracle import foley_oracle as O
@@ -213,7 +214,7 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(rt.EXPORTED_SYMBOLS), declared ^ set(rt.EXPORTED_SYMBOLS)
     for name in declared:
         assert getattr(lib, name) is not None
-    assert lib.foley_abi_version() == rt.ABI_VERSION == 12
+    assert_abi_version()
 
 
 def test_no_cpu_fallback():

@@ -14,6 +14,7 @@ import torch
 from foley_amd import nodes
 from foley_amd.host import config as C, runtime as rt, sampler
 import loudness_ref as LR
+from abi_pin import assert_abi_version
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FS = 48000
@@ -186,7 +187,7 @@ def test_abi_declares_the_loudness_entries():
     for name in NAMES:
         assert name in rt.EXPORTED_SYMBOLS and re.search(r"\bint %s\s*\(" % name, hdr)
         assert getattr(lib, name) is not None
-    assert "#define FOLEY_ABI_VERSION 12" in hdr and rt.ABI_VERSION == 12 and lib.foley_abi_version() == 12
+    assert_abi_version()
     for op in ("op_loudness_energy", "op_loudness_gate", "op_true_peak", "op_loudness_apply"):
         assert callable(getattr(rt, op))
     src = open(os.path.join(ROOT, "comfyui-hunyuanvideo-foley_amd", "csrc", "loudness.hip")).read()

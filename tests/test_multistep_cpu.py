@@ -10,6 +10,7 @@ import types
 import pytest
 import torch
 
+from abi_pin import assert_abi_version
 import multistep_ref as M
 from foley_amd import nodes
 from foley_amd.host import config as C, long_form, runtime as rt, sampler, synth, tables
@@ -159,20 +160,37 @@ def test_spec_refusals():
 def test_abi_declares_the_multistep_entries():
     hdr = open(os.path.join(ROOT, "include", "foley_hip.h")).read()
     lib = rt.load_library()
-    for name in ("foley_set_multistep", "foley_op_solver_step_hist"):
+    for name in ("foley_set_multistep", "foley_op_solver_step"):
         assert name in rt.EXPORTED_SYMBOLS and re.search(r"\bint %s\s*\(" % name, hdr)
         assert getattr(lib, name) is not None
-    assert "#define FOLEY_ABI_VERSION 12" in hdr and rt.ABI_VERSION == 12 and lib.foley_abi_version() == 12
+    assert_abi_version()
     assert "#define FOLEY_STEP_HIST 16" in hdr and tables.STEP_HIST == 16
-    assert callable(rt.op_solver_step_hist) and callable(rt.FoleyContext.set_multistep)
+    assert callable(rt.op_solver_step) and callable(rt.FoleyContext.set_multistep)
     rc = lib.foley_set_multistep(None, 2, None)
     assert rc != 0 and lib.foley_last_error()
-    assert lib.foley_op_solver_step_hist(None, *([None] * 4), 1, 1, 1, 1, 1.0, None, None, None, 0, None) != 0
+    assert lib.foley_op_solver_step(None, None) != 0 and b"descriptor" in lib.foley_last_error()
+    assert lib.foley_op_solver_step(ctypes.byref(rt.StepDescC(hist_slots=1)), None) != 0          # slots without a ring: refused before any launch
     assert b"ring" in lib.foley_last_error()
-    assert ctypes.sizeof(rt.StepHistDescC) == 88            # the header's struct on LP64: pointers 8-aligned, int32 fields padded
+    assert "typedef struct foley_step_desc" in hdr
+    size = int(re.search(r"static_assert\(sizeof\(foley_step_desc\) == (\d+),", hdr).group(1))
+    assert ctypes.sizeof(rt.StepDescC) == size == 168       # the header's struct on LP64: pointers 8-aligned, int32 fields paired
     src = open(os.path.join(ROOT, "comfyui-hunyuanvideo-foley_amd", "csrc", "rowops.hip")).read()
     assert "solver_step_hist_kernel" in src and "getenv" not in src
     assert "oracle" not in open(os.path.join(ROOT, "comfyui-hunyuanvideo-foley_amd", "host", "sampler.py")).read()
+
+
+def test_earlier_step_names_forward_to_the_one_wrapper(monkeypatch):
+    seen = []
+    monkeypatch.setattr(rt, "op_solver_step", lambda *a, **kw: seen.append((a, {k: v for k, v in kw.items() if v is not None})))
+    core = tuple("pred x x_saved d_acc ncfg guidance coef step_ptr rows_out".split())
+    rt.op_solver_step_edit(*core, "x0", "noise")
+    rt.op_solver_step_edit(*core, "x0", "noise", "mask")
+    rt.op_solver_step_windows(*core, "starts", "weights", 7)
+    rt.op_solver_step_guided("gd", *core, edit=("x0", "noise", None))
+    rt.op_solver_step_hist("ring", *core, gd="gd", windows=("starts", "weights", 7), slots=2)
+    assert seen == [(core, dict(edit=("x0", "noise", None))), (core, dict(edit=("x0", "noise", "mask"))),
+                    (core, dict(windows=("starts", "weights", 7))), (core, dict(gd="gd", edit=("x0", "noise", None))),
+                    (core, dict(gd="gd", hist="ring", slots=2, windows=("starts", "weights", 7)))]
 
 
 # ----------------------------------------------------------------------------- plumbing: the sampler entry points

@@ -6,6 +6,7 @@ import ctypes
 import pytest
 import torch
 
+from abi_pin import assert_abi_version
 import multistep_ref as M
 from conftest import record_parity, rel_err
 from foley_amd.host import audio_edit, config as C, long_form, runtime as rt, sampler, synth, tables
@@ -204,4 +205,4 @@ def test_set_multistep_refusals(tiny, dev):
     assert lib.foley_set_multistep(fresh._h, 2, None) == -4                                   # FOLEY_ERR_STATE
     with pytest.raises(rt.FoleyRuntimeError, match="foley_prepare has not been called"):
         fresh.set_multistep(2)
-    assert lib.foley_abi_version() == 12
+    assert_abi_version()

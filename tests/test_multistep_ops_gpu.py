@@ -1,27 +1,20 @@
-"""The history instantiations of the solver step (foley_op_solver_step_hist), element by element: every iteration of a run of
-order + 1 iterations from a NaN-filled ring against tests/multistep_ref.py::step_ref_and_bounds - x, the written slot, the staged
-rows - with the untouched slot and all guard bands bit for bit; the plain, edit and windows forms, the guidance descriptor, the
-zero-weight table against foley_op_solver_step, the refusals."""
+"""The history instantiations of the solver step (foley_op_solver_step with a ring), element by element: every iteration of a
+run of order + 1 iterations from a NaN-filled ring against opcheck.step_ref_and_bounds(..., ring, it) - x, the written slot, the
+staged rows - with the untouched slot and all guard bands bit for bit; the plain, edit and windows forms, the guidance descriptor,
+the zero-weight table against the step without a ring, the refusals."""
 import pytest
 import torch
 
-import guidance_ref as G
-import multistep_ref as M
 import opcheck as oc
 from conftest import record_parity
 from foley_amd.host import long_form, runtime as rt, tables
+from step_harness import DTS, GUIDANCE, StepState, _rand
 
 pytestmark = pytest.mark.gpu
 
-DTS = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 SHAPES = [(2, 128, 50), (3, 128, 33), (1, 128, 1), (2, 40, 65)]      # ragged 32-tiles over L and over C, the single frame
-GUIDANCE = 4.5
 NAN = float("nan")
 _WORST = {}
-
-
-def _rand(shape, seed, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 def _rec(family, ratio):
@@ -38,50 +31,11 @@ def _table(order, n, edit=False):
     return tables.solver_table(sig, "euler", n, multistep_order=order)
 
 
-class _State:
-    """Guarded device state of one run: x (and x_saved / d_acc when `saved`), the NaN-filled ring, the staged rows, the counter."""
-
-    def __init__(self, dev, clips, C, L, ncfg, dtype, slots, seed, saved):
-        f = lambda s: self._filled((clips, C, L), dev, _rand((clips, C, L), s))
-        self.dev, self.ncfg, self.dtype, self.slots = dev, ncfg, dtype, slots
-        self.gx = f(seed)
-        self.gs, self.ga = (f(seed + 1), f(seed + 2)) if saved else (None, None)
-        self.gh = oc.guarded((slots, clips, C, L), torch.float32, dev, rows=(1, 1))      # NaN inside, guard slabs around
-        self.gr = oc.guarded((ncfg * clips * L, C), dtype, dev, rows=(2, 3))
-        self.ctr = oc.guarded((1, 1), torch.int32, dev, rows=(1, 1), fill=0)
-
-    @staticmethod
-    def _filled(shape, dev, src):
-        g = oc.guarded(shape, torch.float32, dev, rows=(1, 1))
-        g.view.copy_(src.to(dev))
-        return g
-
-    def snapshot(self):
-        c = lambda g: g.view.cpu().clone() if g is not None else None
-        return c(self.gx), c(self.gs), c(self.ga), c(self.gh)
-
-    def step(self, pred, coef_dev, **kw):
-        v = lambda g: g.view if g is not None else None
-        rt.op_solver_step_hist(self.gh.view, pred.to(self.dev), self.gx.view, v(self.gs), v(self.ga), self.ncfg, GUIDANCE, coef_dev,
-                               self.ctr.view.view(1), self.gr.view, **kw)
-
-    def check(self, it, r, x_ref, x_bound, ring_before, what):
-        worst = oc.assert_elementwise(self.gx.view, x_ref, x_bound, what + " x")
-        ring = self.gh.view.cpu()
-        worst = max(worst, oc.assert_elementwise(ring[r["slot"]], *r["hist"], what + " written slot"))
-        for s in range(self.slots):
-            if s != r["slot"]:
-                oc.assert_bits_equal(ring[s], ring_before[s], what + f" untouched slot {s}")
-        if self.gs is not None:
-            oc.assert_bits_equal(self.gs.view, r["x_saved"].float(), what + " x_saved")
-            worst = max(worst, oc.assert_elementwise(self.ga.view, *r["d_acc"], what + " d_acc"))
-        assert int(self.ctr.view.item()) == it + 1, what
-        oc.assert_bits_equal(self.gr.view, oc.rows_of(self.gx.view, self.ncfg, self.dtype), what + " rows_out (every CFG copy)")
-        self.gr.view.fill_(NAN)
-        for g in (self.gx, self.gs, self.ga, self.gh, self.gr, self.ctr):
-            if g is not None:
-                g.check(what)
-        return worst
+def _hist_ref(pred, st, coef_row, it, gv=oc.f32(GUIDANCE), gt=oc.f32(GUIDANCE), scale=None):
+    """(the fp64 step with the history terms from the state `st` holds now, the ring as it is before the step)."""
+    x, xs, da, ring = st.snapshot()
+    v, e_v = oc.combine_ref(pred, x.shape[0], x.shape[2], st.ncfg, gv, gt, scale)
+    return oc.step_ref_and_bounds(v, e_v, x, xs, da, coef_row, ring, it), ring
 
 
 def test_tables_carry_what_the_cases_claim():
@@ -102,16 +56,14 @@ def test_step_hist_elementwise(dev, clips, C, L, order, ncfg, dt):
     full history and - order 3 - reads v_{n-2} from the slot it then overwrites; the fourth iteration of order 3 wraps the ring."""
     n = order + 1
     coef = _table(order, n)
-    st = _State(dev, clips, C, L, ncfg, DTS[dt], order - 1, 300, saved=ncfg == 2)
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 300, saved=ncfg == 2, slots=order - 1)
     cd = coef.to(dev)
     worst = 0.0
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 301 + it)
-        x, xs, da, ring = st.snapshot()
-        v, e_v = G.combine_ref(pred, clips, L, ncfg, oc.f32(GUIDANCE), oc.f32(GUIDANCE))
-        r = M.step_ref_and_bounds(v, e_v, x, xs, da, coef[it], ring, it)
+        r, ring = _hist_ref(pred, st, coef[it], it)
         st.step(pred, cd)
-        worst = max(worst, st.check(it, r, *r["x"], ring, f"step_hist order {order} {clips}x{C}x{L} ncfg {ncfg} {dt} it {it}"))
+        worst = max(worst, st.check(it, r, *r["x"], f"step_hist order {order} {clips}x{C}x{L} ncfg {ncfg} {dt} it {it}", ring))
     _rec(f"order{order}", worst)
 
 
@@ -124,15 +76,13 @@ def test_step_hist_three_halves_with_descriptor(dev, order):
     scale = torch.tensor([0.8, 1.0, 1.15])
     sd, cs = sched.to(dev), scale.to(dev)
     gd = rt.guidance_desc(sd, cs)
-    st = _State(dev, clips, C, L, ncfg, torch.bfloat16, order - 1, 320, saved=False)
+    st = StepState(dev, clips, C, L, ncfg, torch.bfloat16, 320, saved=False, slots=order - 1)
     cd = coef.to(dev)
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 321 + it)
-        x, xs, da, ring = st.snapshot()
-        v, e_v = G.combine_ref(pred, clips, L, ncfg, float(sched[it, 0].double()), float(sched[it, 1].double()), scale)
-        r = M.step_ref_and_bounds(v, e_v, x, xs, da, coef[it], ring, it)
+        r, ring = _hist_ref(pred, st, coef[it], it, float(sched[it, 0].double()), float(sched[it, 1].double()), scale)
         st.step(pred, cd, gd=gd)
-        _rec(f"order{order}.guided", st.check(it, r, *r["x"], ring, f"step_hist guided order {order} it {it}"))
+        _rec(f"order{order}.guided", st.check(it, r, *r["x"], f"step_hist guided order {order} it {it}", ring))
     assert torch.equal(cs.cpu(), scale) and torch.equal(sd.cpu(), sched)
 
 
@@ -150,17 +100,15 @@ def test_step_hist_edit_elementwise(dev, clips, C, L, order, dt):
     mask = torch.rand(clips, L, generator=torch.Generator().manual_seed(333))
     mask[:, : L // 3] = 0.0
     mask[:, L // 3: L // 2] = 1.0
-    st = _State(dev, clips, C, L, ncfg, DTS[dt], order - 1, 334, saved=False)
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 334, saved=False, slots=order - 1)
     cd, ops = coef.to(dev), (x0.to(dev), noise.to(dev), mask.to(dev))
     worst = 0.0
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 335 + it)
-        x, xs, da, ring = st.snapshot()
-        v, e_v = G.combine_ref(pred, clips, L, ncfg, oc.f32(GUIDANCE), oc.f32(GUIDANCE))
-        r = M.step_ref_and_bounds(v, e_v, x, xs, da, coef[it], ring, it)
+        r, ring = _hist_ref(pred, st, coef[it], it)
         ref, bound = oc.edit_blend_ref_and_bound(r["x"][0], r["x"][1].e, r["s_next"], x0, noise, mask)
         st.step(pred, cd, edit=ops)
-        worst = max(worst, st.check(it, r, ref, bound, ring, f"step_hist edit order {order} {clips}x{C}x{L} {dt} it {it}"))
+        worst = max(worst, st.check(it, r, ref, bound, f"step_hist edit order {order} {clips}x{C}x{L} {dt} it {it}", ring))
     _rec(f"order{order}.edit", worst)
 
 
@@ -177,14 +125,12 @@ def test_step_hist_windows_elementwise(dev, order, dt):
     coef = _table(order, n, edit=True)
     coef[n - 1, 4] = float(int(coef[n - 1, 4]) & ~tables.STEP_BLEND)          # a history row without the blend
     coef[n - 1, 5] = 0.0
-    st = _State(dev, clips, C, L, ncfg, DTS[dt], order - 1, 350, saved=False)
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 350, saved=False, slots=order - 1)
     cd, sd, wd = coef.to(dev), torch.tensor(starts, dtype=torch.int32, device=dev), plan.weights.to(dev)
     worst = 0.0
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 351 + it)
-        x, xs, da, ring = st.snapshot()
-        v, e_v = G.combine_ref(pred, clips, L, ncfg, oc.f32(GUIDANCE), oc.f32(GUIDANCE))
-        r = M.step_ref_and_bounds(v, e_v, x, xs, da, coef[it], ring, it)
+        r, ring = _hist_ref(pred, st, coef[it], it)
         ref, bound = r["x"]
         blend = bool(r["flags"] & oc.STEP_BLEND)
         assert blend == (it < n - 1)
@@ -193,7 +139,7 @@ def test_step_hist_windows_elementwise(dev, order, dt):
             bound = oc.Bound(e)
         st.step(pred, cd, windows=(sd, wd, plan.Ltot))
         what = f"step_hist windows order {order} {dt} it {it}"
-        worst = max(worst, st.check(it, r, ref, bound, ring, what))
+        worst = max(worst, st.check(it, r, ref, bound, what, ring))
         if blend:                        # the two windows agree on the frames both cover, bit for bit
             xg = st.gx.view.cpu().view(2, n_win, C, L)
             oc.assert_bits_equal(xg[:, 0, :, 20:], xg[:, 1, :, :13], what + " windows agree")
@@ -205,7 +151,7 @@ def test_step_hist_windows_elementwise(dev, order, dt):
 @pytest.mark.parametrize("dt", list(DTS))
 def test_zero_history_weights_are_the_plain_step(dev, dt, flagged):
     """The plain euler table through the history kernel (two slots of NaN), also with STEP_HIST set on rows whose weights are
-    zero: x and the staged rows carry the bits of foley_op_solver_step, and the ring receives the velocities."""
+    zero: x and the staged rows carry the bits of the step without a ring, and the ring receives the velocities."""
     clips, C, L, ncfg, n = 3, 128, 33, 2, 3
     coef = tables.solver_table(tables.sigma_grid(n, 3.0), "euler", n)
     if flagged:
@@ -219,7 +165,7 @@ def test_zero_history_weights_are_the_plain_step(dev, dt, flagged):
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 371 + it).to(dev)
         rt.op_solver_step(pred, xa, None, None, ncfg, GUIDANCE, cd, ca, ra)
-        rt.op_solver_step_hist(ring, pred, xb, None, None, ncfg, GUIDANCE, cd, cb, rb)
+        rt.op_solver_step(pred, xb, None, None, ncfg, GUIDANCE, cd, cb, rb, hist=ring)
         oc.assert_bits_equal(xb, xa, f"zero weights {dt} it {it} x")
         oc.assert_bits_equal(rb, ra, f"zero weights {dt} it {it} rows")
     assert not bool(torch.isnan(ring).any()) and int(cb.item()) == n
@@ -233,10 +179,10 @@ def test_step_hist_refusals(dev):
     ring = torch.zeros(3, clips, C, L, device=dev)
     for kw in (dict(slots=0), dict(slots=3)):
         with pytest.raises(rt.FoleyRuntimeError, match="slots"):
-            rt.op_solver_step_hist(ring, pred, x, None, None, 1, 1.0, coef, ctr, None, **kw)
+            rt.op_solver_step(pred, x, None, None, 1, 1.0, coef, ctr, None, hist=ring, **kw)
     with pytest.raises(rt.FoleyRuntimeError, match="ring"):
-        rt.op_solver_step_hist(None, pred, x, None, None, 1, 1.0, coef, ctr, None, slots=1)
+        rt.op_solver_step(pred, x, None, None, 1, 1.0, coef, ctr, None, hist=None, slots=1)
     with pytest.raises(rt.FoleyRuntimeError, match="exclude"):
-        rt.op_solver_step_hist(ring[:1].contiguous(), pred, x, None, None, 1, 1.0, coef, ctr, None, edit=(x, x, None),
-                               windows=(torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, L, device=dev), L))
+        rt.op_solver_step(pred, x, None, None, 1, 1.0, coef, ctr, None, hist=ring[:1].contiguous(), edit=(x, x, None),
+                          windows=(torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, L, device=dev), L))
     assert int(ctr.item()) == 0 and not bool(x.any())

@@ -14,32 +14,17 @@ import torch
 import opcheck as oc
 from conftest import record_parity
 from foley_amd.host import long_form, runtime as rt, tables
+from step_harness import ALL3, DTS, GUIDANCE, SOLVER_ITERS, STEP_SHAPES, StepState, _rand
 
 pytestmark = pytest.mark.gpu
 
-DTS = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
-ALL3 = list(DTS)
 CAP = 4096 * 256                 # work items one grid1d launch covers without striding (rowops.hip)
-STEP_SHAPES = [(2, 128, 50), (3, 128, 33), (1, 128, 1), (2, 96, 31), (2, 40, 65)]
-SOLVER_ITERS = {"euler": 2, "heun-2": 3, "midpoint-2": 3, "kutta-4": 5}      # every row of each coefficient table, and its first repeat
-GUIDANCE = 4.5
 _WORST = {}
-
-
-def _rand(shape, seed, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
 def _rec(family, ratio):
     _WORST[family] = max(_WORST.get(family, 0.0), float(ratio))
     record_parity(f"elementwise.rowops.{family}", err_over_bound=_WORST[family])
-
-
-def _filled(shape, dtype, dev, src, rows=(1, 1)):
-    """A guarded buffer whose interior starts as `src` (state a kernel updates in place)."""
-    g = oc.guarded(shape, dtype, dev, rows=rows)
-    g.view.copy_(src.to(dev))
-    return g
 
 
 # ----------------------------------------------------------------------------- stand-alone head split
@@ -149,41 +134,10 @@ def test_latent_rows_bits(dev, clips, C, L, ncfg, dt):
 
 
 # ----------------------------------------------------------------------------- solver steps: one bound per iteration
-class _StepState:
-    """x / x_saved / d_acc / rows_out of one run, all guarded; the step counter."""
-
-    def __init__(self, dev, clips, C, L, ncfg, dtype, seed, saved=True, rows=True):
-        self.dev, self.shape, self.ncfg, self.dtype = dev, (clips, C, L), ncfg, dtype
-        self.gx = _filled((clips, C, L), torch.float32, dev, _rand((clips, C, L), seed))
-        self.gs = _filled((clips, C, L), torch.float32, dev, _rand((clips, C, L), seed + 1)) if saved else None
-        self.ga = _filled((clips, C, L), torch.float32, dev, _rand((clips, C, L), seed + 2)) if saved else None
-        self.gr = oc.guarded((ncfg * clips * L, C), dtype, dev, rows=(2, 3)) if rows else None
-        self.ctr = oc.guarded((1, 1), torch.int32, dev, rows=(1, 1), fill=0)
-
-    @property
-    def args(self):
-        v = lambda g: g.view if g is not None else None
-        return v(self.gx), v(self.gs), v(self.ga), v(self.gr)
-
-    def snapshot(self):
-        c = lambda g: g.view.cpu().clone() if g is not None else None
-        return c(self.gx), c(self.gs), c(self.ga)
-
-    def check(self, it, r, x_ref, x_bound, what):
-        """After iteration `it`: x against (x_ref, x_bound), x_saved bit for bit, d_acc in its bound, the counter, the staged rows
-        bit for bit from the device's own x in every CFG copy, all guards."""
-        worst = oc.assert_elementwise(self.gx.view, x_ref, x_bound, what + " x")
-        if self.gs is not None:
-            oc.assert_bits_equal(self.gs.view, r["x_saved"].float(), what + " x_saved")
-            worst = max(worst, oc.assert_elementwise(self.ga.view, *r["d_acc"], what + " d_acc"))
-        assert int(self.ctr.view.item()) == it + 1, what
-        if self.gr is not None:
-            oc.assert_bits_equal(self.gr.view, oc.rows_of(self.gx.view, self.ncfg, self.dtype), what + " rows_out (every CFG copy)")
-            self.gr.view.fill_(float("nan"))
-        for g in (self.gx, self.gs, self.ga, self.gr, self.ctr):
-            if g is not None:
-                g.check(what)
-        return worst
+def _step_ref(pred, st, coef_row):
+    """The fp64 step from the state `st` holds now, two halves (or one) under the scalar GUIDANCE."""
+    x, xs, da, _ = st.snapshot()
+    return oc.solver_step_ref_and_bounds(pred, x, xs, da, coef_row, st.ncfg, GUIDANCE)
 
 
 @pytest.mark.parametrize("dt", ALL3)
@@ -195,14 +149,13 @@ def test_solver_step_elementwise(dev, clips, C, L, solver, ncfg, dt):
     that a row which must reset or overwrite them is seen to do so."""
     n = SOLVER_ITERS[solver]
     coef = tables.solver_table(tables.sigma_grid(n), solver, n)
-    st = _StepState(dev, clips, C, L, ncfg, DTS[dt], 70, saved=not (solver == "euler" and ncfg == 1))
+    st = StepState(dev, clips, C, L, ncfg, DTS[dt], 70, saved=not (solver == "euler" and ncfg == 1))
     cd = coef.to(dev)
     worst = 0.0
     for it in range(n):
         pred = _rand((ncfg * clips * L, C), 71 + it)
-        x, xs, da = st.snapshot()
-        r = oc.solver_step_ref_and_bounds(pred, x, xs, da, coef[it], ncfg, GUIDANCE)
-        rt.op_solver_step(pred.to(dev), *st.args[:3], ncfg, GUIDANCE, cd, st.ctr.view.view(1), st.args[3])
+        r = _step_ref(pred, st, coef[it])
+        st.step(pred, cd)
         worst = max(worst, st.check(it, r, *r["x"], f"solver_step {solver} {clips}x{C}x{L} ncfg {ncfg} {dt} it {it}"))
     _rec(f"solver_step.{solver}", worst)
 
@@ -210,12 +163,11 @@ def test_solver_step_elementwise(dev, clips, C, L, solver, ncfg, dt):
 def test_solver_step_without_rows_out(dev):
     clips, C, L, ncfg = 2, 96, 31, 2
     coef = tables.solver_table(tables.sigma_grid(3), "heun-2", 3)
-    st = _StepState(dev, clips, C, L, ncfg, torch.float32, 80, rows=False)
+    st = StepState(dev, clips, C, L, ncfg, torch.float32, 80, rows=False)
     for it in range(3):
         pred = _rand((ncfg * clips * L, C), 81 + it)
-        x, xs, da = st.snapshot()
-        r = oc.solver_step_ref_and_bounds(pred, x, xs, da, coef[it], ncfg, GUIDANCE)
-        rt.op_solver_step(pred.to(dev), *st.args[:3], ncfg, GUIDANCE, coef.to(dev), st.ctr.view.view(1), None)
+        r = _step_ref(pred, st, coef[it])
+        st.step(pred, coef.to(dev))
         _rec("solver_step.heun-2", st.check(it, r, *r["x"], f"solver_step without rows_out it {it}"))
 
 
@@ -241,16 +193,15 @@ def test_solver_step_edit_elementwise(dev, clips, C, L, solver, dt):
         elif kind == "fractional":
             mask[:, : L // 3] = 0.0
             mask[:, L // 3: L // 2] = 1.0
-        st = _StepState(dev, clips, C, L, ncfg, DTS[dt], 93 + vi, saved=not (solver == "euler" and vi % 2 == 1))
-        x0d, nd, md = x0.to(dev), noise.to(dev), (mask.to(dev) if mask is not None else None)
+        st = StepState(dev, clips, C, L, ncfg, DTS[dt], 93 + vi, saved=not (solver == "euler" and vi % 2 == 1))
+        edit = (x0.to(dev), noise.to(dev), (mask.to(dev) if mask is not None else None))
         for it in range(n):
             pred = _rand((ncfg * clips * L, C), 94 + it)
-            x, xs, da = st.snapshot()
-            r = oc.solver_step_ref_and_bounds(pred, x, xs, da, coef[it], ncfg, GUIDANCE)
+            r = _step_ref(pred, st, coef[it])
             ref, bound = r["x"]
             if r["flags"] & oc.STEP_BLEND:
                 ref, bound = oc.edit_blend_ref_and_bound(ref, bound.e, r["s_next"], x0, noise, mask)
-            rt.op_solver_step_edit(pred.to(dev), *st.args[:3], ncfg, GUIDANCE, cd, st.ctr.view.view(1), st.args[3], x0d, nd, md)
+            st.step(pred, cd, edit=edit)
             worst = max(worst, st.check(it, r, ref, bound, f"solver_step_edit {solver} {clips}x{C}x{L} {dt} variant {vi} it {it}"))
     _rec(f"solver_step_edit.{solver}", worst)
 
@@ -292,19 +243,17 @@ def test_solver_step_windows_elementwise(dev, _clips, C, L, solver, dt):
         plan = long_form.WindowPlan.from_frames(starts, L)
         n_win, ncfg = plan.n_win, 2 - pi % 2
         clips = 2 * n_win
-        st = _StepState(dev, clips, C, L, ncfg, DTS[dt], 120 + pi, saved=not (solver == "euler" and pi % 2 == 1))
+        st = StepState(dev, clips, C, L, ncfg, DTS[dt], 120 + pi, saved=not (solver == "euler" and pi % 2 == 1))
         sd, wd = torch.tensor(starts, dtype=torch.int32, device=dev), plan.weights.to(dev)
-        single = plan.coverage() == 1
         for it in range(n):
             pred = _rand((ncfg * clips * L, C), 121 + it)
-            x, xs, da = st.snapshot()
-            r = oc.solver_step_ref_and_bounds(pred, x, xs, da, coef[it], ncfg, GUIDANCE)
+            r = _step_ref(pred, st, coef[it])
             ref, bound = r["x"]
             blend = bool(r["flags"] & oc.STEP_BLEND)
             if blend:
                 ref, e, _, _, _ = oc.windows_mean_ref_and_bound(ref, bound.e, n_win, starts, plan.weights)
                 bound = oc.Bound(e)
-            rt.op_solver_step_windows(pred.to(dev), *st.args[:3], ncfg, GUIDANCE, cd, st.ctr.view.view(1), st.args[3], sd, wd, plan.Ltot)
+            st.step(pred, cd, windows=(sd, wd, plan.Ltot))
             what = f"solver_step_windows {solver} C{C} L{L} starts {starts} {dt} it {it}"
             worst = max(worst, st.check(it, r, ref, bound, what))
             if blend and n_win > 1:      # the windows that cover a frame agree on it bit for bit

@@ -8,6 +8,7 @@ import torch
 
 import guidance_ref as G
 import step_cache_ref as R
+from abi_pin import assert_abi_version
 from conftest import ROOT, rel_err
 from foley_amd import nodes
 from foley_amd.host import config as C, runtime as rt, sampler, step_cache as S, synth
@@ -163,7 +164,7 @@ def test_new_symbols_declared_and_exported():
     assert re.search(r"int foley_step_cache_report\(foley_ctx\* ctx, float\* rel, int32_t\* skipped, int n\);", hdr)
     assert "#define FOLEY_STEP_CACHE_SCHEDULE 1" in hdr and "#define FOLEY_STEP_CACHE_THRESHOLD 2" in hdr
     assert S.MODE_SCHEDULE == 1 and S.MODE_THRESHOLD == 2
-    assert lib.foley_abi_version() == rt.ABI_VERSION == 12
+    assert_abi_version()
     # the probe's scratch: two floats per workgroup of four rows, per batch row
     assert lib.foley_op_cache_probe_work(1, 50) == 13 * 2 and lib.foley_op_cache_probe_work(6, 33) == 6 * 9 * 2
     assert lib.foley_op_cache_probe_work(0, 50) == 0

@@ -10,6 +10,7 @@ import ctypes
 import pytest
 import torch
 
+from abi_pin import assert_abi_version
 import guidance_ref as G
 import step_cache_ref as R
 from conftest import record_parity, rel_err
@@ -210,7 +211,7 @@ def test_graphs_keyed_on_cache_on_off_only(tiny):
         assert rel_err(_run(model, dac, conds[:1], noise, "euler", 20, spec, False)[2], w) < 1e-6       # each equals its eager run
     # plain -> cached -> plain on one context: the two plain runs are bit-equal
     assert torch.equal(_run(model, dac, conds[:1], noise, "euler", 20, None, True)[2], p0)
-    assert rt.load_library().foley_abi_version() == 12
+    assert_abi_version()
 
 
 # ----------------------------------------------------------------------------- combinations

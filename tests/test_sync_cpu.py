@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from abi_pin import assert_abi_version
 from conftest import ROOT, golden, rel_err
 from foley_amd.host import encoders as E, runtime as rt, sync_score as S, synth
 from opcheck import logmel_emulation as _logmel_emulation
@@ -153,7 +154,7 @@ def test_new_symbols_declared_and_exported():
         assert name in rt.EXPORTED_SYMBOLS
         assert getattr(rt.load_library(), name) is not None
     assert "head_dim must be 128, 96 or 64" in open(os.path.join(ROOT, "comfyui-hunyuanvideo-foley_amd", "csrc", "attention.hip")).read()
-    assert rt.ABI_VERSION == 12
+    assert_abi_version()
 
 
 def test_sync_scores_rejects_cpu_and_short_inputs():

@@ -11,6 +11,7 @@ from foley_amd import nodes
 from foley_amd.host import config as C, prompt_timeline as PT, runtime as rt, sampler, synth
 from oracle import foley_oracle as O
 import timeline_ref as TR
+from abi_pin import assert_abi_version
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = lambda x: float(torch.tensor(x, dtype=torch.float64).to(torch.float32))
@@ -141,7 +142,7 @@ def test_abi_declares_the_timeline_entries():
     hdr = open(os.path.join(ROOT, "include", "foley_hip.h")).read()
     for name in ("foley_prepare_timeline", "foley_op_attention_timeline"):
         assert name in rt.EXPORTED_SYMBOLS and re.search(r"\b%s\s*\(" % name, hdr)
-    assert "#define FOLEY_ABI_VERSION 12" in hdr and rt.ABI_VERSION == 12
+    assert_abi_version()
 
 
 def _node(monkeypatch, duration=5.0, batch_size=2, **kw):

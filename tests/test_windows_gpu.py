@@ -66,7 +66,7 @@ def _run_step_op(dev, solver, steps, rows_dtype, variations, starts, La):
         xp, xsp, dap = x.clone(), x_saved.clone(), d_acc.clone()
         step_p.fill_(it)
         rt.op_solver_step(pred, xp, xsp, dap, ncfg, guid, coef, step_p, rows_p)          # the plain step on the same state
-        rt.op_solver_step_windows(pred, x, x_saved, d_acc, ncfg, guid, coef, step, rows, st_t, w_t, Ltot)
+        rt.op_solver_step(pred, x, x_saved, d_acc, ncfg, guid, coef, step, rows, windows=(st_t, w_t, Ltot))
         torch.cuda.synchronize()
         assert int(step) == it + 1
         for name, got, want in (("x", x, want_x), ("x_saved", x_saved, xs), ("d_acc", d_acc, da)):

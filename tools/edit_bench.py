@@ -89,7 +89,7 @@ def main():
     def steps_blend():
         step.zero_()
         for _ in range(1000):
-            rt.op_solver_step_edit(pred, x, None, None, 2, 4.5, coef, step, rows, x0, noise, mask)
+            rt.op_solver_step(pred, x, None, None, 2, 4.5, coef, step, rows, edit=(x0, noise, mask))
 
     for name, fn in (("solver_step_plain", steps_plain), ("solver_step_blend", steps_blend)):
         r = timed(fn, args.reps, args.warmup)
