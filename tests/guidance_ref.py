@@ -1,8 +1,5 @@
-"""References of the guidance controls (separate video / text scales, schedules, CFG rescale) - the reference project has none
-of them, so the definition lives here.
+"""Op-level reference of the guidance controls (the loop under them, its schedule and its fp64 rescale factor are in loop_ref.py).
 
-restated_loop   the sampling loop of oracle.sample_latents restated over two or three prediction halves with a per-iteration
-                schedule and the rescale factor (fp64 statistics), over O.dit_forward / O.SolverState / O.flow_sigmas.
 factor_ref      fp64 rescale factors and their bound, over opcheck.combine_ref (the guided value and its bound; the solver
                 update behind it is opcheck.step_ref_and_bounds).
 """
@@ -10,58 +7,6 @@ import torch
 
 import opcheck as oc
 from opcheck import U32
-from oracle import foley_oracle as O
-
-
-# ----------------------------------------------------------------------------- the loop
-def schedule_ref(n_iter, g_video, g_text, interval=None):
-    """[n_iter][2] Python floats: (g_video, g_text) on the iterations with start <= i / n_iter < end, (1, 1) on the others."""
-    rows = []
-    for i in range(n_iter):
-        inside = interval is None or interval[0] <= i / n_iter < interval[1]
-        rows.append((float(g_video), float(g_text)) if inside else (1.0, 1.0))
-    return rows
-
-
-def rescale_factor64(v, p_last, phi):
-    """[B, 1, 1] fp64: phi s_pos / s_cfg + (1 - phi) per batch clip over its C x L elements, 1 where s_cfg is 0."""
-    v, p = v.double().flatten(1), p_last.double().flatten(1)
-    s_cfg, s_pos = v.std(1, unbiased=False), p.std(1, unbiased=False)
-    f = torch.where(s_cfg > 0, phi * s_pos / s_cfg.clamp_min(1e-300) + (1.0 - phi), torch.ones_like(s_cfg))
-    return f.view(-1, 1, 1)
-
-
-def restated_loop(sd, heads, noise, text, uncond_text, clip, sync, steps, g_text, solver="euler", g_video=None, interval=None,
-                  rescale=0.0, text_len=77, shift=1.0):
-    """noise [bs, 128, La]; text / uncond_text / clip / sync with batch 1 (shared) or bs.  g_video None: two halves
-    [uncond ; cond] and v = u + g (c - u) with g = g_text; otherwise three halves - h0 negative prompt + the learned empty rows,
-    h1 negative prompt + the visual features, h2 prompt + the features - and v = p0 + g_video (p1 - p0) + g_text (p2 - p1)."""
-    bs = noise.shape[0]
-    sig = O.flow_sigmas(steps, shift)
-    ts = O.flow_timesteps(sig)
-    st = O.SolverState(sig, solver)
-    rep = lambda a: a if a.shape[0] == bs else a.repeat(bs, 1, 1)
-    text_r, unc_r = O.pad_or_trim_text(rep(text), text_len), O.pad_or_trim_text(rep(uncond_text), text_len)
-    clip_r, sync_r = rep(clip), rep(sync)
-    e_clip = sd["empty_clip_feat"].unsqueeze(0).expand(bs, clip.shape[1], -1)
-    e_sync = sd["empty_sync_feat"].unsqueeze(0).expand(bs, sync.shape[1], -1)
-    three = g_video is not None
-    if three:
-        text_in, clip_in, sync_in = torch.cat([unc_r, unc_r, text_r]), torch.cat([e_clip, clip_r, clip_r]), torch.cat([e_sync, sync_r, sync_r])
-    else:
-        text_in, clip_in, sync_in = torch.cat([unc_r, text_r]), torch.cat([e_clip, clip_r]), torch.cat([e_sync, sync_r])
-    n_half = 3 if three else 2
-    sched = schedule_ref(len(ts), g_video if three else g_text, g_text, interval)
-    x = noise.float()
-    for i, t in enumerate(ts):
-        xin = torch.cat([x] * n_half)
-        p = O.dit_forward(sd, heads, xin, t.expand(xin.shape[0]), text_in, clip_in, sync_in).chunk(n_half)
-        gv, gt = sched[i]
-        v = p[0] + gv * (p[1] - p[0]) + gt * (p[2] - p[1]) if three else p[0] + gv * (p[1] - p[0])
-        if rescale > 0.0:
-            v = (rescale_factor64(v, p[-1], rescale) * v.double()).float()
-        x = st.step(v, x)
-    return x
 
 
 # ----------------------------------------------------------------------------- the factor

@@ -1,9 +1,10 @@
 """What the op-level tests of the solver step share: the shapes and seeds' generator, and the guarded device state of one run
-with the checks every iteration gets (test_rowops_elementwise_gpu.py, test_guidance_ops_gpu.py, test_multistep_ops_gpu.py)."""
+with the checks every iteration gets (test_rowops_elementwise_gpu.py, test_guidance_ops_gpu.py, test_multistep_ops_gpu.py); the
+torch restatement of one step that the edit and windows step tests compare with."""
 import torch
 
 import opcheck as oc
-from foley_amd.host import runtime as rt
+from foley_amd.host import runtime as rt, tables
 
 DTS = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
 ALL3 = list(DTS)
@@ -21,6 +22,25 @@ def _filled(shape, dtype, dev, src, rows=(1, 1)):
     g = oc.guarded(shape, dtype, dev, rows=rows)
     g.view.copy_(src.to(dev))
     return g
+
+
+def ref_step(pred, x, x_saved, d_acc, row, ncfg, g, x0=None, noise=None, mask=None):
+    """torch restatement of one step on the kernel's state (test_edit_gpu.py, test_windows_gpu.py): (x, x_saved, d_acc).  With x0
+    and noise (mask None: all ones) a row flagged STEP_BLEND ends in the edit blend; without them it is the plain step."""
+    clips, Cc, L = x.shape
+    w_new, w_acc, dt, w_store, flags, s = [float(v) for v in row[:6]]
+    flags = int(flags)
+    P = pred.view(ncfg, clips, L, Cc).permute(0, 1, 3, 2)
+    v = P[0] + g * (P[1] - P[0]) if ncfg == 2 else P[0]
+    acc = torch.zeros_like(x) if flags & tables.STEP_ACC_RESET else d_acc
+    deriv = w_new * v + w_acc * acc if w_acc != 0 else w_new * v
+    base = x_saved if flags & tables.STEP_USE_SAVED else x
+    xs = x.clone() if flags & tables.STEP_SAVE_X else x_saved
+    xn = base + deriv * dt
+    if x0 is not None and flags & tables.STEP_BLEND:
+        m = torch.ones(1, 1, L, device=x.device) if mask is None else mask.view(-1, 1, L)
+        xn = m * xn + (1 - m) * (s * noise + (1 - s) * x0)
+    return xn, xs, acc + w_store * v
 
 
 class StepState:

@@ -4,20 +4,17 @@ for bit; the captured graph keyed on the set maps; full-width forwards where 64-
 import pytest
 import torch
 
+import loop_harness as H
 from conftest import rel_err
 from foley_amd.host import audio_edit, config as C, sampler, synth, tables
 from oracle import foley_oracle as O
-from test_edit_cpu import oracle_edit_latents
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(synth.synth_dac_state_dict(C.DAC_TINY), dev, C.DAC_TINY)
-    return sd, model, dac
+    return H.tiny_run(dev, 0)
 
 
 def _conds(cfg, dur, sd, kinds, seed0=10):
@@ -25,16 +22,8 @@ def _conds(cfg, dur, sd, kinds, seed0=10):
     return [synth.synth_conditioning(cfg, dur, t2a=(k == "t2a"), sd=sd, seed=seed0 + 3 * i) for i, k in enumerate(kinds)]
 
 
-def _batched(conds):
-    cat = lambda k: torch.cat([c[k] for c in conds])
-    return ({"siglip2_feat": cat("clip"), "syncformer_feat": cat("sync")},
-            {"text_feat": cat("text"), "uncond_text_feat": cat("uncond_text")})
-
-
-def _run(model, dac, vis, txt, noise, solver, steps, use_graph, edit=None):
-    bs = noise.shape[0]
-    return sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, steps, bs, solver, noise=noise,
-                                                  use_graph=use_graph, return_latents=True, edit=edit)
+def _run(model, dac, conds, noise, solver, use_graph, edit=None):
+    return H.run(model, dac, conds, noise, solver, 10, 4.5, use_graph, edit=edit)
 
 
 _ORACLE = {}
@@ -45,13 +34,13 @@ _ORACLE = {}
 def test_per_clip_batch_matches_oracle(tiny, solver, use_graph):
     """fp32, 3 clips under CFG 4.5, every clip with its own text, negative text, clip and sync features: each clip's latents
     against oracle.sample_latents on that clip alone."""
-    sd, model, dac = tiny
+    sd, _dsd, model, dac, _ = tiny
     conds = _conds(C.TINY, 1.0, sd, ["v2a", "v2a", "v2a"])
-    noise = torch.randn(3, 128, 50, generator=torch.Generator().manual_seed(5))
-    vis, txt = _batched(conds)
+    noise = H.noise(3)
+    vis, txt = H.batched(conds)
     plan = sampler.build_plan(model, vis, txt, 50, 4.5, 10, 3, solver)
     assert plan["text"].shape[0] == 6 and plan["clip"].shape[0] == 4          # 3 + 3 text sets, 1 + 3 visual sets
-    _a, _sr, lat = _run(model, dac, vis, txt, noise, solver, 10, use_graph)
+    _a, _sr, lat = _run(model, dac, conds, noise, solver, use_graph)
     for k, c in enumerate(conds):
         key = (solver, k)
         if key not in _ORACLE:
@@ -65,15 +54,14 @@ def test_per_clip_batch_matches_oracle(tiny, solver, use_graph):
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_identical_rows_take_the_unchanged_path(tiny, use_graph):
     """The same conditioning passed as batch_size identical rows equals the batch-1 call bit for bit (latents and audio)."""
-    sd, model, dac = tiny
+    sd, _dsd, model, dac, _ = tiny
     c = synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd)
-    noise = torch.randn(3, 128, 50, generator=torch.Generator().manual_seed(6))
-    vis1, txt1 = _batched([c])
-    visn, txtn = _batched([c, c, c])
+    noise = H.noise(3, 6)
+    visn, txtn = H.batched([c, c, c])
     plan = sampler.build_plan(model, visn, txtn, 50, 4.5, 10, 3, "euler")
     assert plan["text_of"] is None and plan["vis_of"] is None and plan["text"].shape[0] == 2
-    a1, _, l1 = _run(model, dac, vis1, txt1, noise, "euler", 10, use_graph)
-    an, _, ln = _run(model, dac, visn, txtn, noise, "euler", 10, use_graph)
+    a1, _, l1 = _run(model, dac, [c], noise, "euler", use_graph)
+    an, _, ln = _run(model, dac, [c, c, c], noise, "euler", use_graph)
     assert torch.equal(l1, ln) and torch.equal(a1, an)
 
 
@@ -83,16 +71,16 @@ def test_graph_replay_across_set_maps_and_layouts(tiny):
     with per-row visual; and back.  Every run equals its eager run.  A layout change re-allocates the workspace and drops the
     captured iteration (a kept graph would replay the old divisors and buffers); within a layout the maps only change the
     tables and sets foley_prepare_sets rewrites in place, which a replay must read afresh."""
-    sd, model, dac = tiny
+    sd, _dsd, model, dac, _ = tiny
     conds = _conds(C.TINY, 1.0, sd, ["v2a", "t2a", "v2a"], seed0=40)
     conds.append(dict(conds[0], text=conds[1]["text"], uncond_text=conds[1]["uncond_text"]))   # 3: clip 0's video, clip 1's text
     conds.append(dict(conds[2], text=conds[0]["text"], uncond_text=conds[0]["uncond_text"]))   # 4: clip 2's video, clip 0's text
-    noise = torch.randn(3, 128, 50, generator=torch.Generator().manual_seed(7))
+    noise = H.noise(3, 7)
     orders = ((0, 1, 2), (2, 0, 1), (0, 0, 0), (0, 3, 0), (0, 4, 0), (0, 0, 1))
     layouts = {(0, 0, 0): None, (0, 3, 0): "text per row", (0, 4, 0): "visual per row"}
     want = {}
     for o in orders:
-        vis, txt = _batched([conds[i] for i in o])
+        vis, txt = H.batched([conds[i] for i in o])
         plan = sampler.build_plan(model, vis, txt, 50, 4.5, 10, 3, "euler")
         if o in layouts:                                   # the sequence does cover every layout
             per_half = [0, 0, 0, 1, 1, 1]
@@ -101,25 +89,23 @@ def test_graph_replay_across_set_maps_and_layouts(tiny):
                 assert plan["vis_of"] == per_half and plan["text_of"] != per_half
             if layouts[o] == "visual per row":
                 assert plan["text_of"] == per_half and plan["vis_of"] != per_half
-        want[o] = _run(model, dac, vis, txt, noise, "euler", 10, False)[2].clone()
+        want[o] = _run(model, dac, [conds[i] for i in o], noise, "euler", False)[2].clone()
     for o in orders + orders[:2]:
-        vis, txt = _batched([conds[i] for i in o])
-        got = _run(model, dac, vis, txt, noise, "euler", 10, True)[2]
+        got = _run(model, dac, [conds[i] for i in o], noise, "euler", True)[2]
         assert rel_err(got, want[o]) < 1e-6, o
     assert rel_err(want[(0, 1, 2)], want[(2, 0, 1)]) > 1e-2
 
 
 def test_edit_with_per_clip_prompts(tiny):
     """Strength 0.6 with a span mask and per-clip conditioning: each clip against the oracle edit run of that clip alone."""
-    sd, model, dac = tiny
+    sd, _dsd, model, dac, _ = tiny
     conds = _conds(C.TINY, 1.0, sd, ["v2a", "t2a"], seed0=70)
     g = torch.Generator().manual_seed(8)
     noise, x0 = torch.randn(2, 128, 50, generator=g), 0.7 * torch.randn(1, 128, 50, generator=g)
     mask = audio_edit.build_mask(50, [(0.3, 0.6)], 0.1)
-    vis, txt = _batched(conds)
-    _a, _sr, lat = _run(model, dac, vis, txt, noise, "heun-2", 10, True, edit=audio_edit.EditSpec(x0, 0.6, mask))
+    _a, _sr, lat = _run(model, dac, conds, noise, "heun-2", True, edit=audio_edit.EditSpec(x0, 0.6, mask))
     for k, c in enumerate(conds):
-        ref = oracle_edit_latents(sd, C.TINY.heads, noise[k:k + 1], x0, mask, c, 10, 4.5, "heun-2", 0.6)
+        ref = H.ref_loop(sd, [c], noise[k:k + 1], 10, 4.5, "heun-2", edit=(x0, mask, 0.6)).x
         assert rel_err(lat[k:k + 1], ref) < 1e-4, k
 
 
@@ -141,7 +127,7 @@ def test_full_width_forward_with_per_clip_sets(dev, dtype, dur, kinds, sel):
     clips = len(kinds)
     La, Lv, Ls = C.lengths(dur, c)
     conds = _conds(c, dur, sd, kinds, seed0=100)
-    vis, txt = _batched(conds)
+    vis, txt = H.batched(conds)
     x = torch.randn(clips, 128, La, generator=torch.Generator().manual_seed(44)).to(dtype).float()
     steps, it = 10, 4
     model.ctx.prepare(sampler.build_plan(model, vis, txt, La, 4.5, steps, clips, "euler"))

@@ -1,11 +1,12 @@
 """Audio editing without a GPU: the strength -> (k0, i0) rule, the suffix / blend tables, mask building, the refusals, the
-node's keyword plumbing, and the fp32 oracle restatement of the masked loop that tests/test_edit_gpu.py compares against."""
+node's keyword plumbing, and the edit of the restated loop (tests/loop_ref.py) that tests/test_edit_gpu.py compares against."""
 import contextlib
 import types
 
 import pytest
 import torch
 
+import loop_ref as L
 from conftest import rel_err
 from foley_amd import nodes
 from foley_amd.host import audio_edit, config as C, sampler, synth, tables
@@ -13,71 +14,33 @@ from oracle import foley_oracle as O
 
 
 # ----------------------------------------------------------------------------- restatement of the masked loop
-def oracle_edit_latents(sd, heads, noise, x0, mask, cond, steps, guidance, solver, strength, text_len=77):
-    """The edit loop on the CPU oracle: the suffix [i0, steps) of `O.sample_latents`' iterations (same timesteps, same
-    SolverState stage bookkeeping) from sigma_{k0}*noise + (1 - sigma_{k0})*x0, and after every iteration that advances the
-    sigma index to k+1: x <- m*x + (1 - m)*(sigma_{k+1}*noise + (1 - sigma_{k+1})*x0).  fp32, like the oracle's sampler.
-    mask: [La] or [clips, La] (None: all ones)."""
-    k0, i0 = tables.edit_start(steps, solver, strength)
-    bs, La = noise.shape[0], noise.shape[2]
-    sig = O.flow_sigmas(steps)
-    ts = O.flow_timesteps(sig)
-    st = O.SolverState(sig, solver)
-    st.idx = k0
-    m = torch.ones(1, 1, La) if mask is None else (mask.view(1, 1, La) if mask.dim() == 1 else mask.view(-1, 1, La))
-    rep = lambda a: a.repeat(bs, 1, 1)
-    text_r = O.pad_or_trim_text(rep(cond["text"]), text_len)
-    unc_r = O.pad_or_trim_text(rep(cond["uncond_text"]), text_len)
-    clip_r, sync_r = rep(cond["clip"]), rep(cond["sync"])
-    if guidance > 1.0:
-        e_clip = sd["empty_clip_feat"].unsqueeze(0).expand(bs, cond["clip"].shape[1], -1)
-        e_sync = sd["empty_sync_feat"].unsqueeze(0).expand(bs, cond["sync"].shape[1], -1)
-        clip_in, sync_in, text_in = torch.cat([e_clip, clip_r]), torch.cat([e_sync, sync_r]), torch.cat([unc_r, text_r])
-    else:
-        clip_in, sync_in, text_in = clip_r, sync_r, text_r
-    noise, x0 = noise.float(), x0.float()
-    x = sig[k0] * noise + (1 - sig[k0]) * x0
-    for i in range(i0, steps):
-        xin = torch.cat([x, x]) if guidance > 1.0 else x
-        v = O.dit_forward(sd, heads, xin, ts[i].expand(xin.shape[0]), text_in, clip_in, sync_in)
-        if guidance > 1.0:
-            vu, vc = v.chunk(2)
-            v = vu + guidance * (vc - vu)
-        k = st.idx
-        x = st.step(v, x)
-        if st.idx != k:
-            s = sig[st.idx]
-            x = m * x + (1 - m) * (s * noise + (1 - s) * x0)
-    return x
-
-
 @pytest.fixture(scope="module")
 def tiny_cpu():
+    """The arguments of loop_ref.restated_loop up to the noise, the conditioning's four tensors, x0."""
     sd = synth.synth_dit_state_dict(C.TINY)
     cond = synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd)
     g = torch.Generator().manual_seed(5)
     noise = torch.randn(2, 128, 50, generator=g)
     x0 = 0.7 * torch.randn(1, 128, 50, generator=g)
-    return sd, cond, noise, x0
+    return (sd, C.TINY.heads, noise), (cond["text"], cond["uncond_text"], cond["clip"], cond["sync"]), x0
 
 
 def test_restatement_all_ones_at_strength_1_is_the_plain_loop(tiny_cpu):
-    sd, cond, noise, x0 = tiny_cpu
+    a, c, x0 = tiny_cpu
     for solver, steps in (("euler", 6), ("heun-2", 6)):
-        ref = O.sample_latents(sd, C.TINY.heads, noise, cond["text"], cond["uncond_text"], cond["clip"], cond["sync"],
-                               steps, 4.5, solver)
-        ed = oracle_edit_latents(sd, C.TINY.heads, noise, x0, torch.ones(50), cond, steps, 4.5, solver, 1.0)
+        ref = O.sample_latents(*a, *c, steps, 4.5, solver)
+        ed = L.restated_loop(*a, *c, steps, 4.5, solver, edit=(x0, torch.ones(50), 1.0)).x
         assert torch.equal(ed, ref), solver
 
 
 def test_restatement_all_zeros_under_euler_ends_at_x0(tiny_cpu):
-    sd, cond, noise, x0 = tiny_cpu
+    a, c, x0 = tiny_cpu
     for strength in (1.0, 0.5):
-        ed = oracle_edit_latents(sd, C.TINY.heads, noise, x0, torch.zeros(50), cond, 6, 4.5, "euler", strength)
+        ed = L.restated_loop(*a, *c, 6, 4.5, "euler", edit=(x0, torch.zeros(50), strength)).x
         assert torch.equal(ed, x0.expand_as(ed)), strength
     # a span regenerates its frames and keeps the others at x0
     m = audio_edit.build_mask(50, [(0.4, 0.6)], 0.0)
-    ed = oracle_edit_latents(sd, C.TINY.heads, noise, x0, m, cond, 6, 4.5, "euler", 0.6)
+    ed = L.restated_loop(*a, *c, 6, 4.5, "euler", edit=(x0, m, 0.6)).x
     keep = m == 0
     assert torch.equal(ed[..., keep], x0[..., keep].expand(2, -1, -1)) and rel_err(ed[..., ~keep], x0[..., ~keep].expand(2, -1, -1)) > 1e-3
 

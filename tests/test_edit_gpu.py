@@ -1,15 +1,16 @@
 """Audio editing on the HIP engine: the blend step and start-state ops against torch, the 44.1 -> 48 kHz resample against a float64
-restatement, the edit loop against the oracle restatement (tests/test_edit_cpu.py), the exactness properties (all-ones mask =
+restatement, the edit loop against the restated loop (tests/loop_ref.py), the exactness properties (all-ones mask =
 plain run bit for bit, all-zeros mask under euler = x0), the plain / edit keying of the captured graph, and one full-size edit."""
 import math
 
 import pytest
 import torch
 
+import loop_harness as H
 from conftest import rel_err
 from foley_amd.host import audio_edit, config as C, runtime as rt, sampler, synth, tables
 from foley_amd.host.sync_score import sinc_resample_taps
-from test_edit_cpu import oracle_edit_latents
+from step_harness import ref_step
 
 pytestmark = pytest.mark.gpu
 
@@ -17,24 +18,6 @@ DAC_WINDOW_MARGIN = 16      # latent frames: tests/test_dac_window_cpu.py shows 
 
 
 # ----------------------------------------------------------------------------- ops
-def _ref_step(pred, x, x_saved, d_acc, row, ncfg, g, x0, noise, mask):
-    """torch restatement of one edit step on the kernel's state: returns (x, x_saved, d_acc)."""
-    clips, Cc, L = x.shape
-    w_new, w_acc, dt, w_store, flags, s = [float(v) for v in row[:6]]
-    flags = int(flags)
-    P = pred.view(ncfg, clips, L, Cc).permute(0, 1, 3, 2)
-    v = P[0] + g * (P[1] - P[0]) if ncfg == 2 else P[0]
-    acc = torch.zeros_like(x) if flags & tables.STEP_ACC_RESET else d_acc
-    deriv = w_new * v + w_acc * acc if w_acc != 0 else w_new * v
-    base = x_saved if flags & tables.STEP_USE_SAVED else x
-    xs = x.clone() if flags & tables.STEP_SAVE_X else x_saved
-    xn = base + deriv * dt
-    if flags & tables.STEP_BLEND:
-        m = torch.ones(1, 1, L, device=x.device) if mask is None else mask.view(-1, 1, L)
-        xn = m * xn + (1 - m) * (s * noise + (1 - s) * x0)
-    return xn, xs, acc + w_store * v
-
-
 @pytest.mark.parametrize("solver,steps", [("euler", 6), ("heun-2", 6), ("midpoint-2", 7), ("kutta-4", 8)])
 @pytest.mark.parametrize("rows_dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("x0_clips,mask_kind", [(1, "none"), (1, "binary"), (3, "fractional"), (3, "per_clip_binary")])
@@ -61,7 +44,7 @@ def test_blend_step_op(dev, solver, steps, rows_dtype, x0_clips, mask_kind):
     rows_p = torch.empty_like(rows)
     for it in range(steps):
         pred = torch.randn(ncfg * clips * L, Cc, generator=g).to(dev)
-        ref = _ref_step(pred, x, x_saved, d_acc, coef[it].cpu(), ncfg, guid, x0, noise, mask)
+        ref = ref_step(pred, x, x_saved, d_acc, coef[it].cpu(), ncfg, guid, x0, noise, mask)
         xp, xsp, dap = x.clone(), x_saved.clone(), d_acc.clone()
         step_p.fill_(it)
         rt.op_solver_step(pred, xp, xsp, dap, ncfg, guid, coef, step_p, rows_p)          # the plain step on the same state
@@ -124,23 +107,12 @@ def test_resample_44k1_to_48k(dev):
 # ----------------------------------------------------------------------------- loop
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    dsd = synth.synth_dac_state_dict(C.DAC_TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(dsd, dev, C.DAC_TINY)
+    sd, dsd, model, dac, _ = H.tiny_run(dev, 0)
     cond = synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd)
     g = torch.Generator().manual_seed(21)
     noise = torch.randn(2, 128, 50, generator=g)
     x0 = 0.7 * torch.randn(1, 128, 50, generator=g)
     return sd, dsd, model, dac, cond, noise, x0
-
-
-def _feats(cond):
-    return ({"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]},
-            {"text_feat": cond["text"], "uncond_text_feat": cond["uncond_text"]})
-
-
-_ORACLE = {}
 
 
 @pytest.mark.parametrize("solver,steps", [("euler", 10), ("heun-2", 10), ("kutta-4", 16)])
@@ -149,14 +121,9 @@ _ORACLE = {}
 def test_edit_loop_matches_oracle(tiny, solver, steps, strength, use_graph):
     sd, _dsd, model, dac, cond, noise, x0 = tiny
     mask = audio_edit.build_mask(50, [(0.3, 0.6)], 0.1)
-    key = (solver, strength)
-    if key not in _ORACLE:
-        _ORACLE[key] = oracle_edit_latents(sd, C.TINY.heads, noise, x0, mask, cond, steps, 4.5, solver, strength)
-    vis, txt = _feats(cond)
-    _a, _sr, lat = sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, steps, 2, solver, noise=noise,
-                                                          use_graph=use_graph, return_latents=True,
-                                                          edit=audio_edit.EditSpec(x0, strength, mask))
-    assert rel_err(lat, _ORACLE[key]) < 1e-4
+    want = H.ref_loop(sd, [cond], noise, steps, 4.5, solver, edit=(x0, mask, strength)).x
+    lat = H.run(model, dac, [cond], noise, solver, steps, 4.5, use_graph, edit=audio_edit.EditSpec(x0, strength, mask))[2]
+    assert rel_err(lat, want) < 1e-4
 
 
 def test_edit_loop_matches_oracle_past_the_flow_mix_grid_cap(tiny):
@@ -171,8 +138,8 @@ def test_edit_loop_matches_oracle_past_the_flow_mix_grid_cap(tiny):
     g = torch.Generator().manual_seed(22)
     noise, x0 = torch.randn(clips, 128, La, generator=g), 0.7 * torch.randn(1, 128, La, generator=g)
     mask = audio_edit.build_mask(La, [(0.3 * dur, 0.6 * dur)], 0.1)
-    want = oracle_edit_latents(sd, C.TINY.heads, noise, x0, mask, cond, steps, 4.5, "euler", 0.5)
-    vis, txt = _feats(cond)
+    want = H.ref_loop(sd, [cond], noise, steps, 4.5, "euler", edit=(x0, mask, 0.5)).x
+    vis, txt = H.batched([cond])
     _a, _sr, lat = sampler.denoise_process_with_generator(vis, txt, dur, model, dac, 4.5, steps, clips, "euler", noise=noise,
                                                           return_latents=True, edit=audio_edit.EditSpec(x0, 0.5, mask))
     assert rel_err(lat, want) < 1e-4
@@ -181,7 +148,7 @@ def test_edit_loop_matches_oracle_past_the_flow_mix_grid_cap(tiny):
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_all_ones_at_strength_1_is_the_plain_run(tiny, use_graph):
     _sd, _dsd, model, dac, cond, _noise, x0 = tiny
-    vis, txt = _feats(cond)
+    vis, txt = H.batched([cond])
     for solver in ("euler", "heun-2"):
         a0, _, l0 = sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, 10, 2, solver, return_latents=True,
                                                            generator=torch.Generator("cpu").manual_seed(99), use_graph=use_graph)
@@ -193,7 +160,7 @@ def test_all_ones_at_strength_1_is_the_plain_run(tiny, use_graph):
 
 def test_all_zeros_under_euler_returns_x0(tiny):
     _sd, _dsd, model, dac, cond, noise, _x0 = tiny
-    vis, txt = _feats(cond)
+    vis, txt = H.batched([cond])
     x0 = torch.randn(2, 128, 50, generator=torch.Generator().manual_seed(4))
     for strength in (1.0, 0.5):
         _a, _, lat = sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, 10, 2, "euler", noise=noise,
@@ -205,7 +172,7 @@ def test_graph_keyed_on_plain_vs_edit(tiny, dev):
     """One context, use_graph=True: plain -> edit -> plain -> edit of the same shape (strength 1: the same plan, so the
     captured iteration would be reused if it were not keyed); each run equals a fresh context's bit for bit."""
     sd, dsd, model, dac, cond, noise, x0 = tiny
-    vis, txt = _feats(cond)
+    vis, txt = H.batched([cond])
     ed = audio_edit.EditSpec(x0, 1.0, audio_edit.build_mask(50, [(0.2, 0.5)], 0.1))
 
     def run(m, d, edit):
@@ -224,7 +191,7 @@ def test_graph_keyed_on_plain_vs_edit(tiny, dev):
 
 def test_set_edit_refusals(tiny, dev):
     _sd, _dsd, model, dac, cond, noise, x0 = tiny
-    vis, txt = _feats(cond)
+    vis, txt = H.batched([cond])
     plan = sampler.build_plan(model, vis, txt, 50, 4.5, 10, 2, "euler", edit_i0=0)
     model.ctx.prepare(plan)
     z = torch.zeros(2, 128, 50, device=dev)
@@ -246,7 +213,7 @@ def test_full_size_span_regeneration(dev):
     cfg = C.XXL
     sd = synth.synth_dit_state_dict(cfg, device=dev)
     cond = synth.synth_conditioning(cfg, 5.0, t2a=True, sd=sd, device=dev)
-    vis, txt = _feats(cond)
+    vis, txt = H.batched([cond])
     model = sampler.FoleyModel(cfg, sd, torch.bfloat16, dev)
     dac = sampler.FoleyDAC(synth.synth_dac_state_dict(C.DAC48K, device=dev, encoder=True), dev, C.DAC48K)
     t = torch.arange(int(5.2 * 44100), dtype=torch.float32) / 44100

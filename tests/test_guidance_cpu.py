@@ -1,16 +1,17 @@
-"""Separate video / text guidance, guidance schedules and CFG rescale without a GPU: the restated loop of tests/guidance_ref.py
-against the oracle, that every control moves it, the schedule tables, the three-half set maps, the refusals, the C surface."""
+"""Separate video / text guidance, guidance schedules and CFG rescale without a GPU: the restated loop of tests/loop_ref.py under
+them against the oracle, that every control moves it, the schedule tables, the three-half set maps, the refusals, the C surface."""
 import os
 import re
 
 import pytest
 import torch
 
-import guidance_ref as G
+import loop_ref as L
 from abi_pin import assert_abi_version
 from conftest import ROOT, rel_err
 from foley_amd import nodes
 from foley_amd.host import cond_sets, config as C, runtime as rt, sampler, synth, tables
+from loop_harness import ref_loop
 from oracle import foley_oracle as O
 
 SOLVERS = ["euler", "heun-2"]
@@ -24,17 +25,10 @@ def tiny():
     return sd, c, noise
 
 
-_LOOPS = {}
-
-
-def _loop(tiny, solver, **kw):
-    """restated_loop of the fixture's clip, computed once per distinct argument set."""
+def _loop(tiny, solver, g_text, **kw):
+    """The restated loop of the fixture's clip (memoised by the harness: once per distinct argument set)."""
     sd, c, noise = tiny
-    key = (solver,) + tuple(sorted(kw.items()))
-    if key not in _LOOPS:
-        with torch.inference_mode():
-            _LOOPS[key] = G.restated_loop(sd, C.TINY.heads, noise, c["text"], c["uncond_text"], c["clip"], c["sync"], 10, solver=solver, **kw)
-    return _LOOPS[key]
+    return ref_loop(sd, [c], noise, 10, g_text, solver, **kw).x
 
 
 @pytest.mark.parametrize("solver", SOLVERS)
@@ -72,7 +66,7 @@ def test_schedule_tables(solver):
         for interval in (None, (0.0, 1.0), (0.2, 0.7), (0.0, 0.5), (0.35, 1.0)):
             t = tables.guidance_schedule(n_iter, 7.0, 2.5, interval)
             assert t.dtype == torch.float32 and tuple(t.shape) == (n_iter, 2) and n_iter == steps
-            assert t.tolist() == [list(r) for r in G.schedule_ref(n_iter, 7.0, 2.5, interval)], (solver, steps, interval)
+            assert t.tolist() == [list(r) for r in L.schedule_ref(n_iter, 7.0, 2.5, interval)], (solver, steps, interval)
     t = tables.guidance_schedule(10, 7.0, 2.0, (0.2, 0.7))
     assert [i for i in range(10) if t[i, 0] == 7.0] == [2, 3, 4, 5, 6] and bool((t[[0, 1, 7, 8, 9]] == 1.0).all())
     for bad in ((0.5, 0.5), (-0.1, 0.5), (0.2, 1.1), (0.7, 0.2)):

@@ -1,14 +1,12 @@
 """Separate video / text guidance, guidance schedules and CFG rescale on the HIP engine, end to end: against the restated loop
-of tests/guidance_ref.py (the oracle's forward under the new combine), per-clip conditioning under three halves, the unset and
+of tests/loop_ref.py (the oracle's forward under the new combine), per-clip conditioning under three halves, the unset and
 the constant-schedule states bit for bit, the keying of the captured graph, three halves at full width, the refusals."""
-import ctypes
-
 import pytest
 import torch
 
+import loop_harness as H
 from abi_pin import assert_abi_version
-import guidance_ref as G
-from conftest import rel_err
+from conftest import record_parity, rel_err
 from foley_amd.host import audio_edit, config as C, long_form, runtime as rt, sampler, synth, tables
 from oracle import foley_oracle as O
 
@@ -25,39 +23,16 @@ CASES = {                                                   # name -> (cfg_scale
 
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(synth.synth_dac_state_dict(C.DAC_TINY), dev, C.DAC_TINY)
-    conds = [synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd, seed=10 + 3 * i) for i in range(2)]
-    return sd, model, dac, conds
-
-
-def _batched(conds):
-    cat = lambda k: torch.cat([c[k] for c in conds])
-    return ({"siglip2_feat": cat("clip"), "syncformer_feat": cat("sync")},
-            {"text_feat": cat("text"), "uncond_text_feat": cat("uncond_text")})
+    return H.tiny_run(dev, 2)
 
 
 def _run(model, dac, conds, noise, solver, scale, spec, use_graph=False, **kw):
-    vis, txt = _batched(conds)
-    return sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, scale, 10, noise.shape[0], solver, noise=noise,
-                                                  use_graph=use_graph, return_latents=True, guidance=spec, **kw)
+    return H.run(model, dac, conds, noise, solver, 10, scale, use_graph, guidance=spec, **kw)
 
 
-_LOOPS = {}
-
-
-def _loop(sd, c, noise, solver, scale, spec, tag):
-    key = (tag, solver, scale, spec)
-    if key not in _LOOPS:
-        with torch.inference_mode():
-            _LOOPS[key] = G.restated_loop(sd, C.TINY.heads, noise, c["text"], c["uncond_text"], c["clip"], c["sync"], 10, scale, solver,
-                                          g_video=spec.g_video, interval=spec.interval, rescale=spec.rescale)
-    return _LOOPS[key]
-
-
-def _noise(n, seed=5):
-    return torch.randn(n, 128, 50, generator=torch.Generator().manual_seed(seed))
+def _loop(sd, conds, noise, solver, scale, spec, **kw):
+    """The restated loop of 10 iterations under a GuidanceSpec's controls."""
+    return H.ref_loop(sd, conds, noise, 10, scale, solver, g_video=spec.g_video, interval=spec.interval, rescale=spec.rescale, **kw).x
 
 
 # ----------------------------------------------------------------------------- against the restated loop
@@ -65,31 +40,31 @@ def _noise(n, seed=5):
 @pytest.mark.parametrize("use_graph", [False, True])
 @pytest.mark.parametrize("solver", ["euler", "heun-2"])
 def test_matches_the_restated_loop(tiny, solver, use_graph, case):
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     scale, spec = CASES[case]
-    noise = _noise(1)
-    want = _loop(sd, conds[0], noise, solver, scale, spec, "one")
+    noise = H.noise(1)
+    want = _loop(sd, conds[:1], noise, solver, scale, spec)
     _a, _sr, lat = _run(model, dac, conds[:1], noise, solver, scale, spec, use_graph)
     assert model.ctx.plan["ncfg"] == (3 if spec.g_video is not None else 2)
     e = rel_err(lat, want)
     print("%s %s graph=%d: %.2e" % (case, solver, use_graph, e))
     assert e < 1e-4, (case, solver, use_graph, e)
-    plain = _loop(sd, conds[0], noise, solver, 4.5, Spec(), "one")
+    plain = _loop(sd, conds[:1], noise, solver, 4.5, Spec())
     assert rel_err(want, plain) > 1e-2                       # the control is far above the gate
 
 
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_per_clip_conditioning_under_three_halves(tiny, use_graph):
     """Two clips with their own videos and prompts: six batch rows laid out per row, each clip against the loop on it alone."""
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     scale, spec = CASES["all three"]
-    noise = _noise(2, 6)
-    vis, txt = _batched(conds)
+    noise = H.noise(2, 6)
+    vis, txt = H.batched(conds)
     plan = sampler.build_plan(model, vis, txt, 50, scale, 10, 2, "heun-2", guidance=spec)
     assert plan["ncfg"] == 3 and plan["vis_of"] == [0, 0, 1, 2, 3, 4] and plan["text_of"] == [0, 1, 2, 3, 4, 5]
     _a, _sr, lat = _run(model, dac, conds, noise, "heun-2", scale, spec, use_graph)
     for k, c in enumerate(conds):
-        e = rel_err(lat[k:k + 1], _loop(sd, c, noise[k:k + 1], "heun-2", scale, spec, "clip%d" % k))
+        e = rel_err(lat[k:k + 1], _loop(sd, [c], noise[k:k + 1], "heun-2", scale, spec))
         print("graph=%d clip %d: %.2e" % (use_graph, k, e))
         assert e < 1e-4, (use_graph, k, e)
 
@@ -97,8 +72,8 @@ def test_per_clip_conditioning_under_three_halves(tiny, use_graph):
 # ----------------------------------------------------------------------------- the unset state and the constant table: the plain bits
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_constant_schedule_is_the_plain_run(tiny, use_graph):
-    sd, model, dac, conds = tiny
-    noise = _noise(2, 7)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(2, 7)
     a0, _, l0 = _run(model, dac, conds[:1], noise, "heun-2", 4.5, None, use_graph)
     a1, _, l1 = _run(model, dac, conds[:1], noise, "heun-2", 4.5, Spec(interval=(0.0, 1.0)), use_graph)
     assert model.ctx.plan.get("guid_sched") is not None and bool((model.ctx.plan["guid_sched"] == 4.5).all())
@@ -108,7 +83,7 @@ def test_constant_schedule_is_the_plain_run(tiny, use_graph):
 
 
 def test_constant_schedule_is_the_plain_edit_run_and_windowed_run(tiny):
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     const = Spec(interval=(0.0, 1.0))
     g = torch.Generator().manual_seed(8)
     noise, x0 = torch.randn(1, 128, 50, generator=g), 0.7 * torch.randn(1, 128, 50, generator=g)
@@ -128,8 +103,9 @@ def test_constant_schedule_is_the_plain_edit_run_and_windowed_run(tiny):
 
 
 def test_guidance_with_edit_and_with_windows(tiny):
-    """The controls act in edit runs and windowed runs (set in either order with their state), graph replay equals eager."""
-    sd, model, dac, conds = tiny
+    """The controls act in edit runs and windowed runs (set in either order with their state), graph replay equals eager, and
+    the eager run lies within the loop gate of the restated loop under the same options."""
+    sd, _dsd, model, dac, conds = tiny
     scale, spec = CASES["all three"]
     g = torch.Generator().manual_seed(9)
     noise, x0 = torch.randn(1, 128, 50, generator=g), 0.7 * torch.randn(1, 128, 50, generator=g)
@@ -138,6 +114,7 @@ def test_guidance_with_edit_and_with_windows(tiny):
     e1 = _run(model, dac, conds[:1], noise, "heun-2", scale, spec, True, edit=edit)[2]
     base = _run(model, dac, conds[:1], noise, "heun-2", 4.5, None, False, edit=edit)[2]
     assert rel_err(e1, e0) < 1e-6 and rel_err(e0, base) > 1e-2
+    e_edit = rel_err(e0, _loop(sd, conds[:1], noise, "heun-2", scale, spec, edit=(x0, edit.mask, 0.6)))
     plan = long_form.WindowPlan.from_frames([0, 30, 45], 50)
     wn = torch.randn(1, 128, plan.Ltot, generator=g)
     three = [conds[0], conds[1], conds[0]]
@@ -145,8 +122,13 @@ def test_guidance_with_edit_and_with_windows(tiny):
     w1 = _run(model, dac, three, wn, "euler", scale, spec, True, windows=plan)[2]
     wb = _run(model, dac, three, wn, "euler", 4.5, None, False, windows=plan)[2]
     assert rel_err(w1, w0) < 1e-6 and rel_err(w0, wb) > 1e-2
+    e_win = rel_err(w0, _loop(sd, three, wn, "euler", scale, spec, windows=plan))
+    print("guidance with an edit: %.2e, with windows: %.2e" % (e_edit, e_win))
+    record_parity("loop.guidance.edit", rel_err=e_edit)
+    record_parity("loop.guidance.windows", rel_err=e_win)
+    assert e_edit < 1e-4 and e_win < 1e-4, (e_edit, e_win)
     # the other call order on the context itself: windows first, guidance second
-    vis, txt = _batched(three)
+    vis, txt = H.batched(three)
     vis = {k: sampler.window_rows(v, 1, 3, k) for k, v in vis.items()}
     txt = {k: sampler.window_rows(v, 1, 3, k) for k, v in txt.items()}
     pl = sampler.build_plan(model, vis, txt, 50, scale, 10, 3, "euler", edit_i0=0, guidance=spec)
@@ -163,8 +145,8 @@ def test_guidance_with_edit_and_with_windows(tiny):
 def test_graph_keyed_on_the_guidance_state(tiny):
     """One context, use_graph=True: plain -> three halves -> rescale on -> new schedule values -> plain; every run equals its eager
     run.  New values of the same shape only rewrite the table a replay reads: the captured iteration and every buffer stay."""
-    sd, model, dac, conds = tiny
-    noise = _noise(1, 11)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(1, 11)
     seq = [(4.5, None), (2.0, Spec(g_video=7.0)), (2.0, Spec(g_video=7.0, rescale=0.7)), (3.0, Spec(g_video=5.0, rescale=0.4, interval=(0.1, 0.8))),
            (4.5, None)]
     want = [_run(model, dac, conds[:1], noise, "euler", s, sp, False)[2].clone() for s, sp in seq]
@@ -176,15 +158,7 @@ def test_graph_keyed_on_the_guidance_state(tiny):
             assert rel_err(want[i], want[j]) > 1e-3, (i, j)
     assert torch.equal(want[0], want[-1])
 
-    lib = rt.load_library()
-    lib.foley_debug_run_state.argtypes, lib.foley_debug_run_state.restype = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int
-
-    def state():
-        """(iterations captured so far, addresses of the workspace, the schedule table, the factors) - test-only entry."""
-        out = (ctypes.c_uint64 * 4)()
-        rt._check(lib, lib.foley_debug_run_state(model.ctx._h, out), "foley_debug_run_state")
-        return tuple(out)
-
+    state = lambda: H.run_state(model)
     # the same shape with new values - the text scale included, which a table replaces: no new capture, every buffer where it was
     a = _run(model, dac, conds[:1], noise, "euler", 2.0, Spec(g_video=7.0, rescale=0.7), True)[2].clone()
     s0 = state()
@@ -205,8 +179,8 @@ def test_graph_keyed_on_the_guidance_state(tiny):
 
 
 def test_set_guidance_refusals(tiny, dev):
-    sd, model, dac, conds = tiny
-    vis, txt = _batched(conds[:1])
+    sd, _dsd, model, dac, conds = tiny
+    vis, txt = H.batched(conds[:1])
     ctx = model.ctx
     ctx.prepare(sampler.build_plan(model, vis, txt, 50, 1.0, 10, 1, "euler"))                # one half
     with pytest.raises(rt.FoleyRuntimeError, match="one half"):

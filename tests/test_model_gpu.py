@@ -9,6 +9,7 @@ import torch
 
 from conftest import golden, record_parity, rel_err
 from foley_amd.host import config as C, sampler, synth, tables
+from loop_harness import tiny_run
 from oracle import foley_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -45,11 +46,7 @@ def _forward(model, x, t, cond, clip, sync):
 
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    dsd = synth.synth_dac_state_dict(C.DAC_TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(dsd, dev, C.DAC_TINY)
-    return sd, dsd, model, dac
+    return tiny_run(dev, 0)[:4]
 
 
 def test_dit_forward_tiny_golden(tiny):

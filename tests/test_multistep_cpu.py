@@ -1,5 +1,5 @@
 """Multistep solvers without a GPU: the Adams-Bashforth tables of host/tables.py (exactness on polynomials, warm-up, the edit
-suffix), the order of the table-driven loop on an analytic problem (tests/multistep_ref.py), the restated model loop against the
+suffix), the order of the table-driven loop on an analytic problem (tests/multistep_ref.py), the restated model loop (tests/loop_ref.py) against the
 oracle's Euler loop, the refusals, the ABI surface and the keyword plumbing of the sampler entry points and the node."""
 import contextlib
 import ctypes
@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from abi_pin import assert_abi_version
+import loop_ref as L
 import multistep_ref as M
 from foley_amd import nodes
 from foley_amd.host import config as C, long_form, runtime as rt, sampler, synth, tables
@@ -137,9 +138,9 @@ def test_restated_loop_is_the_oracle_without_history_and_moves_with_it():
     one, zero = torch.tensor(1.0), torch.tensor(0.0)
     with torch.inference_mode():
         want = O.sample_latents(*args, "euler")
-        assert torch.equal(M.restated_loop(*args, weights=[(one, zero, zero)] * 10), want)
+        assert torch.equal(L.restated_loop(*args, weights=[(one, zero, zero)] * 10).x, want)
         for order in (2, 3):
-            got = M.restated_loop(*args, order=order)
+            got = L.restated_loop(*args, order=order).x
             rel = float((got - want).norm() / want.norm())
             print("order %d against euler: %.3e" % (order, rel))
             assert rel > 1e-2, (order, rel)

@@ -1,13 +1,12 @@
 """The step cache without a GPU: the policy state machine of host/step_cache.py against hand-worked sequences, the spec and node
-refusals, what build_plan hands to the library, the restated loop of tests/step_cache_ref.py against the plain one, the C surface."""
+refusals, what build_plan hands to the library, the restated loop of tests/loop_ref.py under it against the plain one, the C surface."""
 import os
 import re
 
 import pytest
 import torch
 
-import guidance_ref as G
-import step_cache_ref as R
+import loop_ref as L
 from abi_pin import assert_abi_version
 from conftest import ROOT, rel_err
 from foley_amd import nodes
@@ -121,10 +120,10 @@ def test_restated_loop_idle_is_the_plain_loop_and_skipping_moves_it(tiny):
     sd, c, noise = tiny
     a = (sd, C.TINY.heads, noise, c["text"], c["uncond_text"], c["clip"], c["sync"], 10, 4.5, "heun-2")
     with torch.inference_mode():
-        plain = G.restated_loop(*a)
-        off, _ = R.cached_loop(*a, spec=None)
-        idle, info = R.cached_loop(*a, spec=Spec(threshold=0.0))
-        alt, ia = R.cached_loop(*a, spec=Spec(skip=range(1, 10, 2)))
+        plain = L.restated_loop(*a).x
+        off = L.restated_loop(*a, cache=None).x
+        idle, _, info = L.restated_loop(*a, cache=Spec(threshold=0.0))
+        alt, _, ia = L.restated_loop(*a, cache=Spec(skip=range(1, 10, 2)))
     assert torch.equal(off, plain) and torch.equal(idle, plain)
     assert info["skipped"] == [0] * 10 and info["rel"][0] == -1.0 and all(0.05 < r < 0.3 for r in info["rel"][1:])
     assert ia["skipped"] == [0, 1, 0, 1, 0, 1, 0, 1, 0, 0]

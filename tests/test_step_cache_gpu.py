@@ -1,4 +1,4 @@
-"""The step cache on the HIP engine, end to end: schedule and threshold mode against the restated loop of tests/step_cache_ref.py
+"""The step cache on the HIP engine, end to end: schedule and threshold mode against the restated loop of tests/loop_ref.py
 (the oracle's forward under the cached iteration), the armed-but-idle and unset states bit for bit, the keying of the captured
 graphs, the combinations with guidance and per-clip conditioning, full width in fp32 and bf16, the refusals.
 
@@ -10,9 +10,9 @@ import ctypes
 import pytest
 import torch
 
+import loop_harness as H
+import loop_ref as L
 from abi_pin import assert_abi_version
-import guidance_ref as G
-import step_cache_ref as R
 from conftest import record_parity, rel_err
 from foley_amd.host import audio_edit, config as C, long_form, runtime as rt, sampler, step_cache as S, synth
 
@@ -29,61 +29,28 @@ def alternate(n):
 
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(synth.synth_dac_state_dict(C.DAC_TINY), dev, C.DAC_TINY)
-    conds = [synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd, seed=10 + 3 * i) for i in range(2)]
-    return sd, model, dac, conds
-
-
-def _batched(conds):
-    cat = lambda k: torch.cat([c[k] for c in conds])
-    return ({"siglip2_feat": cat("clip"), "syncformer_feat": cat("sync")},
-            {"text_feat": cat("text"), "uncond_text_feat": cat("uncond_text")})
+    return H.tiny_run(dev, 2)
 
 
 def _run(model, dac, conds, noise, solver, steps, spec, use_graph=False, scale=4.5, **kw):
-    vis, txt = _batched(conds)
-    return sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, scale, steps, noise.shape[0], solver, noise=noise,
-                                                  use_graph=use_graph, return_latents=True, step_cache=spec, **kw)
+    return H.run(model, dac, conds, noise, solver, steps, scale, use_graph, step_cache=spec, **kw)
 
 
-_LOOPS = {}
-
-
-def _ref(sd, conds, noise, solver, steps, spec, tag, scale=4.5, **kw):
-    """cached_loop of the given clips (conditioning batched per clip), once per distinct argument set: (x, info)."""
-    key = (tag, solver, steps, spec, scale) + tuple(sorted(kw.items()))
-    if key not in _LOOPS:
-        cat = lambda k: torch.cat([c[k] for c in conds])
-        with torch.inference_mode():
-            _LOOPS[key] = R.cached_loop(sd, C.TINY.heads, noise, cat("text"), cat("uncond_text"), cat("clip"), cat("sync"), steps, scale,
-                                        solver, spec=spec, **kw)
-    return _LOOPS[key]
-
-
-def _noise(n, seed=5):
-    return torch.randn(n, 128, 50, generator=torch.Generator().manual_seed(seed))
-
-
-def _state(model):
-    """(iterations captured so far, workspace / schedule / factor addresses) - the test-only entry of the library."""
-    lib = rt.load_library()
-    lib.foley_debug_run_state.argtypes, lib.foley_debug_run_state.restype = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int
-    out = (ctypes.c_uint64 * 4)()
-    rt._check(lib, lib.foley_debug_run_state(model.ctx._h, out), "foley_debug_run_state")
-    return tuple(out)
+def _ref(sd, conds, noise, solver, steps, spec, scale=4.5, **kw):
+    """The restated loop of the given clips (conditioning batched per clip) under the spec: (x, info)."""
+    ref = H.ref_loop(sd, conds, noise, steps, scale, solver, cache=spec, **kw)
+    return ref.x, ref.info
 
 
 # ----------------------------------------------------------------------------- schedule mode against the restated loop
 @pytest.mark.parametrize("use_graph", [False, True])
 @pytest.mark.parametrize("solver", list(RUNS))
 def test_schedule_mode_matches_the_restated_loop(tiny, solver, use_graph):
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     n = RUNS[solver]
-    noise = _noise(1)
-    want, info = _ref(sd, conds[:1], noise, solver, n, alternate(n), "one")
-    plain, _ = _ref(sd, conds[:1], noise, solver, n, None, "one")
+    noise = H.noise(1)
+    want, info = _ref(sd, conds[:1], noise, solver, n, alternate(n))
+    plain, _ = _ref(sd, conds[:1], noise, solver, n, None)
     assert rel_err(want, plain) > 1e-2                       # the control, on the references alone: far above the gate
     _a, _sr, lat = _run(model, dac, conds[:1], noise, solver, n, alternate(n), use_graph)
     rep = model.ctx.plan["step_cache_report"]
@@ -112,11 +79,11 @@ def test_threshold_mode(tiny, solver, use_graph):
     """The threshold of each run is one whose accumulated sums stay >= 2 % away from it on every decided iteration of the REFERENCE
     loop (euler / 20 at 0.25: 4.1 %; heun-2 / 10 at 0.3: 6.5 %): the library's fp32 change measure is ~1e-6 from fp64, so no decision
     can flip.  The margin is re-derived here - a changed synthesiser fails loudly instead of silently flipping."""
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     n, th = RUNS[solver], THRESHOLDS[solver]
-    noise = _noise(1)
-    want, info = _ref(sd, conds[:1], noise, solver, n, Spec(threshold=th), "one")
-    mg = R.margin(info, th)
+    noise = H.noise(1)
+    want, info = _ref(sd, conds[:1], noise, solver, n, Spec(threshold=th))
+    mg = L.margin(info, th)
     assert mg >= 0.02, (solver, th, mg)
     sk = info["skipped"]
     assert sum(sk) >= 3 and sk.count(0) >= 3 and 2 in _run_lengths(sk), sk
@@ -137,8 +104,8 @@ IDLE = {"threshold 0": Spec(threshold=0.0), "empty list": Spec(skip=())}
 @pytest.mark.parametrize("idle", list(IDLE))
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_armed_but_idle_is_the_plain_run(tiny, use_graph, idle):
-    sd, model, dac, conds = tiny
-    noise = _noise(2, 7)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(2, 7)
     a0, _, l0 = _run(model, dac, conds[:1], noise, "heun-2", 10, None, use_graph)
     a1, _, l1 = _run(model, dac, conds[:1], noise, "heun-2", 10, IDLE[idle], use_graph)
     assert model.ctx.plan["step_cache_report"]["skipped"] == [0] * 10
@@ -146,7 +113,7 @@ def test_armed_but_idle_is_the_plain_run(tiny, use_graph, idle):
 
 
 def test_armed_but_idle_is_the_plain_edit_run_and_windowed_run(tiny):
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     g = torch.Generator().manual_seed(8)
     noise, x0 = torch.randn(1, 128, 50, generator=g), 0.7 * torch.randn(1, 128, 50, generator=g)
     edit = audio_edit.EditSpec(x0, 0.6, audio_edit.build_mask(50, [(0.3, 0.6)], 0.1))
@@ -166,7 +133,7 @@ def test_armed_but_idle_is_the_plain_edit_run_and_windowed_run(tiny):
 
 def test_skipping_acts_in_edit_and_windowed_runs(tiny):
     """The cache moves edit runs and windowed runs too (their step forms follow a skipped iteration), graph replay equals eager."""
-    sd, model, dac, conds = tiny
+    sd, _dsd, model, dac, conds = tiny
     g = torch.Generator().manual_seed(9)
     noise, x0 = torch.randn(1, 128, 50, generator=g), 0.7 * torch.randn(1, 128, 50, generator=g)
     edit = audio_edit.EditSpec(x0, 0.6, audio_edit.build_mask(50, [(0.3, 0.6)], 0.1))
@@ -189,20 +156,20 @@ def test_skipping_acts_in_edit_and_windowed_runs(tiny):
 
 # ----------------------------------------------------------------------------- graph keying
 def test_graphs_keyed_on_cache_on_off_only(tiny):
-    sd, model, dac, conds = tiny
-    noise = _noise(1, 11)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(1, 11)
     p0 = _run(model, dac, conds[:1], noise, "euler", 20, None, True)[2].clone()
-    s0 = _state(model)
+    s0 = H.run_state(model)
     assert torch.equal(_run(model, dac, conds[:1], noise, "euler", 20, None, True)[2], p0)
-    assert _state(model) == s0                               # unset: one captured iteration, replayed - as ever
+    assert H.run_state(model) == s0                               # unset: one captured iteration, replayed - as ever
     c0 = _run(model, dac, conds[:1], noise, "euler", 20, alternate(20), True)[2].clone()
-    s1 = _state(model)
+    s1 = H.run_state(model)
     assert s1[0] == s0[0] + 1                                # cache on: another key, one new capture (of the three graphs)
     # a new list, then threshold mode with two thresholds: host decisions between the replays - the captured graphs stay
     c1 = _run(model, dac, conds[:1], noise, "euler", 20, Spec(skip=(3, 4, 9)), True)[2].clone()
     c2 = _run(model, dac, conds[:1], noise, "euler", 20, Spec(threshold=0.25), True)[2].clone()
     c3 = _run(model, dac, conds[:1], noise, "euler", 20, Spec(threshold=0.4, max_consecutive=3), True)[2].clone()
-    assert _state(model) == s1
+    assert H.run_state(model) == s1
     outs = [p0, c0, c1, c2, c3]
     for i in range(len(outs)):
         for j in range(i + 1, len(outs)):
@@ -217,11 +184,11 @@ def test_graphs_keyed_on_cache_on_off_only(tiny):
 # ----------------------------------------------------------------------------- combinations
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_three_halves_and_rescale_under_a_schedule(tiny, use_graph):
-    sd, model, dac, conds = tiny
-    noise = _noise(1)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(1)
     guid = dict(g_video=7.0, rescale=0.7)
-    want, info = _ref(sd, conds[:1], noise, "heun-2", 10, alternate(10), "one", scale=2.0, **guid)
-    plain, _ = _ref(sd, conds[:1], noise, "heun-2", 10, None, "one", scale=2.0, **guid)
+    want, info = _ref(sd, conds[:1], noise, "heun-2", 10, alternate(10), scale=2.0, **guid)
+    plain, _ = _ref(sd, conds[:1], noise, "heun-2", 10, None, scale=2.0, **guid)
     assert rel_err(want, plain) > 1e-2
     _a, _sr, lat = _run(model, dac, conds[:1], noise, "heun-2", 10, alternate(10), use_graph, scale=2.0, guidance=Guid(**guid))
     assert model.ctx.plan["ncfg"] == 3 and model.ctx.plan["step_cache_report"]["skipped"] == info["skipped"]
@@ -231,11 +198,11 @@ def test_three_halves_and_rescale_under_a_schedule(tiny, use_graph):
 
 
 def test_three_halves_threshold_mode_takes_the_max_over_three_rows(tiny):
-    sd, model, dac, conds = tiny
-    noise = _noise(1)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(1)
     guid = dict(g_video=7.0, rescale=0.7)
-    th = _pick_threshold(lambda t: _ref(sd, conds[:1], noise, "heun-2", 10, Spec(threshold=t), "one", scale=2.0, **guid)[1])
-    want, info = _ref(sd, conds[:1], noise, "heun-2", 10, Spec(threshold=th), "one", scale=2.0, **guid)
+    th = _pick_threshold(lambda t: _ref(sd, conds[:1], noise, "heun-2", 10, Spec(threshold=t), scale=2.0, **guid)[1])
+    want, info = _ref(sd, conds[:1], noise, "heun-2", 10, Spec(threshold=th), scale=2.0, **guid)
     _a, _sr, lat = _run(model, dac, conds[:1], noise, "heun-2", 10, Spec(threshold=th), True, scale=2.0, guidance=Guid(**guid))
     rep = model.ctx.plan["step_cache_report"]
     assert rep["skipped"] == info["skipped"] and sum(rep["skipped"]) >= 2
@@ -247,7 +214,7 @@ def _pick_threshold(info_of, candidates=(0.3, 0.25, 0.2, 0.35, 0.4, 0.15)):
     """The first candidate whose reference loop skips at least twice and keeps every decided sum >= 2 % from the threshold."""
     for t in candidates:
         info = info_of(t)
-        if sum(info["skipped"]) >= 2 and R.margin(info, t) >= 0.02:
+        if sum(info["skipped"]) >= 2 and L.margin(info, t) >= 0.02:
             return t
     raise AssertionError("no candidate threshold keeps a 2 % margin on the reference loop")
 
@@ -256,14 +223,14 @@ def _pick_threshold(info_of, candidates=(0.3, 0.25, 0.2, 0.35, 0.4, 0.15)):
 def test_two_clips_with_their_own_videos_in_threshold_mode(tiny, use_graph):
     """Two clips, different videos and prompts: four batch rows, ONE decision per iteration - the max over the four.  The reference
     runs the two clips as one batch for that reason; the pattern differs from what either clip would get alone only through it."""
-    sd, model, dac, conds = tiny
-    noise = _noise(2, 6)
-    th = _pick_threshold(lambda t: _ref(sd, conds, noise, "heun-2", 10, Spec(threshold=t), "two")[1])
-    want, info = _ref(sd, conds, noise, "heun-2", 10, Spec(threshold=th), "two")
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(2, 6)
+    th = _pick_threshold(lambda t: _ref(sd, conds, noise, "heun-2", 10, Spec(threshold=t))[1])
+    want, info = _ref(sd, conds, noise, "heun-2", 10, Spec(threshold=th))
     _a, _sr, lat = _run(model, dac, conds, noise, "heun-2", 10, Spec(threshold=th), use_graph)
     assert model.ctx.plan["vis_of"] is not None             # laid out per batch row
     rep = model.ctx.plan["step_cache_report"]
-    print("two clips, threshold %g graph=%d: %s margin %.3f" % (th, use_graph, info["skipped"], R.margin(info, th)))
+    print("two clips, threshold %g graph=%d: %s margin %.3f" % (th, use_graph, info["skipped"], L.margin(info, th)))
     assert rep["skipped"] == info["skipped"]
     assert max(abs(g - w) / w for g, w in zip(rep["rel"][1:], info["rel"][1:])) < 1e-4
     for k in range(2):
@@ -272,8 +239,8 @@ def test_two_clips_with_their_own_videos_in_threshold_mode(tiny, use_graph):
 
 # ----------------------------------------------------------------------------- refusals of the library
 def test_set_step_cache_refusals(tiny, dev):
-    sd, model, dac, conds = tiny
-    vis, txt = _batched(conds[:1])
+    sd, _dsd, model, dac, conds = tiny
+    vis, txt = H.batched(conds[:1])
     ctx = model.ctx
     ctx.prepare(sampler.build_plan(model, vis, txt, 50, 4.5, 10, 1, "euler"))
     with pytest.raises(rt.FoleyRuntimeError, match="n_skip == n_iter"):
@@ -306,8 +273,8 @@ def test_interval_cap_and_polynomial_decide_as_the_python_machine(tiny):
     host/step_cache.StepCachePolicy fed the change the library REPORTED: both work in double precision from the same fp32 values,
     so the patterns are equal with no margin.  The options bind: no skip outside the interval, no run longer than the cap, and
     the run without them skips elsewhere."""
-    sd, model, dac, conds = tiny
-    noise = _noise(1)
+    sd, _dsd, model, dac, conds = tiny
+    noise = H.noise(1)
     spec = Spec(threshold=1.0, poly=(8.0, 1.0, 0.0), interval=(0.2, 0.8), max_consecutive=2)     # 8 rel^2 + rel: ~0.2 per iteration
     for use_graph in (False, True):
         _run(model, dac, conds[:1], noise, "euler", 20, spec, use_graph)
@@ -333,8 +300,8 @@ def test_alternate_schedule_at_full_width(dev):
     noise = torch.randn(1, 128, 50, generator=torch.Generator().manual_seed(31)).to(torch.bfloat16).float()
     a = (sd, c11.heads, noise, cond["text"], cond["uncond_text"], cond["clip"], cond["sync"], 6, 4.5, "euler")
     with torch.inference_mode():
-        want, info = R.cached_loop(*a, spec=alternate(6))
-        plain = G.restated_loop(*a)
+        want, _, info = L.restated_loop(*a, cache=alternate(6))
+        plain = L.restated_loop(*a).x
     assert info["skipped"] == [0, 1, 0, 1, 0, 0] and rel_err(want, plain) > 1e-3
     vis = {"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}
     txt = {"text_feat": cond["text"], "uncond_text_feat": cond["uncond_text"]}

@@ -6,9 +6,10 @@ import ctypes
 import pytest
 import torch
 
+import loop_harness as H
 import timeline_ref as TR
 from conftest import rel_err
-from foley_amd.host import audio_edit, config as C, long_form, prompt_timeline as PT, runtime as rt, sampler, synth
+from foley_amd.host import audio_edit, config as C, long_form, prompt_timeline as PT, runtime as rt, sampler
 from oracle import foley_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +20,7 @@ PLAN = dict(starts=[0, 30, 45], La=50)             # the windows of test_windows
 
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    dsd = synth.synth_dac_state_dict(C.DAC_TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(dsd, dev, C.DAC_TINY)
-    conds = [synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd, seed=10 + 3 * i) for i in range(3)]
+    sd, dsd, model, dac, conds = H.tiny_run(dev, 3)
     texts = torch.cat([O.pad_or_trim_text(c["text"], 77) for c in conds])        # the features of prompts "a", "b", "c"
     unc = O.pad_or_trim_text(conds[0]["uncond_text"], 77)
     return sd, dsd, model, dac, conds[0], texts, unc
@@ -37,18 +34,15 @@ def _timeline(spans, base, crossfade, duration=1.0):
     return PT.parse(spans, base, duration, crossfade)
 
 
-def _feats(cond, texts, unc, tl):
-    rows = texts[[_ROW[p] for p in tl.prompts]] if tl is not None else None
-    return ({"siglip2_feat": cond["clip"], "syncformer_feat": cond["sync"]}, {"text_feat": rows, "uncond_text_feat": unc})
+def _cond(cond, texts, unc, tl, plain=None):
+    """The clip's conditioning with the timeline's prompts as its text rows (no timeline: the one prompt `plain`)."""
+    rows = texts[[_ROW[p] for p in tl.prompts]] if tl is not None else texts[_ROW[plain]:_ROW[plain] + 1]
+    return dict(cond, text=rows, uncond_text=unc)
 
 
 def _run(model, dac, cond, texts, unc, tl, noise, solver="euler", use_graph=False, plain=None, edit=None, windows=None, dtype_model=None):
-    vis, txt = _feats(cond, texts, unc, tl)
-    if tl is None:
-        txt["text_feat"] = texts[_ROW[plain]:_ROW[plain] + 1]
-    return sampler.denoise_process_with_generator(vis, txt, 1.0, dtype_model or model, dac, CFG, STEPS, noise.shape[0],
-                                                  solver, noise=noise, use_graph=use_graph, return_latents=True, timeline=tl, edit=edit,
-                                                  windows=windows)[2]
+    return H.run(dtype_model or model, dac, [_cond(cond, texts, unc, tl, plain)], noise, solver, STEPS, CFG, use_graph, timeline=tl,
+                 edit=edit, windows=windows)[2]
 
 
 _ORACLE = {}
@@ -104,14 +98,6 @@ def test_two_prompt_timeline_differs_from_either_prompt(tiny):
         assert e > 1e-3, (p, e)
 
 
-def _captures(model):
-    lib = rt.load_library()
-    lib.foley_debug_run_state.argtypes, lib.foley_debug_run_state.restype = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int
-    out = (ctypes.c_uint64 * 4)()
-    rt._check(lib, lib.foley_debug_run_state(model.ctx._h, out), "foley_debug_run_state")
-    return int(out[0])
-
-
 def test_graph_keyed_on_the_timeline_state(tiny):
     """One context, use_graph=True: plain, timeline A, timeline B of the same shape (graph kept, tables rewritten), plain, edit
     with a timeline, windowed with a timeline.  Every run equals its eager run."""
@@ -134,9 +120,9 @@ def test_graph_keyed_on_the_timeline_state(tiny):
         assert rel_err(want[a], want[b]) > 1e-3, (a, b)
     caps = {}
     for name, tl, noise, edit, win in seq:
-        c0 = _captures(model)
+        c0 = H.captures(model)
         got = _run(model, dac, cond, texts, unc, tl, noise, use_graph=True, plain="c", edit=edit, windows=win)
-        caps[name] = _captures(model) - c0
+        caps[name] = H.captures(model) - c0
         assert rel_err(got, want[name]) < 1e-6, name
     assert caps["A"] >= 1 and caps["B"] == 0 and caps["plain"] >= 1, caps      # plain <-> timeline re-captures, A -> B keeps the graph
 
@@ -154,18 +140,14 @@ def test_graph_keyed_across_different_options(tiny, dev):
     ed = audio_edit.EditSpec(0.7 * torch.randn(2, 128, LA, generator=g), 1.0, audio_edit.build_mask(LA, [(0.2, 0.5)], 0.1))
     Guid = sampler.GuidanceSpec
     seq = [("plain", {}),
-           ("windows, order 2", dict(bs=1, noise=nw, windows=wplan, multistep=sampler.MultistepSpec(2))),
+           ("windows, order 2", dict(noise=nw, windows=wplan, multistep=sampler.MultistepSpec(2))),
            ("edit, schedule, rescale", dict(edit=ed, guidance=Guid(interval=(0.2, 0.7), rescale=0.7))),
            ("skip list, three halves", dict(scale=2.0, guidance=Guid(g_video=7.0), step_cache=sampler.StepCacheSpec(skip=(3, 6)))),
            ("timeline", dict(tl=_timeline(*THREE))),
            ("plain", {})]
 
-    def call(m, use_graph, tl=None, scale=CFG, bs=2, noise=n2, **kw):
-        vis, txt = _feats(cond, texts, unc, tl)
-        if tl is None:
-            txt["text_feat"] = texts[2:3]
-        return sampler.denoise_process_with_generator(vis, txt, 1.0, m, dac, scale, STEPS, bs, "euler", noise=noise, use_graph=use_graph,
-                                                      return_latents=True, timeline=tl, **kw)[2].clone()
+    def call(m, use_graph, tl=None, scale=CFG, noise=n2, **kw):
+        return H.run(m, dac, [_cond(cond, texts, unc, tl, "c")], noise, "euler", STEPS, scale, use_graph, timeline=tl, **kw)[2].clone()
 
     want = {}
     for name, kw in seq[:-1]:
@@ -178,11 +160,11 @@ def test_graph_keyed_across_different_options(tiny, dev):
     one = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
     got = []
     for name, kw in seq:
-        c0 = _captures(one)
+        c0 = H.captures(one)
         got.append(call(one, True, **kw))
         e = rel_err(got[-1], want[name])
-        print("%s: graph vs eager %.2e, captures +%d" % (name, e, _captures(one) - c0))
-        assert _captures(one) == c0 + 1, name
+        print("%s: graph vs eager %.2e, captures +%d" % (name, e, H.captures(one) - c0))
+        assert H.captures(one) == c0 + 1, name
         assert torch.equal(got[-1], want[name]), (name, e)
     assert torch.equal(got[-1], got[0])
 
@@ -190,8 +172,8 @@ def test_graph_keyed_across_different_options(tiny, dev):
 def test_prepare_timeline_refusals(tiny):
     _sd, _dsd, model, dac, cond, texts, unc = tiny
     tl = _timeline(*THREE)
-    vis, txt = _feats(cond, texts, unc, tl)
-    n = 2 * (cond["clip"].shape[1] + LA)
+    vis, txt = H.batched([_cond(cond, texts, unc, tl)])
+    n = 2 *(cond["clip"].shape[1] + LA)
 
     def plan(**edits):
         p = dict(sampler.build_plan(model, vis, txt, LA, CFG, STEPS, 1, "euler", timeline=tl))

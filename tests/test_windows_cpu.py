@@ -1,10 +1,11 @@
 """Long clips as overlapping windows without a GPU: where the windows start, the blend weights, the refusals, the node's keyword
-plumbing, and the fp32 oracle restatement of the coupled loop that tests/test_windows_gpu.py compares against."""
+plumbing, and the windows of the restated loop (tests/loop_ref.py) that tests/test_windows_gpu.py compares against."""
 import types
 
 import pytest
 import torch
 
+import loop_ref as L
 from conftest import rel_err
 from foley_amd import nodes
 from foley_amd.host import config as C, long_form, sampler, synth
@@ -12,52 +13,7 @@ from oracle import foley_oracle as O
 
 
 # ----------------------------------------------------------------------------- restatement of the coupled loop
-def stitch(x, plan):
-    """x [variations*n_win, C, La] -> [variations, C, Ltot]: the weighted mean per global frame, in window order (fp32)."""
-    V = x.shape[0] // plan.n_win
-    out = torch.zeros(V, x.shape[1], plan.Ltot, dtype=torch.float32)
-    for v in range(V):
-        for k, s in enumerate(plan.starts):
-            out[v, :, s:s + plan.La] += plan.weights[k] * x[plan.clip_index(v, k)]
-    return out
-
-
-def oracle_windowed_latents(sd, heads, noise, conds, plan, steps, guidance, solver, text_len=77):
-    """The coupled loop on the CPU oracle: `O.sample_latents`' iterations (same timesteps, same SolverState stage bookkeeping)
-    on the batch of variations*n_win windows, clip v*n_win + k being the frames [starts[k], starts[k] + La) of noise[v] under
-    conds[k]; after every iteration that advances the sigma index, every global frame is replaced in all the windows that cover
-    it by sum_k weights[k] * x_k (window order, fp32).  Returns the stitched latents [variations, C, Ltot]; the windows' final
-    states are the second value.  noise [variations, C, Ltot]; conds: one conditioning dict per window."""
-    V, n_win, La = noise.shape[0], plan.n_win, plan.La
-    assert len(conds) == n_win and noise.shape[2] == plan.Ltot
-    sig = O.flow_sigmas(steps)
-    ts = O.flow_timesteps(sig)
-    st = O.SolverState(sig, solver)
-    per_clip = lambda key: torch.cat([conds[k][key] for _v in range(V) for k in range(n_win)])
-    text_r = O.pad_or_trim_text(per_clip("text"), text_len)
-    unc_r = O.pad_or_trim_text(per_clip("uncond_text"), text_len)
-    clip_r, sync_r = per_clip("clip"), per_clip("sync")
-    bs = V * n_win
-    if guidance > 1.0:
-        e_clip = sd["empty_clip_feat"].unsqueeze(0).expand(bs, clip_r.shape[1], -1)
-        e_sync = sd["empty_sync_feat"].unsqueeze(0).expand(bs, sync_r.shape[1], -1)
-        clip_in, sync_in, text_in = torch.cat([e_clip, clip_r]), torch.cat([e_sync, sync_r]), torch.cat([unc_r, text_r])
-    else:
-        clip_in, sync_in, text_in = clip_r, sync_r, text_r
-    noise = noise.float()
-    x = torch.stack([noise[v, :, s:s + La] for v in range(V) for s in plan.starts])
-    for i in range(steps):
-        xin = torch.cat([x, x]) if guidance > 1.0 else x
-        v = O.dit_forward(sd, heads, xin, ts[i].expand(xin.shape[0]), text_in, clip_in, sync_in)
-        if guidance > 1.0:
-            vu, vc = v.chunk(2)
-            v = vu + guidance * (vc - vu)
-        k0 = st.idx
-        x = st.step(v, x)
-        if st.idx != k0 and n_win > 1:
-            g = stitch(x, plan)
-            x = torch.stack([g[vv, :, s:s + La] for vv in range(V) for s in plan.starts])
-    return stitch(x, plan) if n_win > 1 else x, x
+KEYS = ("text", "uncond_text", "clip", "sync")
 
 
 @pytest.fixture(scope="module")
@@ -71,10 +27,10 @@ def test_restatement_one_window_is_the_plain_loop(tiny_cpu):
     sd, cond = tiny_cpu
     noise = torch.randn(2, 128, 50, generator=torch.Generator().manual_seed(5))
     plan = long_form.WindowPlan.from_frames([0], 50)
+    c = [cond[k] for k in KEYS]
     for solver, steps in (("euler", 6), ("heun-2", 6)):
-        ref = O.sample_latents(sd, C.TINY.heads, noise, cond["text"], cond["uncond_text"], cond["clip"], cond["sync"],
-                               steps, 4.5, solver)
-        got, _ = oracle_windowed_latents(sd, C.TINY.heads, noise, [cond], plan, steps, 4.5, solver)
+        ref = O.sample_latents(sd, C.TINY.heads, noise, *c, steps, 4.5, solver)
+        got = L.restated_loop(sd, C.TINY.heads, noise, *c, steps, 4.5, solver, windows=plan).x
         assert torch.equal(got, ref), solver
 
 
@@ -86,7 +42,7 @@ def test_restatement_two_disjoint_windows_are_two_runs(tiny_cpu):
     noise = torch.randn(1, 128, 100, generator=torch.Generator().manual_seed(6))
     plan = long_form.WindowPlan.from_frames([0, 50], 50)
     assert torch.equal(plan.weights, torch.ones(2, 50))
-    got, _ = oracle_windowed_latents(sd, C.TINY.heads, noise, [cond, cond2], plan, 6, 4.5, "heun-2")
+    got = L.restated_loop(sd, C.TINY.heads, noise, *[torch.cat([cond[k], cond2[k]]) for k in KEYS], 6, 4.5, "heun-2", windows=plan).x
     for k, c in enumerate((cond, cond2)):
         ref = O.sample_latents(sd, C.TINY.heads, noise[:, :, 50 * k:50 * k + 50], c["text"], c["uncond_text"], c["clip"], c["sync"],
                                6, 4.5, "heun-2")
@@ -97,7 +53,7 @@ def test_restatement_windows_agree_after_euler(tiny_cpu):
     sd, cond = tiny_cpu
     plan = long_form.WindowPlan.from_frames([0, 30], 50)
     noise = torch.randn(1, 128, 80, generator=torch.Generator().manual_seed(7))
-    g, x = oracle_windowed_latents(sd, C.TINY.heads, noise, [cond, cond], plan, 4, 4.5, "euler")
+    g, x, _info = L.restated_loop(sd, C.TINY.heads, noise, *[cond[k] for k in KEYS], 4, 4.5, "euler", windows=plan)
     assert torch.equal(x[0, :, 30:], x[1, :, :20])
     assert rel_err(g[0, :, 30:50], x[0, :, 30:]) < 1e-6
 

@@ -1,32 +1,19 @@
 """Long clips as overlapping windows on the HIP engine: the windows step and the stitch against torch and against the plain step,
-the coupled loop against the oracle restatement (tests/test_windows_cpu.py), the exactness properties (disjoint windows = the
+the coupled loop against the restated loop (tests/loop_ref.py), the exactness properties (disjoint windows = the
 uncoupled batch, one window = the plain call, bit for bit), the keying of the captured graph, the refusals of the ABI, the decode."""
 import pytest
 import torch
 
+import loop_harness as H
 from conftest import rel_err
-from foley_amd.host import audio_edit, config as C, long_form, runtime as rt, sampler, synth, tables
+from foley_amd.host import audio_edit, config as C, long_form, runtime as rt, sampler, tables
 from oracle import foley_oracle as O
-from test_windows_cpu import oracle_windowed_latents
+from step_harness import ref_step
 
 pytestmark = pytest.mark.gpu
 
 
 # ----------------------------------------------------------------------------- ops
-def _ref_step(pred, x, x_saved, d_acc, row, ncfg, g):
-    """torch restatement of one plain step on the kernel's state: (x, x_saved, d_acc)."""
-    clips, Cc, L = x.shape
-    w_new, w_acc, dt, w_store, flags = [float(v) for v in row[:5]]
-    flags = int(flags)
-    P = pred.view(ncfg, clips, L, Cc).permute(0, 1, 3, 2)
-    v = P[0] + g * (P[1] - P[0]) if ncfg == 2 else P[0]
-    acc = torch.zeros_like(x) if flags & tables.STEP_ACC_RESET else d_acc
-    deriv = w_new * v + w_acc * acc if w_acc != 0 else w_new * v
-    base = x_saved if flags & tables.STEP_USE_SAVED else x
-    xs = x.clone() if flags & tables.STEP_SAVE_X else x_saved
-    return base + deriv * dt, xs, acc + w_store * v
-
-
 def _ref_blend(xn, plan, weights):
     """Every global frame replaced in all covering windows by sum_k w[k] * xn_k (fp32, window order)."""
     V = xn.shape[0] // plan.n_win
@@ -60,7 +47,7 @@ def _run_step_op(dev, solver, steps, rows_dtype, variations, starts, La):
     rows_p = torch.empty_like(rows)
     for it in range(steps):
         pred = torch.randn(ncfg * clips * La, Cc, generator=g).to(dev)
-        xn, xs, da = _ref_step(pred, x, x_saved, d_acc, coef[it].cpu(), ncfg, guid)
+        xn, xs, da = ref_step(pred, x, x_saved, d_acc, coef[it].cpu(), ncfg, guid)
         blend = bool(int(coef[it, 4]) & tables.STEP_BLEND)
         want_x = _ref_blend(xn, plan, w_t) if blend else xn
         xp, xsp, dap = x.clone(), x_saved.clone(), d_acc.clone()
@@ -137,35 +124,14 @@ def test_windows_stitch_op(dev):
 # ----------------------------------------------------------------------------- loop
 @pytest.fixture(scope="module")
 def tiny(dev):
-    sd = synth.synth_dit_state_dict(C.TINY)
-    dsd = synth.synth_dac_state_dict(C.DAC_TINY)
-    model = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
-    dac = sampler.FoleyDAC(dsd, dev, C.DAC_TINY)
-    conds = [synth.synth_conditioning(C.TINY, 1.0, t2a=False, sd=sd, seed=10 + 3 * i) for i in range(3)]
-    return sd, dsd, model, dac, conds
+    return H.tiny_run(dev, 3)
 
 
-def _batched(conds):
-    cat = lambda k: torch.cat([c[k] for c in conds])
-    return ({"siglip2_feat": cat("clip"), "syncformer_feat": cat("sync")},
-            {"text_feat": cat("text"), "uncond_text_feat": cat("uncond_text")})
-
-
-def _run(model, dac, conds, noise, solver, plan, use_graph=False, steps=10, edit=None):
-    vis, txt = _batched(conds)
-    return sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, steps, noise.shape[0], solver, noise=noise,
-                                                  use_graph=use_graph, return_latents=True, windows=plan, edit=edit)
+def _run(model, dac, conds, noise, solver, plan, use_graph=False, edit=None):
+    return H.run(model, dac, conds, noise, solver, 10, 4.5, use_graph, windows=plan, edit=edit)
 
 
 PLAN = dict(starts=[0, 30, 45], La=50)             # Ltot 95, frames 45..49 in all three windows
-_ORACLE = {}
-
-
-def _oracle(sd, conds, noise, solver):
-    if solver not in _ORACLE:
-        plan = long_form.WindowPlan.from_frames(**PLAN)
-        _ORACLE[solver] = oracle_windowed_latents(sd, C.TINY.heads, noise, conds, plan, 10, 4.5, solver)
-    return _ORACLE[solver]
 
 
 @pytest.mark.parametrize("solver", ["euler", "heun-2"])
@@ -173,8 +139,8 @@ def _oracle(sd, conds, noise, solver):
 def test_windowed_loop_matches_oracle(tiny, solver, use_graph):
     sd, _dsd, model, dac, conds = tiny
     plan = long_form.WindowPlan.from_frames(**PLAN)
-    noise = torch.randn(1, 128, plan.Ltot, generator=torch.Generator().manual_seed(5))
-    want, _ = _oracle(sd, conds, noise, solver)
+    noise = H.noise(1, 5, plan.Ltot)
+    want = H.ref_loop(sd, conds, noise, 10, 4.5, solver, windows=plan).x
     audio, _sr, lat = _run(model, dac, conds, noise, solver, plan, use_graph)
     assert lat.shape == (1, 128, 95) and audio.shape == (1, 1, 95 * C.DAC_TINY.hop)
     e = rel_err(lat, want)
@@ -187,7 +153,7 @@ def test_windows_agree_on_overlaps_after_euler(tiny, dev):
     _sd, _dsd, model, dac, conds = tiny
     plan = long_form.WindowPlan.from_frames(**PLAN)
     noise = torch.randn(1, 128, plan.Ltot, generator=torch.Generator().manual_seed(5)).to(dev)
-    vis, txt = _batched(conds)
+    vis, txt = H.batched(conds)
     model.ctx.prepare(sampler.build_plan(model, vis, txt, 50, 4.5, 10, 3, "euler", edit_i0=0))
     model.ctx.set_windows(plan.starts, plan.weights.to(dev))
     x = torch.stack([noise[0, :, s:s + 50] for s in plan.starts]).contiguous()
@@ -215,7 +181,7 @@ def test_one_window_is_the_plain_call(tiny):
     plan = long_form.WindowPlan.from_frames([0], 50)
     for use_graph in (False, True):
         gen = lambda: torch.Generator("cpu").manual_seed(99)
-        vis, txt = _batched(conds[:1])
+        vis, txt = H.batched(conds[:1])
         a0, _, l0 = sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, 10, 2, "euler", generator=gen(),
                                                            use_graph=use_graph, return_latents=True)
         a1, _, l1 = sampler.denoise_process_with_generator(vis, txt, 1.0, model, dac, 4.5, 10, 2, "euler", generator=gen(),
@@ -229,7 +195,7 @@ def test_two_variations(tiny):
     windowed run is one draw of [variations, C, Ltot] from the generator, like a plain run's."""
     _sd, _dsd, model, dac, conds = tiny
     plan = long_form.WindowPlan.from_frames(**PLAN)
-    vis, txt = _batched(conds)
+    vis, txt = H.batched(conds)
     _a, _sr, both = sampler.denoise_process_with_generator(vis, txt, 1.9, model, dac, 4.5, 10, 2, "euler", return_latents=True,
                                                            generator=torch.Generator("cpu").manual_seed(7), windows=plan)
     noise = sampler.draw_noise(2, 128, plan.Ltot, torch.float32, torch.Generator("cpu").manual_seed(7))
@@ -262,7 +228,7 @@ def test_graph_keyed_on_the_windows_state(tiny):
 
 def test_set_windows_refusals(tiny, dev):
     sd, _dsd, model, dac, conds = tiny
-    vis, txt = _batched(conds)
+    vis, txt = H.batched(conds)
     w3, w2 = torch.ones(3, 50, device=dev), torch.ones(2, 50, device=dev)
     fresh = sampler.FoleyModel(C.TINY, sd, torch.float32, dev, dac_cfg=C.DAC_TINY)
     with pytest.raises(rt.FoleyRuntimeError, match="foley_prepare has not been called"):

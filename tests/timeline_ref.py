@@ -5,6 +5,7 @@ import contextlib
 import torch
 import torch.nn.functional as F
 
+import loop_ref as L
 import opcheck as oc
 from oracle import foley_oracle as O
 
@@ -115,8 +116,8 @@ def _timed_triple_block(sets_raw, table):
 @contextlib.contextmanager
 def timed_text(sets_raw, table):
     """For the duration of the block, O.triple_block is the copy that applies `table` to the text sets `sets_raw` (O.dit_forward
-    and the loops built on it - O.sample_latents, test_windows_cpu.oracle_windowed_latents - then run with timed text; the `cond`
-    they pass is only used for its shape)."""
+    and the loops built on it - O.sample_latents, loop_ref.restated_loop - then run with timed text; the `cond` they pass is only
+    used for its shape)."""
     keep = O.triple_block
     O.triple_block = _timed_triple_block(sets_raw, table)
     try:
@@ -133,9 +134,9 @@ def table_tensors(flat, rows):
 
 
 def oracle_timeline_latents(sd, heads, noise, sets, flat_table, clip, sync, steps, guidance, solver, text_len=77):
-    """O.sample_latents with timed text.  sets [n_sets, T, cond_dim]: with guidance > 1 [negative ; prompts...], as the plan holds
+    """The restated loop with timed text.  sets [n_sets, T, cond_dim]: with guidance > 1 [negative ; prompts...], as the plan holds
     them; flat_table: prompt_timeline.batch_table(..., ncfg, clips) of the same run."""
     ncfg = 2 if guidance > 1.0 else 1
     raw = O.pad_or_trim_text(sets, text_len)
     with timed_text(raw, table_tensors(flat_table, ncfg * noise.shape[0])):
-        return O.sample_latents(sd, heads, noise, sets[-1:], sets[:1], clip, sync, steps, guidance, solver, text_len=text_len)
+        return L.restated_loop(sd, heads, noise, sets[-1:], sets[:1], clip, sync, steps, guidance, solver, text_len=text_len).x
