@@ -195,6 +195,66 @@ __device__ __forceinline__ const float* rb_row(const RowBcast& b, int r) {
   return p;
 }
 
+// Resolved form: the operands of one launch normally share ONE counter and one row map (run_forward passes the same step_ptr, pitch
+// and layout in every RowBcast of a launch; the bases differ).  The launcher checks that on the host (rb_resolvable) and the
+// kernel then loads the counter once - rb_step_load, its first memory instruction, a scalar load because the address is
+// wave-uniform and nothing in the kernel has stored yet - and computes one element offset per row (rb_map_off) that serves every
+// operand: base + offset is the pointer rb_row returns, bit for bit.  Per operand, rb_row dereferences the counter again (the
+// word was written on another XCD by the previous iteration's step_increment_kernel: a full round trip each) and repeats the
+// divisions of modes 1 and 2, all of it in front of loads that do not depend on the counter at all.
+struct RowMap {
+  long ld, step_stride;
+  int mode, rows_per_cfg, L, Ls;
+  float scale;
+  int per, dense_from, dense_base;
+};
+inline RowMap rb_map_of(const RowBcast& b) { return RowMap{b.ld, b.step_ptr ? b.step_stride : 0, b.mode, b.rows_per_cfg, b.L, b.Ls, b.scale, b.per, b.dense_from, b.dense_base}; }
+inline bool rb_map_equal(const RowMap& a, const RowMap& b) {
+  return a.ld == b.ld && a.step_stride == b.step_stride && a.mode == b.mode && a.rows_per_cfg == b.rows_per_cfg && a.L == b.L && a.Ls == b.Ls &&
+         a.scale == b.scale && a.per == b.per && a.dense_from == b.dense_from && a.dense_base == b.dense_base;
+}
+// Host: can the present operands (p set) of `ops` be addressed through one counter and one map?  On success *step_ptr (in/out: a
+// launch of two row sets passes the same variable twice) holds the counter they share, or stays null when none has one, and *map
+// their map.  An operand without a counter next to one with a counter does not qualify (its step_stride would have to be 0).
+inline bool rb_resolvable(const RowBcast* const* ops, int n, const int** step_ptr, RowMap* map) {
+  bool first = true;
+  *map = RowMap{0, 0, 0, 1, 1, 0, 0.f, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    const RowBcast& b = *ops[i];
+    if (!b.p) continue;
+    if (b.step_ptr) {
+      if (*step_ptr && *step_ptr != b.step_ptr) return false;
+      *step_ptr = b.step_ptr;
+    }
+    const RowMap m = rb_map_of(b);
+    if (first) *map = m;
+    else if (!rb_map_equal(*map, m)) return false;
+    first = false;
+  }
+  return true;
+}
+
+__device__ __forceinline__ int rb_step_load(const int* __restrict__ step_ptr) { return step_ptr ? *step_ptr : 0; }
+
+// rb_row with the counter's value already in a register (step = rb_step_load(b.step_ptr))
+__device__ __forceinline__ const float* rb_row_at(const RowBcast& b, int step, int r) {
+  RowBcast c = b;
+  c.step_ptr = nullptr;
+  return rb_row(c, r) + (b.step_ptr ? (long)step * b.step_stride : 0L);
+}
+
+// element offset of stream row r's operand row at counter value `step`: rb_row(b, r) - b.p for every operand with this map
+__device__ __forceinline__ long rb_map_off(const RowMap& m, int step, int r) {
+  long off = (long)step * m.step_stride;
+  if (m.mode == 1) off += ((long)(r / m.rows_per_cfg) * m.L + (r % m.L)) * m.ld;
+  else if (m.mode == 2) {
+    const int s = rb_nearest_exact(r % m.L, m.scale, m.Ls), cfg = r / m.rows_per_cfg;
+    const int idx = cfg < m.dense_from ? cfg * m.per + (s & (m.per - 1)) : m.dense_base + (cfg - m.dense_from) * m.Ls + s;
+    off += (long)idx * m.ld;
+  }
+  return off;
+}
+
 // Launch hook of the per-kernel profile (foley_profile_forward): when armed, the next launch carries
 // the two events as the dispatch's own start / stop timestamps (hipExtLaunchKernelGGL) - the same
 // begin/end stamps rocprofv3's kernel trace reports, without marker-packet overhead.

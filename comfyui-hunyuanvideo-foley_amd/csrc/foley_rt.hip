@@ -1884,6 +1884,27 @@ extern "C" int foley_dac_encode(foley_ctx* c, const float* wave, int clips, int 
 }
 
 // --------------------------------------------------------------------------- op-level entry points
+// Test-only hook (tests/test_rowbcast_entry_gpu.py; not part of include/foley_hip.h): while set, every row-broadcast operand the
+// calling thread's op entries convert carries a device counter and a step stride, as run_forward's operands do - the operand
+// reads base + *counter * step_stride.  The conversions take p0 and p1 in turn (p1 null: always p0), so two different words
+// give one launch operands with different counters; p0 null switches the hook off.
+static thread_local const int* g_rb_step_ptr[2] = {nullptr, nullptr};
+static thread_local long g_rb_step_stride = 0;
+static thread_local unsigned g_rb_step_n = 0;
+extern "C" void foley_debug_rowbcast_step(const int32_t* p0, const int32_t* p1, int64_t step_stride) {
+  g_rb_step_ptr[0] = p0;
+  g_rb_step_ptr[1] = p1 ? p1 : p0;
+  g_rb_step_stride = (long)step_stride;
+  g_rb_step_n = 0;
+}
+static RowBcast rb_debug_step(RowBcast b) {
+  if (b.p && g_rb_step_ptr[0]) {
+    b.step_ptr = g_rb_step_ptr[g_rb_step_n++ & 1];
+    b.step_stride = g_rb_step_stride;
+  }
+  return b;
+}
+
 static RowBcast to_rb(const foley_rowbcast* r) {
   if (!r || !r->p) return rb_none();
   const int L = r->L > 0 ? r->L : 1, Ls = r->mode == 2 ? (r->Ls > 0 ? r->Ls : 1) : 0;
@@ -1893,7 +1914,7 @@ static RowBcast to_rb(const foley_rowbcast* r) {
     b.dense_from = r->periodic_cfgs > 0 ? r->periodic_cfgs : INT_MAX;
     b.dense_base = r->periodic_cfgs > 0 ? r->periodic_cfgs * per : 0;
   }
-  return b;
+  return rb_debug_step(b);
 }
 
 // descriptor -> GemmArgs (foley_op_gemm and the test-only pair entry below)
@@ -2203,7 +2224,7 @@ extern "C" int foley_op_dac_out(const float* s, const float* w, const float* bia
 extern "C" int foley_op_rows_add_act(const float* a, const float* v, int R, int D, int act_silu, void* out, int out_dtype,
                                      void* stream) {
   if (!out || R < 1 || D < 1) return FAIL(FOLEY_ERR_INVALID, "rows_add_act: null output or empty problem");
-  return launch_rows_add_act(a, v ? rb_vec(v, 0, nullptr) : rb_none(), R, D, act_silu ? 1 : 0, out, out_dtype, (hipStream_t)stream);
+  return launch_rows_add_act(a, v ? rb_debug_step(rb_vec(v, 0, nullptr)) : rb_none(), R, D, act_silu ? 1 : 0, out, out_dtype, (hipStream_t)stream);
 }
 
 extern "C" int foley_op_add_periodic(const float* x, const float* pos, int R, int D, int period, void* out, int out_dtype,

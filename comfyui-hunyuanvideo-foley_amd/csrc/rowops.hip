@@ -52,17 +52,184 @@ template <typename ST> __device__ __forceinline__ f32x4 slab_load4(const void* b
 
 // One wave per row; every global load of the row (x, shift, scale) is issued before the first
 // reduction so the kernel pays one memory round trip, results leave as 8/16-byte vector stores.
+// LnPair: the two row sets of a launch as the caller describes them (the per-operand kernels read it as it is).
 struct LnPair {
   LnArgs a[2];
   int blocks0;
-  long long* dbg;   // tools/ln_timeline.py: 4 wall-clock stamps per workgroup of the wide kernel; null in production
 };
 static long long* g_ln_dbg = nullptr;
 extern "C" void foley_debug_ln_timeline(void* p) { g_ln_dbg = (long long*)p; }
 
+// The resolved launch (common.h RowMap): what the kernels read of one row set, packed so that the selected set arrives in two wide
+// scalar loads at entry - 120 bytes instead of LnArgs' 288 with their fields fetched where they are first used.
+struct LnRes {
+  float* x;
+  void* out;
+  const float *shift, *scale, *gate;   // operand bases (null: absent); the gate belongs to the pending update
+  const float *partials, *bias;        // LnPending
+  long pstride;
+  int M, k;
+  RowMap map;                          // of shift, scale and gate alike
+};
+struct LnResPair {
+  const int* step_ptr;   // the launch's one counter; without one, any readable word (every step_stride is then 0)
+  int blocks0;
+  LnRes a[2];
+  long long* dbg;        // DBG instantiations (tools/ln_timeline.py): 4 wall-clock stamps per workgroup of the wide kernel
+};
+
+// One batch of SB pending slabs of a row.  The loads (clamped slab index keeps them unconditional) leave the slabs as they are
+// stored - a conversion here would wait for them before the operand rows are requested - ...
+template <typename ST> struct SlabRaw { using type = f32x4; };
+template <> struct SlabRaw<bf16_t> { using type = uint2; };
+template <> struct SlabRaw<f16_t> { using type = uint2; };
+template <typename ST> __device__ __forceinline__ f32x4 slab_cvt4(const typename SlabRaw<ST>::type& w) {
+  if constexpr (sizeof(ST) == 4) {
+    return w;
+  } else {
+    const ST* h = (const ST*)&w;
+    f32x4 v = {Cvt<ST>::from(h[0]), Cvt<ST>::from(h[1]), Cvt<ST>::from(h[2]), Cvt<ST>::from(h[3])};
+    return v;
+  }
+}
+template <typename ST, int MAXV, int SB, typename ColFn>
+__device__ __forceinline__ void slab_batch_load(typename SlabRaw<ST>::type (&t)[SB][MAXV], const void* partials, long pstride, int k, int s0, long row_elem,
+                                                ColFn col) {
+#pragma unroll
+  for (int u = 0; u < SB; ++u) {
+    const int s = min(s0 + u, k - 1);
+    const long pe = s * pstride + row_elem;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) t[u][i] = *(const typename SlabRaw<ST>::type*)((const ST*)partials + pe + 4L * col(i));
+  }
+}
+// ... and their sum into acc, in slab order (weight 0 drops the repeats of the last slab)
+template <typename ST, int MAXV, int SB>
+__device__ __forceinline__ void slab_batch_add(f32x4 (&acc)[MAXV], const typename SlabRaw<ST>::type (&t)[SB][MAXV], int k, int s0) {
+#pragma unroll
+  for (int u = 0; u < SB; ++u) {
+    const float w = (s0 + u < k) ? 1.0f : 0.0f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const f32x4 tv = slab_cvt4<ST>(t[u][i]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[i][e] += w * tv[e];
+    }
+  }
+}
+
+// The counter of a resolved launch: one scalar load, issued by ln_step_issue and waited for by ln_step_wait, in the places the
+// kernels choose.  Scalar loads return out of order, so any wait for a kernel argument waits for every scalar load in flight -
+// and the compiler fetches an argument in the block that first uses it.  Every field of the row set is therefore an input of
+// the issuing statement: all are resident (one wait) before the counter's load goes out, and nothing waits for the counter
+// until rb_map_off needs its value - the x, bias and slab loads are issued in between.  The compiler does not track the load:
+// the value must pass through ln_step_wait before its first use.  step_ptr is never null (the launcher sees to it).
+__device__ __forceinline__ int ln_step_issue(const LnRes& A, const int* step_ptr) {
+  int v;
+  asm volatile("s_load_dword %0, %1, 0x0"
+               : "=&s"(v)
+               : "s"(step_ptr), "s"(A.x), "s"(A.out), "s"(A.shift), "s"(A.scale), "s"(A.gate), "s"(A.partials), "s"(A.bias), "s"(A.pstride), "s"(A.M), "s"(A.k),
+                 "s"(A.map.ld), "s"(A.map.step_stride), "s"(A.map.mode), "s"(A.map.rows_per_cfg), "s"(A.map.L), "s"(A.map.Ls), "s"(A.map.scale),
+                 "s"(A.map.per), "s"(A.map.dense_from), "s"(A.map.dense_base));
+  return v;
+}
+__device__ __forceinline__ int ln_step_wait(int v) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v));
+  return v;
+}
+
+// Resolved one-wave-per-row kernel.  Order of the memory work: the counter (scalar), then everything that does not depend on it
+// - x, the bias and the first batch of slabs -, then the row offset (its divisions run under those loads), and only then the
+// wait for the counter and the shift / scale / gate rows.  The arithmetic is ln_mod_each_kernel's, operation for operation.
+template <typename OutT, int MAXV, bool PEND, bool SLAB16 = false>
+__global__ __launch_bounds__(128) void ln_mod_kernel(const LnResPair pr, int D, float eps) {
+  using ST = typename std::conditional<SLAB16, OutT, float>::type;   // slab element type
+  constexpr int SB = 6;
+  const int sel = (int)blockIdx.x >= pr.blocks0 ? 1 : 0;
+  const LnRes& A = pr.a[sel];
+  const int step_sent = ln_step_issue(A, pr.step_ptr);
+  const int M = A.M;
+  OutT* __restrict__ out = (OutT*)A.out;
+  const int row = ((int)blockIdx.x - (sel ? pr.blocks0 : 0)) * 2 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const int nv = D >> 2;  // float4 per row
+  f32x4* xr = (f32x4*)(A.x + (long)row * D);
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  const bool pend = PEND && A.partials;
+  const auto col = [&](int i) { return min(lane + i * 64, nv - 1); };   // clamped: loads stay unconditional
+  f32x4 v[MAXV], hv[MAXV], cv[MAXV], acc[MAXV], gt[MAXV];
+  typename SlabRaw<ST>::type t[PEND ? SB : 1][MAXV];
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) v[i] = xr[col(i)];
+  if (pend) {
+    const f32x4* bp = (const f32x4*)A.bias;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) acc[i] = bp ? bp[col(i)] : z4;
+    if constexpr (PEND) slab_batch_load<ST, MAXV, SB>(t, A.partials, A.pstride, A.k, 0, (long)row * D, col);
+  }
+  const long row_off = rb_map_off(A.map, 0, row);   // the divisions of modes 1 and 2 run under the loads above
+  const long off = row_off + (long)ln_step_wait(step_sent) * A.map.step_stride;
+  const f32x4* sh = A.shift ? (const f32x4*)(A.shift + off) : nullptr;
+  const f32x4* sc = A.scale ? (const f32x4*)(A.scale + off) : nullptr;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    hv[i] = sh ? sh[col(i)] : z4;
+    cv[i] = sc ? sc[col(i)] : z4;
+  }
+  if constexpr (PEND) {
+    if (pend) {
+      // finish the deferred split-K GEMM: x += gate * (sum of partial products + bias), SB slabs in flight at a time
+      const f32x4* gp = (const f32x4*)(A.gate + off);
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) gt[i] = gp[col(i)];
+      for (int s0 = 0; s0 < A.k; s0 += SB) {
+        if (s0 > 0) slab_batch_load<ST, MAXV, SB>(t, A.partials, A.pstride, A.k, s0, (long)row * D, col);
+        slab_batch_add<ST, MAXV, SB>(acc, t, A.k, s0);
+      }
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[i][e] += gt[i][e] * acc[i][e];
+        if (lane + i * 64 < nv) xr[lane + i * 64] = v[i];
+      }
+    }
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i)
+    if (lane + i * 64 < nv) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+  const float mean = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i)
+    if (lane + i * 64 < nv) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float d = v[i][u] - mean;
+        q += d * d;
+      }
+    }
+  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+  OutT* orow = out + (long)row * D;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = lane + i * 64;
+    if (c < nv) {
+      f32x4 y;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) y[u] = (v[i][u] - mean) * rstd * (1.0f + cv[i][u]) + hv[i][u];
+      Pack4<OutT>::store(orow + c * 4, y);
+    }
+  }
+}
+
+// The per-operand path, for a launch whose operands do not share one counter and one row map: every RowBcast resolves itself
+// through rb_row.  One launch of run_forward's 126 per iteration is of this kind - the first LayerNorm of the single-stream
+// blocks, whose pending gate is still the two-stream blocks' vector while shift and scale are per-token rows.
 // SLAB16: the pending slabs hold OutT (a 16-bit type) instead of fp32
 template <typename OutT, int MAXV, bool PEND, bool SLAB16 = false>
-__global__ __launch_bounds__(128) void ln_mod_kernel(const LnPair pr, int D, float eps) {
+__global__ __launch_bounds__(128) void ln_mod_each_kernel(const LnPair pr, int D, float eps) {
   using ST = typename std::conditional<SLAB16, OutT, float>::type;   // slab element type
   const int sel = (int)blockIdx.x >= pr.blocks0 ? 1 : 0;
   const LnArgs& A = pr.a[sel];
@@ -166,11 +333,134 @@ __global__ __launch_bounds__(128) void ln_mod_kernel(const LnPair pr, int D, flo
 #define FOLEY_LN_RPB 1   // rows per workgroup of the multi-wave LayerNorm (A/B builds with -DFOLEY_LN_RPB=2 / 4 through FOLEY_HIP_LIB: 1 row
                          // -0.3 % on the bs=1 loop against 2, 4 rows +0.5 %)
 #endif
+// Statistics and output of the multi-wave kernels, from the row part v each wave holds (after any pending update): each wave
+// reduces its own part to (sum, centred sum of squares) in registers; the parts meet once in LDS and are combined exactly (Chan
+// et al.): M2 = sum_w [M2_w + n_w (mean_w - mean)^2] - one barrier instead of two.  STAMP: the timeline probe's stamps 2 and 3.
+template <typename OutT, int MAXV, int WPR, bool STAMP>
+__device__ __forceinline__ void ln_wide_finish(const f32x4 (&v)[MAXV], const f32x4 (&hv)[MAXV], const f32x4 (&cv)[MAXV], OutT* orow, int c0, int rb,
+                                               int part, int lane, bool live, int D, float eps, long long* stamps) {
+  __shared__ float red[FOLEY_LN_RPB][2][WPR];   // [row of the block][statistic][wave of the row]
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+  s = wave_sum(s);
+  const float nw = (float)(MAXV * 4 * 64);
+  const float mean_w = s / nw;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float d = v[i][u] - mean_w;
+      q += d * d;
+    }
+  q = wave_sum(q);
+  if (lane == 0) {
+    red[rb][0][part] = s;
+    red[rb][1][part] = q;
+  }
+  __syncthreads();
+  float tot = 0.f;
+#pragma unroll
+  for (int w = 0; w < WPR; ++w) tot += red[rb][0][w];     // fixed order: every wave of the row gets the same mean
+  const float mean = tot / (float)D;
+  float qt = 0.f;
+#pragma unroll
+  for (int w = 0; w < WPR; ++w) {
+    const float dm = red[rb][0][w] / nw - mean;
+    qt += red[rb][1][w] + nw * dm * dm;
+  }
+  const float rstd = 1.0f / sqrtf(qt / (float)D + eps);
+  if (STAMP && stamps) stamps[2] = wall_clock64();
+  if (!live) return;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    f32x4 y;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) y[u] = (v[i][u] - mean) * rstd * (1.0f + cv[i][u]) + hv[i][u];
+    Pack4<OutT>::store(orow + (c0 + i * 64) * 4, y);
+  }
+  if (STAMP && stamps) stamps[3] = wall_clock64();
+}
+
+// Resolved multi-wave body; memory work in the order of ln_mod_kernel above: counter, then x / bias / first slab batch, then the
+// row offset, then the counter's wait and the three operand rows.  DBG: the instantiations tools/ln_timeline.py launches - the
+// product ones carry no stamp, branch or store of the probe.
+template <typename OutT, int MAXV, bool PEND, int WPR, int SEL, bool SLAB16, bool DBG>
+__device__ __forceinline__ void ln_mod_wide_body(const LnResPair& pr, int D, float eps) {
+  using ST = typename std::conditional<SLAB16, OutT, float>::type;   // slab element type
+  constexpr int RPB = FOLEY_LN_RPB, SB = 6;
+  const LnRes& A = pr.a[SEL];
+  const int M = A.M;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rb = wave / WPR, part = wave % WPR;               // row of the block (0/1), column part
+  const int row_u = ((int)blockIdx.x - (SEL ? pr.blocks0 : 0)) * RPB + rb;
+  const bool live = row_u < M;
+  const int row = live ? row_u : M - 1;                       // dead waves shadow the last row (no stores)
+  const int c0 = part * (MAXV * 64) + lane;                   // first float4 of this lane; stride 64
+  long long* const stamps = (DBG && threadIdx.x == 0) ? pr.dbg + (long)blockIdx.x * 4 : nullptr;
+  if (DBG && stamps) stamps[0] = wall_clock64();
+  f32x4* xr = (f32x4*)(A.x + (long)row * D);
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  const bool pend = PEND && A.partials;
+  const auto col = [&](int i) { return c0 + i * 64; };
+  f32x4 v[MAXV], hv[MAXV], cv[MAXV], acc[MAXV], gt[MAXV];
+  typename SlabRaw<ST>::type t[PEND ? SB : 1][MAXV];
+  const int step_sent = ln_step_issue(A, pr.step_ptr);
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) v[i] = xr[col(i)];
+  if constexpr (PEND) {
+    if (pend) {
+      const f32x4* bp = (const f32x4*)A.bias;
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) acc[i] = bp ? bp[col(i)] : z4;
+      slab_batch_load<ST, MAXV, SB>(t, A.partials, A.pstride, A.k, 0, (long)row * D, col);
+    }
+  }
+  const long row_off = rb_map_off(A.map, 0, row);   // the divisions of modes 1 and 2 run under the loads above
+  const long off = row_off + (long)ln_step_wait(step_sent) * A.map.step_stride;
+  const f32x4* sh = A.shift ? (const f32x4*)(A.shift + off) : nullptr;
+  const f32x4* sc = A.scale ? (const f32x4*)(A.scale + off) : nullptr;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    hv[i] = sh ? sh[col(i)] : z4;
+    cv[i] = sc ? sc[col(i)] : z4;
+  }
+  if constexpr (PEND) {
+    if (pend) {
+      const f32x4* gp = (const f32x4*)(A.gate + off);
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) gt[i] = gp[col(i)];
+      for (int s0 = 0; s0 < A.k; s0 += SB) {
+        if (s0 > 0) slab_batch_load<ST, MAXV, SB>(t, A.partials, A.pstride, A.k, s0, (long)row * D, col);
+        slab_batch_add<ST, MAXV, SB>(acc, t, A.k, s0);
+      }
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[i][e] += gt[i][e] * acc[i][e];
+        if (live) xr[col(i)] = v[i];
+      }
+    }
+  }
+  if (DBG) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (stamps) stamps[1] = wall_clock64();
+  }
+  ln_wide_finish<OutT, MAXV, WPR, DBG>(v, hv, cv, (OutT*)A.out + (long)row * D, c0, rb, part, lane, live, D, eps, stamps);
+}
+
+template <typename OutT, int MAXV, bool PEND, int WPR, bool SLAB16 = false, bool DBG = false>
+__global__ __launch_bounds__(64 * FOLEY_LN_RPB * WPR) void ln_mod_wide_kernel(const LnResPair pr, int D, float eps) {
+  if ((int)blockIdx.x >= pr.blocks0) ln_mod_wide_body<OutT, MAXV, PEND, WPR, 1, SLAB16, DBG>(pr, D, eps);   // workgroup-uniform
+  else ln_mod_wide_body<OutT, MAXV, PEND, WPR, 0, SLAB16, DBG>(pr, D, eps);
+}
+
+// The per-operand path of the multi-wave kernel (see ln_mod_each_kernel)
 template <typename OutT, int MAXV, bool PEND, int WPR, int SEL, bool SLAB16>
-__device__ __forceinline__ void ln_mod_wide_body(const LnPair& pr, int D, float eps) {
+__device__ __forceinline__ void ln_mod_wide_each_body(const LnPair& pr, int D, float eps) {
   using ST = typename std::conditional<SLAB16, OutT, float>::type;   // slab element type
   constexpr int RPB = FOLEY_LN_RPB;
-  __shared__ float red[RPB][2][WPR];   // [row of the block][statistic][wave of the row]
   constexpr int sel = SEL;
   const LnArgs& A = pr.a[SEL];
   const int M = A.M;
@@ -180,8 +470,6 @@ __device__ __forceinline__ void ln_mod_wide_body(const LnPair& pr, int D, float 
   const bool live = row_u < M;
   const int row = live ? row_u : M - 1;                       // dead waves shadow the last row (no stores)
   const int c0 = part * (MAXV * 64) + lane;                   // first float4 of this lane; stride 64
-  const bool stamp = pr.dbg && threadIdx.x == 0;
-  if (stamp) pr.dbg[(long)blockIdx.x * 4 + 0] = wall_clock64();
   f32x4* xr = (f32x4*)(A.x + (long)row * D);
   const f32x4* sh = A.shift.p ? (const f32x4*)rb_row(A.shift, row) : nullptr;
   const f32x4* sc = A.scale.p ? (const f32x4*)rb_row(A.scale, row) : nullptr;
@@ -231,60 +519,13 @@ __device__ __forceinline__ void ln_mod_wide_body(const LnPair& pr, int D, float 
       if (live) xr[c0 + i * 64] = v[i];
     }
   }
-  if (pr.dbg) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (stamp) pr.dbg[(long)blockIdx.x * 4 + 1] = wall_clock64();
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < MAXV; ++i) s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
-  // Each wave reduces its own part to (sum, centred sum of squares) in registers; the parts meet once in LDS and
-  // are combined exactly (Chan et al.): M2 = sum_w [M2_w + n_w (mean_w - mean)^2] - one barrier instead of two.
-  s = wave_sum(s);
-  const float nw = (float)(MAXV * 4 * 64);
-  const float mean_w = s / nw;
-  float q = 0.f;
-#pragma unroll
-  for (int i = 0; i < MAXV; ++i)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float d = v[i][u] - mean_w;
-      q += d * d;
-    }
-  q = wave_sum(q);
-  if (lane == 0) {
-    red[rb][0][part] = s;
-    red[rb][1][part] = q;
-  }
-  __syncthreads();
-  float tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < WPR; ++w) tot += red[rb][0][w];     // fixed order: every wave of the row gets the same mean
-  const float mean = tot / (float)D;
-  float qt = 0.f;
-#pragma unroll
-  for (int w = 0; w < WPR; ++w) {
-    const float dm = red[rb][0][w] / nw - mean;
-    qt += red[rb][1][w] + nw * dm * dm;
-  }
-  const float rstd = 1.0f / sqrtf(qt / (float)D + eps);
-  if (stamp) pr.dbg[(long)blockIdx.x * 4 + 2] = wall_clock64();
-  if (!live) return;
-  OutT* orow = (OutT*)A.out + (long)row * D;
-#pragma unroll
-  for (int i = 0; i < MAXV; ++i) {
-    f32x4 y;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) y[u] = (v[i][u] - mean) * rstd * (1.0f + cv[i][u]) + hv[i][u];
-    Pack4<OutT>::store(orow + (c0 + i * 64) * 4, y);
-  }
-  if (stamp) pr.dbg[(long)blockIdx.x * 4 + 3] = wall_clock64();
+  ln_wide_finish<OutT, MAXV, WPR, false>(v, hv, cv, (OutT*)A.out + (long)row * D, c0, rb, part, lane, live, D, eps, nullptr);
 }
 
 template <typename OutT, int MAXV, bool PEND, int WPR, bool SLAB16 = false>
-__global__ __launch_bounds__(64 * FOLEY_LN_RPB * WPR) void ln_mod_wide_kernel(const LnPair pr, int D, float eps) {
-  if ((int)blockIdx.x >= pr.blocks0) ln_mod_wide_body<OutT, MAXV, PEND, WPR, 1, SLAB16>(pr, D, eps);   // workgroup-uniform
-  else ln_mod_wide_body<OutT, MAXV, PEND, WPR, 0, SLAB16>(pr, D, eps);
+__global__ __launch_bounds__(64 * FOLEY_LN_RPB * WPR) void ln_mod_wide_each_kernel(const LnPair pr, int D, float eps) {
+  if ((int)blockIdx.x >= pr.blocks0) ln_mod_wide_each_body<OutT, MAXV, PEND, WPR, 1, SLAB16>(pr, D, eps);   // workgroup-uniform
+  else ln_mod_wide_each_body<OutT, MAXV, PEND, WPR, 0, SLAB16>(pr, D, eps);
 }
 
 // ------------------------------------------------------------------ q/k RMSNorm + RoPE + head split
@@ -390,8 +631,9 @@ __global__ __launch_bounds__(256) void qkv_split_kernel(const QkvPair pr) {
 template <typename OutT>
 __global__ void rows_add_act_kernel(const float* __restrict__ a, RowBcast v, int R, int D, int act_silu,
                                     OutT* __restrict__ out) {
+  const int step = rb_step_load(v.p ? v.step_ptr : nullptr);   // first memory instruction; the `a` loads do not wait for it
   const long n = (long)R * D;
-  const float* vr = v.p ? rb_row(v, 0) : nullptr;
+  const float* vr = v.p ? rb_row_at(v, step, 0) : nullptr;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float y = a ? a[i] : 0.f;
     if (vr) y += vr[i % D];
@@ -1045,7 +1287,23 @@ int launch_ln_mod_pair(const LnArgs& a0, const LnArgs& a1, int D, float eps, int
   pr.a[0] = a0;
   pr.a[1] = a1;
   pr.blocks0 = (a0.M + 1) / 2;
-  pr.dbg = g_ln_dbg;
+  // One counter and one row map per row set (and the one counter for both sets): the resolved kernels; else every operand for itself
+  LnResPair rp{};
+  bool resolved = true;
+  for (int i = 0; i < 2; ++i) {
+    const LnArgs& a = pr.a[i];
+    const bool pd = a.M > 0 && a.pend.partials;
+    LnRes& r = rp.a[i];
+    r = LnRes{a.x, a.out, a.shift.p, a.scale.p, pd ? a.pend.gate.p : nullptr, pd ? a.pend.partials : nullptr, pd ? a.pend.bias : nullptr,
+              pd ? a.pend.stride : 0, a.M, pd ? a.pend.k : 0, RowMap{}};
+    const RowBcast none{};
+    const RowBcast* ops[3] = {&a.shift, &a.scale, pd ? &a.pend.gate : &none};
+    if (a.M > 0 && !rb_resolvable(ops, 3, &rp.step_ptr, &r.map)) resolved = false;
+  }
+  // no counter: the kernels' unconditional load reads a word of x instead, and every step_stride is 0
+  if (!rp.step_ptr) rp.step_ptr = (const int*)(a0.M > 0 ? a0.x : a1.x);
+  rp.blocks0 = pr.blocks0;
+  rp.dbg = g_ln_dbg;
   dim3 grid(pr.blocks0 + (a1.M + 1) / 2), block(128);
   const int need = (D / 4 + 63) / 64;   // float4 per lane
   if (out_dtype != FOLEY_F32 && !foley_is_half(out_dtype)) return foley_set_err("ln_mod: bad dtype", __FILE__, __LINE__);
@@ -1057,56 +1315,73 @@ int launch_ln_mod_pair(const LnArgs& a0, const LnArgs& a1, int D, float eps, int
   if ((h0 >= 0 && h1 >= 0 && h0 != h1) || (slab_dt != 0 && slab_dt != out_dtype))
     return foley_set_err("ln_mod: 16-bit pending slabs must have the output dtype (and agree between the two row sets)", __FILE__, __LINE__);
   const bool s16 = slab_dt != 0;
-#define FOLEY_LN(V)                                                                                        \
-  {                                                                                                        \
-    if (pend) {                                                                                            \
-      if (f32o) FOLEY_LAUNCH((ln_mod_kernel<float, V, true>), grid, block, 0, st, pr, D, eps);       \
-      else if (f16o && s16) FOLEY_LAUNCH((ln_mod_kernel<f16_t, V, true, true>), grid, block, 0, st, pr, D, eps);  \
-      else if (f16o) FOLEY_LAUNCH((ln_mod_kernel<f16_t, V, true>), grid, block, 0, st, pr, D, eps);  \
-      else if (s16) FOLEY_LAUNCH((ln_mod_kernel<bf16_t, V, true, true>), grid, block, 0, st, pr, D, eps);  \
-      else FOLEY_LAUNCH((ln_mod_kernel<bf16_t, V, true>), grid, block, 0, st, pr, D, eps);           \
-    } else {                                                                                               \
-      if (f32o) FOLEY_LAUNCH((ln_mod_kernel<float, V, false>), grid, block, 0, st, pr, D, eps);      \
-      else if (f16o) FOLEY_LAUNCH((ln_mod_kernel<f16_t, V, false>), grid, block, 0, st, pr, D, eps); \
-      else FOLEY_LAUNCH((ln_mod_kernel<bf16_t, V, false>), grid, block, 0, st, pr, D, eps);          \
-    }                                                                                                      \
+  // K: the kernel family (resolved or per operand), P: its argument
+#define FOLEY_LN_PEND(K, P, G, B, ...)                                                         \
+  {                                                                                            \
+    if (f32o) FOLEY_LAUNCH((K<float, __VA_ARGS__>), G, B, 0, st, P, D, eps);                   \
+    else if (f16o && s16) FOLEY_LAUNCH((K<f16_t, __VA_ARGS__, true>), G, B, 0, st, P, D, eps); \
+    else if (f16o) FOLEY_LAUNCH((K<f16_t, __VA_ARGS__>), G, B, 0, st, P, D, eps);              \
+    else if (s16) FOLEY_LAUNCH((K<bf16_t, __VA_ARGS__, true>), G, B, 0, st, P, D, eps);        \
+    else FOLEY_LAUNCH((K<bf16_t, __VA_ARGS__>), G, B, 0, st, P, D, eps);                       \
+  }
+#define FOLEY_LN_PLAIN(K, P, G, B, ...)                                                          \
+  {                                                                                              \
+    if (f32o) FOLEY_LAUNCH((K<float, __VA_ARGS__>), G, B, 0, st, P, D, eps);                     \
+    else if (f16o) FOLEY_LAUNCH((K<f16_t, __VA_ARGS__>), G, B, 0, st, P, D, eps);                \
+    else FOLEY_LAUNCH((K<bf16_t, __VA_ARGS__>), G, B, 0, st, P, D, eps);                         \
+  }
+#define FOLEY_LN_ANY(K, P, G, B, V, ...)                           \
+  {                                                                \
+    if (pend) FOLEY_LN_PEND(K, P, G, B, V, true, ##__VA_ARGS__)    \
+    else FOLEY_LN_PLAIN(K, P, G, B, V, false, ##__VA_ARGS__)       \
   }
   // rows that split evenly over 2 waves (D = 1536: 2 waves x 3 float4 per lane; 1408 / 256: one wave).  Two waves per row since
   // the slabs are 16-bit (round 3, one box: bs=1 loop 347.4 -> 345.8 ms, bs=8 1525.7 -> 1520.2, 30 s 1488.7 -> 1478.6 against three
   // waves, which were better with fp32 slabs in round 2)
   const int total_rows = a0.M + a1.M;
-  if (total_rows <= 4096 && D % (4 * 64 * 2) == 0 && D / (4 * 64 * 2) <= 4) {
+  const bool wide = total_rows <= 4096 && D % (4 * 64 * 2) == 0 && D / (4 * 64 * 2) <= 4;
+  if (rp.dbg) {   // tools/ln_timeline.py: the probe's instantiations
+    if (!(resolved && wide && out_dtype == FOLEY_BF16 && D == 1536))
+      return foley_set_err("ln_mod: the timeline probe is built for the resolved two-wave kernel, bf16 output, D = 1536", __FILE__, __LINE__);
+    rp.blocks0 = (a0.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB;
+    const dim3 gridw(rp.blocks0 + (a1.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB), blk(64 * FOLEY_LN_RPB * 2);
+    if (pend && s16) FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, 3, true, 2, true, true>), gridw, blk, 0, st, rp, D, eps);
+    else if (pend) FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, 3, true, 2, false, true>), gridw, blk, 0, st, rp, D, eps);
+    else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, 3, false, 2, false, true>), gridw, blk, 0, st, rp, D, eps);
+    FOLEY_LAUNCH_CHECK();
+    return 0;
+  }
+  if (wide) {
     LnPair prw = pr;   // the two-wave kernel takes FOLEY_LN_RPB rows per workgroup
-    prw.blocks0 = (a0.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB;
+    prw.blocks0 = rp.blocks0 = (a0.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB;
     const dim3 gridw(prw.blocks0 + (a1.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB), blk(64 * FOLEY_LN_RPB * 2);
-#define FOLEY_LNW(V)                                                                                                  \
-    {                                                                                                                  \
-      if (pend) {                                                                                                      \
-        if (f32o) FOLEY_LAUNCH((ln_mod_wide_kernel<float, V, true, 2>), gridw, blk, 0, st, prw, D, eps);                \
-        else if (f16o && s16) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, true, 2, true>), gridw, blk, 0, st, prw, D, eps);  \
-        else if (f16o) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, true, 2>), gridw, blk, 0, st, prw, D, eps);           \
-        else if (s16) FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, true, 2, true>), gridw, blk, 0, st, prw, D, eps);     \
-        else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, true, 2>), gridw, blk, 0, st, prw, D, eps);                    \
-      } else {                                                                                                         \
-        if (f32o) FOLEY_LAUNCH((ln_mod_wide_kernel<float, V, false, 2>), gridw, blk, 0, st, prw, D, eps);               \
-        else if (f16o) FOLEY_LAUNCH((ln_mod_wide_kernel<f16_t, V, false, 2>), gridw, blk, 0, st, prw, D, eps);          \
-        else FOLEY_LAUNCH((ln_mod_wide_kernel<bf16_t, V, false, 2>), gridw, blk, 0, st, prw, D, eps);                   \
-      }                                                                                                                \
+#define FOLEY_LNW(V)                                                             \
+    {                                                                            \
+      if (resolved) FOLEY_LN_ANY(ln_mod_wide_kernel, rp, gridw, blk, V, 2)       \
+      else FOLEY_LN_ANY(ln_mod_wide_each_kernel, prw, gridw, blk, V, 2)          \
     }
     const int v2 = D / (4 * 64 * 2);
     if (v2 == 1) FOLEY_LNW(1)
     else if (v2 == 2) FOLEY_LNW(2)
     else if (v2 == 3) FOLEY_LNW(3)
     else FOLEY_LNW(4)
+#undef FOLEY_LNW
     FOLEY_LAUNCH_CHECK();
     return 0;
   }
-#undef FOLEY_LNW
-  if (need <= 2) FOLEY_LN(2)
-  else if (need <= 4) FOLEY_LN(4)
-  else if (need <= 6) FOLEY_LN(6)
-  else FOLEY_LN(8)
-#undef FOLEY_LN
+#define FOLEY_LNN(V)                                                             \
+  {                                                                              \
+    if (resolved) FOLEY_LN_ANY(ln_mod_kernel, rp, grid, block, V)                \
+    else FOLEY_LN_ANY(ln_mod_each_kernel, pr, grid, block, V)                    \
+  }
+  if (need <= 2) FOLEY_LNN(2)
+  else if (need <= 4) FOLEY_LNN(4)
+  else if (need <= 6) FOLEY_LNN(6)
+  else FOLEY_LNN(8)
+#undef FOLEY_LNN
+#undef FOLEY_LN_ANY
+#undef FOLEY_LN_PLAIN
+#undef FOLEY_LN_PEND
   FOLEY_LAUNCH_CHECK();
   return 0;
 }
