@@ -32,9 +32,15 @@ def _desc(dt, epi, M, N, K, o, keep):
     if o.get("conv"):   # channels-last conv k=3 'same' over segments of o["conv"] rows
         d.taps, d.tapC, d.dil, d.tap0, d.lda = 3, K // 3, 1, -1, o.get("lda", K // 3)
         d.segV = d.segS = o["conv"]
+    elif o.get("sconv"):   # strided conv k = 2 x stride over clips of Tin rows (runtime.gemm_desc sconv=): M = clips x (Tin // stride)
+        Tin, st = o["sconv"]
+        d.taps, d.tapC, d.dil, d.tap0, d.lda = 2 * st, K // (2 * st), 1, -((st + 1) // 2), K // (2 * st)
+        d.segV, d.segS, d.rstride = Tin // st, Tin, st
     else:
         d.taps, d.tapC, d.dil, d.tap0, d.lda = 1, K, 1, 0, o.get("lda", K)
         d.segV = d.segS = M
+    if o.get("vrows"):   # virtual rows: product row r reads source row (r // segV) x segS + r % segV
+        d.segV, d.segS = o["vrows"]
     if o.get("misaligned_A"):
         d.A += 8
     d.out0 = next(addr) + (8 if o.get("scalar_out") else 0)
@@ -86,6 +92,10 @@ def plan(case):
 # opt-in; scalar_out = an output address that rules out the vector epilogue; lda / ldw = row pitches in elements.
 # D = 1536 (mlp 6144, conv hidden 4096); M = 500 / 2000 / 3000 / 4000 = 5 s x 1 / 20 s / 30 s / 5 s x 8 clips of audio tokens.
 CASES = {
+    'store_1': (dict(epi='store', mnk=(1, 1536, 1536)), (3, 1, 0, 0)),
+    'store_2': (dict(epi='store', mnk=(2, 1536, 1536)), (3, 1, 0, 0)),
+    'store_1_n13824': (dict(epi='store', mnk=(1, 13824, 1536)), (25, 1, 0, 0)),
+    'store_2_n13824': (dict(epi='store', mnk=(2, 13824, 1536)), (25, 1, 0, 0)),
     'gelu_fc1_16': (dict(epi='gelu', mnk=(16, 6144, 1536)), (3, 1, 0, 0)),
     'qkv_16': (dict(epi='qkv', mnk=(16, 4608, 1536)), (27, 1, 0, 0)),
     'cross_q_16': (dict(epi='qkv', mnk=(16, 1536, 1536), nK=1), (2, 1, 0, 0)),

@@ -8,6 +8,8 @@ rows) get guard rows / guard slabs only.
 
 Coverage is asserted: test_every_tile_has_a_case asks the library which tile ids exist, the automatic-tile cases assert the
 (tile, K split, panel groups) of tests/test_gemm_plan_cpu.py through foley_debug_gemm_plan on the descriptor they launch.
+tests/test_gemm_edges_gpu.py takes run_gemm_case to every tile's M, N, K and segment edges and to the mapped operands (virtual
+rows, strided conv).
 """
 import ctypes as C
 import functools
@@ -66,12 +68,19 @@ def _both16(t):
 
 
 @functools.lru_cache(maxsize=3)
-def _operands(M, N, K, conv, kind, gated, seed):
+def _operands(M, N, K, conv, kind, gated, seed, mapped=None):
     """kind: 'f32' | 'h' (values exact in bf16 and fp16) | 'fp8' (weights additionally exact in e4m3fn).  conv = (B, L, C) or None.
+    mapped = ('vrows', segV, segS): M = segs segV product rows over segs segS source rows, row r reads source row
+    (r // segV) segS + r % segV;  mapped = ('sconv', B, Tin, Cin, stride): the strided conv k = 2 stride, pad ceil(stride / 2), of B
+    clips of Tin rows (K = 2 stride Cin, M = B (Tin // stride)), reference F.conv1d in fp64, mag the same conv on absolute values.
     Returns a dict: src (rows as the kernel reads them), W, b, ref0 / mag0 (without the bias)."""
     if conv:
         B, L, Cc = conv
         src = _rand((B * L, Cc), seed)
+    elif mapped and mapped[0] == "vrows":
+        src = _rand((M // mapped[1] * mapped[2], K), seed)
+    elif mapped:
+        src = _rand((mapped[1] * mapped[2], mapped[3]), seed)
     else:
         src = _rand((M, K), seed)
     W = _rand((N, K), seed + 1, 1 / math.sqrt(K))
@@ -82,7 +91,19 @@ def _operands(M, N, K, conv, kind, gated, seed):
         src, W = _both16(src), _both16(W)
     if kind == "fp8":
         W = W.to(torch.float8_e4m3fn).float()
-    cols = oc.conv3_cols(src.view(*conv)) if conv else src
+    if mapped and mapped[0] == "sconv":      # W [N, 2 stride Cin] is packers.conv_to_gemm of the conv weight w [N, Cin, 2 stride]
+        _, B, Tin, Cin, st = mapped
+        w = W.view(N, 2 * st, Cin).transpose(1, 2).double()
+        assert torch.equal(packers.conv_to_gemm(w.float()).double(), W.double())
+        x = src.view(B, Tin, Cin).transpose(1, 2).double()
+        cv = lambda a, ww: torch.nn.functional.conv1d(a, ww, None, stride=st, padding=math.ceil(st / 2)).transpose(1, 2).reshape(M, N)
+        ref0, mag0 = cv(x, w), cv(x.abs(), w.abs())
+        return dict(src=src, W=W, b=b, ref0=ref0, mag0=mag0)
+    if mapped:
+        segV, segS = mapped[1:]
+        cols = src[(torch.arange(M // segV)[:, None] * segS + torch.arange(segV)[None]).reshape(-1)]
+    else:
+        cols = oc.conv3_cols(src.view(*conv)) if conv else src
     ref0, mag0 = oc.gemm_ref64(cols, W, None)
     return dict(src=src, W=W, b=b, ref0=ref0, mag0=mag0)
 
@@ -96,15 +117,22 @@ def _ref(ops):
 
 # ----------------------------------------------------------------------------- one GEMM under the checks
 def run_gemm_case(dev, name, epi, mnk, dt, tile=0, conv=None, fp8=False, misalign=False, want_plan=None, want_tile=None, ksplit=None,
-                  qkv=None, slabs16=True, seed=100):
-    """Launch one problem and check it.  qkv = (B, L, H, Lv, nK): the fused head split of B clips of L tokens at token offset Lv."""
+                  qkv=None, slabs16=True, seed=100, vrows=None, sconv=None, n_slabs=8):
+    """Launch one problem and check it; any M >= 1 (an odd M gives the row-broadcast operands - addend, gate - ONE half of M rows).
+    qkv = (B, L, H, Lv, nK): the fused head split of B clips of L tokens at token offset Lv.
+    vrows = (segV, segS): virtual rows - product row r reads source row (r // segV) segS + r % segV; source rows [segV, segS) of
+    every segment, which the mapping never reads, are NaN on the device.
+    sconv = (B, Tin, Cin, stride): the DAC encoder's strided conv (K = 2 stride Cin, M = B (Tin // stride)); the B clips sit
+    between two guard segments of Tin NaN rows: a tap that leaves its clip must read a zero, never the neighbouring rows."""
     M, N, K = mnk
     kind = "f32" if dt == torch.float32 else ("fp8" if fp8 else "h")
     rec_epi = epi
     if epi == "gate_split_f32slabs":      # deferred split-K of 16-bit operands into fp32 slabs (slab_bound's plain e_y branch)
         epi, slabs16 = "gate_split", False
     gated = epi == "silugate"
-    ops = _operands(M, N, K, conv, kind, gated, seed)
+    mapped = ("vrows",) + tuple(vrows) if vrows else (("sconv",) + tuple(sconv) if sconv else None)
+    assert sum(m is not None for m in (conv, vrows, sconv)) <= 1
+    ops = _operands(M, N, K, conv, kind, gated, seed, mapped) if mapped else _operands(M, N, K, conv, kind, gated, seed)
     ref, mag = _ref(ops)
     e_y = (K + 4) * oc.U32 * mag
     Ad = ops["src"].to(dev, dt)
@@ -114,6 +142,18 @@ def run_gemm_case(dev, name, epi, mnk, dt, tile=0, conv=None, fp8=False, misalig
     kw = dict(epilogue=EPI_CODE[epi], tile=tile, gelu_erf=(epi == "gelu_erf"))
     if conv:
         kw["conv"] = (conv[1], conv[2], 3, 1)
+    if vrows:
+        assert M % vrows[0] == 0 and vrows[0] <= vrows[1]
+        Ad.view(M // vrows[0], vrows[1], K)[:, vrows[0]:] = float("nan")
+        kw.update(vrows=tuple(vrows), M=M)
+    if sconv:
+        B, Tin, Cin, st = sconv
+        assert M == B * (Tin // st) and K == 2 * st * Cin
+        hold = torch.full(((B + 2) * Tin, Cin), float("nan"), dtype=dt, device=dev)
+        hold[Tin:(B + 1) * Tin] = Ad
+        Ad = hold[Tin:(B + 1) * Tin]
+        assert Ad.data_ptr() % 16 == 0
+        kw["sconv"] = (Tin, Cin, st)
     guards, checks = [], []
     h16 = dt != torch.float32
     if epi == "qkv":
@@ -125,17 +165,17 @@ def run_gemm_case(dev, name, epi, mnk, dt, tile=0, conv=None, fp8=False, misalig
     assert g.view.data_ptr() % 16 == (8 if misalign else 0) and (g.pitch * es) % 16 == 0
     guards.append(g)
     kw["ldc"] = g.pitch
-    L2 = M // 2
+    halves, L2 = (2, M // 2) if M % 2 == 0 else (1, M)      # an odd M: one half of M rows (rows_per_cfg = M)
     if epi == "addend":
-        add = _rand((2, L2, N), seed + 5)
+        add = _rand((halves, L2, N), seed + 5)
         kw["rb"] = rt.rowbcast(add.to(dev), 1, rows_per_cfg=L2, L=L2)
     if epi in ("gate", "gate_split"):
-        x0, gate = _rand((M, N), seed + 6), _rand((2, L2, N), seed + 7, 0.5)
+        x0, gate = _rand((M, N), seed + 6), _rand((halves, L2, N), seed + 7, 0.5)
         g.view.copy_(x0.to(dev))
         kw["rb"] = rt.rowbcast(gate.to(dev), 1, rows_per_cfg=L2, L=L2)
         kw["ksplit"] = 1 if epi == "gate" else (2 if ksplit is None else ksplit)
         if epi == "gate_split" and h16:
-            gs = oc.guarded((8, M, N), dt if slabs16 else torch.float32, dev, rows=(1, 1))
+            gs = oc.guarded((n_slabs, M, N), dt if slabs16 else torch.float32, dev, rows=(1, 1))
             guards.append(gs)
             kw["partials"] = gs.view
         elif ksplit == 0:
@@ -335,6 +375,10 @@ DAC_CASES = {
     "conv1_res_64": ("conv1_res", 2, 100, 64, 64, 1), "conv1_res_128": ("conv1_res", 1, 37, 128, 128, 1),
     "convT_s2": ("convT", 2, 23, 128, 64, 2), "convT_s3": ("convT", 2, 23, 128, 64, 3), "convT_s4": ("convT", 2, 23, 128, 64, 4),
     "convT_s5": ("convT", 2, 23, 128, 64, 5), "convT_s8": ("convT", 2, 23, 128, 64, 8),
+    # tiny T: T <= 3 dil - every outer tap of the k = 7 conv leaves the clip on BOTH sides (T = 5 at dilation 9, T = 2 at dilation 3: the
+    # centre tap alone is ever in range) - and the transposed conv of ONE input row (M = clips (Tin + 1) = 4 virtual rows)
+    "conv7_d9_T5": ("conv7", 2, 5, 64, 64, 9), "conv7_d3_T2": ("conv7", 2, 2, 64, 64, 3),
+    "convT_s2_T1": ("convT", 2, 1, 128, 64, 2), "convT_s5_T1": ("convT", 2, 1, 128, 64, 5),
 }
 DAC_TILES = [0, 1, 2, 3, 4, 5, 6, 8]
 
