@@ -199,6 +199,12 @@ struct IterArgs {
   // write, which the step reads as step.clip_scale (all null: off - no such launches, another topology)
   float *guid_part = nullptr, *guid_scale = nullptr;
   const float* guid_phi = nullptr;
+  // projected guidance: the two launches in front of the step, in the rescale launches' place - the mode, the per-iteration
+  // rows, the scratch, and what they write: the coefficients and (APG) the plane, which the step reads as step.proj_coef /
+  // step.proj_plane (mode 0: off - no such launches, the step kernels without projection)
+  int proj_mode = 0;
+  const float* proj_rows = nullptr;
+  float *proj_part = nullptr, *proj_coef = nullptr, *proj_plane = nullptr;
   // step cache: the residual the two bodies address and the probe's buffers (all null: off - the one straight-line iteration; on:
   // the three graphs head / full body / skip body).  Mode, threshold and skip list are host decisions between replays: not here.
   float *sc_delta = nullptr, *sc_mprev = nullptr, *sc_part = nullptr, *sc_rel = nullptr;
@@ -239,6 +245,7 @@ struct RunOptions {
   int sc_lo = 0, sc_hi = 0, sc_maxc = 0;  // iterations [lo, hi) may skip; longest run of skips (0: no cap)
   int tl_sets = 0;                        // foley_prepare_timeline: the number of text sets (0: one text set per batch row)
   int ms_order = 0;                       // foley_set_multistep: 0 a one-step method, 2 or 3
+  int proj_mode = 0;                      // foley_set_projected_guidance: 0 off, FOLEY_GUIDANCE_APG, FOLEY_GUIDANCE_ZERO_STAR
 };
 
 struct foley_ctx {
@@ -283,6 +290,9 @@ struct foley_ctx {
   DevBuf tl_a, tl_b, tl_alpha;
   // multistep: the ring of order - 1 velocity slots [clips, latent_dim, La] fp32 that the history step kernels read and feed
   DevBuf ms_hist;
+  // projected guidance: the rows [n_iter][4], the per-workgroup sums, the coefficients [clips][2] and APG's plane [clips*La, latent_dim]
+  DevBuf proj_rows, proj_part, proj_coef, proj_plane;
+  std::vector<float> proj_host;           // [n_iter*4] source of the copy
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -306,6 +316,13 @@ static IterArgs iter_args(const foley_ctx* c) {
     a.guid_part = (float*)c->guid_part.p;
     a.guid_phi = (const float*)c->guid_sched.p + 2 * (size_t)pl.n_iter;
     s.clip_scale = a.guid_scale = (float*)c->guid_scale.p;
+  }
+  if (o.proj_mode) {   // this iteration's coefficients (and APG's plane), before the step applies them (a window is a clip)
+    a.proj_mode = o.proj_mode;
+    a.proj_rows = (const float*)c->proj_rows.p;
+    a.proj_part = (float*)c->proj_part.p;
+    s.proj_coef = a.proj_coef = (float*)c->proj_coef.p;
+    s.proj_plane = a.proj_plane = o.proj_mode == FOLEY_GUIDANCE_APG ? (float*)c->proj_plane.p : nullptr;
   }
   if (o.edit) {   // the edit operands are ctx-owned copies, so their addresses stand for them; so do those of the windows tables
     s.form = STEP_FORM_EDIT;
@@ -1354,9 +1371,11 @@ extern "C" int foley_profile_forward(foley_ctx* c, const float* latents, int ite
 
 // --------------------------------------------------------------------------- sampler loop
 // The solver update of the prediction in buf.pred, as iter_args() states it (guided / edit / windows form, with or without
-// history), behind the statistics of CFG rescale: shared by the plain iteration and the two bodies of a cached one.
+// history), behind the statistics of CFG rescale or the two launches of projected guidance: shared by the plain iteration and the
+// two bodies of a cached one.
 static int run_step(const IterArgs& a, hipStream_t st) {
   if (a.guid_scale) TRY(launch_guidance_stats(a.step, a.guid_part, a.guid_phi, 0.f, a.guid_scale, st));
+  if (a.proj_mode) TRY(launch_guidance_project(a.step, a.proj_mode, a.proj_rows, a.proj_part, a.proj_coef, a.proj_plane, st));
   return launch_solver_step(a.step, st);
 }
 
@@ -1498,6 +1517,8 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
   if (!(rescale >= 0.f && rescale <= 1.f)) return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: rescale must lie in [0, 1]");
   if (rescale > 0.f && c->cfg.latent_dim > 256)
     return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: rescale serves at most 256 latent channels (guidance_stats_kernel)");
+  if (rescale > 0.f && c->opt.proj_mode)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: rescale does not combine with projected guidance (foley_set_projected_guidance)");
   std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
   hipStream_t st = (hipStream_t)stream_v;
   HIPTRY(hipSetDevice(c->device));
@@ -1515,6 +1536,43 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
   HIPTRY(hipStreamSynchronize(st));   // guid_host may be rewritten by the next call
   c->opt.guid_sched_on = sched != nullptr;
   c->opt.guid_rescale_on = rescale > 0.f;
+  return 0;
+}
+
+extern "C" int foley_set_projected_guidance(foley_ctx* c, int mode, const float* rows, int n_rows, void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_projected_guidance: foley_prepare has not been called");
+  if (mode == 0) {   // the plain combine
+    c->opt.proj_mode = 0;
+    return 0;
+  }
+  if (mode != FOLEY_GUIDANCE_APG && mode != FOLEY_GUIDANCE_ZERO_STAR)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: unknown mode (0 off, 1 APG, 2 CFG-Zero*)");
+  const foley_plan& pl = c->plan;
+  if (pl.ncfg != 2) return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: projection takes two halves (plan.ncfg != 2)");
+  if (c->opt.guid_rescale_on)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: the run has a rescale state (foley_set_guidance); projection does not combine with it");
+  if (!rows || n_rows != pl.n_iter)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: the table must have one row per iteration of the plan (n_rows != n_iter)");
+  for (size_t k = 0; k < 4 * (size_t)n_rows; ++k)
+    if (!std::isfinite(rows[k])) return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: non-finite rows");
+  for (int i = 0; i < n_rows; ++i)
+    if (rows[4 * i + 2] < 0.f) return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: the norm threshold must not be negative (R < 0)");
+  if (c->cfg.latent_dim > 256)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: projection serves at most 256 latent channels (guidance_proj_stats_kernel)");
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the buffers may be in use by a previous loop on this stream
+  const size_t nf = 4 * (size_t)pl.n_iter;
+  TRY(grow(c->proj_rows, nf * 4));
+  TRY(grow(c->proj_part, (size_t)guidance_project_floats(pl.clips, pl.La) * 4));
+  TRY(grow(c->proj_coef, (size_t)pl.clips * 2 * 4));
+  if (mode == FOLEY_GUIDANCE_APG) TRY(grow(c->proj_plane, (size_t)pl.clips * pl.La * c->cfg.latent_dim * 4));
+  c->proj_host.assign(rows, rows + nf);
+  HIPTRY(hipMemcpyAsync(c->proj_rows.p, c->proj_host.data(), nf * 4, hipMemcpyHostToDevice, st));
+  HIPTRY(hipStreamSynchronize(st));   // proj_host may be rewritten by the next call
+  c->opt.proj_mode = mode;
   return 0;
 }
 
@@ -2156,16 +2214,46 @@ extern "C" int foley_op_qkv_split(const float* qkv, int M, int L, int H, int nK,
 
 // The solver step, one entry for every form and option: the descriptor translated into the StepArgs the sampler loop launches
 // with.  launch_solver_step checks the form's operands and the ring (a buffer with 1 or 2 slots, or neither).
-extern "C" int foley_op_solver_step(const foley_step_desc* d, void* stream) {
+static int op_solver_step(const foley_step_desc* d, const foley_projection_desc* proj, void* stream) {
   if (!d) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step: null descriptor");
   if (d->x0 && d->n_win) return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step: edit and windows operands exclude each other");
+  if (proj) {
+    if (proj->mode != FOLEY_GUIDANCE_APG && proj->mode != FOLEY_GUIDANCE_ZERO_STAR)
+      return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_projected: unknown mode (1 APG, 2 CFG-Zero*)");
+    if (!proj->coef || (proj->mode == FOLEY_GUIDANCE_APG && !proj->plane))
+      return FAIL(FOLEY_ERR_INVALID, "foley_op_solver_step_projected: the descriptor needs its coefficients and, for APG, its plane");
+  }
   StepArgs s{d->pred, d->x, d->x_saved, d->d_acc, d->clips, d->C, d->L, d->ncfg, d->guidance, d->coef, d->step_ptr, d->rows_out, d->rows_dtype};
   s.sched = d->gd.sched; s.clip_scale = d->gd.clip_scale;
   s.form = d->x0 ? STEP_FORM_EDIT : d->n_win ? STEP_FORM_WINDOWS : STEP_FORM_PLAIN;
   s.x0 = d->x0; s.noise = d->noise; s.mask = d->mask; s.x0_clips = d->x0_clips; s.mask_clips = d->mask_clips;
   s.n_win = d->n_win; s.Ltot = d->Ltot; s.starts = d->starts; s.weights = d->weights;
   s.hist = d->hist; s.hist_slots = d->hist_slots;
+  if (proj) {
+    s.proj_coef = proj->coef;
+    s.proj_plane = proj->mode == FOLEY_GUIDANCE_APG ? proj->plane : nullptr;
+  }
   return launch_solver_step(s, (hipStream_t)stream);
+}
+extern "C" int foley_op_solver_step(const foley_step_desc* d, void* stream) { return op_solver_step(d, nullptr, stream); }
+extern "C" int foley_op_solver_step_projected(const foley_step_desc* d, const foley_projection_desc* proj, void* stream) {
+  return op_solver_step(d, proj, stream);
+}
+
+extern "C" int64_t foley_op_guidance_project_work(int clips, int La) {
+  return clips < 1 || La < 1 ? 0 : (int64_t)guidance_project_floats(clips, La);
+}
+
+extern "C" int foley_op_guidance_project(const foley_projection_desc* proj, const foley_guidance_desc* gd, const float* pred, int clips,
+                                         int C, int La, float guidance, const int32_t* step_ptr, float* work, int64_t work_floats,
+                                         void* stream) {
+  if (!proj || !proj->rows || !proj->coef)
+    return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_project: the descriptor's rows are read and its coef receives the coefficients");
+  if (clips < 1 || La < 1 || !work || work_floats < (int64_t)guidance_project_floats(clips, La))
+    return FAIL(FOLEY_ERR_INVALID, "foley_op_guidance_project: work buffer smaller than foley_op_guidance_project_work(clips, La) floats");
+  StepArgs s{pred, nullptr, nullptr, nullptr, clips, C, La, 2, guidance, nullptr, (int32_t*)step_ptr, nullptr, FOLEY_F32};
+  if (gd) s.sched = gd->sched;
+  return launch_guidance_project(s, proj->mode, proj->rows, work, proj->coef, proj->plane, (hipStream_t)stream);
 }
 
 extern "C" int64_t foley_op_cache_probe_work(int Bc, int La) { return Bc < 1 || La < 1 ? 0 : (int64_t)cache_probe_floats(Bc, La); }

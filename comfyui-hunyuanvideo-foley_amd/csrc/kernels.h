@@ -262,6 +262,11 @@ struct StepArgs {
   // hist_slots after those reads.
   float* hist = nullptr;
   int hist_slots = 0;
+  // projected guidance (null: none - the kernels without it; two halves only): proj_coef [clips][2] {a_c, a_w} of this iteration
+  // (launch_guidance_project) replaces the combine by v = fma(a_c, c, rnd(a_w * w)) with w = proj_plane [clips*L, C] (APG: the
+  // momentum average m, laid out like a pred half) or, without a plane, the unconditional half u (CFG-Zero*)
+  const float* proj_coef = nullptr;
+  const float* proj_plane = nullptr;
   // memberwise: the runtime keys its captured iteration on what it launches (a C++20 default, accepted under -std=c++17)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wc++20-extensions"
@@ -276,6 +281,15 @@ int launch_solver_step(const StepArgs& a, hipStream_t st);
 // that is set (a captured graph then replays with a new value), from `phi` otherwise.
 long guidance_stats_floats(int clips, int L);
 int launch_guidance_stats(const StepArgs& a, float* part, const float* phi_ptr, float phi, float* clip_scale, hipStream_t st);
+// Projected guidance (APG, mode 1; CFG-Zero*, mode 2; two halves): per clip the inner products of this iteration's prediction
+// halves over the clip's C x L elements, then coef[b] = {a_c, a_w} from them, the iteration's scale g (a.sched column 0 at row
+// *a.step_ptr, else a.guidance) and row *a.step_ptr {eta, beta, R, live} of `rows` [n_iter][4].  APG also leaves the momentum
+// average m = (c - u) + beta * m_prev in `plane` [clips*L, C] (in place; beta == 0.0f reads nothing).  Two launches: per-workgroup
+// sums into `part` (guidance_project_floats(clips, L) floats), then one wave per clip merges them in a fixed order - no atomics,
+// repeated runs give the same bits.  a.proj_coef / a.proj_plane are not read: the operands are the arguments.
+constexpr int PROJ_APG = 1, PROJ_ZERO_STAR = 2;
+long guidance_project_floats(int clips, int L);
+int launch_guidance_project(const StepArgs& a, int mode, const float* rows, float* part, float* coef, float* plane, hipStream_t st);
 // Step cache (foley_set_step_cache).  Probe: per row of a0 [Bc*La, D] the first block's modulated input m = LayerNorm(a0; eps) *
 // (1 + scale) + shift in fp32; m replaces m_prev [Bc*La, D] in place and rel[b] = sum|m - m_prev| /
 // sum|m_prev| over batch row b's La x D elements (0 when the denominator is 0).  Two launches: per-workgroup records into `part`

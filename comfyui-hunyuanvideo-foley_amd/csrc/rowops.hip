@@ -709,11 +709,22 @@ constexpr int STEP_SAVE_X = 1, STEP_USE_SAVED = 2, STEP_ACC_RESET = 4, STEP_BLEN
 // `guidance` and the two-half expression is the one the step kernels always had: plain runs keep their bits.  `scale` (the CFG
 // rescale factors, or null) multiplies the result by scale[b].  Two halves fuse the product into the sum; three halves round both
 // products and add them in order.
+// PROJ (projected guidance, foley_set_projected_guidance; two halves): the combine is v = fma(a_c, cnd, rnd(a_w * w)) with
+// {a_c, a_w} = a.proj_coef[b] of this iteration (guidance_proj_coef_kernel) and w the momentum plane's element (APG) or, without a
+// plane, u (CFG-Zero*).  a_c = 1, a_w = 0 (g == 1) returns cnd itself, both 0 (a dead row) a zero.  Like HIST it is a template
+// parameter: the kernels without it are the code they were.
+template <bool PROJ = false>
 __device__ __forceinline__ float guided_value(const StepArgs& a, int it, int b, long r, int c, const float* __restrict__ scale) {
 #pragma clang fp contract(off)
   const long half = (long)a.clips * a.L * a.C;
   const float* p = a.pred + r * a.C + c;
   float v;
+  if (PROJ) {
+    const float cnd = p[half];
+    const float w = a.proj_plane ? a.proj_plane[r * a.C + c] : p[0];
+    const float t = a.proj_coef[2 * b + 1] * w;
+    return __builtin_fmaf(a.proj_coef[2 * b], cnd, t);
+  }
   if (a.ncfg == 2) {
     const float g = a.sched ? a.sched[2 * it] : a.guidance;
     const float u = p[0], cnd = p[half];
@@ -744,12 +755,13 @@ __device__ __forceinline__ StepCoef step_coef(const StepArgs& a, int it) {
 
 // phase 1: the guided value of clip b's rows lb .. lb + 31 (lb may be negative; rows outside [0, L) give 0), read [l][c] (coalesced
 // over c) into the tile that phase 2 reads transposed
+template <bool PROJ = false>
 __device__ __forceinline__ void step_guided_tile(float (*tile)[33], const StepArgs& a, int it, int b, int lb, int c0) {
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   for (int i = ty; i < 32; i += 8) {
     const int l = lb + i, c = c0 + tx;
     float v = 0.f;
-    if (l >= 0 && l < a.L && c < a.C) v = guided_value(a, it, b, (long)b * a.L + l, c, a.clip_scale);
+    if (l >= 0 && l < a.L && c < a.C) v = guided_value<PROJ>(a, it, b, (long)b * a.L + l, c, PROJ ? nullptr : a.clip_scale);
     tile[i][tx] = v;
   }
 }
@@ -811,7 +823,7 @@ __device__ __forceinline__ float edit_blend(float xn, float m, float s, float no
   return m * xn + (1.f - m) * tgt;
 }
 
-template <typename OutT, bool EDIT, bool HIST>
+template <typename OutT, bool EDIT, bool HIST, bool PROJ = false>
 __device__ __forceinline__ void solver_step_body(const StepArgs& a) {
   __shared__ float tile[32][33];
   const int it = *a.step_ptr;
@@ -819,7 +831,7 @@ __device__ __forceinline__ void solver_step_body(const StepArgs& a) {
   const int b = blockIdx.z;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  step_guided_tile(tile, a, it, b, l0, c0);
+  step_guided_tile<PROJ>(tile, a, it, b, l0, c0);
   __syncthreads();
   const float* x0b = EDIT ? a.x0 + (a.x0_clips == 1 ? 0L : (long)b * a.C * a.L) : nullptr;
   const float* mb = EDIT && a.mask ? a.mask + (a.mask_clips == 1 ? 0L : (long)b * a.L) : nullptr;
@@ -846,6 +858,11 @@ template <typename OutT, bool EDIT>
 __global__ __launch_bounds__(256) void solver_step_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, false>(a); }
 template <typename OutT, bool EDIT>
 __global__ __launch_bounds__(256) void solver_step_hist_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, true>(a); }
+// So is the projected combine (a.proj_coef set): the same bodies with guided_value<true>.
+template <typename OutT, bool EDIT>
+__global__ __launch_bounds__(256) void solver_step_proj_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, false, true>(a); }
+template <typename OutT, bool EDIT>
+__global__ __launch_bounds__(256) void solver_step_proj_hist_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, true, true>(a); }
 
 // Windows form (long clips): the clips of one variation are overlapping windows of ONE long clip - clip v*n_win + k covers the
 // global frames [starts[k], starts[k] + L) of variation v - and the step is indexed by GLOBAL frame: a thread owns (g, c) and
@@ -861,7 +878,7 @@ __device__ __forceinline__ float windows_accumulate(bool first, float wk, float 
   return first ? wk * xn : __builtin_fmaf(wk, xn, xb);
 }
 
-template <typename OutT, bool HIST>
+template <typename OutT, bool HIST, bool PROJ = false>
 __device__ __forceinline__ void solver_step_windows_body(const StepArgs& a) {
   __shared__ float tile[32][33];
   const int it = *a.step_ptr;
@@ -876,7 +893,7 @@ __device__ __forceinline__ void solver_step_windows_body(const StepArgs& a) {
     const int s0 = a.starts[k];
     if (s0 >= g0 + 32 || s0 + a.L <= g0) continue;   // the window misses this tile (uniform over the block)
     const int b = b0 + k;
-    step_guided_tile(tile, a, it, b, g0 - s0, c0);
+    step_guided_tile<PROJ>(tile, a, it, b, g0 - s0, c0);
     __syncthreads();
     // phase 2: update x [b][c][l] (coalesced over l)
     const int l = g0 + tx - s0;
@@ -930,6 +947,10 @@ template <typename OutT>
 __global__ __launch_bounds__(256) void solver_step_windows_kernel(const StepArgs a) { solver_step_windows_body<OutT, false>(a); }
 template <typename OutT>
 __global__ __launch_bounds__(256) void solver_step_windows_hist_kernel(const StepArgs a) { solver_step_windows_body<OutT, true>(a); }
+template <typename OutT>
+__global__ __launch_bounds__(256) void solver_step_windows_proj_kernel(const StepArgs a) { solver_step_windows_body<OutT, false, true>(a); }
+template <typename OutT>
+__global__ __launch_bounds__(256) void solver_step_windows_proj_hist_kernel(const StepArgs a) { solver_step_windows_body<OutT, true, true>(a); }
 
 // Stitch the windows of every variation into one long clip: G[v][c][g] = sum_k weights[k][g - starts[k]] * x[v*n_win + k][c][g - starts[k]]
 // over the covering windows, in window order.  Where the covering windows hold the identical bits (after a blend row: under euler
@@ -1068,6 +1089,126 @@ __global__ __launch_bounds__(64) void guidance_scale_kernel(const float* __restr
   float f = 1.0f;
   if (acc[2] > 0.f) f = ph * sqrtf(acc[4] / acc[2]) + (1.0f - ph);   // the counts cancel in the ratio of the deviations
   clip_scale[b] = f;
+}
+
+// ------------------------------------------------------------------ projected guidance: per-clip inner products, then two coefficients
+// APG (Sadat et al. 2024) and CFG-Zero* (Fan et al. 2025) over two halves u = pred half 0, c = pred half 1; <a,b> is the sum over
+// a clip's C x L elements, g the iteration's scale and {eta, beta, R, live} = rows[*step_ptr].  Every line below is one fp32
+// operation as written (contraction off, the fused ones named):
+//   launch 1, per element (APG)   d = c - u;  m = beta != 0 ? fma(beta, m_prev, d) : d;  plane <- m  (beta == 0.0f reads no plane)
+//   launch 1, per lane            over its rows i ascending, inside a row its channels lane + 64 j ascending:
+//                                   APG    s0 = fma(m, c, s0)  s1 = fma(c, c, s1)  s2 = fma(m, m, s2)
+//                                   Zero*  s0 = fma(c, u, s0)  s1 = fma(u, u, s1)
+//                                 then wave_sum of each, the four waves through LDS added in wave order by thread 0:
+//                                 one record {s0, s1, s2} per workgroup (PJ_REC floats; Zero* leaves s2 = 0)
+//   launch 2, one wave per clip   lane j adds records j, j + 64, ... ascending; lane 0 adds the 64 lanes' sums in lane order
+//     APG    n = sqrtf(s2);  r = (R > 0 && n > R) ? R / n : 1;  rho = s1 > 0 ? s0 / s1 : 0;  t = (g - 1) * r;
+//            a_w = live * t;  a_c = live * fma(t, (eta - 1) * rho, 1)
+//     Zero*  s = s1 > 0 ? s0 / s1 : 0;  a_c = live * g;  a_w = live * ((1 - g) * s)
+// and the step's v = fma(a_c, c, rnd(a_w * w)), w = m (APG; the plane keeps the unclipped m) or u (Zero*): guided_value<true>.
+// g == 1 gives t = 0, a_w = 0 and a_c = live exactly; live == 0 gives two zeros.  APG with eta = 1, beta = 0, R = 0 has a_c = 1,
+// a_w = g - 1: plain CFG to rounding (v = c + (g - 1)(c - u), not the step's fma(g, c - u, u)), not bit-equal to it.
+// The geometry is guidance_stats_kernel's (GS_ROWS rows per workgroup, GS_RW per wave, a lane takes channels lane + 64 j, every
+// load issued before the first sum), every order is fixed and nothing is atomic: the same input gives the same bits.  Every access
+// is guarded by (l < L, c < C); masked elements enter the sums as fma(0, 0, s) = s.
+constexpr int PJ_REC = 3;
+
+template <int JC, int MODE>
+__global__ __launch_bounds__(256) void guidance_proj_stats_kernel(const float* __restrict__ pred, float* plane,
+                                                                  const float* __restrict__ rows, const int* __restrict__ step_ptr,
+                                                                  int clips, int C, int L, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ float red[4][PJ_REC];
+  constexpr bool APG = MODE == PROJ_APG;
+  const int it = *step_ptr;
+  const float beta = APG ? rows[4 * it + 1] : 0.f;
+  const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int l0 = blockIdx.x * GS_ROWS + wave * GS_RW;
+  const long half = (long)clips * L * C;
+  float u[GS_RW][JC], cn[GS_RW][JC], mp[GS_RW][JC];
+#pragma unroll
+  for (int i = 0; i < GS_RW; ++i)
+#pragma unroll
+    for (int j = 0; j < JC; ++j) {
+      const int l = l0 + i, c = lane + 64 * j;
+      const bool ok = l < L && c < C;
+      const long e = ((long)b * L + l) * C + c;
+      u[i][j] = ok ? pred[e] : 0.f;
+      cn[i][j] = ok ? pred[half + e] : 0.f;
+      mp[i][j] = (APG && ok && beta != 0.f) ? plane[e] : 0.f;
+    }
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < GS_RW; ++i)
+#pragma unroll
+    for (int j = 0; j < JC; ++j) {
+      if (APG) {
+        const int l = l0 + i, c = lane + 64 * j;
+        const float d = cn[i][j] - u[i][j];
+        const float m = (beta != 0.f) ? __builtin_fmaf(beta, mp[i][j], d) : d;
+        if (l < L && c < C) plane[((long)b * L + l) * C + c] = m;
+        s0 = __builtin_fmaf(m, cn[i][j], s0);
+        s1 = __builtin_fmaf(cn[i][j], cn[i][j], s1);
+        s2 = __builtin_fmaf(m, m, s2);
+      } else {
+        s0 = __builtin_fmaf(cn[i][j], u[i][j], s0);
+        s1 = __builtin_fmaf(u[i][j], u[i][j], s1);
+      }
+    }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  if (APG) s2 = wave_sum(s2);
+  if (lane == 0) {
+    red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* o = part + ((long)b * gridDim.x + blockIdx.x) * PJ_REC;
+    for (int k = 0; k < PJ_REC; ++k) {
+      float acc = red[0][k];
+      for (int w = 1; w < 4; ++w) acc = acc + red[w][k];
+      o[k] = acc;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void guidance_proj_coef_kernel(const float* __restrict__ part, int nblk, int mode,
+                                                                const float* __restrict__ rows, const float* __restrict__ sched,
+                                                                float guidance, const int* __restrict__ step_ptr,
+                                                                float* __restrict__ coef) {
+#pragma clang fp contract(off)
+  __shared__ float red[64][PJ_REC];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  float acc[PJ_REC] = {0.f, 0.f, 0.f};
+  for (int k = lane; k < nblk; k += 64) {
+    const float* rec = part + ((long)b * nblk + k) * PJ_REC;
+    for (int q = 0; q < PJ_REC; ++q) acc[q] = acc[q] + rec[q];
+  }
+  for (int q = 0; q < PJ_REC; ++q) red[lane][q] = acc[q];
+  __syncthreads();
+  if (lane != 0) return;
+  for (int j = 1; j < 64; ++j)
+    for (int q = 0; q < PJ_REC; ++q) acc[q] = acc[q] + red[j][q];
+  const int it = *step_ptr;
+  const float g = sched ? sched[2 * it] : guidance;
+  const float eta = rows[4 * it], R = rows[4 * it + 2], live = rows[4 * it + 3];
+  float a_c, a_w;
+  if (mode == PROJ_APG) {
+    const float n = sqrtf(acc[2]);
+    const float r = (R > 0.f && n > R) ? R / n : 1.0f;
+    const float rho = acc[1] > 0.f ? acc[0] / acc[1] : 0.f;
+    const float t = (g - 1.0f) * r;
+    const float q = (eta - 1.0f) * rho;
+    a_w = live * t;
+    a_c = live * __builtin_fmaf(t, q, 1.0f);
+  } else {
+    const float s = acc[1] > 0.f ? acc[0] / acc[1] : 0.f;
+    const float t = (1.0f - g) * s;
+    a_c = live * g;
+    a_w = live * t;
+  }
+  coef[2 * b] = a_c;
+  coef[2 * b + 1] = a_w;
 }
 
 __global__ void step_increment_kernel(int* p) { *p = *p + 1; }
@@ -1529,6 +1670,18 @@ template <typename OutT>
 static void launch_step_form(const StepArgs& a, hipStream_t st) {
   const bool win = a.form == STEP_FORM_WINDOWS;
   const dim3 grid(((win ? a.Ltot : a.L) + 31) / 32, (a.C + 31) / 32, win ? a.clips / a.n_win : a.clips), block(256);
+  if (a.proj_coef) {   // projected guidance: the instantiations of the same forms with the projected combine
+    if (a.hist) {
+      if (win) FOLEY_LAUNCH(solver_step_windows_proj_hist_kernel<OutT>, grid, block, 0, st, a);
+      else if (a.form == STEP_FORM_EDIT) FOLEY_LAUNCH((solver_step_proj_hist_kernel<OutT, true>), grid, block, 0, st, a);
+      else FOLEY_LAUNCH((solver_step_proj_hist_kernel<OutT, false>), grid, block, 0, st, a);
+    } else {
+      if (win) FOLEY_LAUNCH(solver_step_windows_proj_kernel<OutT>, grid, block, 0, st, a);
+      else if (a.form == STEP_FORM_EDIT) FOLEY_LAUNCH((solver_step_proj_kernel<OutT, true>), grid, block, 0, st, a);
+      else FOLEY_LAUNCH((solver_step_proj_kernel<OutT, false>), grid, block, 0, st, a);
+    }
+    return;
+  }
   if (a.hist) {   // a multistep run: the history instantiation of the same form
     if (win) FOLEY_LAUNCH(solver_step_windows_hist_kernel<OutT>, grid, block, 0, st, a);
     else if (a.form == STEP_FORM_EDIT) FOLEY_LAUNCH((solver_step_hist_kernel<OutT, true>), grid, block, 0, st, a);
@@ -1551,6 +1704,9 @@ int launch_solver_step(const StepArgs& a, hipStream_t st) {
   }
   if ((a.hist || a.hist_slots) && (!a.hist || a.hist_slots < 1 || a.hist_slots > 2))
     return foley_set_err("solver_step: a history ring needs its buffer and 1 or 2 slots", __FILE__, __LINE__);
+  if (a.proj_plane && !a.proj_coef) return foley_set_err("solver_step: a projection plane needs its coefficients", __FILE__, __LINE__);
+  if (a.proj_coef && (a.ncfg != 2 || a.clip_scale))
+    return foley_set_err("solver_step: projected guidance takes two halves (ncfg 2) and no rescale factors", __FILE__, __LINE__);
   if (a.rows_dtype == FOLEY_BF16) launch_step_form<bf16_t>(a, st);
   else if (a.rows_dtype == FOLEY_F16) launch_step_form<f16_t>(a, st);
   else launch_step_form<float>(a, st);
@@ -1575,6 +1731,36 @@ int launch_guidance_stats(const StepArgs& a, float* part, const float* phi_ptr, 
   else FOLEY_LAUNCH(guidance_stats_kernel<4>, grid, block, 0, st, a, part);
   FOLEY_LAUNCH_CHECK();
   FOLEY_LAUNCH(guidance_scale_kernel, dim3(a.clips), dim3(64), 0, st, (const float*)part, nblk, phi_ptr, phi, clip_scale);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+long guidance_project_floats(int clips, int L) { return (long)clips * ((L + GS_ROWS - 1) / GS_ROWS) * PJ_REC; }
+
+template <int MODE>
+static void launch_proj_stats(const StepArgs& a, const float* rows, float* part, float* plane, dim3 grid, hipStream_t st) {
+  const dim3 block(256);
+  if (a.C <= 64) FOLEY_LAUNCH((guidance_proj_stats_kernel<1, MODE>), grid, block, 0, st, a.pred, plane, rows, (const int*)a.step_ptr, a.clips, a.C, a.L, part);
+  else if (a.C <= 128) FOLEY_LAUNCH((guidance_proj_stats_kernel<2, MODE>), grid, block, 0, st, a.pred, plane, rows, (const int*)a.step_ptr, a.clips, a.C, a.L, part);
+  else FOLEY_LAUNCH((guidance_proj_stats_kernel<4, MODE>), grid, block, 0, st, a.pred, plane, rows, (const int*)a.step_ptr, a.clips, a.C, a.L, part);
+}
+
+int launch_guidance_project(const StepArgs& a, int mode, const float* rows, float* part, float* coef, float* plane, hipStream_t st) {
+  if (mode != PROJ_APG && mode != PROJ_ZERO_STAR) return foley_set_err("guidance_project: unknown mode (1 APG, 2 CFG-Zero*)", __FILE__, __LINE__);
+  if (a.ncfg != 2) return foley_set_err("guidance_project: projected guidance takes two halves (ncfg 2)", __FILE__, __LINE__);
+  if (!a.pred || !a.step_ptr || !rows || !part || !coef || a.clips < 1 || a.clips > 65535 || a.C < 1 || a.L < 1)
+    return foley_set_err("guidance_project: pred, step_ptr, rows, work and coefficient buffers required; 1 <= clips <= 65535", __FILE__, __LINE__);
+  if (mode == PROJ_APG && !plane) return foley_set_err("guidance_project: APG needs its momentum plane", __FILE__, __LINE__);
+  if (a.C > 256) return foley_set_err("guidance_project: at most 256 channels", __FILE__, __LINE__);
+  if ((long)a.clips * a.C * a.L >= (1L << 31) || (long)a.C * a.L >= (1L << 24))
+    return foley_set_err("guidance_project: clip too large (C*L < 2^24 elements per clip)", __FILE__, __LINE__);
+  const int nblk = (a.L + GS_ROWS - 1) / GS_ROWS;
+  const dim3 grid(nblk, a.clips);
+  if (mode == PROJ_APG) launch_proj_stats<PROJ_APG>(a, rows, part, plane, grid, st);
+  else launch_proj_stats<PROJ_ZERO_STAR>(a, rows, part, nullptr, grid, st);
+  FOLEY_LAUNCH_CHECK();
+  FOLEY_LAUNCH(guidance_proj_coef_kernel, dim3(a.clips), dim3(64), 0, st, (const float*)part, nblk, mode, rows, a.sched, a.guidance,
+               (const int*)a.step_ptr, coef);
   FOLEY_LAUNCH_CHECK();
   return 0;
 }

@@ -102,6 +102,12 @@ class GuidanceDescC(C.Structure):
     _fields_ = [("sched", C.c_void_p), ("clip_scale", C.c_void_p)]
 
 
+class ProjectionDescC(C.Structure):
+    """foley_projection_desc: device pointers of the rows [n_iter, 4], the coefficients [clips, 2] and APG's plane [clips*L, C]
+    (0: absent), and the mode (FOLEY_GUIDANCE_APG 1, FOLEY_GUIDANCE_ZERO_STAR 2)."""
+    _fields_ = [("rows", C.c_void_p), ("coef", C.c_void_p), ("plane", C.c_void_p), ("mode", C.c_int32)]
+
+
 class StepDescC(C.Structure):
     """foley_step_desc: every operand of foley_op_solver_step - the core ones, then the optional guidance descriptor, velocity
     ring [hist_slots, clips, C, L], x0 / noise / mask of the edit form and starts / weights of the windows form (0: absent)."""
@@ -145,6 +151,7 @@ _SIGNATURES = {
     "foley_set_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_set_windows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "foley_set_guidance": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p]),
+    "foley_set_projected_guidance": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "foley_set_step_cache": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int,
                                        C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "foley_step_cache_report": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_int]),
@@ -188,6 +195,10 @@ _SIGNATURES = {
     "foley_op_guidance_stats_work": (C.c_int64, [C.c_int, C.c_int]),
     "foley_op_guidance_stats": (C.c_int, [C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    "foley_op_guidance_project_work": (C.c_int64, [C.c_int, C.c_int]),
+    "foley_op_guidance_project": (C.c_int, [C.POINTER(ProjectionDescC), C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "foley_op_solver_step_projected": (C.c_int, [C.POINTER(StepDescC), C.POINTER(ProjectionDescC), C.c_void_p]),
     "foley_op_cache_probe_work": (C.c_int64, [C.c_int, C.c_int]),
     "foley_op_cache_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(RowBcastC), C.POINTER(RowBcastC),
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -520,6 +531,19 @@ class FoleyContext:
             arr = (C.c_float * (2 * n))(*t.flatten().tolist())
         with torch.cuda.device(self.device):
             _check(self.lib, self.lib.foley_set_guidance(self._h, arr, n, float(rescale), _stream()), "foley_set_guidance")
+
+    def set_projected_guidance(self, mode: int = 0, rows: Optional[torch.Tensor] = None):
+        """foley_set_projected_guidance after prepare(): mode 1 (APG) or 2 (CFG-Zero*) with `rows` [n_iter, 4] fp32 {eta, beta, R,
+        live} per loop iteration (tables.projection_rows; any device, the library copies it from the host); mode 0 clears."""
+        arr, n = None, 0
+        if rows is not None:
+            t = rows.detach().to("cpu", torch.float32).contiguous()
+            if t.dim() != 2 or t.shape[1] != 4:
+                raise FoleyRuntimeError("set_projected_guidance: the rows are [n_iter, 4] (eta, beta, R, live per iteration)")
+            n = int(t.shape[0])
+            arr = (C.c_float * (4 * n))(*t.flatten().tolist())
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_set_projected_guidance(self._h, int(mode), arr, n, _stream()), "foley_set_projected_guidance")
 
     def set_step_cache(self, mode: int = 0, skip=None, threshold: float = 0.0, poly=None, interval=None, max_consecutive: int = 0):
         """foley_set_step_cache after prepare() (host/step_cache.py states the policy): mode 0 clears; 1 = schedule with `skip`, one
@@ -1016,12 +1040,26 @@ def guidance_desc(sched: Optional[torch.Tensor] = None, clip_scale: Optional[tor
     return GuidanceDescC(_ptr(sched), _ptr(clip_scale))
 
 
+def projection_desc(mode: int, rows: Optional[torch.Tensor], coef: Optional[torch.Tensor], plane: Optional[torch.Tensor] = None) -> ProjectionDescC:
+    """Projection descriptor of op_guidance_project and op_solver_step(proj=): rows [n_iter, 4], coef [clips, 2] and plane
+    [clips*L, C] fp32 device tensors (plane None: CFG-Zero*)."""
+    for t, what in ((rows, "rows"), (coef, "coef"), (plane, "plane")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise FoleyRuntimeError(f"projection_desc: {what} must be a contiguous fp32 tensor")
+    if rows is not None and (rows.dim() != 2 or rows.shape[1] != 4):
+        raise FoleyRuntimeError("projection_desc: rows is [n_iter, 4]")
+    return ProjectionDescC(_ptr(rows), _ptr(coef), _ptr(plane), int(mode))
+
+
 def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows_out, *, gd: Optional[GuidanceDescC] = None,
-                   hist: Optional[torch.Tensor] = None, slots: Optional[int] = None, edit=None, windows=None):
+                   hist: Optional[torch.Tensor] = None, slots: Optional[int] = None, edit=None, windows=None,
+                   proj: Optional[ProjectionDescC] = None, projected_entry: bool = False):
     """foley_op_solver_step: x_saved / d_acc may be None for single-stage tables (euler), rows_out None to leave the next input
     rows unstaged.  gd: a guidance_desc; hist: a velocity ring [slots, clips, C, L] fp32 (slots 1 or 2, taken from the tensor
     unless given).  edit=(x0 [1 | clips, C, L], noise [clips, C, L], mask [1 | clips, L] or [L] or None: all ones) selects the
-    edit form, windows=(starts [n_win] int32, weights [n_win, L] fp32, Ltot) with x [variations*n_win, C, L] the windows form."""
+    edit form, windows=(starts [n_win] int32, weights [n_win, L] fp32, Ltot) with x [variations*n_win, C, L] the windows form.
+    proj: a projection_desc - the step goes through foley_op_solver_step_projected (projected_entry: that entry with a null
+    descriptor, which is foley_op_solver_step bit for bit)."""
     lib = load_library()
     clips, Cc, L = x.shape
     if hist is not None and (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.dim() != 4
@@ -1040,6 +1078,10 @@ def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows
     if windows is not None:
         starts, weights, Ltot = windows
         d.n_win, d.starts, d.weights, d.Ltot = _windows_tables(x, starts, weights), _ptr(starts), _ptr(weights), int(Ltot)
+    if proj is not None or projected_entry:
+        _check(lib, lib.foley_op_solver_step_projected(C.byref(d), C.byref(proj) if proj is not None else None, _stream()),
+               "foley_op_solver_step_projected")
+        return
     _check(lib, lib.foley_op_solver_step(C.byref(d), _stream()), "foley_op_solver_step")
 
 
@@ -1074,6 +1116,18 @@ def op_guidance_stats(pred, clips, L, ncfg, guidance, sched, step_ptr, rescale, 
     _check(lib, lib.foley_op_guidance_stats(C.byref(gd), _ptr(pred), clips, int(pred.shape[1]), L, ncfg, float(guidance),
                                             _ptr(step_ptr), float(rescale), _ptr(work), n, _stream()), "foley_op_guidance_stats")
     return out
+
+
+def op_guidance_project(proj: ProjectionDescC, pred, clips, La, guidance, sched, step_ptr) -> None:
+    """foley_op_guidance_project: pred [2*clips*La, C] fp32 -> proj.coef [clips, 2] (and, APG, proj.plane updated in place)."""
+    lib = load_library()
+    if pred.dtype != torch.float32 or pred.dim() != 2 or pred.shape[0] != 2 * clips * La:
+        raise FoleyRuntimeError("op_guidance_project: pred [2*clips*La, C] fp32")
+    n = int(lib.foley_op_guidance_project_work(clips, La))
+    work = torch.empty(max(n, 1), dtype=torch.float32, device=pred.device)
+    gd = guidance_desc(sched, None)
+    _check(lib, lib.foley_op_guidance_project(C.byref(proj), C.byref(gd), _ptr(pred), clips, int(pred.shape[1]), La, float(guidance),
+                                              _ptr(step_ptr), _ptr(work), n, _stream()), "foley_op_guidance_project")
 
 
 def op_cache_probe(a0: torch.Tensor, Bc: int, eps: float, shift: Optional[RowBcastC], scale: Optional[RowBcastC], m_prev: torch.Tensor,

@@ -7,6 +7,7 @@ tables; every FLOP of the hot path runs in the HIP library.
 """
 from __future__ import annotations
 
+import math
 import threading
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -146,6 +147,45 @@ def fp8_time_dtype(model):
 
 
 @dataclass(frozen=True)
+class ProjectionSpec:
+    """Projected guidance in place of the two-half combine (foley_set_projected_guidance, tables.projection_rows).
+      mode            "apg": adaptive projected guidance (Sadat et al. 2024) - the guidance difference c - u is averaged over the
+                      iterations with weight `momentum`, clipped to the norm `norm_threshold` and split into the part parallel to
+                      the conditional prediction, which `eta` scales, and the orthogonal part.  eta = 1, momentum = 0 and no
+                      threshold is plain CFG to rounding (not bit for bit).
+                      "cfg_zero_star": CFG-Zero* (Fan et al. 2025) - the unconditional prediction is scaled by <c,u>/<u,u> per
+                      clip before the combine.
+      eta             APG, in [0, 1].
+      momentum        APG, |momentum| < 1 (the paper's default is negative).
+      norm_threshold  APG, >= 0, in the model's velocity units (uncalibrated for this model); 0: no clip.
+      zero_init       the first `zero_init` loop iterations of the full run use a zero velocity (both modes)."""
+    mode: str
+    eta: float = 0.0
+    momentum: float = -0.5
+    norm_threshold: float = 0.0
+    zero_init: int = 0
+
+    def check(self, steps: Optional[int] = None) -> None:
+        if self.mode not in tables.PROJECTION_MODES:
+            raise ValueError(f"guidance_mode must be one of {list(tables.PROJECTION_MODES)}, got {self.mode!r}")
+        for name in ("eta", "momentum", "norm_threshold"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"projection {name} must be a finite number, got {v!r}")
+        if not 0.0 <= float(self.eta) <= 1.0:
+            raise ValueError(f"apg eta must lie in [0, 1], got {self.eta}")
+        if not abs(float(self.momentum)) < 1.0:
+            raise ValueError(f"apg momentum must satisfy |momentum| < 1, got {self.momentum}")
+        if float(self.norm_threshold) < 0.0:
+            raise ValueError(f"apg norm_threshold must be >= 0, got {self.norm_threshold}")
+        z = self.zero_init
+        if isinstance(z, bool) or not isinstance(z, int) or z < 0:
+            raise ValueError(f"zero_init_steps must be an integer >= 0, got {z!r}")
+        if steps is not None and z >= int(steps):
+            raise ValueError(f"zero_init_steps ({z}) must be smaller than the number of steps ({int(steps)})")
+
+
+@dataclass(frozen=True)
 class GuidanceSpec:
     """How the prediction halves become one velocity, beyond the scalar `guidance_scale` (which stays the text scale and the
     only scale of a two-half run).
@@ -153,12 +193,23 @@ class GuidanceSpec:
                 visual features, h2 prompt + the same features - combined as v = p0 + g_video (p1 - p0) + g_text (p2 - p1).
       interval  (start, end) in fractions of the loop: the scales hold on the iterations with start <= i / n_iter < end, the
                 others use (1, 1).  Every half still runs on every iteration (the run keeps its shape).
-      rescale   phi in [0, 1]: the step uses f v, f = phi std(h_last) / std(v) + (1 - phi) per clip (windows: per window)."""
+      rescale   phi in [0, 1]: the step uses f v, f = phi std(h_last) / std(v) + (1 - phi) per clip (windows: per window).
+      projection  a ProjectionSpec: APG or CFG-Zero* in place of the two-half combine (two halves only: no video scale, no
+                rescale, guidance_scale > 1); it combines with the interval."""
     g_video: Optional[float] = None
     interval: Optional[Tuple[float, float]] = None
     rescale: float = 0.0
+    projection: Optional[ProjectionSpec] = None
 
-    def check(self, guidance_scale: float) -> None:
+    def check(self, guidance_scale: float, steps: Optional[int] = None) -> None:
+        if self.projection is not None:
+            self.projection.check(steps)
+            if self.g_video is not None:
+                raise ValueError("projected guidance takes two halves: it does not combine with a video scale (video_cfg_scale)")
+            if float(self.rescale) > 0.0:
+                raise ValueError("projected guidance does not combine with cfg_rescale > 0")
+            if not guidance_scale > 1.0:
+                raise ValueError(f"projected guidance needs guidance: cfg_scale > 1, got {guidance_scale}")
         if not 0.0 <= float(self.rescale) <= 1.0:
             raise ValueError(f"guidance rescale must lie in [0, 1], got {self.rescale}")
         if self.g_video is None and not guidance_scale > 1.0 and (self.interval is not None or self.rescale > 0.0):
@@ -197,6 +248,8 @@ def apply_guidance(ctx: FoleyContext, plan: dict) -> None:
     """foley_set_guidance with what build_plan put into the plan (after prepare, next to set_edit / set_windows)."""
     if plan.get("guid_sched") is not None or plan.get("guid_rescale", 0.0) > 0.0:
         ctx.set_guidance(plan.get("guid_sched"), plan.get("guid_rescale", 0.0))
+    if plan.get("proj_rows") is not None:
+        ctx.set_projected_guidance(int(plan["proj_mode"]), plan["proj_rows"])
 
 
 def apply_step_cache(ctx: FoleyContext, plan: dict) -> None:
@@ -249,7 +302,7 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
     if step_cache is not None:
         step_cache.check(int(steps))
     if guidance is not None:
-        guidance.check(guidance_scale)
+        guidance.check(guidance_scale, int(steps))
     three = guidance is not None and guidance.g_video is not None
     use_cfg = guidance_scale > 1.0 or three
     f32 = lambda t: t.to(device=dev, dtype=torch.float32)
@@ -340,6 +393,12 @@ def build_plan(model: FoleyModel, visual_feats: Dict[str, torch.Tensor], text_fe
         plan["guid_sched"] = sched[edit_i0 or 0:].contiguous()
     if guidance is not None:
         plan["guid_rescale"] = float(guidance.rescale)
+    if guidance is not None and guidance.projection is not None:
+        # an edit run takes the suffix of the plain run's rows; its first row starts the momentum average
+        pj = guidance.projection
+        plan["proj_mode"] = tables.PROJECTION_MODES[pj.mode]
+        plan["proj_rows"] = tables.projection_rows(steps, pj.mode, pj.eta, pj.momentum, pj.norm_threshold, pj.zero_init,
+                                                   start=edit_i0 or 0)
     if ms_order is not None:
         plan["multistep_order"] = ms_order
     if step_cache is not None:

@@ -141,6 +141,35 @@ def guidance_schedule(n_iter: int, g_video: float, g_text: float, interval=None)
     return rows
 
 
+PROJECTION_MODES = {"apg": 1, "cfg_zero_star": 2}      # FOLEY_GUIDANCE_APG, FOLEY_GUIDANCE_ZERO_STAR
+
+
+def projection_rows(n_iter: int, mode, eta: float = 0.0, momentum: float = -0.5, norm_threshold: float = 0.0, zero_init: int = 0,
+                    start: int = 0) -> torch.Tensor:
+    """[n_iter - start, 4] fp32 rows {eta, beta, R, live} of the loop iterations [start, n_iter) (foley_set_projected_guidance),
+    computed in fp64 and rounded once.  mode "apg" (or 1): eta scales the part of the guidance difference parallel to the
+    conditional prediction, beta = `momentum` is the weight of the running average on every row but the first (row `start` has
+    beta = 0: the run has no average yet, and the plane is not read), R = `norm_threshold` clips the norm of the averaged
+    difference (0: no clip).  mode "cfg_zero_star" (or 2): eta, beta and R are 0.  live = 0 on the rows i < zero_init of the full
+    run (a zero velocity), 1 elsewhere.  i counts loop iterations, so a multi-stage solver counts its stages, as every other table
+    does; an edit run passes start = i0 and gets the rows [i0, n_iter)."""
+    n_iter, start, zero_init = int(n_iter), int(start), int(zero_init)
+    m = PROJECTION_MODES.get(mode, mode)
+    if m not in PROJECTION_MODES.values():
+        raise ValueError(f"projection mode must be one of {list(PROJECTION_MODES)}, got {mode!r}")
+    if n_iter < 1 or not 0 <= start < n_iter:
+        raise ValueError(f"projection rows need n_iter >= 1 and 0 <= start < n_iter, got n_iter {n_iter}, start {start}")
+    if zero_init < 0:
+        raise ValueError(f"zero_init must be >= 0, got {zero_init}")
+    rows = torch.zeros(n_iter, 4, dtype=torch.float64)
+    if m == PROJECTION_MODES["apg"]:
+        rows[:, 0], rows[:, 1], rows[:, 2] = float(eta), float(momentum), float(norm_threshold)
+        rows[start, 1] = 0.0
+    rows[:, 3] = 1.0
+    rows[:zero_init, 3] = 0.0
+    return rows[start:].to(torch.float32).contiguous()
+
+
 def edit_start(steps: int, solver: str, strength: float):
     """(k0, i0) of an edit run at `strength`: the run is the suffix [i0, steps) of the plain run's iterations, starting from the
     source noised to sigma_{k0}.  Counted in whole solver steps (the diffusers img2img rule): n_full = steps // stages,

@@ -339,7 +339,8 @@ class HunyuanFoleySampler:
                        prompts=None, negative_prompts=None, images=None, window_s=None, window_overlap_s=2.0,
                        video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0, cache_threshold=None, cache_skip=None,
                        cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25,
-                       loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False, multistep_order=None):
+                       loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False, multistep_order=None,
+                       guidance_mode=None, apg_eta=0.0, apg_momentum=-0.5, apg_norm_threshold=0.0, zero_init_steps=0):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -395,7 +396,14 @@ class HunyuanFoleySampler:
         the `euler` solver - Adams-Bashforth on the run's sigma grid, which reuses the velocities of the one or two steps before
         and so reaches second order at Euler's price of one model call per step.  Order 3 is a third-order formula behind a
         first-order first step: second order overall, with a smaller constant.  It combines with every other option and does not
-        combine with heun-2 / midpoint-2 / kutta-4."""
+        combine with heun-2 / midpoint-2 / kutta-4.
+
+        Projected guidance (keyword-only, not sockets; host/sampler.py::ProjectionSpec): `guidance_mode` "apg" (adaptive projected
+        guidance: `apg_eta` in [0, 1] scales the part of the guidance difference parallel to the conditional prediction,
+        `apg_momentum`, |.| < 1, averages the difference over the iterations, `apg_norm_threshold` >= 0 clips its norm - in the
+        model's velocity units, uncalibrated; 0: off) or "cfg_zero_star" (the unconditional prediction is rescaled per clip before
+        the combine); `zero_init_steps` iterations at the start use a zero velocity.  Two halves with cfg_scale > 1 only: it does
+        not combine with video_cfg_scale or cfg_rescale > 0.  None: the plain combine, bit for bit, and nothing new is launched."""
         model, deps = hunyuan_model, hunyuan_deps
         ms_kw = {}
         if multistep_order is not None:            # refused here, before the encoders run
@@ -428,7 +436,17 @@ class HunyuanFoleySampler:
         elif cache_interval is not None or cache_max_consecutive is not None:
             raise ValueError("cache_interval / cache_max_consecutive limit threshold mode: pass cache_threshold")
         guidance = None
-        if video_cfg_scale is not None or guidance_interval is not None or cfg_rescale:
+        projection = None
+        if guidance_mode is not None:              # refused here, before the encoders run
+            projection = _sampler.ProjectionSpec(guidance_mode, apg_eta, apg_momentum, apg_norm_threshold, zero_init_steps)
+        elif apg_eta != 0.0 or apg_momentum != -0.5 or apg_norm_threshold != 0.0 or zero_init_steps != 0:
+            raise ValueError("apg_eta / apg_momentum / apg_norm_threshold / zero_init_steps belong to projected guidance: pass guidance_mode")
+        if projection is not None:
+            guidance = _sampler.GuidanceSpec(None if video_cfg_scale is None else float(video_cfg_scale),
+                                             None if guidance_interval is None else tuple(float(t) for t in guidance_interval),
+                                             float(cfg_rescale), projection)
+            guidance.check(cfg_scale, int(steps))
+        elif video_cfg_scale is not None or guidance_interval is not None or cfg_rescale:
             if video_cfg_scale is not None and image is None and images is None and features is None:
                 raise ValueError("video_cfg_scale needs visual input (image / images): without it the two lower guidance "
                                  "halves are identical")

@@ -253,6 +253,35 @@ int foley_set_windows(foley_ctx* ctx, int n_win, const int32_t* starts, const fl
  * plan.ncfg == 1, n_rows != plan.n_iter, rescale outside [0, 1]: FOLEY_ERR_INVALID; before foley_prepare: FOLEY_ERR_STATE. */
 int foley_set_guidance(foley_ctx* ctx, const float* sched, int n_rows, float rescale, void* stream);
 
+/* Projected guidance (additive within ABI 13; opt-in): APG (adaptive projected guidance, Sadat et al. 2024) and CFG-Zero* (Fan et al.
+ * 2025) in place of the two-half combine.  Per batch clip, u and c are the clip's unconditional and conditional prediction rows,
+ * <a,b> the sum over the clip's latent_dim x La elements, g the iteration's scale (the schedule's column 0 under foley_set_guidance,
+ * else plan.guidance) and {eta, beta, R, live} row i of `rows` for loop iteration i (multi-stage solvers: every stage is an
+ * iteration):
+ *   FOLEY_GUIDANCE_APG        m = (c - u) + beta m_prev (an fp32 plane [clips*La, latent_dim], context-owned, updated in place;
+ *                             beta == 0 reads nothing, so the first row of a run does not depend on what the plane holds);
+ *                             r = (R > 0 && |m| > R) ? R / |m| : 1;  rho = <c,c> > 0 ? <m,c> / <c,c> : 0;
+ *                             a_w = live (g - 1) r;  a_c = live (1 + (g - 1)(eta - 1) r rho);  w = m (the plane keeps the unclipped m)
+ *   FOLEY_GUIDANCE_ZERO_STAR  s = <u,u> > 0 ? <c,u> / <u,u> : 0;  a_c = live g;  a_w = live (1 - g) s;  w = u
+ *   both                      v = fma(a_c, c, rnd(a_w w)) in fp32
+ * g == 1 gives v == c exactly (iterations outside a guidance interval), live == 0 a zero velocity (an euler row then leaves x and
+ * the staged rows as they are).  APG with eta = 1, beta = 0, R = 0 is plain CFG to rounding, not bit for bit: v = c + (g - 1)(c - u)
+ * against the plain step's fma(g, c - u, u).  R is in the model's velocity units.
+ *   rows   [n_rows, 4] fp32 on the HOST; n_rows must equal plan.n_iter (an edit run passes the rows [i0, steps) with beta = 0 on
+ *          its first).  Copied to a context-owned buffer: new values of the same shape keep the captured graph.
+ *   mode 0 clears the state, as does foley_prepare.
+ * Two launches per iteration in front of the step, where the rescale launches sit (under the step cache: in the full body and in
+ * the skip body), deterministic: fixed merge order, no atomics.  The statistics are per clip, so a clip's result does not depend on
+ * what it is batched with; in a windowed run every window is a clip and its coefficients apply before the blend.  It combines with
+ * foley_set_edit, foley_set_windows, foley_set_multistep (the ring stores v as the step used it), foley_set_step_cache, a
+ * schedule, timed prompts and per-clip conditioning.  The captured iteration is keyed on the mode and the buffers.
+ * plan.ncfg != 2, a rescale state next to projection (in either call order; foley_set_guidance refuses rescale > 0 under projection
+ * too), n_rows != plan.n_iter, non-finite rows, R < 0, an unknown mode, more than 256 latent channels: FOLEY_ERR_INVALID; before
+ * foley_prepare: FOLEY_ERR_STATE. */
+#define FOLEY_GUIDANCE_APG 1
+#define FOLEY_GUIDANCE_ZERO_STAR 2
+int foley_set_projected_guidance(foley_ctx* ctx, int mode, const float* rows, int n_rows, void* stream);
+
 /* Step cache (additive within ABI 12; opt-in): reuse the blocks' residual on iterations whose model input barely moved - what
  * DiT samplers call TeaCache / first-block cache.  For one model call of loop iteration i (multi-stage solvers: every stage is an
  * iteration) let a0 be the audio stream after audio_embedder + add_sync, aN the stream after the last block and m the first
@@ -540,6 +569,25 @@ int foley_op_solver_step(const foley_step_desc* d, void* stream);
 int64_t foley_op_guidance_stats_work(int clips, int L);
 int foley_op_guidance_stats(const foley_guidance_desc* gd, const float* pred, int clips, int C, int L, int ncfg, float guidance,
                             const int32_t* step_ptr, float rescale, float* work, int64_t work_floats, void* stream);
+/* Projected guidance at op level (see foley_set_projected_guidance), every operand on the DEVICE: rows [n_iter, 4] {eta, beta, R,
+ * live} read at row *step_ptr, coef [clips, 2] {a_c, a_w}, plane [clips*L, C] fp32 (APG; NULL for CFG-Zero*), mode
+ * FOLEY_GUIDANCE_APG or FOLEY_GUIDANCE_ZERO_STAR.
+ * guidance_project: the two launches of one iteration - the inner products of pred [2*clips*La, C] (C <= 256), APG's plane update,
+ *   then proj->coef from them, g (gd->sched column 0 at row *step_ptr when gd and its table are given, else `guidance`) and the
+ *   row.  `work`: scratch of at least foley_op_guidance_project_work(clips, La) floats.  Bit-identical on repetition (APG with
+ *   beta != 0: from the same plane).
+ * solver_step_projected: foley_op_solver_step with v = fma(a_c, c, rnd(a_w w)) from proj->coef, w = proj->plane (APG) or u: every
+ *   form and the history ring as there; ncfg must be 2 and d->gd.clip_scale NULL.  proj NULL: foley_op_solver_step bit for bit. */
+typedef struct foley_projection_desc {
+  const float* rows;
+  float* coef;
+  float* plane;
+  int32_t mode;
+} foley_projection_desc;
+int64_t foley_op_guidance_project_work(int clips, int La);
+int foley_op_guidance_project(const foley_projection_desc* proj, const foley_guidance_desc* gd, const float* pred, int clips, int C,
+                              int La, float guidance, const int32_t* step_ptr, float* work, int64_t work_floats, void* stream);
+int foley_op_solver_step_projected(const foley_step_desc* d, const foley_projection_desc* proj, void* stream);
 /* The step cache's kernels (see foley_set_step_cache), all operands on the DEVICE, fp32, 16-byte aligned for the probe.
  * cache_probe: a0 [Bc*La, D] (D a multiple of 4 up to 2048) -> m = LayerNorm(a0; eps) * (1 + scale) + shift written over m_prev
  *   [Bc*La, D], rel[b] = sum|m - m_prev| / sum|m_prev| of batch row b (0 when the denominator is 0).

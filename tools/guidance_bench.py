@@ -1,6 +1,6 @@
 """Cost of the guidance controls: xxl (bf16), a synthetic 5 s video, 50-step Euler, bs=1 and bs=8, as the plain two-half run
-(CFG 4.5), the same with a guidance schedule (interval), with CFG rescale, and as a three-half run (separate video and text
-scales: 1.5x the rows).  Variants are interleaved per repetition; each figure is the median wall time of a full sampling call
+(CFG 4.5), the same with a guidance schedule (interval), with CFG rescale, with projected guidance (`apg`: momentum -0.5, eta 0;
+`zero_star`: CFG-Zero* with one zero-velocity iteration), and as a three-half run (separate video and text scales: 1.5x the rows).  Variants are interleaved per repetition; each figure is the median wall time of a full sampling call
 (noise upload, prepare, loop, DAC decode, synchronised).
 
     python tools/guidance_bench.py [--reps 3] [--steps 50] [--bs 1,8] [--only plain,rescale]
@@ -48,7 +48,10 @@ def main():
         sampler.denoise_process_with_generator(vis, txt, a.secs, models[(bs, name)], dac, 4.5, a.steps, bs, "euler",
                                                generator=gen.manual_seed(0), guidance=spec)
 
-    variants = {"plain": None, "schedule": Spec(interval=(0.2, 0.7)), "rescale": Spec(rescale=0.7), "three_halves": Spec(g_video=3.0)}
+    Proj = sampler.ProjectionSpec
+    variants = {"plain": None, "schedule": Spec(interval=(0.2, 0.7)), "rescale": Spec(rescale=0.7),
+                "apg": Spec(projection=Proj("apg", 0.0, -0.5)), "zero_star": Spec(projection=Proj("cfg_zero_star", zero_init=1)),
+                "three_halves": Spec(g_video=3.0)}
     runs = {"bs%d_%s" % (bs, k): (lambda bs=bs, k=k, sp=sp: call(bs, k, sp)) for bs in (int(b) for b in a.bs.split(",")) for k, sp in variants.items()}
     if a.only:
         runs = {k: f for k, f in runs.items() if any(o in k for o in a.only.split(","))}
