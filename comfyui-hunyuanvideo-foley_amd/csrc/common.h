@@ -77,6 +77,48 @@ template <> struct Cvt<f16_t> {
   static __device__ __forceinline__ float from(f16_t v) { return (float)v; }
 };
 
+// ---- store policy ---------------------------------------------------------------------------
+// 8- and 16-byte vector global stores with a compile-time cache policy.  A destination is a wave-uniform base pointer, the
+// extent in bytes the launch may write behind it (< 2 GiB) and the lane's byte offset:
+//   ST_DEFAULT  plain store: the line stays dirty in the XCD's L2 until the end-of-kernel write-back
+//   ST_WT       write-through (sc1): the bytes leave the L2 with the store, while the other workgroups of the launch still
+//               compute; the line is dropped from the L2, so the consumer - the NEXT launch, which could not rely on another
+//               XCD's L2 anyway - reads it from the fabric.  One buffer store through a resource over [base, base + bytes):
+//               offsets past the extent are dropped by the hardware
+//   ST_NT       non-temporal hint (the line is kept, marked for early eviction; NOT a write-through)
+// Builtins only: the compiler counts and schedules them like any other store.  A ST_WT launch must not read, in the same launch,
+// a line that another lane stores this way (L1 copies are not refreshed): every user keeps "one lane owns its 8 / 16 byte run".
+enum StorePolicy { ST_DEFAULT = 0, ST_WT = 1, ST_NT = 2 };
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+template <int POL> struct GStore {
+  static __device__ __forceinline__ void st16(void* base, unsigned bytes, unsigned off, const u32x4 v) {
+    if constexpr (POL == ST_WT) {
+      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+      __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)off, 0, 16);   // aux 16 = sc1
+    } else if constexpr (POL == ST_NT) {
+      __builtin_nontemporal_store(v, (u32x4*)((char*)base + off));
+    } else {
+      *(u32x4*)((char*)base + off) = v;
+    }
+  }
+  static __device__ __forceinline__ void st8(void* base, unsigned bytes, unsigned off, const u32x2 v) {
+    if constexpr (POL == ST_WT) {
+      const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+      __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, 16);
+    } else if constexpr (POL == ST_NT) {
+      __builtin_nontemporal_store(v, (u32x2*)((char*)base + off));
+    } else {
+      *(u32x2*)((char*)base + off) = v;
+    }
+  }
+};
+// Host: may a launch that writes `bytes` behind one base take ST_WT?  (31-bit buffer offsets)
+inline bool store_wt_fits(long bytes) { return bytes > 0 && bytes < 0x7fff0000L; }
+// TEST-ONLY (foley_debug_store_policy; not in include/foley_hip.h, not for production callers): 1 = every launch keeps the default
+// stores whatever its planner says, 0 = as planned.  One process-wide word read by the GEMM and LayerNorm launchers: it acts on
+// every stream and thread and is not synchronised - the bit-equality tests set it around single-threaded launches.
+extern int g_foley_store_default;
+
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
 // torch GELU(approximate="tanh")
 __device__ __forceinline__ float gelu_tanh_f(float x) {

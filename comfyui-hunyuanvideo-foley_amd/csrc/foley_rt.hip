@@ -2057,7 +2057,8 @@ extern "C" int foley_debug_gemm_pair(const foley_gemm_desc* d0, const foley_gemm
 // Test-only (tests/test_gemm_plan_cpu.py): the launcher's plan for one problem (d1 null) or a pair, without touching the device -
 // descriptors may carry fake (16-byte aligned) addresses.  out = {tile, K split, panel groups, k_rot}; krot_ok opts in to K-origin
 // rotation as run_forward does for single-clip forwards.
-extern "C" int foley_debug_gemm_plan(const foley_gemm_desc* d0, const foley_gemm_desc* d1, int krot_ok, int32_t out[4]) {
+// out[0..3] = tile, K split, panel groups, K-origin rotation; n_out > 4 adds out[4] = write-through output stores (GemmPlan::wt_out)
+static int debug_gemm_plan(const foley_gemm_desc* d0, const foley_gemm_desc* d1, int krot_ok, int32_t* out, int n_out) {
   if (!out) return FAIL(FOLEY_ERR_INVALID, "null output");
   GemmArgs g0, g1;
   if (int rc = d1 ? gemm_pair_args_of(d0, d1, g0, g1) : gemm_args_of(d0, g0)) return rc;
@@ -2070,8 +2071,20 @@ extern "C" int foley_debug_gemm_plan(const foley_gemm_desc* d0, const foley_gemm
   }
   if (p.err) return FAIL(FOLEY_ERR_INVALID, p.err);
   out[0] = p.tile; out[1] = p.ksplit; out[2] = p.n_groups; out[3] = p.k_rot;
+  if (n_out > 4) out[4] = p.wt_out;
   return 0;
 }
+extern "C" int foley_debug_gemm_plan(const foley_gemm_desc* d0, const foley_gemm_desc* d1, int krot_ok, int32_t out[4]) {
+  return debug_gemm_plan(d0, d1, krot_ok, out, 4);
+}
+// the same plan with the fields added since the four-word form was fixed
+extern "C" int foley_debug_gemm_plan_ex(const foley_gemm_desc* d0, const foley_gemm_desc* d1, int krot_ok, int32_t out[8]) {
+  if (out) for (int i = 4; i < 8; ++i) out[i] = 0;
+  return debug_gemm_plan(d0, d1, krot_ok, out, 8);
+}
+// tests: 1 = every launch keeps the default stores whatever it planned (bit-equality twins of the write-through launches); 0 = as planned
+int g_foley_store_default = 0;
+extern "C" void foley_debug_store_policy(int keep_default) { g_foley_store_default = keep_default ? 1 : 0; }
 
 extern "C" int foley_op_attention_hd(const void* q, const void* k, const void* v, int in_dtype, int vt_pitch, int Bq,
                                      int H, int Sq, int Skv, int kv_bdiv, void* outA, void* outB, int split,

@@ -254,6 +254,29 @@ __device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs& g, f32x16 (&ac
 
   if constexpr (EPI == EPI_GATE_RES) {
     if (g.ksplit > 1) {   // deferred split-K: raw partial product of this K range
+      if (g.wt_out) {
+        // One-round grids (GemmPlan::wt_out): the slab leaves the L2 with the store, while the other K ranges still compute,
+        // instead of in the end-of-kernel write-back.  Same values, same lane -> address map as the plain loops below; every
+        // lane owns its 8 / 16 byte run and nothing in this launch reads a slab.
+        unsigned char* const sb = (unsigned char*)g.partials + (long)ks * g.partial_stride * (g.partial_half ? 2 : 4);
+        const unsigned slab_bytes = (unsigned)g.M * (unsigned)g.N * (g.partial_half ? 2u : 4u);   // extent of one slab (< 2 GiB: plan_gemm)
+#pragma unroll
+        for (int p = 0; p < PASSES; ++p) {
+          const int row = row0 + p * RP;
+          if (!(col_ok && row < g.M)) continue;
+          const f32x4 a = *(const f32x4*)(tile + (p * RP + tr) * BN + ca);
+          const unsigned eo = (unsigned)row * (unsigned)g.N + (unsigned)gcol;
+          if (g.partial_half) {
+            if constexpr (sizeof(T) == 2) {
+              const u32x2 w = {pack_h2<T>(a[0], a[1]), pack_h2<T>(a[2], a[3])};
+              GStore<ST_WT>::st8(sb, slab_bytes, eo * 2u, w);
+            }
+          } else {
+            GStore<ST_WT>::st16(sb, slab_bytes, eo * 4u, __builtin_bit_cast(u32x4, a));
+          }
+        }
+        return;
+      }
       if (g.partial_half) {   // slabs in the operand type: 8-byte stores of four rounded partials
         if constexpr (sizeof(T) == 2) {
           T* ps = (T*)g.partials + ks * g.partial_stride + gcol;

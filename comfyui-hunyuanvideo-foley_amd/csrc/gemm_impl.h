@@ -526,6 +526,7 @@ int launch_typed(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int tile_
     GemmArgs r = q;
     if (r.ldw <= 0) r.ldw = r.K;
     r.ksplit = plan.ksplit, r.n_groups = plan.n_groups, r.k_rot = plan.k_rot, r.vec_out = vec_out;
+    r.wt_out = g_foley_store_default ? 0 : plan.wt_out;
     if (gemm_fits_buffer_range<T>(r)) {   // the direct-to-LDS loops address their operands through 32-bit buffer offsets
       r.a_bytes = (unsigned)gemm_a_bytes<T>(r);
       r.w_bytes = (unsigned)gemm_w_bytes<T>(r);

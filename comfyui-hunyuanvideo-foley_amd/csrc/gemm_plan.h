@@ -64,8 +64,15 @@ struct GemmPlan {
   int tile = 0, ksplit = 1, n_groups = 0, k_rot = 0;
   int vec_out[2] = {0, 0};   // per problem: the LDS-transposed vector epilogue
   bool attn_fused = false;   // EPI_QKV_SPLIT: the cross attention runs in the epilogue (EPI_QKV_ATTN)
+  int wt_out = 0;            // write-through output stores (GemmArgs::wt_out): one-round grids of 16-bit operands only
   const char* err = nullptr;
 };
+
+// Workgroups of a launch on tile `ti`: both problems, every K range
+inline long plan_workgroups(const TileInfo& ti, const GemmArgs& g, const GemmArgs* g1, int epi, int ksplit) {
+  auto tiles = [&](const GemmArgs& q) { return (long)((q.M + ti.bm - 1) / ti.bm) * ((q.N + ti.bn - 1) / ti.bn); };
+  return (tiles(g) + (g1 ? tiles(*g1) : 0)) * (epi == EPI_GATE_RES ? ksplit : 1);
+}
 
 template <typename T>
 const char* check_args(const GemmArgs& g) {
@@ -397,6 +404,19 @@ GemmPlan plan_gemm(const GemmArgs& g_in, const GemmArgs* g1_in, int epi, int til
   }
   plan.tile = tile;
   plan.ksplit = g.ksplit;
+  // Write-through output stores (common.h GStore): a launch of ONE round of workgroups (<= 256: the single-clip regime) ends in
+  // the write-back of everything its epilogues left dirty in the L2s, with all 256 CUs waiting.  Stored write-through, those
+  // bytes leave while the other workgroups are still in their K loops.  Larger problems - more than one round, or the
+  // planner's large-M side (M >= 1536: the 256x256 K-range route fits 20 s / 30 s clips into one round too, with outputs
+  // beyond the L2s, matrix-pipe bound) - and the fp32 parity mode keep the plain stores.  Served: the deferred split-K slabs
+  // of the vector epilogue, which the next launch reads once (the other epilogues' outputs keep the plain stores: DESIGN.md
+  // section 4, "Round 8").
+  if (sizeof(T) == 2 && g.M + (g1 ? g1s.M : 0) < 1536 && plan_workgroups(tile_info(tile), g, g1, epi, g.ksplit) <= 256) {
+    auto slab_ok = [&](const GemmArgs& q, int vec) {
+      return vec && q.partials && store_wt_fits((long)q.M * q.N * (g.partial_half ? 2 : 4));   // (the pair shares g's slab type)
+    };
+    if (epi == EPI_GATE_RES && g.ksplit > 1 && slab_ok(g, plan.vec_out[0]) && (!g1 || slab_ok(g1s, plan.vec_out[1]))) plan.wt_out = 1;
+  }
   return plan;
 }
 

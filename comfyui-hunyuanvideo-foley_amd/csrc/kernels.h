@@ -86,6 +86,9 @@ struct GemmArgs {
   float* partials;    // slab base (fp32 view; with partial_half the slabs hold the 16-bit OPERAND type, 2 bytes per element)
   int partial_half;   // 1: slabs are stored in the operand type T (bf16 / fp16) - half the slab bytes written here and read by
                       // the LayerNorm; the sum of k rounded partials carries about the error of ONE rounding of the total
+  int wt_out;         // set by the launcher (GemmPlan::wt_out): the slabs are stored write-through (common.h GStore<ST_WT>).  It sits in
+                      // what was padding next to partial_half: the argument block keeps its size and offsets, and the epilogue
+                      // reads both words in one scalar load
   long partial_stride;
   int partial_cap;
   int n_groups;       // set by the launcher, large grids: > 0 = tile order [column-panel group][M tile][panel inside the group] with this many

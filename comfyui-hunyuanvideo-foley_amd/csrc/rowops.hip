@@ -16,9 +16,13 @@ namespace {
 // ------------------------------------------------------------------ LayerNorm (+ AdaLN modulate)
 // reference: nn.LayerNorm(elementwise_affine=False) + modulate() (modulate_layers.py:19-30) and
 // SingleStreamBlock's norm*(1+scale)+shift (hifi_foley.py:368,387)
+// store_wt: the same four values write-through, at byte offset `off` behind a wave-uniform base (common.h GStore)
 template <typename OutT> struct Pack4;
 template <> struct Pack4<float> {
   static __device__ __forceinline__ void store(float* p, const f32x4 v) { *(f32x4*)p = v; }
+  static __device__ __forceinline__ void store_wt(void* base, unsigned bytes, unsigned off, const f32x4 v) {
+    GStore<ST_WT>::st16(base, bytes, off, __builtin_bit_cast(u32x4, v));
+  }
 };
 template <> struct Pack4<bf16_t> {
   static __device__ __forceinline__ void store(bf16_t* p, const f32x4 v) {
@@ -26,6 +30,10 @@ template <> struct Pack4<bf16_t> {
     w.x = pack_bf16x2(v[0], v[1]);
     w.y = pack_bf16x2(v[2], v[3]);
     *(uint2*)p = w;
+  }
+  static __device__ __forceinline__ void store_wt(void* base, unsigned bytes, unsigned off, const f32x4 v) {
+    const u32x2 w = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    GStore<ST_WT>::st8(base, bytes, off, w);
   }
 };
 
@@ -35,6 +43,10 @@ template <> struct Pack4<f16_t> {
     w.x = pack_f16x2(v[0], v[1]);
     w.y = pack_f16x2(v[2], v[3]);
     *(uint2*)p = w;
+  }
+  static __device__ __forceinline__ void store_wt(void* base, unsigned bytes, unsigned off, const f32x4 v) {
+    const u32x2 w = {pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3])};
+    GStore<ST_WT>::st8(base, bytes, off, w);
   }
 };
 
@@ -59,6 +71,9 @@ struct LnPair {
 };
 static long long* g_ln_dbg = nullptr;
 extern "C" void foley_debug_ln_timeline(void* p) { g_ln_dbg = (long long*)p; }
+// tests: did this thread's last LayerNorm launch take the write-through kernel (launch_ln_mod_pair)?
+static thread_local int g_ln_last_wt = 0;
+extern "C" int foley_debug_ln_last_wt() { return g_ln_last_wt; }
 
 // The resolved launch (common.h RowMap): what the kernels read of one row set, packed so that the selected set arrives in two wide
 // scalar loads at entry - 120 bytes instead of LnArgs' 288 with their fields fetched where they are first used.
@@ -336,9 +351,13 @@ __global__ __launch_bounds__(128) void ln_mod_each_kernel(const LnPair pr, int D
 // Statistics and output of the multi-wave kernels, from the row part v each wave holds (after any pending update): each wave
 // reduces its own part to (sum, centred sum of squares) in registers; the parts meet once in LDS and are combined exactly (Chan
 // et al.): M2 = sum_w [M2_w + n_w (mean_w - mean)^2] - one barrier instead of two.  STAMP: the timeline probe's stamps 2 and 3.
-template <typename OutT, int MAXV, int WPR, bool STAMP>
+// WT: the output leaves write-through - wt_base is the (wave-uniform) base of the row set's output, wt_bytes its extent and wt_row
+// the byte offset of this row in it; the values and the lane -> address map are those of the plain stores.  The policy is a
+// compile-time parameter: the WT = false instances are the code they were.
+template <typename OutT, int MAXV, int WPR, bool STAMP, bool WT = false>
 __device__ __forceinline__ void ln_wide_finish(const f32x4 (&v)[MAXV], const f32x4 (&hv)[MAXV], const f32x4 (&cv)[MAXV], OutT* orow, int c0, int rb,
-                                               int part, int lane, bool live, int D, float eps, long long* stamps) {
+                                               int part, int lane, bool live, int D, float eps, long long* stamps, void* wt_base = nullptr,
+                                               unsigned wt_bytes = 0, unsigned wt_row = 0) {
   __shared__ float red[FOLEY_LN_RPB][2][WPR];   // [row of the block][statistic][wave of the row]
   float s = 0.f;
 #pragma unroll
@@ -378,15 +397,18 @@ __device__ __forceinline__ void ln_wide_finish(const f32x4 (&v)[MAXV], const f32
     f32x4 y;
 #pragma unroll
     for (int u = 0; u < 4; ++u) y[u] = (v[i][u] - mean) * rstd * (1.0f + cv[i][u]) + hv[i][u];
-    Pack4<OutT>::store(orow + (c0 + i * 64) * 4, y);
+    if constexpr (WT) Pack4<OutT>::store_wt(wt_base, wt_bytes, wt_row + (unsigned)((c0 + i * 64) * 4 * sizeof(OutT)), y);
+    else Pack4<OutT>::store(orow + (c0 + i * 64) * 4, y);
   }
   if (STAMP && stamps) stamps[3] = wall_clock64();
 }
 
 // Resolved multi-wave body; memory work in the order of ln_mod_kernel above: counter, then x / bias / first slab batch, then the
 // row offset, then the counter's wait and the three operand rows.  DBG: the instantiations tools/ln_timeline.py launches - the
-// product ones carry no stamp, branch or store of the probe.
-template <typename OutT, int MAXV, bool PEND, int WPR, int SEL, bool SLAB16, bool DBG>
+// product ones carry no stamp, branch or store of the probe.  WT: the launcher's store policy for small grids (ln_mod_wide_wt_kernel):
+// the x write-back and the output rows are stored write-through (common.h GStore<ST_WT>) - they leave the L2 while other rows are
+// still being read.  A template parameter, so that the launches that do not take it run the code they ran before.
+template <typename OutT, int MAXV, bool PEND, int WPR, int SEL, bool SLAB16, bool DBG, bool WT = false>
 __device__ __forceinline__ void ln_mod_wide_body(const LnResPair& pr, int D, float eps) {
   using ST = typename std::conditional<SLAB16, OutT, float>::type;   // slab element type
   constexpr int RPB = FOLEY_LN_RPB, SB = 6;
@@ -435,11 +457,19 @@ __device__ __forceinline__ void ln_mod_wide_body(const LnResPair& pr, int D, flo
         if (s0 > 0) slab_batch_load<ST, MAXV, SB>(t, A.partials, A.pstride, A.k, s0, (long)row * D, col);
         slab_batch_add<ST, MAXV, SB>(acc, t, A.k, s0);
       }
+      // The residual update reads and writes x in place; the read stays on the default path.  Each 16-byte run of a row is
+      // WRITTEN by one lane only, and among the live waves it is read by that lane only: the lanes that share a 128-byte line
+      // belong to one wave, whose loads of the line are all behind it when its first store goes out.  One exception, as with
+      // the plain stores: with an odd row count the dead wave pair of the last workgroup shadows row M - 1 and loads its x
+      // while the live pair stores it.  Harmless: dead waves store nothing, and their statistics go to their own red[rb].
 #pragma unroll
       for (int i = 0; i < MAXV; ++i) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[i][e] += gt[i][e] * acc[i][e];
-        if (live) xr[col(i)] = v[i];
+        if (live) {
+          if constexpr (WT) GStore<ST_WT>::st16(A.x, (unsigned)M * (unsigned)D * 4u, (unsigned)row * (unsigned)D * 4u + (unsigned)col(i) * 16u, __builtin_bit_cast(u32x4, v[i]));
+          else xr[col(i)] = v[i];
+        }
       }
     }
   }
@@ -447,13 +477,22 @@ __device__ __forceinline__ void ln_mod_wide_body(const LnResPair& pr, int D, flo
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (stamps) stamps[1] = wall_clock64();
   }
-  ln_wide_finish<OutT, MAXV, WPR, DBG>(v, hv, cv, (OutT*)A.out + (long)row * D, c0, rb, part, lane, live, D, eps, stamps);
+  if constexpr (WT)
+    ln_wide_finish<OutT, MAXV, WPR, DBG, true>(v, hv, cv, (OutT*)A.out + (long)row * D, c0, rb, part, lane, live, D, eps, stamps, A.out,
+                                               (unsigned)M * (unsigned)D * (unsigned)sizeof(OutT), (unsigned)row * (unsigned)D * (unsigned)sizeof(OutT));
+  else ln_wide_finish<OutT, MAXV, WPR, DBG>(v, hv, cv, (OutT*)A.out + (long)row * D, c0, rb, part, lane, live, D, eps, stamps);
 }
 
 template <typename OutT, int MAXV, bool PEND, int WPR, bool SLAB16 = false, bool DBG = false>
 __global__ __launch_bounds__(64 * FOLEY_LN_RPB * WPR) void ln_mod_wide_kernel(const LnResPair pr, int D, float eps) {
   if ((int)blockIdx.x >= pr.blocks0) ln_mod_wide_body<OutT, MAXV, PEND, WPR, 1, SLAB16, DBG>(pr, D, eps);   // workgroup-uniform
   else ln_mod_wide_body<OutT, MAXV, PEND, WPR, 0, SLAB16, DBG>(pr, D, eps);
+}
+// the same kernel with write-through stores (small grids: launch_ln_mod_pair)
+template <typename OutT, int MAXV, bool PEND, int WPR, bool SLAB16 = false>
+__global__ __launch_bounds__(64 * FOLEY_LN_RPB * WPR) void ln_mod_wide_wt_kernel(const LnResPair pr, int D, float eps) {
+  if ((int)blockIdx.x >= pr.blocks0) ln_mod_wide_body<OutT, MAXV, PEND, WPR, 1, SLAB16, false, true>(pr, D, eps);   // workgroup-uniform
+  else ln_mod_wide_body<OutT, MAXV, PEND, WPR, 0, SLAB16, false, true>(pr, D, eps);
 }
 
 // The per-operand path of the multi-wave kernel (see ln_mod_each_kernel)
@@ -1424,6 +1463,7 @@ int launch_ln_mod_pair(const LnArgs& a0, const LnArgs& a1, int D, float eps, int
         (a->pend.k < 1 || a->pend.stride % 4 || ((uintptr_t)a->pend.partials & 15) || ((uintptr_t)a->pend.bias & 15) ||
          !a->pend.gate.p || ((uintptr_t)a->pend.gate.p & 15) || a->pend.gate.ld % 4 || a->pend.gate.step_stride % 4))
       return foley_set_err("ln_mod: bad pending split-K descriptor", __FILE__, __LINE__);
+  g_ln_last_wt = 0;
   LnPair pr;
   pr.a[0] = a0;
   pr.a[1] = a1;
@@ -1496,9 +1536,14 @@ int launch_ln_mod_pair(const LnArgs& a0, const LnArgs& a1, int D, float eps, int
     LnPair prw = pr;   // the two-wave kernel takes FOLEY_LN_RPB rows per workgroup
     prw.blocks0 = rp.blocks0 = (a0.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB;
     const dim3 gridw(prw.blocks0 + (a1.M + FOLEY_LN_RPB - 1) / FOLEY_LN_RPB), blk(64 * FOLEY_LN_RPB * 2);
-#define FOLEY_LNW(V)                                                             \
+    // Small grids (the single-clip regime: every workgroup resident at once, at most four two-wave workgroups per CU) store x and
+    // the output rows write-through; larger ones, whose rows exceed the L2s anyway, keep the plain stores.
+    const bool wt = resolved && !g_foley_store_default && gridw.x <= 4 * 256 && store_wt_fits((long)(a0.M > a1.M ? a0.M : a1.M) * D * 4);
+    g_ln_last_wt = wt ? 1 : 0;
+#define FOLEY_LNW(V)                                                          \
     {                                                                            \
-      if (resolved) FOLEY_LN_ANY(ln_mod_wide_kernel, rp, gridw, blk, V, 2)       \
+      if (wt) FOLEY_LN_ANY(ln_mod_wide_wt_kernel, rp, gridw, blk, V, 2)          \
+      else if (resolved) FOLEY_LN_ANY(ln_mod_wide_kernel, rp, gridw, blk, V, 2)  \
       else FOLEY_LN_ANY(ln_mod_wide_each_kernel, prw, gridw, blk, V, 2)          \
     }
     const int v2 = D / (4 * 64 * 2);
