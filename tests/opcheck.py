@@ -401,6 +401,66 @@ def both16(t):
     return t
 
 
+ATTN_SCORE_CLASSES = ("rise", "first", "last_half", "hole")
+
+
+@functools.lru_cache(maxsize=4)
+def attn_edge_operands(ops, B, H, Sq, Skv, hd, div, seed, f32=False):
+    """q [B, H, Sq, hd], k / v [B // div, H, Skv, hd] of an attention edge case (tests/test_attention_edges_gpu.py and the emulation
+    checks of tests/test_opcheck_cpu.py share them): fp32 tensors, exact in bf16 AND fp16 unless f32 - one fp64 reference serves
+    both 16-bit types.  Every (batch, head) entry of k and v is drawn on its own, so shared entries (div > 1) are distinct.
+    ops = 'rand': i.i.d. normal.
+    ops = 'onoff': every probability is 1 or ~ e^-12 before the division by the row sum, so the rounding of P to 16 bits costs
+    nothing and the case is fair at ANY key count (u_p is HALF the unit round-off, an allowance that rests on a row averaging over
+    many rounded probabilities: with two i.i.d. keys the once-rounded arithmetic itself reaches 1.3 of the bound, see
+    tests/test_opcheck_cpu.py::test_attention_edge_inputs_are_fair).  Even queries carry q[..., 0] = 8, odd ones q[..., 1] = 8;
+    k[..., 0] and k[..., 1] are 0 (the key is ON for those queries: score exactly 0) or -12 sqrt(hd) / 8 (OFF: score -12), drawn per
+    key; q is otherwise non-zero in dimensions [2, hd / 2) only and k in [hd / 2, hd): their products vanish unless a kernel pairs
+    the wrong dimensions.  A query with no ON key sees equal scores, again exact.
+    Else a score class: dimension 0 carries a profile t[key] (q[..., 0] = 8 and
+    k[..., 0] = t sqrt(hd) / 8, so the score is t[key] plus noise), the other dimensions i.i.d. normal / 2 (noise of ~ 0.25 in the
+    score; with |t| <= 32 the bound's d_s stays below 3e-4):
+        rise       t steps up by 1.5 from one 32-key block to the next, centred on 0 (|t| <= 13 at 18 blocks): the running maximum
+                   rises in every key tile of every kernel (32- and 64-key tiles, the four key runs, each key half of the pair kernel),
+                   the ragged last tile included, and a block weighs e^-1.5 of the next, so a row still averages over ~ 40 keys.
+                   Every third query carries q[..., 0] = -8: its maximum is in the FIRST block, so the lanes of one wave disagree
+                   about the rescale.
+        first      t = 10 in the first 32-key block, -5 behind it: no later tile raises the maximum.
+        last_half  t = 0 but t[Skv - 1] = ln(Skv - 1): the last key carries about half of each row's weight.
+        hole       t = 31, but t = -32 in one tile in the middle (64 keys from 64 (n64 // 2); 32 keys from 32 (n32 // 2) where fewer
+                   than three 64-key tiles exist): 63 below the maximum, its probabilities are 0 in fp16 and ~ 1e-27 in bf16."""
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    q, k, v = rnd(B, H, Sq, hd), rnd(B // div, H, Skv, hd), rnd(B // div, H, Skv, hd)
+    if ops == "onoff":
+        q, k = q * 0.5, k * 0.5
+        q[..., :2], q[..., hd // 2:], k[..., :hd // 2] = 0.0, 0.0, 0.0
+        q[:, :, 0::2, 0] = 8.0
+        q[:, :, 1::2, 1] = 8.0
+        k[..., :2] = torch.where(torch.rand(B // div, H, Skv, 2, generator=g) < 0.5, 0.0, -12.0 * math.sqrt(hd) / 8.0)
+    elif ops != "rand":
+        assert ops in ATTN_SCORE_CLASSES, ops
+        key, n32, n64 = torch.arange(Skv), (Skv + 31) // 32, (Skv + 63) // 64
+        if ops == "rise":
+            t = 1.5 * ((key // 32).double() - (n32 - 1) / 2)
+        elif ops == "first":
+            t = torch.where(key < 32, 10.0, -5.0).double()
+        elif ops == "last_half":
+            t = torch.zeros(Skv, dtype=torch.float64)
+            t[-1] = math.log(max(Skv - 1, 1))
+        else:
+            lo, w = (64 * (n64 // 2), 64) if n64 >= 3 else (32 * (n32 // 2), 32)
+            t = torch.where((key >= lo) & (key < lo + w), -32.0, 31.0).double()
+        q, k = q * 0.5, k * 0.5
+        q[..., 0] = 8.0
+        if ops == "rise":
+            q[:, :, 2::3, 0] = -8.0
+        k[..., 0] = (t * math.sqrt(hd) / 8.0).float()
+    if not f32:
+        q, k, v = both16(q), both16(k), both16(v)
+    return q, k, v
+
+
 def head_q64(y, gain, cos, sin, eps):
     """RoPE(RMSNorm(y)) in fp64: y [M, H, 128], gain [128], cos / sin [M, 64] (the table rows of each row's position)."""
     y = y.double()

@@ -10,6 +10,7 @@ Shapes: 500 x 1536 x 1536 for bf16 and fp32 operands.  fp16 operands use the bs 
 gate (8e-4) already sees a 64-wide K slice lost on a 1 x 16 strip (0.2 * 4 / 876 = 9e-4), so "missed by the old gate" can only be
 stated for fp16 where the grid is large - which is where the 256x256 tiles and the panel-group order run.
 """
+import functools
 import math
 import re
 
@@ -18,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 import opcheck as oc
+import test_attention_edges_gpu as ae
 from conftest import rel_err
 
 F32_TOL, BF16_TOL, F16_TOL = 2e-6, 6e-3, 8e-4                         # test_ops_gpu.py: the per-dtype GEMM gates
@@ -296,30 +298,68 @@ def test_layernorm_pending_slabs_inside():
 
 
 # ----------------------------------------------------------------------------- attention
-def _attn_kernel(q, k, v, dt, skip_last_tile_of=None):
-    """Tiled online softmax over 32-key tiles in fp32, P rounded to the operand type before P V, the row sum from the unrounded
-    P (attention.hip).  skip_last_tile_of = (b, h, row): that query never sees the last key tile."""
+def _attn_kernel(q, k, v, dt, skip_last_tile_of=None, kt=32, part=None, out_dt=None, psplit=False, lose_second_half_of=None, drop_wave=None):
+    """Tiled online softmax in fp32 over key tiles of `kt` keys (32; 64: attn_bf16_long_kernel, ONE maximum per 64 keys), P rounded
+    ONCE to the operand type before P V, the row sum from the unrounded P (attention.hip); the store in out_dt (default dt).
+    part: the keys are partitioned, every part walks its tiles on its own and the parts' (m, l, O) are merged at the end, in the
+    kernels' own order -
+        'runs4'   four contiguous runs of 32-key tiles, run w = tiles [nt w / 4, nt (w + 1) / 4) in integers (attn_bf16_kernel,
+                  attn_lds_kernel; a run may be empty: m = -inf, l = 0): m* = max m, w_x = exp(m_x - m*), L = sum w_x l_x,
+                  O = (sum_x w_x O_x) (1 / L), x = 0 .. 3
+        'halves'  keys [64 t, 64 t + 32) of every 64-key tile / keys [64 t + 32, 64 t + 64) (attn_bf16_pair_kernel; the second
+                  half of the last tile may hold no key): m = max(m_a, m_b), l = l_a f_a + l_b f_b, O = O_a f_a + O_b f_b.
+    psplit: P travels as its rounding plus the rounded residual (attn_bf16_wide_kernel<64> in bf16).
+    Planted defects: skip_last_tile_of = (b, h, row): that query never sees the last key tile; lose_second_half_of = (b, h, row):
+    ('halves') it never sees the second key half of the last 64-key tile; drop_wave = (w, (b, h, row)): ('runs4') the merge of
+    that query leaves out run w."""
     B, H, Sq, hd = q.shape
     Skv = k.shape[2]
     qf, kf, vf = q.float(), k.float(), v.float()
-    m = torch.full((B, H, Sq, 1), float("-inf"))
-    l = torch.zeros(B, H, Sq, 1)
-    o = torch.zeros(B, H, Sq, hd)
-    tiles = list(range(0, Skv, 32))
-    for kt in tiles:
-        s = qf @ kf[:, :, kt:kt + 32].transpose(2, 3) / math.sqrt(hd)
-        m_new = torch.maximum(m, s.amax(-1, keepdim=True))
-        p = torch.exp(s - m_new)
-        if skip_last_tile_of is not None and kt == tiles[-1]:
-            b, h, r = skip_last_tile_of
-            p[b, h, r] = 0.0
-            m_new[b, h, r] = m[b, h, r]
-        alpha = torch.exp(m - m_new)
-        l = l * alpha + p.sum(-1, keepdim=True)
-        pr = p.to(dt).float() if dt != torch.float32 else p
-        o = o * alpha + pr @ vf[:, :, kt:kt + 32]
-        m = m_new
-    return (o / l).transpose(1, 2).reshape(B, Sq, H * hd).to(dt)
+
+    def walk(tiles, width, last_defect=None):
+        m = torch.full((B, H, Sq, 1), float("-inf"))
+        l = torch.zeros(B, H, Sq, 1)
+        o = torch.zeros(B, H, Sq, hd)
+        for k0 in tiles:
+            s = qf @ kf[:, :, k0:k0 + width].transpose(2, 3) / math.sqrt(hd)
+            m_new = torch.maximum(m, s.amax(-1, keepdim=True))
+            p = torch.exp(s - m_new)
+            if last_defect is not None and k0 == tiles[-1]:
+                b, h, r = last_defect
+                p[b, h, r] = 0.0
+                m_new[b, h, r] = m[b, h, r]
+            alpha = torch.where(m_new == m, torch.ones_like(m), torch.exp(m - m_new))      # the rescale is skipped where no maximum moved
+            l = l * alpha + p.sum(-1, keepdim=True)
+            pr = p.to(dt).float() if dt != torch.float32 else p
+            o = o * alpha + pr @ vf[:, :, k0:k0 + width]
+            if psplit:
+                o = o + (p - pr).to(dt).float() @ vf[:, :, k0:k0 + width]
+            m = m_new
+        return m, l, o
+
+    if part is None:
+        m, l, o = walk(list(range(0, Skv, kt)), kt, skip_last_tile_of)
+        res = o * (1.0 / l)
+    elif part == "runs4":
+        nt = (Skv + 31) // 32
+        runs = [walk([32 * t for t in range(nt * w // 4, nt * (w + 1) // 4)], 32) for w in range(4)]
+        mstar = functools.reduce(torch.maximum, [r[0] for r in runs])
+        wt = [torch.exp(r[0] - mstar) for r in runs]
+        if drop_wave is not None:
+            w, (b, h, r) = drop_wave
+            wt[w][b, h, r] = 0.0
+        L, acc = torch.zeros(B, H, Sq, 1), torch.zeros(B, H, Sq, hd)
+        for x in range(4):
+            L = L + wt[x] * runs[x][1]
+            acc = acc + wt[x] * runs[x][2]
+        res = acc * (1.0 / L)
+    else:
+        assert part == "halves"
+        (ma, la, oa), (mb, lb, ob) = (walk(list(range(32 * half, Skv, 64)), 32, lose_second_half_of if half else None) for half in (0, 1))
+        m = torch.maximum(ma, mb)
+        fa, fb = torch.exp(ma - m), torch.exp(mb - m)
+        res = (oa * fa + ob * fb) * (1.0 / (la * fa + lb * fb))
+    return res.transpose(1, 2).reshape(B, Sq, H * hd).to(out_dt or dt)
 
 
 @pytest.mark.parametrize("dt", DT, ids=IDS)
@@ -332,6 +372,68 @@ def test_attention_tiled_inside_and_missing_key_tile_caught(dt):
     assert oc.assert_elementwise(_attn_kernel(q, k, v, dt), ref, bound, "tiled attention") <= 1.0
     bad = _attn_kernel(q, k, v, dt, skip_last_tile_of=(1, 2, 289))
     _missed_and_caught(dt, bad, ref, bound, "last key tile missing", gate=ATTN_TOL[dt], box=(290 + 289, 290 + 289, 2 * hd, 3 * hd - 1))
+
+
+def _edge_emulation(form, kind):
+    """The arithmetic of a 16-bit form of tests/test_attention_edges_gpu.py FORMS as _attn_kernel options."""
+    if form == "attn_bf16_kernel" or form.startswith("attn_lds_kernel"):
+        return dict(part="runs4")
+    if "pair" in form:
+        return dict(part="halves")
+    if "long" in form:
+        return dict(kt=64)
+    return dict(psplit=form == "attn_bf16_wide_kernel<64>" and kind == "bf16")
+
+
+def _edge_ratio(c):
+    """err / bound of the form's emulation on the operands of edge case c (long / pair forms: the first clip's heads)."""
+    dt, odt = ae.DTS[c["kind"]], ae.DTS[c["out"]]
+    q, k, v = ae.operands(c)
+    if c["form"] in ae.LONG:
+        q, k, v = q[:1], k[:1], v[:1]
+    ref, bound = oc.attention_ref_and_bound(q, k, v, odt, p_dtype=dt)
+    got = _attn_kernel(q.to(dt), k.to(dt), v.to(dt), dt, out_dt=odt, **_edge_emulation(c["form"], c["kind"]))
+    return float(((got.double() - ref).abs() / bound.total(ref, got.double())).max())
+
+
+@pytest.mark.parametrize("form", [f for f, v in ae.FORMS.items() if v[1] != ["f32"]], ids=ae._slug)
+def test_attention_edge_inputs_are_fair(form):
+    """The condition under which the GPU cases may assert 1.0: the form's own arithmetic - fp32, its key tiles and partition, P
+    rounded once - stays within the bound on the very operands of the scores cases, the fp32-output cases and the cases of 2 .. 96
+    keys, in bf16 and fp16.  (A few keys average little, and u_p is half the unit round-off: see
+    test_grouped_attention_reference_and_leaking_query.)"""
+    cases = ae.sweep_cases("scores", form) + ae.sweep_cases("out", form) + [c for c in ae.sweep_cases("skv", form) if 2 <= c["Skv"] <= 96]
+    worst = {}
+    for c in cases:
+        r = _edge_ratio(c)
+        worst[(c["name"], c["kind"])] = r
+        print(f"{form} {c['name']} {c['kind']} -> {c['out']}: emulation err / bound {r:.3f}")
+    over = {k: round(r, 3) for k, r in worst.items() if not r <= 1.0}
+    assert not over, over
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_attention_lost_second_key_half_missed_by_the_norm_gate_and_caught(dt):
+    """attn_bf16_pair_kernel: 548 keys, four of them in the second half of the last 64-key tile; one query of 2 x 12 x 400 loses them
+    (0.7 % of its weights): 9e-4 in the norm, one row of one head outside the bound."""
+    B, H, Sq, Skv, hd = 2, 12, 400, 548, 128
+    q, k, v = (_rand((B, H, S, hd), 60 + i).to(dt) for i, S in enumerate((Sq, Skv, Skv)))
+    ref, bound = oc.attention_ref_and_bound(q, k, v, dt, p_dtype=dt)
+    assert oc.assert_elementwise(_attn_kernel(q, k, v, dt, part="halves"), ref, bound, "key halves merged") <= 1.0
+    bad = _attn_kernel(q, k, v, dt, part="halves", lose_second_half_of=(1, 5, 399))
+    _missed_and_caught(dt, bad, ref, bound, "second key half of the last tile lost", gate=ATTN_TOL[dt], box=(400 + 399, 400 + 399, 5 * hd, 6 * hd - 1))
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_attention_dropped_wave_in_the_merge_missed_by_the_norm_gate_and_caught(dt):
+    """attn_bf16_kernel / attn_lds_kernel: 98 keys = four key tiles, one per wave, the last with 2 keys; the merge of one query of
+    4 x 12 x 580 leaves out the last wave's state (2 % of its weights): ~ 1e-3 in the norm, one row of one head outside the bound."""
+    B, H, Sq, Skv, hd = 4, 12, 580, 98, 128
+    q, k, v = (_rand((B, H, S, hd), 70 + i).to(dt) for i, S in enumerate((Sq, Skv, Skv)))
+    ref, bound = oc.attention_ref_and_bound(q, k, v, dt, p_dtype=dt)
+    assert oc.assert_elementwise(_attn_kernel(q, k, v, dt, part="runs4"), ref, bound, "four key runs merged") <= 1.0
+    bad = _attn_kernel(q, k, v, dt, part="runs4", drop_wave=(3, (2, 7, 311)))
+    _missed_and_caught(dt, bad, ref, bound, "one wave's state dropped in the merge", gate=ATTN_TOL[dt], box=(2 * 580 + 311, 2 * 580 + 311, 7 * hd, 8 * hd - 1))
 
 
 # ----------------------------------------------------------------------------- cross attention fused into the q projection

@@ -9,7 +9,7 @@ rows) get guard rows / guard slabs only.
 Coverage is asserted: test_every_tile_has_a_case asks the library which tile ids exist, the automatic-tile cases assert the
 (tile, K split, panel groups) of tests/test_gemm_plan_cpu.py through foley_debug_gemm_plan on the descriptor they launch.
 tests/test_gemm_edges_gpu.py takes run_gemm_case to every tile's M, N, K and segment edges and to the mapped operands (virtual
-rows, strided conv).
+rows, strided conv); tests/test_attention_edges_gpu.py takes every attention form (_attn_form_of) to its query, key and split edges.
 """
 import ctypes as C
 import functools
@@ -601,6 +601,32 @@ def _attn_kernel_of(B, H, Sq, Skv, hd, half, pitch):
     if wide:
         return f"attn_bf16_wide_kernel<{hd}>"
     return "attn_bf16_kernel"
+
+
+ATTN_LDS_MAX = 160 * 1024                            # launch_attention: the LDS a staged launch may ask for
+ATTN_MERGE_BYTES = 4 * 3 * 16 * 64 * 4 + 2 * 4 * 32 * 4      # its `mrg`: four waves' partial O (three fragments each) + their m and l = 50 176 B
+
+
+def _attn_lds_layout(Skv, pitch):
+    """launch_attention's LDS arithmetic for attn_lds_kernel: (img, merge_off, lgCV) - the operand images [K | V^T | Q] in bytes,
+    where the merge records go (behind the images when img + mrg fits 160 KiB, else 0: over them, after a barrier), and the log2
+    of the 16-byte chunks per LDS row of the V^T image (16 chunks up to a pitch of 128, else 32)."""
+    nt, lgcv = (Skv + 31) // 32, 5 if pitch > 128 else 4
+    img = nt * 32 * 256 + (128 << (lgcv + 4)) + 32 * 256
+    return img, (img if img + ATTN_MERGE_BYTES <= ATTN_LDS_MAX else 0), lgcv
+
+
+def _attn_form_of(B, H, Sq, Skv, hd, half, pitch):
+    """_attn_kernel_of down to the selectable FORM: the fp32 kernel by head dim, attn_lds_kernel by where its merge records lie
+    and by the width of its V^T image (tests/test_attention_edges_gpu.py names every form and takes each to its edges)."""
+    kernel = _attn_kernel_of(B, H, Sq, Skv, hd, half, pitch)
+    if kernel == "attn_kernel":
+        return f"attn_kernel<{hd}>"
+    if kernel == "attn_lds_kernel":
+        img, merge_off, lgcv = _attn_lds_layout(Skv, pitch)
+        assert img == (Skv + 31) // 32 * 32 * 256 + (128 << ((5 if pitch > 128 else 4) + 4)) + 32 * 256      # the term _attn_kernel_of stages by
+        return f"attn_lds_kernel[merge_off {'!=' if merge_off else '=='} 0, lgCV {lgcv}]"
+    return kernel
 
 
 # name -> (B, H, Sq, Skv, split, kv_bdiv, head dim, operand kinds, kernel).  Every case: a ragged last key tile, `split` inside a query
