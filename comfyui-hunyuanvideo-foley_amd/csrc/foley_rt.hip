@@ -213,6 +213,8 @@ struct IterArgs {
   int tl_sets = 0;
   const int *tl_a = nullptr, *tl_b = nullptr;
   const float* tl_alpha = nullptr;
+  // FlowEdit: the step of a (source, target) pair batch in place of the solver step, complete (z null: off - the solver step)
+  FlowEditArgs flowedit{};
   bool operator==(const IterArgs&) const = default;
 };
 
@@ -246,6 +248,9 @@ struct RunOptions {
   int tl_sets = 0;                        // foley_prepare_timeline: the number of text sets (0: one text set per batch row)
   int ms_order = 0;                       // foley_set_multistep: 0 a one-step method, 2 or 3
   int proj_mode = 0;                      // foley_set_projected_guidance: 0 off, FOLEY_GUIDANCE_APG, FOLEY_GUIDANCE_ZERO_STAR
+  bool flowedit = false;                  // foley_set_flowedit; on: plan.clips = 2V pair clips, the state is z [V, latent_dim, La]
+  int fe_src_clips = 1, fe_noise_rows = 1, fe_mask_clips = 0;   // mask clips 0: no mask (all ones)
+  float fe_g_src = 0.f, fe_g_tar = 0.f, fe_sigma0 = 1.f;
 };
 
 struct foley_ctx {
@@ -293,6 +298,8 @@ struct foley_ctx {
   // projected guidance: the rows [n_iter][4], the per-workgroup sums, the coefficients [clips][2] and APG's plane [clips*La, latent_dim]
   DevBuf proj_rows, proj_part, proj_coef, proj_plane;
   std::vector<float> proj_host;           // [n_iter*4] source of the copy
+  // FlowEdit: the source latents, the noise table [noise_rows, V, latent_dim, La] and the mask
+  DevBuf fe_x_src, fe_noise, fe_mask;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -344,6 +351,16 @@ static IterArgs iter_args(const foley_ctx* c) {
   }
   if (o.tl_sets) {
     a.tl_sets = o.tl_sets; a.tl_a = (const int*)c->tl_a.p; a.tl_b = (const int*)c->tl_b.p; a.tl_alpha = (const float*)c->tl_alpha.p;
+  }
+  if (o.flowedit) {   // ctx-owned copies again: their addresses, the counts and the scales stand for the operands
+    FlowEditArgs& f = a.flowedit;
+    f.pred = c->buf.pred; f.z = c->buf.x_cur; f.coef = pl.solver_coef; f.step_ptr = c->buf.step_ctr;
+    f.rows_out = c->buf.xin; f.rows_dtype = c->cfg.compute_dtype;
+    f.V = pl.clips / 2; f.C = c->cfg.latent_dim; f.L = pl.La; f.n_iter = pl.n_iter;
+    f.x_src = (const float*)c->fe_x_src.p; f.noise = (const float*)c->fe_noise.p;
+    f.mask = o.fe_mask_clips ? (const float*)c->fe_mask.p : nullptr;
+    f.src_clips = o.fe_src_clips; f.noise_rows = o.fe_noise_rows; f.mask_clips = o.fe_mask_clips;
+    f.g_src = o.fe_g_src; f.g_tar = o.fe_g_tar;
   }
   return a;
 }
@@ -548,7 +565,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   hipSetDevice(c->device);
   ctx_free_plan(c);
   for (DevBuf* b : {&c->dacP, &c->dacQ, &c->dacR, &c->dacZ, &c->smod_tab, &c->svec_tab, &c->edit_x0, &c->edit_noise, &c->edit_mask, &c->win_starts, &c->win_weights, &c->guid_sched,
-                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel, &c->tl_a, &c->tl_b, &c->tl_alpha, &c->ms_hist}) release(*b);
+                    &c->guid_part, &c->guid_scale, &c->sc_delta, &c->sc_mprev, &c->sc_part, &c->sc_rel, &c->tl_a, &c->tl_b, &c->tl_alpha, &c->ms_hist, &c->fe_x_src, &c->fe_noise, &c->fe_mask}) release(*b);
   if (c->sc_rel_host) (void)hipHostFree(c->sc_rel_host);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
@@ -1376,6 +1393,7 @@ extern "C" int foley_profile_forward(foley_ctx* c, const float* latents, int ite
 static int run_step(const IterArgs& a, hipStream_t st) {
   if (a.guid_scale) TRY(launch_guidance_stats(a.step, a.guid_part, a.guid_phi, 0.f, a.guid_scale, st));
   if (a.proj_mode) TRY(launch_guidance_project(a.step, a.proj_mode, a.proj_rows, a.proj_part, a.proj_coef, a.proj_plane, st));
+  if (a.flowedit.z) return launch_flowedit_step(a.flowedit, st);   // a pair batch: the difference step, which stages both branches
   return launch_solver_step(a.step, st);
 }
 
@@ -1452,6 +1470,7 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
   }
   if (!x0 || !noise) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0 and noise are required (all three null clears the edit state)");
   if (c->opt.n_win) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: the run has windows (foley_set_windows); editing a long clip is not supported");
+  if (c->opt.flowedit) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: the run has a FlowEdit state (foley_set_flowedit); the two edits do not combine");
   const foley_plan& pl = c->plan;
   if (x0_clips != 1 && x0_clips != pl.clips) return FAIL(FOLEY_ERR_INVALID, "foley_set_edit: x0_clips must be 1 or the plan's clips");
   if (mask && mask_clips != 1 && mask_clips != pl.clips)
@@ -1473,6 +1492,59 @@ extern "C" int foley_set_edit(foley_ctx* c, const float* x0, int x0_clips, const
   return 0;
 }
 
+extern "C" int foley_set_flowedit(foley_ctx* c, const float* x_src, int src_clips, const float* noise, int noise_rows, const float* mask,
+                                  int mask_clips, float g_src, float g_tar, float sigma0, void* stream_v) {
+  if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
+  if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_flowedit: foley_prepare has not been called");
+  if (!x_src) {
+    c->opt.flowedit = false;
+    return 0;
+  }
+  const foley_plan& pl = c->plan;
+  const RunOptions& o = c->opt;
+  if (!noise) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the noise table is required (x_src NULL clears the state)");
+  if (pl.ncfg != 2 || pl.clips % 2 != 0)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the plan is a CFG batch of (source, target) pairs: plan.ncfg must be 2 and plan.clips even");
+  const int V = pl.clips / 2;
+  if (noise_rows != 1 && noise_rows != pl.n_iter)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: noise_rows must be 1 (one fixed draw) or the plan's n_iter (fresh noise)");
+  if (src_clips != 1 && src_clips != V) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: src_clips must be 1 or V = plan.clips / 2");
+  if (mask && mask_clips != 1 && mask_clips != V) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: mask_clips must be 1 or V = plan.clips / 2");
+  if (!std::isfinite(g_src) || !std::isfinite(g_tar) || !(g_src > 1.f) || !(g_tar > 1.f))
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: g_src and g_tar must be finite and > 1 (both branches run under CFG)");
+  if (!(sigma0 >= 0.f && sigma0 <= 1.f)) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: sigma0 must lie in [0, 1]");
+  if (o.edit) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run is an edit run (foley_set_edit); the two edits do not combine");
+  if (o.n_win) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run has windows (foley_set_windows); editing a long clip is not supported");
+  if (o.ms_order) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run has a multistep state (foley_set_multistep); the step keeps no velocity history");
+  if (o.proj_mode) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run has a projected-guidance state (foley_set_projected_guidance)");
+  if (o.guid_sched_on || o.guid_rescale_on)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run has a guidance schedule / rescale state (foley_set_guidance); the branches take their own constant scales");
+  if (o.sc_mode) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run has a step-cache state (foley_set_step_cache)");
+  if (o.tl_sets) return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: the run has a prompt timeline (foley_prepare_timeline)");
+  std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
+  hipStream_t st = (hipStream_t)stream_v;
+  HIPTRY(hipSetDevice(c->device));
+  HIPTRY(hipStreamSynchronize(st));   // the buffers may be in use by a previous loop on this stream
+  std::vector<float> rows((size_t)pl.n_iter * 8);
+  HIPTRY(hipMemcpy(rows.data(), pl.solver_coef, rows.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < pl.n_iter; ++i)
+    if (!((int)rows[8 * (size_t)i + 4] & FOLEY_STEP_BLEND))
+      return FAIL(FOLEY_ERR_INVALID, "foley_set_flowedit: every solver_coef row must carry FOLEY_STEP_BLEND with sigma_{k+1} in column 5 (an euler edit table; multi-stage solvers are not supported)");
+  const size_t plane = (size_t)c->cfg.latent_dim * pl.La * 4;
+  TRY(grow(c->fe_x_src, (size_t)src_clips * plane));
+  TRY(grow(c->fe_noise, (size_t)noise_rows * V * plane));
+  if (mask) TRY(grow(c->fe_mask, (size_t)mask_clips * pl.La * 4));
+  HIPTRY(hipMemcpyAsync(c->fe_x_src.p, x_src, (size_t)src_clips * plane, hipMemcpyDeviceToDevice, st));
+  HIPTRY(hipMemcpyAsync(c->fe_noise.p, noise, (size_t)noise_rows * V * plane, hipMemcpyDeviceToDevice, st));
+  if (mask) HIPTRY(hipMemcpyAsync(c->fe_mask.p, mask, (size_t)mask_clips * pl.La * 4, hipMemcpyDeviceToDevice, st));
+  c->opt.flowedit = true;
+  c->opt.fe_src_clips = src_clips;
+  c->opt.fe_noise_rows = noise_rows;
+  c->opt.fe_mask_clips = mask ? mask_clips : 0;
+  c->opt.fe_g_src = g_src; c->opt.fe_g_tar = g_tar; c->opt.fe_sigma0 = sigma0;
+  return 0;
+}
+
 extern "C" int foley_set_windows(foley_ctx* c, int n_win, const int32_t* starts, const float* weights, void* stream_v) {
   if (!c) return FAIL(FOLEY_ERR_INVALID, "null context");
   if (!c->prepared) return FAIL(FOLEY_ERR_STATE, "foley_set_windows: foley_prepare has not been called");
@@ -1481,6 +1553,7 @@ extern "C" int foley_set_windows(foley_ctx* c, int n_win, const int32_t* starts,
     return 0;
   }
   if (c->opt.edit) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the run is an edit run (foley_set_edit); editing a long clip is not supported");
+  if (c->opt.flowedit) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the run has a FlowEdit state (foley_set_flowedit); editing a long clip is not supported");
   const foley_plan& pl = c->plan;
   if (pl.clips % n_win != 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: the plan's clips must be a multiple of n_win");
   if (starts[0] != 0) return FAIL(FOLEY_ERR_INVALID, "foley_set_windows: starts[0] must be 0");
@@ -1511,6 +1584,8 @@ extern "C" int foley_set_guidance(foley_ctx* c, const float* sched, int n_rows, 
     return 0;
   }
   const foley_plan& pl = c->plan;
+  if (c->opt.flowedit)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: the run has a FlowEdit state (foley_set_flowedit); its branches take their own constant scales");
   if (pl.ncfg == 1) return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: the plan has one half (ncfg 1): there is nothing to guide");
   if (sched && n_rows != pl.n_iter)
     return FAIL(FOLEY_ERR_INVALID, "foley_set_guidance: the schedule must have one row per iteration of the plan (n_rows == n_iter)");
@@ -1549,6 +1624,8 @@ extern "C" int foley_set_projected_guidance(foley_ctx* c, int mode, const float*
   if (mode != FOLEY_GUIDANCE_APG && mode != FOLEY_GUIDANCE_ZERO_STAR)
     return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: unknown mode (0 off, 1 APG, 2 CFG-Zero*)");
   const foley_plan& pl = c->plan;
+  if (c->opt.flowedit)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: the run has a FlowEdit state (foley_set_flowedit); projection does not combine with it");
   if (pl.ncfg != 2) return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: projection takes two halves (plan.ncfg != 2)");
   if (c->opt.guid_rescale_on)
     return FAIL(FOLEY_ERR_INVALID, "foley_set_projected_guidance: the run has a rescale state (foley_set_guidance); projection does not combine with it");
@@ -1584,6 +1661,8 @@ extern "C" int foley_set_multistep(foley_ctx* c, int order, void* stream_v) {
     return 0;
   }
   if (order != 2 && order != 3) return FAIL(FOLEY_ERR_INVALID, "foley_set_multistep: order must be 0 or 1 (off), 2 or 3");
+  if (c->opt.flowedit)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_multistep: the run has a FlowEdit state (foley_set_flowedit); its step keeps no velocity history");
   const foley_plan& pl = c->plan;
   std::lock_guard<std::mutex> setup_lock(g_setup_mutex);
   hipStream_t st = (hipStream_t)stream_v;
@@ -1605,6 +1684,8 @@ extern "C" int foley_set_step_cache(foley_ctx* c, int mode, const uint8_t* skip,
     return 0;
   }
   const foley_plan& pl = c->plan;
+  if (c->opt.flowedit)
+    return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: the run has a FlowEdit state (foley_set_flowedit); the step cache does not combine with it");
   if (mode != FOLEY_STEP_CACHE_SCHEDULE && mode != FOLEY_STEP_CACHE_THRESHOLD)
     return FAIL(FOLEY_ERR_INVALID, "foley_set_step_cache: mode must be 0 (off), 1 (schedule) or 2 (threshold)");
   if (mode == FOLEY_STEP_CACHE_SCHEDULE && (!skip || n_skip != pl.n_iter))
@@ -1675,7 +1756,8 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   hipStream_t st = (hipStream_t)stream_v;
   HIPTRY(hipSetDevice(c->device));
   const foley_plan& pl = c->plan;
-  const size_t xbytes = (size_t)pl.clips * c->cfg.latent_dim * pl.La * 4;
+  // under a FlowEdit state the latents are z [V, latent_dim, La], V = clips / 2: the first V planes of the state buffer
+  const size_t xbytes = (size_t)(c->opt.flowedit ? pl.clips / 2 : pl.clips) * c->cfg.latent_dim * pl.La * 4;
   GraphKey key = graph_key_now(c);
   const bool cached = c->opt.sc_mode != 0;
   if (c->graph_exec && !(c->graph_key == key)) ctx_drop_graph(c);
@@ -1713,7 +1795,8 @@ extern "C" int foley_sample(foley_ctx* c, float* latents, int use_graph, foley_p
   HIPTRY(hipEventRecord(c->ev0, st));
   HIPTRY(hipMemcpyAsync(c->buf.x_cur, latents, xbytes, hipMemcpyDeviceToDevice, st));
   HIPTRY(hipMemsetAsync(c->buf.step_ctr, 0, sizeof(int), st));
-  TRY(launch_latent_rows(c->buf.x_cur, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->buf.xin, c->cfg.compute_dtype, st));
+  if (c->opt.flowedit) TRY(launch_flowedit_stage(key.args.flowedit, c->opt.fe_sigma0, 0, st));   // both branches at sigma_{k0}
+  else TRY(launch_latent_rows(c->buf.x_cur, pl.clips, c->cfg.latent_dim, pl.La, pl.ncfg, c->buf.xin, c->cfg.compute_dtype, st));
   StepCachePolicy policy;
   if (cached) {
     c->sc_rep_rel.assign(pl.n_iter, -1.f);
@@ -2251,6 +2334,32 @@ static int op_solver_step(const foley_step_desc* d, const foley_projection_desc*
 extern "C" int foley_op_solver_step(const foley_step_desc* d, void* stream) { return op_solver_step(d, nullptr, stream); }
 extern "C" int foley_op_solver_step_projected(const foley_step_desc* d, const foley_projection_desc* proj, void* stream) {
   return op_solver_step(d, proj, stream);
+}
+
+// FlowEdit at op level: the descriptor translated into the FlowEditArgs the sampler loop launches with
+static FlowEditArgs flowedit_args_of(const foley_flowedit_desc* d) {
+  FlowEditArgs a;
+  a.pred = d->pred; a.z = d->z; a.x_src = d->x_src; a.noise = d->noise; a.mask = d->mask; a.coef = d->coef;
+  a.step_ptr = d->step_ptr; a.rows_out = d->rows_out;
+  a.V = d->V; a.C = d->C; a.L = d->L; a.n_iter = d->n_iter; a.rows_dtype = d->rows_dtype;
+  a.src_clips = d->src_clips; a.noise_rows = d->noise_rows; a.mask_clips = d->mask_clips;
+  a.g_src = d->g_src; a.g_tar = d->g_tar;
+  return a;
+}
+extern "C" int foley_op_flowedit_step(const foley_flowedit_desc* d, void* stream) {
+  if (!d) return FAIL(FOLEY_ERR_INVALID, "foley_op_flowedit_step: null descriptor");
+  if (!d->coef || d->n_iter < 1) return FAIL(FOLEY_ERR_INVALID, "foley_op_flowedit_step: coef [n_iter, 8] is required");
+  HIPTRY(hipStreamSynchronize((hipStream_t)stream));
+  std::vector<float> rows((size_t)d->n_iter * 8);
+  HIPTRY(hipMemcpy(rows.data(), d->coef, rows.size() * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < d->n_iter; ++i)
+    if (!((int)rows[8 * (size_t)i + 4] & FOLEY_STEP_BLEND))
+      return FAIL(FOLEY_ERR_INVALID, "foley_op_flowedit_step: every coef row must carry FOLEY_STEP_BLEND with sigma_{k+1} in column 5");
+  return launch_flowedit_step(flowedit_args_of(d), (hipStream_t)stream);
+}
+extern "C" int foley_op_flowedit_stage(const foley_flowedit_desc* d, float sigma, int noise_row, void* stream) {
+  if (!d) return FAIL(FOLEY_ERR_INVALID, "foley_op_flowedit_stage: null descriptor");
+  return launch_flowedit_stage(flowedit_args_of(d), sigma, noise_row, (hipStream_t)stream);
 }
 
 extern "C" int64_t foley_op_guidance_project_work(int clips, int La) {

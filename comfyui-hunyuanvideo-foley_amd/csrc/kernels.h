@@ -277,6 +277,35 @@ struct StepArgs {
 #pragma clang diagnostic pop
 };
 int launch_solver_step(const StepArgs& a, hipStream_t st);
+// FlowEdit (Kulikov et al. 2024; foley_set_flowedit): one edited clip is a (source, target) pair of batch clips - clip v reads the
+// source prompt, clip V + v the target prompt - and the state is z [V, C, L], started at x_src.  One step, at iteration it = *step_ptr
+// with row {., ., dt, ., flags, s_next, ., .} of coef:
+//   v_s = fma(g_src, c_s - u_s, u_s), v_t = fma(g_tar, c_t - u_t, u_t)        guided_value's two-half expression on clips v and V + v
+//   d = v_t - v_s;  d = m*d under a mask (m = mask[v][l]: 1 = edit, 0 = keep);  z = fma(d, dt, z)
+// and the rows of the NEXT model call, from s = s_next and n = noise row min(it + 1, noise_rows - 1):
+//   z_src = fma(1 - s, x_src, rnd(s*n))      (the edit form's target expression)   -> rows of clip v, both cfg halves
+//   z_tar = (z - x_src) + z_src              (z == x_src gives z_src bit for bit)  -> rows of clip V + v, both cfg halves
+// m == 0 leaves z bit for bit (d = +-0), m == 1 is the unmasked update.  launch_flowedit_stage is the staging alone, from a scalar
+// sigma and a given noise row: the first model input of a run.
+struct FlowEditArgs {
+  const float* pred = nullptr;    // [2*2V*L, C] model output rows: halves [uncond ; cond] of the clips [src_0.. ; tar_0..]
+  float* z = nullptr;             // [V, C, L] the edited latents (updated in place)
+  const float* x_src = nullptr;   // [src_clips, C, L] source latents (clip stride 0 when src_clips == 1)
+  const float* noise = nullptr;   // [noise_rows, V, C, L]: a row per iteration, or one fixed draw
+  const float* mask = nullptr;    // [mask_clips, L] or null (all ones)
+  const float* coef = nullptr;    // [n_iter, 8]
+  int* step_ptr = nullptr;        // device iteration counter; the one-thread launch that follows the step advances it
+  void* rows_out = nullptr;       // next model input rows (T) [2*2V*L, C] (or null: nothing staged)
+  int V = 0, C = 0, L = 0, n_iter = 0, rows_dtype = 0;
+  int src_clips = 0, noise_rows = 0, mask_clips = 0;
+  float g_src = 0.f, g_tar = 0.f;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-extensions"
+  bool operator==(const FlowEditArgs&) const = default;
+#pragma clang diagnostic pop
+};
+int launch_flowedit_step(const FlowEditArgs& a, hipStream_t st);
+int launch_flowedit_stage(const FlowEditArgs& a, float sigma, int noise_row, hipStream_t st);
 // CFG rescale: clip_scale[b] = phi * std(last half of clip b) / std(guided v of clip b) + (1 - phi) over the clip's C x L elements
 // (1.0f when the guided std is 0), from `a.pred` at iteration *a.step_ptr with the combine of the step kernels (a.clip_scale is
 // not read).  Two launches: per-workgroup centred partial statistics into `part` (guidance_stats_floats(clips, L) floats), then

@@ -856,9 +856,15 @@ __device__ __forceinline__ void step_stage_rows(const float (*tile)[33], const S
 // solver step - the kept frames are pulled back onto the source's forward-noised path:
 //   x <- m*x + (1-m)*(s*noise + (1-s)*x0),  s = sigma_{k+1} (column 5 of the row), m = mask[clip][l] (1 = regenerate).
 // The blend is two rounded products so that m = 1 returns x and m = 0 the target bit for bit: an all-ones mask is a plain run.
+// The source's point on the flow-match path at sigma s: one fused multiply-add over a rounded product.  The FlowEdit step stages
+// its source branch from the same expression.
+__device__ __forceinline__ float edit_target(float s, float noise, float x0) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(1.f - s, x0, s * noise);
+}
 __device__ __forceinline__ float edit_blend(float xn, float m, float s, float noise, float x0) {
 #pragma clang fp contract(off)
-  const float tgt = __builtin_fmaf(1.f - s, x0, s * noise);
+  const float tgt = edit_target(s, noise, x0);
   return m * xn + (1.f - m) * tgt;
 }
 
@@ -902,6 +908,100 @@ template <typename OutT, bool EDIT>
 __global__ __launch_bounds__(256) void solver_step_proj_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, false, true>(a); }
 template <typename OutT, bool EDIT>
 __global__ __launch_bounds__(256) void solver_step_proj_hist_kernel(const StepArgs a) { solver_step_body<OutT, EDIT, true, true>(a); }
+
+// FlowEdit (kernels.h FlowEditArgs): the step integrates the DIFFERENCE of the target-prompt and source-prompt velocities of a
+// (source, target) pair of batch clips, so what both prompts agree on cancels.  Kernels of their own, built from the routines of
+// the forms above: step_guided_tile / guided_value for the two velocities, edit_target for the source branch's next input.
+__device__ __forceinline__ float flowedit_update(float z, float vs, float vt, bool masked, float m, float dt) {
+#pragma clang fp contract(off)
+  float d = vt - vs;
+  if (masked) d = m * d;
+  return __builtin_fmaf(d, dt, z);
+}
+// the pair of next model inputs at sigma s; in this order z == xs gives zt == zs bit for bit
+__device__ __forceinline__ void flowedit_pair(float z, float xs, float n, float s, float& zs, float& zt) {
+#pragma clang fp contract(off)
+  zs = edit_target(s, n, xs);
+  zt = (z - xs) + zs;
+}
+
+// phase 2 of variation v's tile, coalesced over l.  UPDATE: z takes the step from the velocity tiles ts / tt (read transposed).
+// Then both tiles receive the inputs of the next model call at sigma s from noise row nr: ts the source branch, tt the target.
+template <bool UPDATE>
+__device__ __forceinline__ void flowedit_phase2(float (*ts)[33], float (*tt)[33], const FlowEditArgs& a, int v, int l0, int c0, float dt,
+                                                float s, int nr) {
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const long plane = (long)a.C * a.L;
+  const float* xs = a.x_src + (a.src_clips == 1 ? 0L : (long)v * plane);
+  const float* mb = a.mask ? a.mask + (a.mask_clips == 1 ? 0L : (long)v * a.L) : nullptr;
+  const float* nz = a.noise + ((long)nr * a.V + v) * plane;
+  float* zv = a.z + (long)v * plane;
+  for (int i = ty; i < 32; i += 8) {
+    const int c = c0 + i, l = l0 + tx;
+    float zs = 0.f, zt = 0.f;
+    if (c < a.C && l < a.L) {
+      const long ci = (long)c * a.L + l;
+      float z = zv[ci];
+      if (UPDATE) {
+        z = flowedit_update(z, ts[tx][i], tt[tx][i], mb != nullptr, mb ? mb[l] : 1.f, dt);
+        zv[ci] = z;
+      }
+      flowedit_pair(z, xs[ci], nz[ci], s, zs, zt);
+    }
+    ts[tx][i] = zs;
+    tt[tx][i] = zt;
+  }
+}
+
+// phase 3: the tiles [l][c] as the next model input rows of source clip v and target clip V + v, both cfg halves, coalesced over c
+template <typename OutT>
+__device__ __forceinline__ void flowedit_stage_rows(const float (*ts)[33], const float (*tt)[33], const FlowEditArgs& a, int v, int l0, int c0) {
+  if (!a.rows_out) return;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int clips = 2 * a.V;
+  OutT* out = (OutT*)a.rows_out;
+  for (int i = ty; i < 32; i += 8) {
+    const int l = l0 + i, c = c0 + tx;
+    if (l < a.L && c < a.C) {
+      const OutT s = Cvt<OutT>::to(ts[i][tx]), t = Cvt<OutT>::to(tt[i][tx]);
+      for (int g = 0; g < 2; ++g) {
+        out[(((long)g * clips + v) * a.L + l) * a.C + c] = s;
+        out[(((long)g * clips + a.V + v) * a.L + l) * a.C + c] = t;
+      }
+    }
+  }
+}
+
+// one workgroup per (32-frame tile, 32-channel tile, variation), like solver_step_body
+template <typename OutT>
+__global__ __launch_bounds__(256) void flowedit_step_kernel(const FlowEditArgs a) {
+  __shared__ float ts[32][33], tt[32][33];
+  const int it = *a.step_ptr;
+  const float* cf = a.coef + (long)it * 8;
+  const float dt = cf[2], s_next = cf[5];
+  const int v = blockIdx.z;
+  const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  // phase 1: the guided velocities of the pair's clips, each with its own scale
+  const StepArgs gs{a.pred, nullptr, nullptr, nullptr, 2 * a.V, a.C, a.L, 2, a.g_src, nullptr, nullptr, nullptr, FOLEY_F32};
+  const StepArgs gt{a.pred, nullptr, nullptr, nullptr, 2 * a.V, a.C, a.L, 2, a.g_tar, nullptr, nullptr, nullptr, FOLEY_F32};
+  step_guided_tile(ts, gs, it, v, l0, c0);
+  step_guided_tile(tt, gt, it, a.V + v, l0, c0);
+  __syncthreads();
+  const int nr = a.noise_rows == 1 ? 0 : (it + 1 < a.noise_rows ? it + 1 : a.noise_rows - 1);
+  flowedit_phase2<true>(ts, tt, a, v, l0, c0, dt, s_next, nr);
+  __syncthreads();
+  flowedit_stage_rows<OutT>(ts, tt, a, v, l0, c0);
+}
+
+// the staging half alone: the rows of the first model call from (z, x_src, noise row nr, sigma)
+template <typename OutT>
+__global__ __launch_bounds__(256) void flowedit_stage_kernel(const FlowEditArgs a, float sigma, int nr) {
+  __shared__ float ts[32][33], tt[32][33];
+  const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  flowedit_phase2<false>(ts, tt, a, blockIdx.z, l0, c0, 0.f, sigma, nr);
+  __syncthreads();
+  flowedit_stage_rows<OutT>(ts, tt, a, blockIdx.z, l0, c0);
+}
 
 // Windows form (long clips): the clips of one variation are overlapping windows of ONE long clip - clip v*n_win + k covers the
 // global frames [starts[k], starts[k] + L) of variation v - and the step is indexed by GLOBAL frame: a thread owns (g, c) and
@@ -1757,6 +1857,45 @@ int launch_solver_step(const StepArgs& a, hipStream_t st) {
   else launch_step_form<float>(a, st);
   FOLEY_LAUNCH_CHECK();
   FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+static int flowedit_args_ok(const FlowEditArgs& a) {
+  if (!a.z || !a.x_src || !a.noise) return foley_set_err("flowedit: z, x_src and noise are required", __FILE__, __LINE__);
+  if (a.V < 1 || a.V > 32767 || a.C < 1 || a.L < 1 || a.n_iter < 1)
+    return foley_set_err("flowedit: 1 <= V <= 32767, C, L, n_iter >= 1", __FILE__, __LINE__);
+  if ((a.src_clips != 1 && a.src_clips != a.V) || (a.mask && a.mask_clips != 1 && a.mask_clips != a.V))
+    return foley_set_err("flowedit: src_clips / mask_clips must be 1 or V", __FILE__, __LINE__);
+  if (a.noise_rows != 1 && a.noise_rows != a.n_iter)
+    return foley_set_err("flowedit: noise_rows must be 1 or n_iter", __FILE__, __LINE__);
+  if (a.rows_out && a.rows_dtype != FOLEY_F32 && a.rows_dtype != FOLEY_BF16 && a.rows_dtype != FOLEY_F16)
+    return foley_set_err("flowedit: rows_dtype must be fp32, bf16 or fp16", __FILE__, __LINE__);
+  return 0;
+}
+
+int launch_flowedit_step(const FlowEditArgs& a, hipStream_t st) {
+  if (!a.pred || !a.coef || !a.step_ptr) return foley_set_err("flowedit_step: pred, coef and step_ptr are required", __FILE__, __LINE__);
+  if (int rc = flowedit_args_ok(a)) return rc;
+  const dim3 grid((a.L + 31) / 32, (a.C + 31) / 32, a.V), block(256);
+  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(flowedit_step_kernel<bf16_t>, grid, block, 0, st, a);
+  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(flowedit_step_kernel<f16_t>, grid, block, 0, st, a);
+  else FOLEY_LAUNCH(flowedit_step_kernel<float>, grid, block, 0, st, a);
+  FOLEY_LAUNCH_CHECK();
+  FOLEY_LAUNCH(step_increment_kernel, dim3(1), dim3(1), 0, st, a.step_ptr);
+  FOLEY_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_flowedit_stage(const FlowEditArgs& a, float sigma, int noise_row, hipStream_t st) {
+  if (!a.rows_out) return foley_set_err("flowedit_stage: rows_out is required", __FILE__, __LINE__);
+  if (int rc = flowedit_args_ok(a)) return rc;
+  if (noise_row < 0 || noise_row >= a.noise_rows) return foley_set_err("flowedit_stage: noise_row outside [0, noise_rows)", __FILE__, __LINE__);
+  if (!(sigma >= 0.f && sigma <= 1.f)) return foley_set_err("flowedit_stage: sigma must lie in [0, 1]", __FILE__, __LINE__);
+  const dim3 grid((a.L + 31) / 32, (a.C + 31) / 32, a.V), block(256);
+  if (a.rows_dtype == FOLEY_BF16) FOLEY_LAUNCH(flowedit_stage_kernel<bf16_t>, grid, block, 0, st, a, sigma, noise_row);
+  else if (a.rows_dtype == FOLEY_F16) FOLEY_LAUNCH(flowedit_stage_kernel<f16_t>, grid, block, 0, st, a, sigma, noise_row);
+  else FOLEY_LAUNCH(flowedit_stage_kernel<float>, grid, block, 0, st, a, sigma, noise_row);
   FOLEY_LAUNCH_CHECK();
   return 0;
 }

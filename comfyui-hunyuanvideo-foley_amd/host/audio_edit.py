@@ -12,6 +12,14 @@ With a multistep order (sampler.MultistepSpec) the suffix has no velocity histor
 there (tables.edit_solver_table(..., multistep_order=)), and the ring keeps the velocities, not the blended samples.
 Under euler the last sigma is 0, so kept frames end at exactly x0; the multi-stage solvers end where the plain run ends
 (sigma > 0 for them: every loop iteration is one solver stage, the reference's quirk that SolverState reproduces).
+
+FlowEdit (FlowEditSpec; Kulikov et al. 2024, inversion-free text-based editing) changes WHAT the clip sounds like and keeps its
+timing: every variation is a (source-prompt, target-prompt) pair of batch clips, and the loop integrates the difference of the two
+guided velocities from z = x0 over the same suffix [i0, steps) of the euler run (foley_set_flowedit, rowops.hip).  What both
+prompts agree on - the timing, which comes from the video and sync features - cancels.  Each iteration noises the source afresh
+(noise="fresh": one row of flowedit_noise per iteration) or with one fixed draw (noise="fixed").  Frames the mask keeps (m = 0)
+stay at x0 bit for bit.  Not built: the paper's n_min tail of plain target sampling, n_avg > 1, and frames past the end of the
+source audio (refused: they have no source).
 """
 from __future__ import annotations
 
@@ -55,6 +63,43 @@ class EditSpec:
         if mask is not None and mask.dim() == 2 and mask.shape[0] == clips and clips > 1:
             mask = mask[lo:hi]
         return EditSpec(x0, self.strength, mask)
+
+
+FLOWEDIT_NOISE = ("fresh", "fixed")
+
+
+@dataclass
+class FlowEditSpec:
+    """What `sampler.denoise_process_with_generator(..., edit=)` needs for a FlowEdit run: source latents x0 [1 | V, C, La] fp32
+    (1: shared by every variation), strength in (0, 1] (how far up the schedule the edit starts), the edit mask [La] or
+    [1 | V, La] in [0, 1] (1 = edit, 0 = keep; None: all ones), the CFG scale of the source branch (the run's guidance_scale is the
+    target branch's) and the noise policy: "fresh" draws a row per iteration, "fixed" one row for the run."""
+    x0: torch.Tensor
+    strength: float = 1.0
+    mask: Optional[torch.Tensor] = None
+    source_scale: float = 2.0
+    noise: str = "fresh"
+
+    def check(self, sampler: str, guidance_scale: float) -> None:
+        if sampler != "euler":
+            raise ValueError(f"FlowEdit needs the euler solver (its step integrates one velocity difference per sigma step), got {sampler!r}")
+        if self.noise not in FLOWEDIT_NOISE:
+            raise ValueError(f"edit_noise must be one of {list(FLOWEDIT_NOISE)}, got {self.noise!r}")
+        for name, v in (("cfg_scale", guidance_scale), ("source_cfg_scale", self.source_scale)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not v > 1.0:
+                raise ValueError(f"FlowEdit runs both branches under classifier-free guidance: {name} must be finite and > 1, got {v!r}")
+
+    def n_rows(self, n_iter: int) -> int:
+        return int(n_iter) if self.noise == "fresh" else 1
+
+    device_operands = EditSpec.device_operands
+
+
+def flowedit_noise(generator: Optional[torch.Generator], n_rows: int, V: int, C: int, La: int, dtype: torch.dtype) -> torch.Tensor:
+    """The noise table of a FlowEdit run [n_rows, V, C, La]: ONE torch.randn draw from the run's CPU generator in the model's dtype
+    (the rule of sampler.draw_noise), in pinned memory where the host can pin."""
+    pin = torch.cuda.is_available()
+    return torch.randn((int(n_rows), int(V), int(C), int(La)), generator=generator, device="cpu", dtype=dtype, pin_memory=pin)
 
 
 # ----------------------------------------------------------------------------- mask
@@ -134,11 +179,20 @@ def encode_source(wave48: torch.Tensor, model, dac, La: int) -> torch.Tensor:
     return params[:, :model.cfg.latent_dim].contiguous()
 
 
+def check_flowedit_length(La: int, frame_rate: int, n_samples: int, hop: int, sample_rate: int) -> None:
+    """FlowEdit edits what is there: a clip longer than the source audio is refused (those frames have no source)."""
+    if n_samples // hop < La:
+        raise ValueError(f"the clip ({La / frame_rate:g} s) is longer than the input audio ({n_samples / sample_rate:.3f} s): FlowEdit "
+                         "edits the source and the frames past its end have none; shorten the duration or use audio= without source_prompt")
+
+
 def prepare_edit(audio: dict, model, dac, audio_len_in_s: float, steps: int, solver: str, batch_size: int,
                  strength: float = 1.0, regenerate: Optional[Sequence[Tuple[float, float]]] = None,
-                 crossfade_s: float = 0.1) -> EditSpec:
+                 crossfade_s: float = 0.1, flowedit: Optional[dict] = None):
     """The EditSpec of a node call: source latents of `audio`, the mask of `regenerate` (plus the extension tail when the clip
-    is longer than the audio) and the strength, with every refusal raised before any sampling work."""
+    is longer than the audio) and the strength, with every refusal raised before any sampling work.
+    flowedit ({"source_scale", "noise"}): the FlowEditSpec of the call instead - the mask of `regenerate` restricts the edit in time
+    (None without spans: the whole clip), and a clip longer than the source audio is refused."""
     check_encoder(dac)
     tables.edit_start(steps, solver, strength)                # refuses n_keep = 0 / strength outside (0, 1]
     B = audio["waveform"].shape[0] if audio["waveform"].dim() == 3 else 1
@@ -149,6 +203,12 @@ def prepare_edit(audio: dict, model, dac, audio_len_in_s: float, steps: int, sol
     hop = dac.cfg.hop
     wave = prepare_waveform(audio, model, dac)
     src_frames = wave.shape[1] // hop
+    if flowedit is not None:
+        check_flowedit_length(La, fr, wave.shape[1], hop, dac.sample_rate)
+        mask = build_mask(La, regenerate, crossfade_s, frame_rate=fr) if regenerate is not None else None
+        x0 = encode_source(wave, model, dac, La)
+        return FlowEditSpec(x0=x0, strength=float(strength), mask=mask, source_scale=float(flowedit.get("source_scale", 2.0)),
+                            noise=flowedit.get("noise", "fresh"))
     if src_frames < La and float(strength) != 1.0:
         raise ValueError(f"the clip ({La / fr:g} s) is longer than the input audio ({wave.shape[1] / dac.sample_rate:.3f} s): "
                          "the frames past its end have no source to noise, so extension needs strength 1.0")

@@ -119,6 +119,15 @@ class StepDescC(C.Structure):
                 ("n_win", C.c_int32), ("starts", C.c_void_p), ("weights", C.c_void_p), ("Ltot", C.c_int32)]
 
 
+class FlowEditDescC(C.Structure):
+    """foley_flowedit_desc: every operand of foley_op_flowedit_step / foley_op_flowedit_stage (0: absent)."""
+    _fields_ = [("pred", C.c_void_p), ("z", C.c_void_p), ("x_src", C.c_void_p), ("noise", C.c_void_p), ("mask", C.c_void_p),
+                ("coef", C.c_void_p), ("step_ptr", C.c_void_p), ("rows_out", C.c_void_p),
+                ("V", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("n_iter", C.c_int32), ("rows_dtype", C.c_int32),
+                ("src_clips", C.c_int32), ("noise_rows", C.c_int32), ("mask_clips", C.c_int32),
+                ("g_src", C.c_float), ("g_tar", C.c_float)]
+
+
 class ProfEntryC(C.Structure):
     _fields_ = [("label", C.c_char * 80), ("calls", C.c_int32), ("total_ms", C.c_float), ("flop", C.c_double),
                 ("bytes", C.c_double), ("kernel", C.c_char * 200)]
@@ -150,6 +159,8 @@ _SIGNATURES = {
     "foley_abort": (C.c_int, [C.c_void_p]),
     "foley_set_edit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_set_windows": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "foley_set_flowedit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                     C.c_float, C.c_void_p]),
     "foley_set_guidance": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p]),
     "foley_set_projected_guidance": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
     "foley_set_step_cache": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_double, C.POINTER(C.c_double), C.c_int,
@@ -199,6 +210,8 @@ _SIGNATURES = {
     "foley_op_guidance_project": (C.c_int, [C.POINTER(ProjectionDescC), C.POINTER(GuidanceDescC), C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "foley_op_solver_step_projected": (C.c_int, [C.POINTER(StepDescC), C.POINTER(ProjectionDescC), C.c_void_p]),
+    "foley_op_flowedit_step": (C.c_int, [C.POINTER(FlowEditDescC), C.c_void_p]),
+    "foley_op_flowedit_stage": (C.c_int, [C.POINTER(FlowEditDescC), C.c_float, C.c_int, C.c_void_p]),
     "foley_op_cache_probe_work": (C.c_int64, [C.c_int, C.c_int]),
     "foley_op_cache_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(RowBcastC), C.POINTER(RowBcastC),
                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
@@ -502,6 +515,34 @@ class FoleyContext:
             _check(self.lib, self.lib.foley_set_edit(self._h, _ptr(x0), x0_clips, _ptr(noise), _ptr(mask), mask_clips, _stream()),
                    "foley_set_edit")
         self._edit_keep = (x0, noise, mask)     # borrowed only until the copies on the stream are done
+
+    def set_flowedit(self, x_src: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                     g_src: float = 2.0, g_tar: float = 4.5, sigma0: float = 1.0):
+        """foley_set_flowedit after prepare() of the 2V-clip pair plan: x_src [1 | V, C, La], noise [n_iter | 1, V, C, La], mask [La]
+        or [1 | V, La] (None: all ones), fp32 on this context's device; the library copies them.  g_src / g_tar: the CFG scales of
+        the source and target branches, sigma0: the sigma the first rows are staged at.  x_src None clears the state; sample()
+        then takes and returns z [V, C, La]."""
+        def _f32(t):
+            if t is None:
+                return None
+            if t.dtype != torch.float32 or t.device != self.device:
+                raise FoleyRuntimeError("set_flowedit: operands must be fp32 tensors on the context's device")
+            return t.contiguous()
+        x_src, noise, mask = _f32(x_src), _f32(noise), _f32(mask)
+        if x_src is not None:
+            if x_src.dim() != 3 or noise is None or noise.dim() != 4 or tuple(noise.shape[2:]) != tuple(x_src.shape[1:]):
+                raise FoleyRuntimeError("set_flowedit: x_src is [1 | V, C, La] and noise [n_iter | 1, V, C, La]")
+            pl = getattr(self, "plan", None)
+            if pl is not None and (2 * noise.shape[1] != int(pl["clips"]) or x_src.shape[2] != int(pl["La"])
+                                   or (mask is not None and mask.shape[-1] != int(pl["La"]))):
+                raise FoleyRuntimeError("set_flowedit: the operands must match the plan (noise of V = clips / 2 variations, La frames)")
+        src_clips = x_src.shape[0] if x_src is not None else 0
+        noise_rows = noise.shape[0] if noise is not None else 0
+        mask_clips = (1 if mask.dim() == 1 else mask.shape[0]) if mask is not None else 0
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_set_flowedit(self._h, _ptr(x_src), src_clips, _ptr(noise), noise_rows, _ptr(mask), mask_clips,
+                                                         float(g_src), float(g_tar), float(sigma0), _stream()), "foley_set_flowedit")
+        self._flowedit_keep = (x_src, noise, mask)     # borrowed only until the copies on the stream are done
 
     def set_windows(self, starts, weights: Optional[torch.Tensor]):
         """foley_set_windows after prepare(): `starts` - n_win latent-frame offsets (host ints), `weights` [n_win, La] fp32 on
@@ -1083,6 +1124,42 @@ def op_solver_step(pred, x, x_saved, d_acc, ncfg, guidance, coef, step_ptr, rows
                "foley_op_solver_step_projected")
         return
     _check(lib, lib.foley_op_solver_step(C.byref(d), _stream()), "foley_op_solver_step")
+
+
+def flowedit_desc(pred, z, x_src, noise, mask, coef, step_ptr, rows_out, g_src: float, g_tar: float) -> FlowEditDescC:
+    """foley_flowedit_desc from device tensors: z [V, C, L], x_src [1 | V, C, L], noise [noise_rows, V, C, L], mask [L] or
+    [1 | V, L] or None, coef [n_iter, 8]; pred / coef / step_ptr may be None for op_flowedit_stage, rows_out for op_flowedit_step."""
+    V, Cc, L = z.shape
+    for t, what in ((pred, "pred"), (z, "z"), (x_src, "x_src"), (noise, "noise"), (mask, "mask"), (coef, "coef")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise FoleyRuntimeError(f"flowedit_desc: {what} must be a contiguous fp32 tensor")
+    if x_src.dim() != 3 or tuple(x_src.shape[1:]) != (Cc, L) or noise.dim() != 4 or tuple(noise.shape[1:]) != (V, Cc, L):
+        raise FoleyRuntimeError("flowedit_desc: x_src [src_clips, C, L] and noise [noise_rows, V, C, L] must match z [V, C, L]")
+    if mask is not None and mask.shape[-1] != L:
+        raise FoleyRuntimeError("flowedit_desc: mask must have L columns")
+    if pred is not None and tuple(pred.shape) != (4 * V * L, Cc):
+        raise FoleyRuntimeError("flowedit_desc: pred is [2*2V*L, C]")
+    if rows_out is not None and (rows_out.numel() != 4 * V * L * Cc or not rows_out.is_contiguous()):
+        raise FoleyRuntimeError("flowedit_desc: rows_out is [2*2V*L, C]")
+    mask_clips = (1 if mask.dim() == 1 else int(mask.shape[0])) if mask is not None else 0
+    return FlowEditDescC(_ptr(pred), _ptr(z), _ptr(x_src), _ptr(noise), _ptr(mask), _ptr(coef), _ptr(step_ptr), _ptr(rows_out),
+                         V, Cc, L, int(coef.shape[0]) if coef is not None else int(noise.shape[0]), _rows_dt(rows_out),
+                         int(x_src.shape[0]), int(noise.shape[0]), mask_clips, float(g_src), float(g_tar))
+
+
+def op_flowedit_step(pred, z, x_src, noise, mask, coef, step_ptr, rows_out, g_src: float, g_tar: float) -> None:
+    """foley_op_flowedit_step: one FlowEdit iteration on z [V, C, L] in place from pred [2*2V*L, C]; rows_out [2*2V*L, C] (or
+    None) receives the next model input rows of both branches; *step_ptr is read as the iteration and advanced."""
+    lib = load_library()
+    d = flowedit_desc(pred, z, x_src, noise, mask, coef, step_ptr, rows_out, g_src, g_tar)
+    _check(lib, lib.foley_op_flowedit_step(C.byref(d), _stream()), "foley_op_flowedit_step")
+
+
+def op_flowedit_stage(z, x_src, noise, rows_out, sigma: float, noise_row: int = 0) -> None:
+    """foley_op_flowedit_stage: rows_out [2*2V*L, C] from z, x_src and noise row `noise_row` at `sigma`."""
+    lib = load_library()
+    d = flowedit_desc(None, z, x_src, noise, None, None, None, rows_out, 0.0, 0.0)
+    _check(lib, lib.foley_op_flowedit_stage(C.byref(d), float(sigma), int(noise_row), _stream()), "foley_op_flowedit_stage")
 
 
 # The four names callers used before ABI 13, kept as plain forwards so that code written against them still runs.  Options go through

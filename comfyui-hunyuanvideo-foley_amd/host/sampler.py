@@ -15,7 +15,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.nn.functional as F
 
-from . import cond_sets, packers, prompt_timeline as _ptl, runtime, step_cache as _sc, tables
+from . import audio_edit as _audio_edit, cond_sets, packers, prompt_timeline as _ptl, runtime, step_cache as _sc, tables
 from .config import DAC48K, DACConfig, DiTConfig
 from .runtime import FoleyContext, FoleyRuntimeError
 from .step_cache import StepCacheSpec
@@ -426,6 +426,9 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     edit (host/audio_edit.EditSpec: x0, strength, mask): audio-to-audio / span regeneration - the suffix of the plain run's
     iterations that `strength` selects, started from the source latents x0 noised to that point, with the kept frames of the
     mask held on the source's forward-noised path (foley_set_edit).  The noise is drawn exactly as for a plain run.
+    A host/audio_edit.FlowEditSpec (x0, strength, mask, source_scale, noise) is a FlowEdit run instead - see _denoise_flowedit:
+    text_feats carries `source_text_feat` (batch 1) next to `text_feat` (the target, batch 1), batch_size is the number of
+    variations V, and the model runs a batch of 2V clips.  It takes none of the other options.
 
     windows (host/long_form.WindowPlan): a long clip as one batch of overlapping windows - see _denoise_windows.  A plan of
     one window takes the plain path exactly; `windows` together with `edit` is refused.
@@ -447,6 +450,12 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     run, bit for bit, with its single captured graph."""
     if multistep is not None:
         multistep.check(sampler)
+    if isinstance(edit, _audio_edit.FlowEditSpec):
+        if any(o is not None for o in (windows, guidance, step_cache, timeline, multistep, noise)):
+            raise ValueError("a FlowEdit run (edit=FlowEditSpec) takes no windows, guidance controls, step cache, timeline, multistep "
+                             "order or preset noise: it draws its own noise table from the generator")
+        return _denoise_flowedit(visual_feats, text_feats, audio_len_in_s, model, dac, guidance_scale, num_inference_steps, batch_size,
+                                 sampler, edit, generator, use_graph, progress, return_latents, _abort_event)
     if windows is not None and windows.n_win > 1:
         if edit is not None:
             raise ValueError("windows= and edit= together: editing a long clip is not supported")
@@ -477,6 +486,53 @@ def denoise_process_with_generator(visual_feats, text_feats, audio_len_in_s, mod
     keep_step_cache_report(model.ctx, plan)
     audio = model.ctx.dac_decode(latents)
     # (the reference's "trim to exact length" slices the size-1 channel axis: a no-op)
+    sr = dac.sample_rate if dac is not None else model.dac_cfg.sample_rate
+    if return_latents:
+        return audio, sr, latents
+    return audio, sr
+
+
+def flowedit_features(visual_feats, text_feats, V: int):
+    """The conditioning of the 2V-clip pair batch [src_0 .. src_{V-1}, tar_0 .. tar_{V-1}]: the source prompt's row for the first V
+    clips, the target's for the others; the visual features and the negative prompt are shared (batch 1)."""
+    src, tar, unc = text_feats.get("source_text_feat"), text_feats["text_feat"], text_feats["uncond_text_feat"]
+    if src is None:
+        raise ValueError("a FlowEdit run needs text_feats['source_text_feat'] (the source prompt, batch 1) next to 'text_feat' (the target)")
+    for t, what in ((src, "source_text_feat"), (tar, "text_feat"), (unc, "uncond_text_feat"), (visual_feats["siglip2_feat"], "siglip2_feat"),
+                    (visual_feats["syncformer_feat"], "syncformer_feat")):
+        if t.dim() != 3 or t.shape[0] != 1:
+            raise ValueError(f"a FlowEdit run shares its conditioning among the variations: {what} must have batch 1, got {tuple(t.shape)}")
+    Lt = max(src.shape[1], tar.shape[1])
+    src, tar = pad_or_trim_text(src, Lt), pad_or_trim_text(tar.to(src), Lt)
+    text = torch.cat([src.expand(V, -1, -1), tar.expand(V, -1, -1)])
+    return dict(visual_feats), {"text_feat": text, "uncond_text_feat": unc}
+
+
+def _denoise_flowedit(visual_feats, text_feats, audio_len_in_s, model: FoleyModel, dac: FoleyDAC, guidance_scale, num_inference_steps,
+                      variations, sampler, edit, generator, use_graph, progress, return_latents, _abort_event):
+    """FlowEdit (host/audio_edit.FlowEditSpec): every variation is a (source-prompt, target-prompt) pair of batch clips, so the
+    plan is a 2V-clip per-clip-prompt CFG batch over the suffix [i0, steps) of the euler run with the blend rows; the state is
+    z [V, C, La], started at the source latents, and the library's step integrates the difference of the pair's guided velocities
+    (foley_set_flowedit).  The noise table is ONE draw [n_iter | 1, V, C, La] from the run's generator (audio_edit.flowedit_noise).
+    The run takes one device: denoise_process_multi does not shard it, a pair must not be split."""
+    edit.check(sampler, guidance_scale)
+    cfg = model.cfg
+    V = int(variations)
+    La = int(audio_len_in_s * cfg.frame_rate)
+    k0, i0 = tables.edit_start(num_inference_steps, sampler, edit.strength)
+    x0, mask = edit.device_operands(model.device, V, La)
+    vis, txt = flowedit_features(visual_feats, text_feats, V)
+    plan = build_plan(model, vis, txt, La, guidance_scale, num_inference_steps, 2 * V, sampler, edit_i0=i0)
+    prepare_run(model, dac, plan)
+    table = _audio_edit.flowedit_noise(generator, edit.n_rows(plan["n_iter"]), V, cfg.latent_dim, La, model.dtype)
+    table = table.to(device=model.device, dtype=torch.float32, non_blocking=True).contiguous()
+    sigma0 = float(tables.sigma_grid(num_inference_steps, cfg.flow_shift)[k0])
+    model.ctx.set_flowedit(x0, table, mask, g_src=float(edit.source_scale), g_tar=float(guidance_scale), sigma0=sigma0)
+    latents = x0.expand(V, -1, -1).contiguous().clone()
+    if _abort_event is not None and _abort_event.is_set():
+        raise FoleyRuntimeError("sampling aborted: another replica failed")
+    model.ctx.sample(latents, use_graph=use_graph, progress=progress)
+    audio = model.ctx.dac_decode(latents)
     sr = dac.sample_rate if dac is not None else model.dac_cfg.sample_rate
     if return_latents:
         return audio, sr, latents
@@ -645,6 +701,9 @@ def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Se
     from .distributed import shard_range
     if multistep is not None:
         multistep.check(sampler)
+    if isinstance(edit, _audio_edit.FlowEditSpec):
+        raise ValueError("a FlowEdit run is not sharded over replicas: every variation is a (source, target) pair of batch clips that "
+                         "must stay on one device; call denoise_process_with_generator")
     if not replicas:
         raise FoleyRuntimeError("no replicas")
     m0 = replicas[0][0]

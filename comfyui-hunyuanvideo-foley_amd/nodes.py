@@ -340,7 +340,8 @@ class HunyuanFoleySampler:
                        video_cfg_scale=None, guidance_interval=None, cfg_rescale=0.0, cache_threshold=None, cache_skip=None,
                        cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25,
                        loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False, multistep_order=None,
-                       guidance_mode=None, apg_eta=0.0, apg_momentum=-0.5, apg_norm_threshold=0.0, zero_init_steps=0):
+                       guidance_mode=None, apg_eta=0.0, apg_momentum=-0.5, apg_norm_threshold=0.0, zero_init_steps=0,
+                       source_prompt=None, source_cfg_scale=2.0, edit_noise="fresh"):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -403,8 +404,29 @@ class HunyuanFoleySampler:
         `apg_momentum`, |.| < 1, averages the difference over the iterations, `apg_norm_threshold` >= 0 clips its norm - in the
         model's velocity units, uncalibrated; 0: off) or "cfg_zero_star" (the unconditional prediction is rescaled per clip before
         the combine); `zero_init_steps` iterations at the start use a zero velocity.  Two halves with cfg_scale > 1 only: it does
-        not combine with video_cfg_scale or cfg_rescale > 0.  None: the plain combine, bit for bit, and nothing new is launched."""
+        not combine with video_cfg_scale or cfg_rescale > 0.  None: the plain combine, bit for bit, and nothing new is launched.
+
+        FlowEdit (keyword-only, not sockets; host/audio_edit.py::FlowEditSpec): `source_prompt` describes what `audio` sounds like
+        and the `prompt` widget what it should sound like instead; the clip keeps its timing, which both prompts share through the
+        video.  `cfg_scale` is the target prompt's guidance scale, `source_cfg_scale` the source prompt's (2.0: uncalibrated for
+        this model); `strength` is how far up the schedule the edit starts, `regenerate` / `crossfade_s` restrict it in time, and
+        `edit_noise` "fresh" noises the source anew every step, "fixed" with one draw.  Every variation runs as two clips of the
+        model batch, so the run costs what a CFG batch of 2 x batch_size clips costs, on one device.  euler only, both scales > 1; it
+        does not combine with window_s, prompts= / negative_prompts= / images= / features=, prompt_timeline, the guidance controls,
+        multistep_order or the step cache, and a duration past the end of `audio` is refused.  The loudness stage combines with it.
+        None: every run is what it was, bit for bit, and nothing new is launched."""
         model, deps = hunyuan_model, hunyuan_deps
+        flowedit = None
+        if source_prompt is not None:              # refused here, before the encoders run
+            flowedit = self._check_flowedit(audio, duration, sampler, cfg_scale, source_cfg_scale, edit_noise, deps, dict(
+                window_s=window_s, prompts=prompts, negative_prompts=negative_prompts, images=images, features=features,
+                prompt_timeline=prompt_timeline, video_cfg_scale=video_cfg_scale, guidance_interval=guidance_interval,
+                cfg_rescale=cfg_rescale or None, guidance_mode=guidance_mode, multistep_order=multistep_order,
+                cache_threshold=cache_threshold, cache_skip=cache_skip, cache_interval=cache_interval,
+                cache_max_consecutive=cache_max_consecutive))
+        elif source_cfg_scale != 2.0 or edit_noise != "fresh":
+            raise ValueError("source_cfg_scale / edit_noise belong to FlowEdit: pass source_prompt")
+        text_prompts = None if flowedit is None else [source_prompt, prompt]     # CLAP then encodes [negative, source, target] in one call
         ms_kw = {}
         if multistep_order is not None:            # refused here, before the encoders run
             _sampler.MultistepSpec(multistep_order).check(sampler)
@@ -489,7 +511,8 @@ class HunyuanFoleySampler:
         elif image is not None:
             visual, text, audio_len_in_s = self._video_features(image, duration, frame_rate, prompt,
                                                                 negative_prompt, deps, device, model.dtype,
-                                                                **({"prompt_list": list(timeline.prompts)} if timeline is not None else {}))
+                                                                **({"prompt_list": list(timeline.prompts)} if timeline is not None else
+                                                                   {"prompt_list": text_prompts} if text_prompts is not None else {}))
         else:
             # text-to-audio: learned "empty" visual rows (nodes.py:326-333)
             clip_len = int(duration * 8)
@@ -497,14 +520,17 @@ class HunyuanFoleySampler:
             visual = {"siglip2_feat": model.get_empty_clip_sequence(bs=1, len=clip_len),
                       "syncformer_feat": model.get_empty_sync_sequence(bs=1, len=sync_len)}
             # a timeline: all its distinct prompts in ONE call, one row each behind the negative prompt's
-            res = encode_text_feat([negative_prompt] + (list(timeline.prompts) if timeline is not None else [prompt]), deps, device,
-                                   model.dtype)
+            res = encode_text_feat([negative_prompt] + (list(timeline.prompts) if timeline is not None else text_prompts or [prompt]),
+                                   deps, device, model.dtype)
             text = {"text_feat": res[1:], "uncond_text_feat": res[:1]}
+        if flowedit is not None:                # rows [source, target] of the one CLAP call
+            text = {"source_text_feat": text["text_feat"][:1], "text_feat": text["text_feat"][1:2], "uncond_text_feat": text["uncond_text_feat"]}
         edit = None
         if audio is not None:
             from .host import audio_edit as _edit
             edit = _edit.prepare_edit(audio, model, deps["dac_model"], audio_len_in_s, steps, sampler, batch_size,
-                                      strength=strength, regenerate=regenerate, crossfade_s=crossfade_s)
+                                      strength=strength, regenerate=regenerate, crossfade_s=crossfade_s,
+                                      **({"flowedit": flowedit} if flowedit is not None else {}))
         elif strength != 1.0 or regenerate is not None:
             raise ValueError("strength / regenerate edit an input clip: pass it as audio=")
         pbar = None
@@ -522,7 +548,7 @@ class HunyuanFoleySampler:
                 visual, text, audio_len_in_s, model, deps["dac_model"], guidance_scale=cfg_scale,
                 num_inference_steps=steps, batch_size=batch_size, sampler=sampler, generator=rng, progress=progress,
                 windows=windows, guidance=guidance, step_cache=step_cache, **tl_kw, **ms_kw)
-        elif batch_size > 1 and n_dev > 1 and model.arena is not None:
+        elif batch_size > 1 and n_dev > 1 and model.arena is not None and flowedit is None:   # a FlowEdit pair is not split
             # clips are independent: shard them over the node's GPUs (host/sampler.py::denoise_process_multi; the widget
             # list is the reference's, so the switch is an environment variable - INTEGRATION.md)
             devs = [model.device] + [torch.device("cuda", i) for i in range(n_dev) if i != model.device.index]
@@ -547,6 +573,35 @@ class HunyuanFoleySampler:
         waveform_batch = audio.float().cpu()
         first = {"waveform": waveform_batch[0].unsqueeze(0), "sample_rate": sr}
         return (first, {"waveform": waveform_batch, "sample_rate": sr})
+
+    @staticmethod
+    def _check_flowedit(audio, duration, sampler, cfg_scale, source_cfg_scale, edit_noise, deps, others):
+        """Every refusal of a FlowEdit call that needs no encoder, with its reason; returns prepare_edit's `flowedit` argument."""
+        from .host import audio_edit as _edit
+        if audio is None:
+            raise ValueError("source_prompt edits an input clip: pass it as audio=")
+        _edit.FlowEditSpec(None, source_scale=source_cfg_scale, noise=edit_noise).check(sampler, cfg_scale)
+        reasons = {
+            "window_s": "editing a long clip is not supported",
+            "prompts": "one source and one target prompt serve the batch", "negative_prompts": "one negative prompt serves both branches",
+            "images": "the variations share one video", "features": "the node encodes [negative, source, target] itself",
+            "prompt_timeline": "the prompts of the two branches are constant in time",
+            "video_cfg_scale": "each branch takes two halves with its own constant scale",
+            "guidance_interval": "each branch takes two halves with its own constant scale",
+            "cfg_rescale": "each branch takes two halves with its own constant scale",
+            "guidance_mode": "projected guidance is not built for the velocity difference",
+            "multistep_order": "the step keeps no velocity history",
+            "cache_threshold": "the step cache is not built for the pair batch", "cache_skip": "the step cache is not built for the pair batch",
+            "cache_interval": "the step cache is not built for the pair batch",
+            "cache_max_consecutive": "the step cache is not built for the pair batch"}
+        for name, why in reasons.items():
+            if others.get(name) is not None:
+                raise ValueError(f"source_prompt (FlowEdit) does not combine with {name}: {why}")
+        wave, sr = audio["waveform"], int(audio["sample_rate"])
+        dac = deps.get("dac_model")
+        rate, hop = int(getattr(dac, "sample_rate", 48000)), int(getattr(getattr(dac, "cfg", None), "hop", 960))
+        _edit.check_flowedit_length(int(duration * rate / hop), rate // hop, wave.shape[-1] * rate // sr, hop, rate)
+        return {"source_scale": float(source_cfg_scale), "noise": edit_noise}
 
     @staticmethod
     @torch.inference_mode()

@@ -334,6 +334,36 @@ int foley_step_cache_report(foley_ctx* ctx, float* rel, int32_t* skipped, int n)
 #define FOLEY_STEP_HIST 16
 int foley_set_multistep(foley_ctx* ctx, int order, void* stream);
 
+/* FlowEdit (additive within ABI 13; opt-in): inversion-free prompt editing of a source clip (Kulikov et al. 2024).  One edited clip
+ * occupies TWO clips of the model batch - a source-branch clip under the source prompt and a target-branch clip under the target
+ * prompt, sharing the visual features and the negative prompt - and the loop integrates the difference of their guided velocities
+ * from the source latents, so what both prompts agree on (here: the timing, which comes from the video) cancels.  With V
+ * variations the plan has clips = 2V, ordered [src_0 .. src_{V-1}, tar_0 .. tar_{V-1}], and ncfg = 2 (foley_prepare_sets with one
+ * text set per branch); it is the plan of the SUFFIX [i0, n_iter) of an euler run with FOLEY_STEP_BLEND rows (sigma_{k+1} in
+ * column 5), as for foley_set_edit.  The state is z [V, latent_dim, La], started at x_src.  Per iteration i, fp32, contraction off:
+ *   v_s = fma(g_src, c_s - u_s, u_s);  v_t = fma(g_tar, c_t - u_t, u_t)      (the two-half combine of clips v and V + v)
+ *   d = v_t - v_s;  d = m*d under a mask (m = mask[v][l], 1 = edit, 0 = keep);  z = fma(d, dt, z)
+ * and the rows of the next model call from s = sigma_{k+1} and n = noise row min(i + 1, noise_rows - 1):
+ *   z_src = fma(1 - s, x_src, rnd(s*n)) -> clip v;   z_tar = (z - x_src) + z_src -> clip V + v        (both cfg halves)
+ * m == 0 keeps a frame at x_src bit for bit through the whole run, m == 1 gives the unmasked update bit for bit; equal prompts and
+ * scales give the identity to rounding (the two clips pass the GEMMs at different rows).  Not built: the paper's n_min tail of
+ * plain target sampling, n_avg > 1, frames past the end of the source.
+ *   x_src [src_clips, latent_dim, La] fp32, src_clips 1 (shared) or V
+ *   noise [noise_rows, V, latent_dim, La] fp32, noise_rows plan.n_iter (fresh noise: row i serves iteration i) or 1 (one fixed draw)
+ *   mask  [mask_clips, La] fp32 in [0, 1] or NULL (all ones), mask_clips 1 or V
+ *   g_src, g_tar  the CFG scales of the branches, finite and > 1 (plan.guidance is not read)
+ *   sigma0        sigma_{k0} of the first iteration: foley_sample stages the first rows at it from noise row 0
+ * All operands are on the DEVICE and are copied into context-owned, grow-only buffers (captured graphs never hold the caller's
+ * pointers); the captured iteration is keyed on the FlowEdit operands, so a context alternates between plain and FlowEdit runs
+ * safely and new values of the same shape only rewrite what a replay reads.  foley_prepare clears the state, as does a call with
+ * x_src NULL.  Under the state foley_sample takes and returns z [V, latent_dim, La].
+ * plan.ncfg != 2, odd plan.clips, noise_rows not in {1, plan.n_iter}, clip counts other than 1 / V, a scale <= 1 or not finite,
+ * sigma0 outside [0, 1], a solver_coef row without FOLEY_STEP_BLEND (a multi-stage table), or an edit, windows, multistep,
+ * projected-guidance, guidance-schedule / rescale, step-cache or timeline state on the context: FOLEY_ERR_INVALID - those setters
+ * refuse a FlowEdit state in turn.  Before foley_prepare: FOLEY_ERR_STATE. */
+int foley_set_flowedit(foley_ctx* ctx, const float* x_src, int src_clips, const float* noise, int noise_rows, const float* mask,
+                       int mask_clips, float g_src, float g_tar, float sigma0, void* stream);
+
 /* DAC-VAE decoder: latents [clips, latent_dim, T] fp32 -> waveform [clips, 1, T*hop] fp32. */
 int foley_dac_decode(foley_ctx* ctx, const float* latents, int clips, int T, float* wave, void* stream);
 
@@ -588,6 +618,33 @@ int64_t foley_op_guidance_project_work(int clips, int La);
 int foley_op_guidance_project(const foley_projection_desc* proj, const foley_guidance_desc* gd, const float* pred, int clips, int C,
                               int La, float guidance, const int32_t* step_ptr, float* work, int64_t work_floats, void* stream);
 int foley_op_solver_step_projected(const foley_step_desc* d, const foley_projection_desc* proj, void* stream);
+/* FlowEdit at op level (see foley_set_flowedit), every operand on the DEVICE: pred [2*2V*L, C] (halves [uncond ; cond] of the clips
+ * [src_0 .. src_{V-1}, tar_0 .. tar_{V-1}]), z [V, C, L] updated in place, x_src [src_clips, C, L], noise [noise_rows, V, C, L]
+ * (noise_rows 1 or n_iter), mask [mask_clips, L] or NULL, coef [n_iter, 8] read at row *step_ptr, rows_out [2*2V*L, C] in rows_dtype
+ * (NULL: nothing staged).
+ * flowedit_step: one iteration - the update of z, then the rows of the next model call from coef column 5 and noise row
+ *   min(*step_ptr + 1, noise_rows - 1); a one-thread launch then advances *step_ptr.  The coefficient rows are read back and
+ *   checked (every row carries FOLEY_STEP_BLEND), which synchronises the stream: an op for tests and tools, not for a hot loop.
+ * flowedit_stage: the staging alone, at `sigma` in [0, 1] from noise row `noise_row`: rows_out from z, x_src and the noise (pred,
+ *   coef and step_ptr are not read).  sigma 0 stages x_src and z themselves. */
+typedef struct foley_flowedit_desc {
+  const float* pred;
+  float* z;
+  const float* x_src;
+  const float* noise;
+  const float* mask;
+  const float* coef;
+  int32_t* step_ptr;
+  void* rows_out;
+  int32_t V, C, L, n_iter, rows_dtype;
+  int32_t src_clips, noise_rows, mask_clips;
+  float g_src, g_tar;
+} foley_flowedit_desc;
+#if defined(__cplusplus) && defined(__LP64__)
+static_assert(sizeof(foley_flowedit_desc) == 104, "foley_flowedit_desc: LP64 layout (the bindings mirror it field by field)");
+#endif
+int foley_op_flowedit_step(const foley_flowedit_desc* d, void* stream);
+int foley_op_flowedit_stage(const foley_flowedit_desc* d, float sigma, int noise_row, void* stream);
 /* The step cache's kernels (see foley_set_step_cache), all operands on the DEVICE, fp32, 16-byte aligned for the probe.
  * cache_probe: a0 [Bc*La, D] (D a multiple of 4 up to 2048) -> m = LayerNorm(a0; eps) * (1 + scale) + shift written over m_prev
  *   [Bc*La, D], rel[b] = sum|m - m_prev| / sum|m_prev| of batch row b (0 when the denominator is 0).
