@@ -309,6 +309,9 @@ struct foley_ctx {
   // reference-keyed weight store (weights.hip): ctx-owned packed arena
   void* wstore = nullptr;
   void (*wstore_free)(void*) = nullptr;
+  // low-rank adapters merged into the registered weights (lora.hip): pristine copies of the touched packed tensors
+  void* lora = nullptr;
+  void (*lora_free)(void*) = nullptr;
 };
 
 // What an iteration of the prepared run is launched with under the current options (IterArgs).  No launches; reads the context only.
@@ -370,6 +373,18 @@ void** foley_ctx_wstore_slot(foley_ctx* c) { return &c->wstore; }
 void foley_ctx_set_wstore_free(foley_ctx* c, void (*fn)(void*)) { c->wstore_free = fn; }
 const foley_config* foley_ctx_config(foley_ctx* c) { return &c->cfg; }
 int foley_ctx_device(foley_ctx* c) { return c->device; }
+// internal hooks for lora.hip (not part of the C ABI)
+void** foley_ctx_lora_slot(foley_ctx* c) { return &c->lora; }
+void foley_ctx_set_lora_free(foley_ctx* c, void (*fn)(void*)) { c->lora_free = fn; }
+bool foley_ctx_tensor(foley_ctx* c, const char* name, void** p, int* dtype, std::vector<int64_t>* shape) {
+  auto it = c->tensors.find(name);
+  if (it == c->tensors.end()) return false;
+  *p = const_cast<void*>(it->second.p);
+  *dtype = it->second.dtype;
+  *shape = it->second.shape;
+  return true;
+}
+void foley_ctx_weights_changed(foley_ctx* c) { c->prepared = false; }   // cached tables depend on the weights (as in foley_set_tensor)
 
 static size_t esize(int dtype) { return foley_is_half(dtype) ? 2 : (dtype == FOLEY_F8E4M3 || dtype == FOLEY_F8E5M2) ? 1 : 4; }
 
@@ -542,8 +557,8 @@ extern "C" const char* foley_last_error(void) { return g_err.c_str(); }
 
 extern "C" int foley_ctx_create(int device, const foley_config* cfg, foley_ctx** out) {
   if (!cfg || !out) return FAIL(FOLEY_ERR_INVALID, "null argument");
-  if (cfg->hidden % cfg->heads || cfg->hidden / cfg->heads != 128)
-    return FAIL(FOLEY_ERR_INVALID, "head_dim must be 128");
+  // (the sampling path needs head_dim 128 and says so in foley_prepare; loading and merging weights work at any head_dim)
+  if (cfg->heads < 1 || cfg->hidden < 1 || cfg->hidden % cfg->heads) return FAIL(FOLEY_ERR_INVALID, "hidden must be a multiple of heads");
   if (cfg->compute_dtype != FOLEY_DT_F32 && cfg->compute_dtype != FOLEY_DT_BF16 && cfg->compute_dtype != FOLEY_DT_F16)
     return FAIL(FOLEY_ERR_INVALID, "compute_dtype must be f32, bf16 or f16");
   if (cfg->dac_n_rates < 1 || cfg->dac_n_rates > 8) return FAIL(FOLEY_ERR_INVALID, "bad dac_n_rates");
@@ -570,6 +585,7 @@ extern "C" void foley_ctx_destroy(foley_ctx* c) {
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   for (auto e : c->prof.pool) hipEventDestroy(e);
+  if (c->lora && c->lora_free) c->lora_free(c->lora);
   if (c->wstore && c->wstore_free) c->wstore_free(c->wstore);
   delete c;
 }
@@ -683,6 +699,7 @@ static int prepare_impl(foley_ctx* c, const foley_plan* pl, const foley_cond_set
   hipStream_t st = (hipStream_t)stream_v;
   HIPTRY(hipSetDevice(c->device));
   const foley_config& f = c->cfg;
+  if (f.hidden / f.heads != 128) return FAIL(FOLEY_ERR_INVALID, "head_dim must be 128");
   if (pl->ncfg < 1 || pl->ncfg > 3 || pl->clips < 1 || pl->La < 1 || pl->Lv < 1 || pl->Ls < 8 || pl->Ls % 8 ||
       pl->Lt < 1 || pl->n_iter < 1)
     return FAIL(FOLEY_ERR_INVALID, "bad plan dimensions");

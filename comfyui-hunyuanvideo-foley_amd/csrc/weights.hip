@@ -15,6 +15,7 @@
 // loaders bit for bit on the DiT; the DAC weight-norm fold differs by fp32 reduction order only).
 #include "../../include/foley_hip.h"
 #include "kernels.h"
+#include "weight_map.h"
 
 #include <dlfcn.h>
 
@@ -30,6 +31,7 @@ void** foley_ctx_wstore_slot(foley_ctx* c);
 void foley_ctx_set_wstore_free(foley_ctx* c, void (*fn)(void*));
 const foley_config* foley_ctx_config(foley_ctx* c);
 int foley_ctx_device(foley_ctx* c);
+void foley_lora_forget(foley_ctx* c);   // lora.hip: drop the pristine copies of merged adapters without writing them back
 
 namespace {
 
@@ -47,94 +49,6 @@ namespace {
       return FOLEY_ERR_HIP;                                      \
     }                                                            \
   } while (0)
-
-enum { DT_F16 = FOLEY_F16 };   // fp16: a checkpoint dtype and (precision=fp16) a compute / arena dtype
-
-__host__ __device__ inline int dt_size(int dt) {
-  return (dt == FOLEY_F8E4M3 || dt == FOLEY_F8E5M2) ? 1 : (dt == FOLEY_BF16 || dt == DT_F16) ? 2 : 4;
-}
-
-// ---- scalar conversions (device); fp8 follows the OCP formats torch implements, round-to-nearest-even.  NaNs decode to the
-// bits torch's casts give (sign kept, payload left-aligned, quiet bit set), so a loaded arena equals the packers' byte for byte.
-__device__ inline float f16_to_f32(uint16_t h) {
-  const uint32_t s = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 31, m = h & 1023;
-  if (e == 0) {
-    if (m == 0) return __uint_as_float(s);
-    float v = (float)m * 5.9604644775390625e-08f;   // 2^-24
-    return (h & 0x8000) ? -v : v;
-  }
-  if (e == 31) return __uint_as_float(s | 0x7f800000u | (m ? 0x00400000u : 0u) | (m << 13));
-  return __uint_as_float(s | ((e + 112) << 23) | (m << 13));
-}
-template <int EB, int MB, bool FN>   // exponent / mantissa bits; FN: no infinities, NaN = all ones (e4m3fn)
-__device__ inline float f8_to_f32(uint8_t v) {
-  constexpr int BIAS = (1 << (EB - 1)) - 1;
-  const uint32_t s = (uint32_t)(v & 0x80) << 24;
-  const int e = (v >> MB) & ((1 << EB) - 1), m = v & ((1 << MB) - 1);
-  if (FN ? ((v & 0x7f) == 0x7f) : (e == (1 << EB) - 1 && m != 0))
-    return __uint_as_float(s | 0x7f800000u | (FN ? 0u : 0x00400000u) | ((uint32_t)m << (23 - MB)));
-  if (!FN && e == (1 << EB) - 1) return __uint_as_float(s | 0x7f800000u);
-  if (e == 0) {
-    float x = (float)m * exp2f((float)(1 - BIAS - MB));
-    return s ? -x : x;
-  }
-  return __uint_as_float(s | ((uint32_t)(e - BIAS + 127) << 23) | ((uint32_t)m << (23 - MB)));
-}
-template <int EB, int MB, bool FN>
-__device__ inline uint8_t f32_to_f8(float f) {
-  constexpr int BIAS = (1 << (EB - 1)) - 1;
-  const uint32_t u = __float_as_uint(f);
-  const uint8_t s = (uint8_t)((u >> 24) & 0x80);
-  const uint32_t a = u & 0x7fffffffu;
-  if (a > 0x7f800000u) return s | 0x7f;                                    // NaN
-  const float maxv = FN ? 448.0f : 57344.0f;
-  const float af = __uint_as_float(a);
-  if (FN) {
-    if (af > 464.0f) return s | 0x7f;                                      // beyond the rounding range of 448: NaN (torch e4m3fn)
-  } else if (af >= 61440.0f) {
-    return s | 0x7c;                                                       // rounds to infinity (e5m2)
-  }
-  (void)maxv;
-  const int e = (int)(a >> 23) - 127;                                      // unbiased exponent
-  if (e < 1 - BIAS) {                                                      // subnormal of the target: fixed grid 2^(1-BIAS-MB)
-    const float q = af * exp2f((float)(BIAS - 1 + MB));
-    const float r = rintf(q);                                              // round-to-nearest-even
-    return s | (uint8_t)r;                                                 // r == 2^MB lands on the first normal: same bits
-  }
-  uint32_t m = a & 0x7fffffu;
-  const uint32_t drop = 23 - MB, half = 1u << (drop - 1);
-  uint32_t keep = m >> drop;
-  const uint32_t rem = m & ((1u << drop) - 1);
-  int eb = e + BIAS;
-  if (rem > half || (rem == half && (keep & 1))) {
-    if (++keep == (1u << MB)) {
-      keep = 0;
-      ++eb;
-    }
-  }
-  const uint8_t out = (uint8_t)((eb << MB) | keep);
-  if (FN && (out & 0x7f) == 0x7f) return s | 0x7f;
-  return s | out;
-}
-
-__device__ inline float load_as_f32(const void* p, long i, int dt) {
-  switch (dt) {
-    case FOLEY_F32: return ((const float*)p)[i];
-    case FOLEY_BF16: return bf16_to_f32(((const bf16_t*)p)[i]);
-    case DT_F16: return f16_to_f32(((const uint16_t*)p)[i]);
-    case FOLEY_F8E4M3: return f8_to_f32<4, 3, true>(((const uint8_t*)p)[i]);
-    default: return f8_to_f32<5, 2, false>(((const uint8_t*)p)[i]);
-  }
-}
-__device__ inline void store_from_f32(void* p, long i, int dt, float v) {
-  switch (dt) {
-    case FOLEY_F32: ((float*)p)[i] = v; break;
-    case FOLEY_BF16: ((bf16_t*)p)[i] = f32_to_bf16(v); break;
-    case DT_F16: ((f16_t*)p)[i] = (f16_t)v; break;
-    case FOLEY_F8E4M3: ((uint8_t*)p)[i] = f32_to_f8<4, 3, true>(v); break;
-    default: ((uint8_t*)p)[i] = f32_to_f8<5, 2, false>(v); break;
-  }
-}
 
 // ---- generic strided pack: out[o(idx)] = round_out(round_mid(in[i(idx)] * scale[idx[scale_dim]]))
 struct PackDesc {
@@ -326,9 +240,9 @@ struct Src {   // a checkpoint tensor as handed to foley_load_tensor
   std::vector<int64_t> shape;
 };
 
-int launch_pack(WStore& w, const std::string& slot, const Src& src, std::initializer_list<long> size,
-                std::initializer_list<long> in_strides, std::initializer_list<long> out_strides, long in_off, long out_off,
-                hipStream_t st, const float* scale = nullptr, int scale_dim = -1, int mid_dt = -1) {
+int launch_pack_n(WStore& w, const std::string& slot, const Src& src, int nd, const long* size, const long* in_strides,
+                  const long* out_strides, long in_off, long out_off, hipStream_t st, const float* scale = nullptr,
+                  int scale_dim = -1, int mid_dt = -1) {
   auto it = w.index.find(slot);
   if (it == w.index.end()) return W_FAIL(FOLEY_ERR_INVALID, "internal: unknown packed tensor");
   Slot& s = w.slots[it->second];
@@ -339,17 +253,12 @@ int launch_pack(WStore& w, const std::string& slot, const Src& src, std::initial
   d.out_dt = s.dt;
   d.mid_dt = mid_dt;
   for (int k = 0; k < 5; ++k) { d.size[k] = 1; d.is[k] = 0; d.os[k] = 0; }
-  int k = 5 - (int)size.size();
-  auto a = size.begin();
-  auto b = in_strides.begin();
-  auto c = out_strides.begin();
-  for (; a != size.end(); ++a, ++b, ++c, ++k) { d.size[k] = *a; d.is[k] = *b; d.os[k] = *c; }
+  long n = 1;
+  for (int i = 0, k = 5 - nd; i < nd; ++i, ++k) { d.size[k] = size[i]; d.is[k] = in_strides[i]; d.os[k] = out_strides[i]; n *= size[i]; }
   d.in_off = in_off;
   d.out_off = out_off;
   d.scale = scale;
-  d.scale_dim = scale_dim >= 0 ? scale_dim + (5 - (int)size.size()) : -1;
-  long n = 1;
-  for (long v : size) n *= v;
+  d.scale_dim = scale_dim >= 0 ? scale_dim + (5 - nd) : -1;
   if (n <= 0) return 0;
   const long blocks = (n + 255) / 256;
   FOLEY_LAUNCH(pack_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, st, d);
@@ -357,6 +266,12 @@ int launch_pack(WStore& w, const std::string& slot, const Src& src, std::initial
   if (e != hipSuccess) return W_FAIL(FOLEY_ERR_HIP, hipGetErrorString(e));
   if (s.parts_seen.insert(out_off).second) s.parts_done += 1;   // parts of a slot are told apart by where they land
   return 0;
+}
+int launch_pack(WStore& w, const std::string& slot, const Src& src, std::initializer_list<long> size,
+                std::initializer_list<long> in_strides, std::initializer_list<long> out_strides, long in_off, long out_off,
+                hipStream_t st, const float* scale = nullptr, int scale_dim = -1, int mid_dt = -1) {
+  return launch_pack_n(w, slot, src, (int)size.size(), size.begin(), in_strides.begin(), out_strides.begin(), in_off, out_off, st,
+                       scale, scale_dim, mid_dt);
 }
 
 bool shape_is(const Src& s, std::initializer_list<int64_t> want) {   // trailing singleton dims are ignored
@@ -370,127 +285,28 @@ bool shape_is(const Src& s, std::initializer_list<int64_t> want) {   // trailing
     return W_FAIL(FOLEY_ERR_INVALID, ("tensor '" + key + "' has an unexpected shape").c_str());     \
   }
 
-int plain(WStore& w, const std::string& slot, const Src& s, int64_t N, int64_t K, hipStream_t st, const std::string& key,
-          int mid_dt = -1) {
-  NEED(K == 1 ? numel(s.shape) == N : shape_is(s, {N, K}));
-  return launch_pack(w, slot, s, {N, K}, {K, 1}, {K, 1}, 0, 0, st, nullptr, -1, mid_dt);
+// one checkpoint tensor through its map (weight_map.h): the shape check, then the strided store
+int pack_mapped(WStore& w, const KeyMap& m, const Src& s, hipStream_t st, const std::string& key, const float* scale = nullptr,
+                int scale_dim = -1) {
+  NEED(m.shape_ok && (m.by_numel ? numel(s.shape) == m.O * m.I * m.k : shape_is(s, {m.O, m.I, m.k})));
+  return launch_pack_n(w, m.slot, s, m.nd, m.size, m.is, m.os, 0, m.out_off, st, scale, scale_dim, m.mid_dt);
+}
+int plain(WStore& w, const std::string& slot, const Src& s, int64_t N, int64_t K, hipStream_t st, const std::string& key) {
+  return pack_mapped(w, keymap::plain(slot, N, K), s, st, key);
 }
 // [O, I, k] -> [O, k*I] (K index = tap*I + c), optional per-O scale
 int conv_pack(WStore& w, const std::string& slot, const Src& s, int64_t O, int64_t I, int64_t k, hipStream_t st,
               const std::string& key, const float* scale = nullptr) {
-  NEED(shape_is(s, {O, I, k}) || (k == 1 && shape_is(s, {O, I})));
-  return launch_pack(w, slot, s, {O, k, I}, {I * k, 1, k}, {k * I, I, 1}, 0, 0, st, scale, 0);
-}
-// SwiGLU half `slot01` (0: w1, 1: w3) of [Hh, I(, k)] into alternating 32-row groups of [2*Hh, k*I]
-int gate_pack(WStore& w, const std::string& slot, const Src& s, int slot01, int64_t Hh, int64_t I, int64_t k, hipStream_t st,
-              const std::string& key) {
-  NEED(Hh % 32 == 0 && (shape_is(s, {Hh, I, k}) || (k == 1 && shape_is(s, {Hh, I}))));
-  const long KI = k * I;
-  return launch_pack(w, slot, s, {Hh / 32, 32, k, I}, {32 * I * k, I * k, 1, k}, {64 * KI, KI, I, 1}, 0, slot01 * 32 * KI, st);
+  return pack_mapped(w, keymap::conv(slot, O, I, k), s, st, key, scale, 0);
 }
 
 int load_dit(WStore& w, const std::string& key, const Src& s, hipStream_t st, bool* handled) {
-  const foley_config& f = w.cfg;
-  const int64_t D = f.hidden, H = f.heads, hd = D / H;
-  *handled = true;
-  auto blk = [&](const char* prefix, int* b, std::string* rest) {
-    const size_t n = strlen(prefix);
-    if (key.compare(0, n, prefix)) return false;
-    const size_t dot = key.find('.', n);
-    if (dot == std::string::npos) return false;
-    *b = atoi(key.substr(n, dot - n).c_str());
-    *rest = key.substr(dot + 1);
-    return true;
-  };
-  int b = 0;
-  std::string r;
-  if (blk("triple_blocks.", &b, &r)) {
-    if (b < 0 || b >= f.depth_triple) return W_FAIL(FOLEY_ERR_INVALID, ("block index out of range: " + key).c_str());
-    const std::string p = "t" + std::to_string(b) + ".";
-    static const struct { const char* ref; const char* packed; int n_mul; int k_kind; } LIN[] = {
-        {"audio_mod.linear", "a_mod", 9, 0}, {"v_cond_mod.linear", "v_mod", 9, 0},
-        {"audio_self_attn_qkv", "a_qkv", 3, 0}, {"v_cond_attn_qkv", "v_qkv", 3, 0},
-        {"audio_self_proj", "a_proj", 1, 0}, {"v_cond_self_proj", "v_proj", 1, 0},
-        {"audio_cross_q", "a_cq", 1, 0}, {"v_cond_cross_q", "v_cq", 1, 0}, {"text_cross_kv", "t_kv", 2, 0},
-        {"audio_cross_proj", "a_cproj", 1, 0}, {"v_cond_cross_proj", "v_cproj", 1, 0},
-        {"audio_mlp.fc1", "a_fc1", -1, 0}, {"v_cond_mlp.fc1", "v_fc1", -1, 0},
-        {"audio_mlp.fc2", "a_fc2", 1, 1}, {"v_cond_mlp.fc2", "v_fc2", 1, 1}};
-    for (const auto& L : LIN) {
-      const std::string m = L.ref;
-      const int64_t N = L.n_mul < 0 ? f.mlp_hidden : L.n_mul * D, K = L.k_kind ? f.mlp_hidden : D;
-      if (r == m + ".weight") return plain(w, p + L.packed + ".w", s, N, K, st, key);
-      if (r == m + ".bias") return plain(w, p + L.packed + ".b", s, N, 1, st, key);
-    }
-    static const struct { const char* ref; const char* packed; } GAIN[] = {
-        {"audio_self_q_norm", "a_qn"}, {"audio_self_k_norm", "a_kn"}, {"v_cond_attn_q_norm", "v_qn"},
-        {"v_cond_attn_k_norm", "v_kn"}, {"audio_cross_q_norm", "a_cqn"}, {"v_cond_cross_q_norm", "v_cqn"},
-        {"text_cross_k_norm", "t_kn"}};
-    for (const auto& G : GAIN)
-      if (r == std::string(G.ref) + ".weight") return plain(w, p + G.packed, s, hd, 1, st, key);
-    *handled = false;
-    return 0;
-  }
-  if (blk("single_blocks.", &b, &r)) {
-    if (b < 0 || b >= f.depth_single) return W_FAIL(FOLEY_ERR_INVALID, ("block index out of range: " + key).c_str());
-    const std::string p = "s" + std::to_string(b) + ".";
-    const int64_t Hc = f.conv_hidden;
-    if (r == "modulation.linear.weight") {
-      NEED(shape_is(s, {6 * D, D}));
-      return launch_pack(w, "smod_all.w", s, {6 * D, D}, {D, 1}, {D, 1}, 0, (long)b * 6 * D * D, st);
-    }
-    if (r == "modulation.linear.bias") {
-      NEED(numel(s.shape) == 6 * D);
-      return launch_pack(w, "smod_all.b", s, {6 * D}, {1}, {1}, 0, (long)b * 6 * D, st);
-    }
-    if (r == "linear_qkv.weight") {   // rows "(H D K)" -> "(K H D)"  (hifi_foley.py:362)
-      NEED(shape_is(s, {3 * D, D}));
-      return launch_pack(w, p + "qkv.w", s, {3, H, hd, D}, {D, hd * 3 * D, 3 * D, 1}, {H * hd * D, hd * D, D, 1}, 0, 0, st);
-    }
-    if (r == "linear_qkv.bias") {
-      NEED(numel(s.shape) == 3 * D);
-      return launch_pack(w, p + "qkv.b", s, {3, H, hd}, {1, hd * 3, 3}, {H * hd, hd, 1}, 0, 0, st);
-    }
-    if (r == "q_norm.weight") return plain(w, p + "qn", s, hd, 1, st, key);
-    if (r == "k_norm.weight") return plain(w, p + "kn", s, hd, 1, st, key);
-    if (r == "linear1.weight") return conv_pack(w, p + "lin1.w", s, D, D, 3, st, key);
-    if (r == "linear1.bias") return plain(w, p + "lin1.b", s, D, 1, st, key);
-    if (r == "linear2.w1.weight") return gate_pack(w, p + "w13.w", s, 0, Hc, D, 3, st, key);
-    if (r == "linear2.w3.weight") return gate_pack(w, p + "w13.w", s, 1, Hc, D, 3, st, key);
-    if (r == "linear2.w2.weight") return conv_pack(w, p + "w2.w", s, D, Hc, 3, st, key);
-    *handled = false;
-    return 0;
-  }
-  const bool f8time = w.wfmt != 0 && foley_is_half(f.compute_dtype);   // golden g8 "Q14": the first time-embedding bias passes through fp8
-  if (key == "audio_embedder.proj.weight") return plain(w, "audio_in.w", s, D, f.latent_dim, st, key);
-  if (key == "audio_embedder.proj.bias") return plain(w, "audio_in.b", s, D, 1, st, key);
-  if (key == "visual_proj.w1.weight") return gate_pack(w, "vis.w13.w", s, 0, D, f.clip_dim, 1, st, key);
-  if (key == "visual_proj.w3.weight") return gate_pack(w, "vis.w13.w", s, 1, D, f.clip_dim, 1, st, key);
-  if (key == "visual_proj.w2.weight") return plain(w, "vis.w2.w", s, D, D, st, key);
-  if (key == "cond_in.linear_1.weight") return plain(w, "cond1.w", s, D, f.cond_dim, st, key);
-  if (key == "cond_in.linear_1.bias") return plain(w, "cond1.b", s, D, 1, st, key);
-  if (key == "cond_in.linear_2.weight") return plain(w, "cond2.w", s, D, D, st, key);
-  if (key == "cond_in.linear_2.bias") return plain(w, "cond2.b", s, D, 1, st, key);
-  if (key == "time_in.mlp.0.weight") return plain(w, "time0.w", s, D, f.time_freq_dim, st, key);
-  if (key == "time_in.mlp.0.bias")
-    return plain(w, "time0.b", s, D, 1, st, key, f8time ? (w.wfmt == 1 ? FOLEY_F8E4M3 : FOLEY_F8E5M2) : -1);
-  if (key == "time_in.mlp.2.weight") return plain(w, "time2.w", s, D, D, st, key);
-  if (key == "time_in.mlp.2.bias") return plain(w, "time2.b", s, D, 1, st, key);
-  if (key == "sync_in.0.weight") return plain(w, "sync0.w", s, D, f.sync_dim, st, key);
-  if (key == "sync_in.0.bias") return plain(w, "sync0.b", s, D, 1, st, key);
-  if (key == "sync_in.2.w1.weight") return gate_pack(w, "sync.w13.w", s, 0, f.sync_hidden, D, 1, st, key);
-  if (key == "sync_in.2.w3.weight") return gate_pack(w, "sync.w13.w", s, 1, f.sync_hidden, D, 1, st, key);
-  if (key == "sync_in.2.w2.weight") return plain(w, "sync.w2.w", s, D, f.sync_hidden, st, key);
-  if (key == "sync_pos_emb") {
-    NEED(numel(s.shape) == 8 * (int64_t)f.sync_dim);
-    return launch_pack(w, "sync_pos", s, {8, f.sync_dim}, {f.sync_dim, 1}, {f.sync_dim, 1}, 0, 0, st);
-  }
-  if (key == "final_layer.linear.weight") return plain(w, "final.w", s, f.latent_dim, D, st, key);
-  if (key == "final_layer.linear.bias") return plain(w, "final.b", s, f.latent_dim, 1, st, key);
-  if (key == "empty_clip_feat") return plain(w, "empty_clip", s, f.clip_dim, 1, st, key);
-  if (key == "empty_sync_feat") return plain(w, "empty_sync", s, f.sync_dim, 1, st, key);
-  if (key.compare(0, 29, "final_layer.adaLN_modulation.") == 0) return 0;   // dead code with 3-D conditioning
-  *handled = false;
-  return 0;
+  KeyMap m;
+  const int kind = dit_key_map(w.cfg, w.wfmt, key, &m);
+  *handled = kind != KEY_FOREIGN;
+  if (kind == KEY_BAD_BLOCK) return W_FAIL(FOLEY_ERR_INVALID, ("block index out of range: " + key).c_str());
+  if (kind != KEY_MAPPED) return 0;
+  return pack_mapped(w, m, s, st, key);
 }
 
 // ---- DAC decoder: weight-normed convs arrive as (g, v) pairs or already folded
@@ -621,6 +437,7 @@ extern "C" int foley_weights_begin(foley_ctx* c, int weight_format) {
     return W_FAIL(FOLEY_ERR_INVALID, "fp8 weight storage needs bf16 / fp16 compute");
   W_HIP(hipSetDevice(foley_ctx_device(c)));
   void** slot = foley_ctx_wstore_slot(c);
+  foley_lora_forget(c);   // copies of an arena that is about to go
   if (*slot) {
     wstore_free(*slot);
     *slot = nullptr;

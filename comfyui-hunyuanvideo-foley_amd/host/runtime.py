@@ -128,6 +128,12 @@ class FlowEditDescC(C.Structure):
                 ("g_src", C.c_float), ("g_tar", C.c_float)]
 
 
+class LoraPairC(C.Structure):
+    _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("dtype", C.c_int32), ("rank", C.c_int32),
+                ("down_ndim", C.c_int32), ("up_ndim", C.c_int32), ("down_shape", C.c_int64 * 3), ("up_shape", C.c_int64 * 3),
+                ("scale", C.c_float)]
+
+
 class ProfEntryC(C.Structure):
     _fields_ = [("label", C.c_char * 80), ("calls", C.c_int32), ("total_ms", C.c_float), ("flop", C.c_double),
                 ("bytes", C.c_double), ("kernel", C.c_char * 200)]
@@ -151,6 +157,11 @@ _SIGNATURES = {
     "foley_weights_mark_received": (C.c_int, [C.c_void_p]),
     "foley_bcast_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "foley_bcast_local": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "foley_lora_begin": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "foley_lora_merge": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(LoraPairC), C.c_void_p]),
+    "foley_lora_end": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "foley_lora_clear": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "foley_lora_backup_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "foley_prepare": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.c_void_p]),
     "foley_prepare_sets": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.POINTER(CondSetsC), C.c_void_p]),
     "foley_prepare_timeline": (C.c_int, [C.c_void_p, C.POINTER(FoleyPlanC), C.POINTER(TextTimelineC), C.c_void_p]),
@@ -427,6 +438,44 @@ class FoleyContext:
         if rc != 0:
             raise FoleyRuntimeError(f"hipMemcpy of slot {s['name']} failed ({rc})")
         return out
+
+    # ---- low-rank adapters merged into the registered weights (csrc/lora.hip; host/lora.py drives these)
+    def lora_begin(self):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_lora_begin(self._h, _stream()), "foley_lora_begin")
+
+    def lora_merge(self, ref_key: str, adapters):
+        """All adapters of one reference key: [(down, up, scale), ...] device tensors of one dtype per pair (f32 / bf16 / f16),
+        down [r, I(, k)], up [O, r(, 1)].  They are borrowed until lora_end returns - the caller keeps them alive."""
+        pairs = (LoraPairC * max(len(adapters), 1))()
+        for p, (down, up, scale) in zip(pairs, adapters):
+            if down.dtype != up.dtype:
+                raise FoleyRuntimeError(f"lora: '{ref_key}': down is {down.dtype}, up is {up.dtype}")
+            if down.dim() > 3 or up.dim() > 3 or down.dim() < 1:
+                raise FoleyRuntimeError(f"lora: '{ref_key}': shape does not match (down {tuple(down.shape)}, up {tuple(up.shape)})")
+            p.down, p.up = _ptr(down), _ptr(up)
+            p.dtype = _TORCH2DT.get(down.dtype, -1)
+            p.rank = int(down.shape[0])
+            p.down_ndim, p.up_ndim = down.dim(), up.dim()
+            p.down_shape[:down.dim()] = list(down.shape)
+            p.up_shape[:up.dim()] = list(up.shape)
+            p.scale = float(scale)
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_lora_merge(self._h, ref_key.encode(), len(adapters), pairs, _stream()),
+                   f"foley_lora_merge({ref_key})")
+
+    def lora_end(self):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_lora_end(self._h, _stream()), "foley_lora_end")
+
+    def lora_clear(self):
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.foley_lora_clear(self._h, _stream()), "foley_lora_clear")
+
+    def lora_backup_bytes(self) -> int:
+        n = C.c_uint64()
+        _check(self.lib, self.lib.foley_lora_backup_bytes(self._h, C.byref(n)), "foley_lora_backup_bytes")
+        return int(n.value)
 
     def bcast_weights(self, nccl_comm: int, root: int = 0):
         with torch.cuda.device(self.device):

@@ -607,11 +607,13 @@ def replicate(model: FoleyModel, dac: Optional[FoleyDAC], devices: Sequence) -> 
     list, one ncclBroadcast per (device, arena) inside ncclGroupStart / End) - the in-process counterpart of the single
     broadcast of host/distributed.py; `model.last_broadcast_s` keeps its wall time.  A second context on a device that
     already holds one (the 1-GPU test set-up: RCCL communicators want distinct devices) takes a device-local copy.
-    Replicas are cached on the model."""
+    Replicas are cached on the model.  A root that carries merged LoRA adapters (host/lora.py) is restored before its arena
+    is copied, and the set is then ensured on the root and on every replica returned, so each context owns its pristine copies."""
     from . import runtime as _rt
     if model.arena is None:
         raise FoleyRuntimeError("replicate() needs a model packed by the host packers (an arena it can copy)")
     cache = model.__dict__.setdefault("_replicas", {})
+    lora_specs = getattr(model, "_lora_specs", None)
     slots, pending = [], []                         # per requested device: ("own", ) | ("cached", key) ; new replicas to fill
     for d in devices:
         d = torch.device(d)
@@ -626,6 +628,9 @@ def replicate(model: FoleyModel, dac: Optional[FoleyDAC], devices: Sequence) -> 
         slots.append(("cached", key))
         if key not in cache and key not in [p[0] for p in pending]:
             pending.append((key, d))
+    if pending and lora_specs is not None:      # new replicas copy the loaded weights, not the merged ones
+        from . import lora as _lora
+        _lora.ensure(model, None)
     if pending:
         bufs = {}
         for key, d in pending:
@@ -672,7 +677,12 @@ def replicate(model: FoleyModel, dac: Optional[FoleyDAC], devices: Sequence) -> 
             if dac is not None:
                 dd = FoleyDAC.from_arena(packers.Arena(dac.arena.buffer.numel(), dac.arena.table, d, buffer=bufs[key][1]), d, dac.cfg)
             cache[key] = (m, dd)
-    return [(model, dac) if kind == "own" else cache[key] for kind, key in slots]
+    reps = [(model, dac) if kind == "own" else cache[key] for kind, key in slots]
+    if lora_specs is not None or any(getattr(m, "_lora_fp", None) is not None for m, _ in reps):
+        from . import lora as _lora
+        for m in dict.fromkeys([model] + [m for m, _ in reps]):   # a no-op wherever the set is merged already
+            _lora.ensure(m, lora_specs)
+    return reps
 
 
 def denoise_process_multi(visual_feats, text_feats, audio_len_in_s, replicas: Sequence, guidance_scale: float,

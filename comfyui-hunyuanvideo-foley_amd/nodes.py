@@ -341,7 +341,7 @@ class HunyuanFoleySampler:
                        cache_interval=None, cache_max_consecutive=None, prompt_timeline=None, prompt_crossfade_s=0.25,
                        loudness_lufs=None, true_peak_dbtp=-1.0, peak_limiter=False, multistep_order=None,
                        guidance_mode=None, apg_eta=0.0, apg_momentum=-0.5, apg_norm_threshold=0.0, zero_init_steps=0,
-                       source_prompt=None, source_cfg_scale=2.0, edit_noise="fresh"):
+                       source_prompt=None, source_cfg_scale=2.0, edit_noise="fresh", loras=None):
         """`features` (not a ComfyUI socket) lets callers inject precomputed conditioning
         {'siglip2_feat','syncformer_feat','text_feat','uncond_text_feat'} - used by tests/bench.  Each may have batch 1 (shared)
         or batch_size (one row per clip).
@@ -414,8 +414,23 @@ class HunyuanFoleySampler:
         model batch, so the run costs what a CFG batch of 2 x batch_size clips costs, on one device.  euler only, both scales > 1; it
         does not combine with window_s, prompts= / negative_prompts= / images= / features=, prompt_timeline, the guidance controls,
         multistep_order or the step cache, and a duration past the end of `audio` is refused.  The loudness stage combines with it.
-        None: every run is what it was, bit for bit, and nothing new is launched."""
+        None: every run is what it was, bit for bit, and nothing new is launched.
+
+        LoRA adapters (keyword-only, not a socket; host/lora.py): `loras` [(file name or state dict, strength), ...] - the
+        adapters are merged into the model's packed weights, in list order, before anything else runs (a refused file costs no
+        encoder pass), and stay merged until a call asks for another set.  A bare file name is looked up in ComfyUI's `loras`
+        folder, then in `foley`.  PEFT / diffusers, ComfyUI-native and kohya spellings are served; DoRA, LoHa, LoKr and weight
+        diffs are refused by name.  Strength 0 drops an adapter, negative strengths are allowed.  The merge is in place, so the
+        loop runs at its plain speed and fp8 weights stay fp8; it combines with every other option.  None on a model with nothing
+        merged: nothing is imported or launched and the run is the plain one, bit for bit; None on a model that carries a set
+        restores the loaded weights first (logged)."""
         model, deps = hunyuan_model, hunyuan_deps
+        if loras is not None or getattr(model, "_lora_fp", None) is not None:      # first: refused before the encoders run
+            from .host import lora as _lora
+            want = [(self._lora_path(src), strength) for src, strength in _lora.normalize(loras)]
+            if _lora.ensure(model, want):
+                log.info("LoRA: %s", "merged %d adapter(s) into the packed weights" % len(want) if want else
+                         "restored the loaded weights (no loras= on a model that carried a set)")
         flowedit = None
         if source_prompt is not None:              # refused here, before the encoders run
             flowedit = self._check_flowedit(audio, duration, sampler, cfg_scale, source_cfg_scale, edit_noise, deps, dict(
@@ -573,6 +588,18 @@ class HunyuanFoleySampler:
         waveform_batch = audio.float().cpu()
         first = {"waveform": waveform_batch[0].unsqueeze(0), "sample_rate": sr}
         return (first, {"waveform": waveform_batch, "sample_rate": sr})
+
+    @staticmethod
+    def _lora_path(src):
+        """A state dict or an existing path as it is; a bare file name through ComfyUI's `loras` folder, then `foley`."""
+        if not isinstance(src, (str, os.PathLike)) or os.path.exists(src):
+            return src
+        fp = _folder_paths()
+        for folder in ("loras", "foley"):
+            full = fp.get_full_path(folder, os.fspath(src)) if fp is not None and folder in fp.folder_names_and_paths else None
+            if full:
+                return full
+        raise FileNotFoundError(f"LoRA file '{src}' not found (looked in the loras and foley model folders)")
 
     @staticmethod
     def _check_flowedit(audio, duration, sampler, cfg_scale, source_cfg_scale, edit_noise, deps, others):

@@ -143,6 +143,44 @@ int foley_bcast_weights(foley_ctx* ctx, void* nccl_comm, int root, void* stream)
  * `devices`, cached; ncclGroupStart / ncclBroadcast per (device, buffer) / ncclGroupEnd), then every device is synchronised. */
 int foley_bcast_local(int ndev, const int* devices, int nbuf, void* const* bufs, const uint64_t* bytes);
 
+/* ---- Low-rank adapters (LoRA) merged into the packed weights, in place (additive within ABI 13; csrc/lora.hip).  For a
+ * checkpoint tensor W[O, I(, k)] named by its REFERENCE state-dict key (`triple_blocks.3.audio_self_attn_qkv.weight`,
+ * `single_blocks.7.linear2.w1.weight`, ...) and adapters j = 0..n-1 in the caller's order, down_j [r_j, I(, k)], up_j [O, r_j(, 1)]:
+ *     stored'[o, c] = rnd_store( f32(pristine[o, c]) + sum_j scale_j * sum_q up_j[o, q] * down_j[q, c] ),  c over the flattened (I, k)
+ * `pristine` is the value the packed tensor held before any adapter (for bf16 / fp16 / fp8 storage: its stored rounding), operands
+ * are widened to fp32, accumulation is fp32 in a fixed order, rnd_store is the loader's round-to-nearest-even store of the tensor's
+ * dtype.  The destination is the tensor registered under the key's packed name - foley_set_tensor's or the arena of
+ * foley_weights_begin - at unchanged addresses, so a captured loop iteration stays valid and an fp8 arena stays fp8.  The first
+ * time a packed tensor is touched the library copies it to a buffer of its own (at most one more arena in total); every merge
+ * starts from those copies, so a set of adapters gives the same bytes whatever was merged before it.
+ *   foley_lora_begin(ctx, stream)       every touched tensor back to its pristine bytes; forget the merged set
+ *   foley_lora_merge(ctx, key, n, pairs, stream)   ALL adapters of one key in one call (n in [1, 8]); a second call for the same
+ *                                       key before foley_lora_end is refused.  Targets: every weight matrix of the DiT, the
+ *                                       embedders included; biases, norm gains, sync_pos_emb, the empty features and the DAC are
+ *                                       not targetable.  Unknown or non-targetable keys, shapes that do not match, an `up` with a
+ *                                       kernel > 1, rank outside [1, 256], a non-finite scale, operands other than f32 / bf16 /
+ *                                       f16: FOLEY_ERR_INVALID with a message naming the key and the reason, nothing written.
+ *                                       The operands are device memory, borrowed until foley_lora_end returns.
+ *   foley_lora_end(ctx, stream)         waits for the merges; the next run needs foley_prepare (as after foley_set_tensor)
+ *   foley_lora_clear(ctx, stream)       foley_lora_begin + free the copies (foley_ctx_destroy frees them too)
+ *   foley_lora_backup_bytes(ctx, &n)    bytes the pristine copies hold now
+ * Re-registering or rewriting a packed tensor while a set is merged: call foley_lora_clear first (a copy whose tensor has moved
+ * is dropped unused; foley_weights_begin drops them all). */
+typedef struct {
+  const void* down;        /* [rank, I(, k)], contiguous, the checkpoint's own (I, k) order */
+  const void* up;          /* [O, rank(, 1)], contiguous */
+  int32_t dtype;           /* FOLEY_DT_F32 / FOLEY_DT_BF16 / FOLEY_DT_F16, both operands */
+  int32_t rank;
+  int32_t down_ndim, up_ndim;            /* 2 or 3 */
+  int64_t down_shape[3], up_shape[3];
+  float scale;             /* strength * alpha / rank, formed by the caller */
+} foley_lora_pair;
+int foley_lora_begin(foley_ctx* ctx, void* stream);
+int foley_lora_merge(foley_ctx* ctx, const char* ref_key, int n, const foley_lora_pair* pairs, void* stream);
+int foley_lora_end(foley_ctx* ctx, void* stream);
+int foley_lora_clear(foley_ctx* ctx, void* stream);
+int foley_lora_backup_bytes(foley_ctx* ctx, uint64_t* bytes);
+
 /* Step-invariant precompute for one run; allocates/reuses the context workspace. */
 int foley_prepare(foley_ctx* ctx, const foley_plan* plan, void* stream);
 
